@@ -1,6 +1,6 @@
 """bench.py -- structures/s (energy + force + stress) of the HIP engine on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -15,6 +15,8 @@ architecture (tests/golden/weights_seed0.npz -- the pretrained blobs are not ava
 One step = one pass of the hot path (chg_predict, task "efs") over the rank's 1024 device-resident
 structures plus the download of E/F/S to the host.  Ranks hold disjoint structures (weak scaling,
 no data-path collective); with N > 1 the per-structure energies are all-gathered over RCCL each step.
+``--dump-outputs DIR`` (e.g. bench_outputs/, git-ignored) writes rank 0's E / F / S of the last timed step as DIR/e.npy,
+f.npy, s.npy: the inputs are seeded, so two builds run with the same arguments compare output for output.
 
 Prints ONE JSON line (rank 0):
   roofline       the kernel with the largest share of the step (fp32-MFMA-bound), HIP events on the engine stream
@@ -160,6 +162,27 @@ def li9co7o16_supercell(scale=(2, 2, 2)):
 
     d = np.load(os.path.join(REPO, "tests", "golden", "case_li9co7o16.npz"))
     return Structure(Lattice(d["lattice_f64"]), d["atomic_number"], d["frac_coord_f64"]).make_supercell(list(scale))
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, res: dict, atom_off) -> dict:
+    """``--dump-outputs``: the arrays the last timed step handed its caller (E, F, S of this rank's batch) as ``<out_dir>/<name>.npy``,
+    float32, for comparing two builds output for output on identical inputs.  Past DUMP_LIMIT_BYTES a fixed sample of whole structures
+    (numpy default_rng(0), sorted) is written instead, with every array restricted to those structures.  Returns name -> shape."""
+    arrays = {k: np.ascontiguousarray(v, np.float32) for k, v in res.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = len(arrays["e"])
+        n_keep = max(1, int(0.9 * DUMP_LIMIT_BYTES * n / total))
+        keep = np.sort(np.random.default_rng(0).choice(n, size=n_keep, replace=False))
+        atoms = np.concatenate([np.arange(atom_off[i], atom_off[i + 1]) for i in keep])
+        arrays = {k: a[atoms] if k == "f" else a[keep] for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -1089,7 +1112,12 @@ def main() -> None:
     ap.add_argument("--total-structures", type=int, default=0,
                     help="strong-scaling mode: this many structures of the headline workload in TOTAL, split evenly over the ranks "
                          "(the default mode is weak: --structures per rank)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's E / F / S of the last timed step as DIR/<name>.npy (float32, at most "
+                         "64 MB: a fixed sample of structures beyond that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "LOCAL_RANK" not in os.environ and int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
         raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))   # not under a launcher: start the N ranks ourselves
@@ -1148,6 +1176,7 @@ def main() -> None:
     total_structures = args.total_structures or world * args.structures
     value = total_structures / (elapsed / args.steps)
     energies_in_gather = int(np.isfinite(gathered).sum()) if gathered is not None else args.structures
+    dumped = dump_outputs(args.dump_outputs, res, packed.atom_off) if args.dump_outputs and rank == 0 else None
 
     # device-only time of one step and the per-kernel split (HIP events on the engine stream)
     eng.timer_start()
@@ -1334,6 +1363,8 @@ def main() -> None:
             "kernel_ms_per_step": {k: round(v[1] / prof_steps, 3) for k, v in ranked},
             "configs": configs,
         }
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"], parity = cpu_leg(weights, graphs[:128], checks)
             try:    # the reference ITSELF, timed where it exists: the build container (tools/cpu_reference_baseline.py; it does not travel here)

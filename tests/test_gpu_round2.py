@@ -156,16 +156,18 @@ def test_full_size_batch_every_structure_against_the_oracle(hip_engine, golden_w
 
 
 def test_device_graph_build_against_the_compiled_reference(hip_engine):
-    """The device builder vs the reference's own C builder (oracle/_ref/libref_graph.so = create_graph.c compiled
-    in place) DIRECTLY: the neighbour list found on the device goes into the reference's create_graph +
-    line-graph code and every index array must come out identical."""
-    from chgnet_amd.graph.converter import build_graph_arrays
-    from oracle import ref_graph
+    """The device builder vs the reference's own C builder (create_graph.c compiled in place) DIRECTLY: the neighbour list
+    found on the device is the one the reference's create_graph + line-graph code was fed (tests/golden/ref_graph_c.json,
+    make_ref_graph_golden.py), and every index array must come out as the reference built it."""
+    import json
 
-    if not ref_graph.available():
-        pytest.fail("oracle/_ref/libref_graph.so is missing: build() compiles it and it travels with the snapshot")
+    from chgnet_amd.graph.converter import build_graph_arrays
+    from golden.make_golden_helpers import array_digest
+
+    with open(os.path.join(GOLDEN, "ref_graph_c.json")) as fh:
+        fx = json.load(fh)
     structs = _structures_for_graph_tests()
-    for r_atom, r_bond in ((6.0, 3.0), (5.0, 3.0), (4.0, 4.0)):
+    for j, (r_atom, r_bond) in enumerate(((6.0, 3.0), (5.0, 3.0), (4.0, 4.0))):
         batch = hip_engine.build_batch(structs, r_atom, r_bond)
         pb = batch.packed
         f = lambda name, n: hip_engine.debug_fetch_i32(batch, name, n)  # noqa: E731
@@ -185,13 +187,16 @@ def test_device_graph_build_against_the_compiled_reference(hip_engine):
                 continue                                               # isolated atoms only: nothing to index
             host = build_graph_arrays(np.asarray(s.frac_coords, np.float64), np.asarray(s.lattice.matrix, np.float64), r_atom, r_bond)
             assert np.array_equal(host["atom_graph"], np.stack([ec[sl] - a_off[b], en[sl] - a_off[b]], 1)) and np.array_equal(host["image"], img[sl])
-            ref = ref_graph.reference_graph(len(s), ec[sl] - a_off[b], en[sl] - a_off[b], img[sl], host["distance"], r_bond)
-            assert np.array_equal(ref["directed2undirected"], d2u[sl] - u_off[b]), (b, "d2u")
-            assert np.array_equal(ref["undirected2directed"], u2d[u_off[b]:u_off[b + 1]] - e_off[b]), (b, "u2d")
+            ref = fx[f"gpu_{b}_{j}"]
+            fed = {"center": ec[sl] - a_off[b], "neighbor": en[sl] - a_off[b], "image": img[sl], "distance": host["distance"]}
+            for key, v in fed.items():                                 # the list the reference was fed
+                assert array_digest(v) == ref[key], (b, key)
+            assert array_digest(d2u[sl] - u_off[b]) == ref["directed2undirected"], (b, "d2u")
+            assert array_digest(u2d[u_off[b]:u_off[b + 1]] - e_off[b]) == ref["undirected2directed"], (b, "u2d")
             rows = np.flatnonzero(a_owner == b)
             got_bg = np.stack([a_ctr[rows] - a_off[b], bn[a_b1c[rows]] - u_off[b], a_d1[rows] - e_off[b], bn[a_b2c[rows]] - u_off[b],
                                a_d2[rows] - e_off[b]], 1) if len(rows) else np.zeros((0, 5), np.int32)
-            assert np.array_equal(ref["bond_graph"].reshape(-1, 5), got_bg), (b, "bond_graph")
+            assert array_digest(got_bg) == ref["bond_graph"], (b, "bond_graph")
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -175,26 +175,30 @@ def _cases_for_native_reference():
 
 
 def test_builder_matches_the_references_compiled_c_algorithm():
-    """oracle/_ref: the reference's create_graph.c compiled from where it lies (`make -C oracle`), fed the
-    same neighbour list (in our order and in a shuffled order): every array identical."""
-    from oracle import ref_graph
+    """What the reference's create_graph.c built (tests/golden/ref_graph_c.json, make_ref_graph_golden.py: the library compiled
+    from where it lies) from the same neighbour list, in our order and in a shuffled order: every array identical."""
+    import json
 
-    if not ref_graph.available() and ref_graph.build() is None:
-        pytest.skip("oracle/_ref/libref_graph.so not built and /root/reference absent")
-    rng = np.random.default_rng(3)
-    for s in _cases_for_native_reference():
-        for r_atom, r_bond in ((6.0, 3.0), (5.0, 3.0), (4.0, 4.0)):
+    from golden.make_golden_helpers import array_digest
+
+    with open(os.path.join(GOLDEN, "ref_graph_c.json")) as fh:
+        fx = json.load(fh)
+    rng = np.random.default_rng(3)                      # the shuffles the fixture was made with
+    for i, s in enumerate(_cases_for_native_reference()):
+        for j, (r_atom, r_bond) in enumerate(((6.0, 3.0), (5.0, 3.0), (4.0, 4.0))):
             a = build_graph_arrays(s.frac_coords, s.lattice.matrix, r_atom, r_bond)
             nl = {"center": a["atom_graph"][:, 0].astype(np.int64), "neighbor": a["atom_graph"][:, 1].astype(np.int64),
                   "image": a["image"].astype(np.int64), "distance": a["distance"]}
-            for shuffle in (False, True):
+            for shuffle in (0, 1):
                 if shuffle and len(nl["center"]):
                     perm = np.concatenate([rng.permutation(np.flatnonzero(nl["center"] == c)) for c in range(len(s))])
                     nl = {k: v[perm] for k, v in nl.items()}
-                ref = ref_graph.reference_graph(len(s), nl["center"], nl["neighbor"], nl["image"], nl["distance"], r_bond)
+                ref = fx[f"cpu_{i}_{j}_{shuffle}"]
+                for key in ("center", "neighbor", "image", "distance"):          # the list the reference was fed
+                    assert array_digest(nl[key]) == ref[key], (key, i, r_atom, r_bond, shuffle)
                 got = graph_arrays_from_neighbors(len(s), nl["center"], nl["neighbor"], nl["image"], nl["distance"], r_bond)
                 for key in ("atom_graph", "directed2undirected", "undirected2directed", "bond_graph"):
-                    assert np.array_equal(got[key].reshape(ref[key].shape), ref[key]), (key, r_atom, r_bond, shuffle)
+                    assert array_digest(got[key]) == ref[key], (key, i, r_atom, r_bond, shuffle)
 
 
 def test_cutoff_boundary_rules_known_answer():

@@ -85,36 +85,27 @@ def test_documented_pretrained_targets_are_recorded():
     assert abs(t.LIMNO2_E - (-7.36769)) < 1e-9 and len(t.LIMNO2_MAGMOM) == 8
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/chgnet"), reason="live reference only in the build container")
-def test_oracle_matches_live_reference_on_fresh_input(golden_weights):
-    """Fresh random structure, reference imported from /root/reference (never on the GPU box)."""
-    from oracle._refimport import load_reference
-
-    load_reference(fast_graph=True)            # with the reference's compiled cygraph: its "fast" converter is real
-    from chgnet.graph.converter import CrystalGraphConverter as RefConverter
-    from chgnet.model.model import CHGNet as RefCHGNet
-
-    from chgnet_amd import CrystalGraphConverter, Structure
-    from chgnet_amd.graph.converter import build_graph_arrays
+def fresh_structure():
+    """A random 5-atom cell that none of the case fixtures was made from."""
+    from chgnet_amd import Structure
     from chgnet_amd.graph.structure import Lattice
-    from golden.make_golden_helpers import DuckStructure
+
+    rng = np.random.default_rng(99)
+    return Structure(Lattice(np.diag([4.1, 4.4, 5.0]) + rng.normal(0, 0.2, (3, 3))), [3, 8, 25, 8, 27], rng.random((5, 3)))
+
+
+def test_oracle_matches_live_reference_on_fresh_input(golden_weights):
+    """Fresh random structure through the reference's own converter (algorithm "fast": its compiled cygraph, fed our neighbour
+    list) and its CHGNet.predict_graph: what they returned is tests/golden/ref_fresh_input.npz (make_ref_check_golden.py)."""
+    from chgnet_amd import CrystalGraphConverter
 
     torch.set_num_threads(1)
-    model = RefCHGNet()
-    model.load_state_dict({k: torch.tensor(v) for k, v in golden_weights.items()})
-    rng = np.random.default_rng(99)
-    s = Structure(Lattice(np.diag([4.1, 4.4, 5.0]) + rng.normal(0, 0.2, (3, 3))), [3, 8, 25, 8, 27], rng.random((5, 3)))
-    g = CrystalGraphConverter()(s)
-    # the reference's own converter, end to end (structure -> neighbour list -> cygraph -> CrystalGraph)
-    a = build_graph_arrays(s.frac_coords, s.lattice.matrix, 6.0, 3.0)
-    nl = {"center": a["atom_graph"][:, 0].astype(np.int64), "neighbor": a["atom_graph"][:, 1].astype(np.int64),
-          "image": a["image"].astype(np.int64), "distance": a["distance"]}
-    conv = RefConverter(atom_graph_cutoff=6, bond_graph_cutoff=3, algorithm="fast")
-    assert conv.algorithm == "fast"
-    rg = conv(DuckStructure(s, nl))
+    d = np.load(os.path.join(GOLDEN, "ref_fresh_input.npz"))
+    g = CrystalGraphConverter()(fresh_structure())
     for attr in ("atom_graph", "directed2undirected", "undirected2directed", "bond_graph", "neighbor_image"):
-        assert np.array_equal(getattr(rg, attr).numpy().reshape(getattr(g, attr).shape), getattr(g, attr)), attr
-    ref = model.predict_graph(rg, task="efsm", return_site_energies=True, return_atom_feas=True, return_crystal_feas=True)
+        assert np.array_equal(d[f"graph/{attr}"].reshape(getattr(g, attr).shape), getattr(g, attr)), attr
+    ref = {k[len("out/"):]: d[k] for k in d.files if k.startswith("out/")}
+    assert set(ref) == set(TOL)
     out = OracleCHGNet(golden_weights).predict_graph(g, "efsm", return_site_energies=True, return_atom_feas=True, return_crystal_feas=True)
     for key in ref:
         assert np.abs(out[key] - ref[key]).max() <= 5 * TOL[key], key

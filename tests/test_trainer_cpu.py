@@ -30,37 +30,36 @@ def _batch(rng, missing: bool):
     return targ, pred
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/chgnet"), reason="live reference only in the build container")
-@pytest.mark.parametrize("criterion", ["MSE", "MAE", "Huber"])
-@pytest.mark.parametrize(("missing", "allow"), [(False, True), (True, True), (False, False)])
+LOSS_CRITERIA = ("MSE", "MAE", "Huber")
+LOSS_MASKING = ((False, True), (True, True), (False, False))
+LOSS_CASES = [(c, missing, allow) for c in LOSS_CRITERIA for missing, allow in LOSS_MASKING]
+
+
+def loss_kwargs(criterion: str, allow: bool) -> dict:
+    return dict(target_str="efsm", criterion=criterion, energy_loss_ratio=1.3, force_loss_ratio=0.7, stress_loss_ratio=0.2,
+                mag_loss_ratio=0.4, delta=0.3, allow_missing_labels=allow)
+
+
+@pytest.mark.parametrize("criterion", LOSS_CRITERIA)
+@pytest.mark.parametrize(("missing", "allow"), LOSS_MASKING)
 def test_combined_loss_equals_the_references(criterion, missing, allow):
-    """Loss value, MAEs, MAE sizes and d loss / d prediction against chgnet.trainer.trainer.CombinedLoss + autograd; also without
-    label masking, where the reference's sizes count target ROWS ([N,3], [3B,3]) instead of elements (trainer.py:826, 840)."""
-    from oracle._refimport import load_reference
-
-    load_reference(fast_graph=True)
-    from chgnet.trainer.trainer import CombinedLoss as RefLoss
-
+    """Loss value, MAEs, MAE sizes and d loss / d prediction against chgnet.trainer.trainer.CombinedLoss + autograd (its outputs on
+    this batch: tests/golden/ref_combined_loss.npz, make_ref_check_golden.py); also without label masking, where the reference's
+    sizes count target ROWS ([N,3], [3B,3]) instead of elements (trainer.py:826, 840)."""
     rng = np.random.default_rng(3)
     targ, pred = _batch(rng, missing)
-    kw = dict(target_str="efsm", criterion=criterion, energy_loss_ratio=1.3, force_loss_ratio=0.7, stress_loss_ratio=0.2,
-              mag_loss_ratio=0.4, delta=0.3, allow_missing_labels=allow)
-    ours, grads = CombinedLoss(**kw).gradients(targ, pred)
-    tp = {"e": torch.tensor(pred["e"], requires_grad=True), "f": [torch.tensor(x, requires_grad=True) for x in pred["f"]],
-          "s": [torch.tensor(x, requires_grad=True) for x in pred["s"]], "m": [torch.tensor(x, requires_grad=True) for x in pred["m"]]}
-    tt = {"e": torch.tensor(targ["e"]), "f": [torch.tensor(x) for x in targ["f"]], "s": [torch.tensor(x) for x in targ["s"]],
-          "m": [None if x is None else torch.tensor(x) for x in targ["m"]]}
-    ref = RefLoss(**kw)(tt, tp)
+    ours, grads = CombinedLoss(**loss_kwargs(criterion, allow)).gradients(targ, pred)
+    d = np.load(os.path.join(REPO, "tests", "golden", "ref_combined_loss.npz"))
+    ref = {k.split("/", 1)[1]: d[k] for k in d.files if k.startswith(f"{criterion}_{int(missing)}_{int(allow)}/")}
+    assert np.array_equal(ref["pred_e"], pred["e"])                 # the batch the reference saw
     assert abs(ours["loss"] - float(ref["loss"])) < 1e-12
     for k in "efsm":
         assert abs(ours[f"{k}_MAE"] - float(ref[f"{k}_MAE"])) < 1e-12, k
         assert ours[f"{k}_MAE_size"] == int(ref[f"{k}_MAE_size"]), k
-    ref["loss"].backward()
-    assert np.allclose(grads["e"], tp["e"].grad.numpy(), atol=1e-14)
-    assert np.allclose(grads["f"], np.concatenate([x.grad.numpy() for x in tp["f"]]), atol=1e-14)
-    assert np.allclose(grads["s"].reshape(-1, 3), np.concatenate([x.grad.numpy() for x in tp["s"]]), atol=1e-14)
-    gm = np.concatenate([np.zeros(len(x)) if x.grad is None else x.grad.numpy() for x in tp["m"]])
-    assert np.allclose(grads["m"], gm, atol=1e-14)
+    assert np.allclose(grads["e"], ref["grad_e"], atol=1e-14)
+    assert np.allclose(grads["f"], ref["grad_f"], atol=1e-14)
+    assert np.allclose(grads["s"].reshape(-1, 3), ref["grad_s"], atol=1e-14)
+    assert np.allclose(grads["m"], ref["grad_m"], atol=1e-14)
 
 
 def test_adam_equals_torch_adam():
