@@ -30,4 +30,8 @@ def __getattr__(name):  # lazy: keeps `import chgnet_amd` free of the HIP librar
         from chgnet_amd.calculator import CHGNetCalculator
 
         return CHGNetCalculator
+    if name in ("StructOptimizer", "TrajectoryObserver"):
+        from chgnet_amd import relax
+
+        return getattr(relax, name)
     raise AttributeError(name)

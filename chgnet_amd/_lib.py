@@ -25,6 +25,7 @@ EXPORTED_SYMBOLS = (
     "chg_comm_all_gather_f32_device", "chg_comm_all_reduce_sum_f32_device", "chg_comm_reserve", "chg_comm_info",
     "chg_backward_allreduce", "chg_batch_all_gather_energy", "chg_engine_stream", "chg_engine_device",
     "chg_host_alloc", "chg_host_free",
+    "chg_relax_create", "chg_relax_run", "chg_relax_download", "chg_relax_free", "chg_test_relax_step",
 )
 
 
@@ -58,6 +59,19 @@ class OutHost(ctypes.Structure):
     _fields_ = [(n, c_float_p) for n in ("energy", "force", "stress", "magmom", "site_energy", "atom_fea", "crystal_fea")]
 
 
+class RelaxParams(ctypes.Structure):
+    _fields_ = [("fmax", ctypes.c_double), ("max_steps", ctypes.c_int32), ("relax_cell", ctypes.c_int32),
+                ("dt", ctypes.c_double), ("maxstep", ctypes.c_double), ("dtmax", ctypes.c_double), ("finc", ctypes.c_double),
+                ("fdec", ctypes.c_double), ("astart", ctypes.c_double), ("fa", ctypes.c_double), ("nmin", ctypes.c_int32),
+                ("exp_cell_factor", ctypes.c_double), ("r_atom", ctypes.c_double), ("r_bond", ctypes.c_double),
+                ("numerical_tol", ctypes.c_double), ("stress_weight", ctypes.c_double)]
+
+
+class RelaxOutHost(ctypes.Structure):
+    _fields_ = [("frac", ctypes.POINTER(ctypes.c_double)), ("lattice", ctypes.POINTER(ctypes.c_double)), ("energy", c_float_p),
+                ("force", c_float_p), ("stress", c_float_p), ("magmom", c_float_p), ("n_steps", c_int_p), ("status", c_int_p)]
+
+
 _LIB = None
 
 
@@ -67,7 +81,7 @@ def hip_lib_path() -> str:
     return os.environ.get("CHGNET_HIP_LIB", HIP_LIB)   # override: kernel timing experiments only
 
 
-ABI_VERSION = 3   # include/chgnet_hip.h CHG_ABI_VERSION
+ABI_VERSION = 4   # include/chgnet_hip.h CHG_ABI_VERSION
 
 
 def load() -> ctypes.CDLL:
@@ -153,6 +167,13 @@ def load() -> ctypes.CDLL:
     lib.chg_debug_fetch.argtypes = [vp, vp, ctypes.c_char_p, c_float_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
     lib.chg_test_rows_gemm.argtypes = [vp, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     lib.chg_test_split_gemm.argtypes = [vp, c_float_p, c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    dp = ctypes.POINTER(ctypes.c_double)
+    lib.chg_relax_create.argtypes = [vp, ctypes.POINTER(StructsHost), ctypes.POINTER(RelaxParams), ctypes.POINTER(vp)]
+    lib.chg_relax_run.argtypes = [vp, vp, ctypes.c_int32, c_int_p]
+    lib.chg_relax_download.argtypes = [vp, vp, ctypes.POINTER(RelaxOutHost)]
+    lib.chg_relax_free.argtypes = [vp, vp]
+    lib.chg_test_relax_step.argtypes = [vp, ctypes.POINTER(RelaxParams), ctypes.c_int32, c_int_p, dp, dp, dp, c_int_p, c_float_p, c_float_p,
+                                        c_float_p, c_float_p, dp, dp]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is ctypes.c_int and name not in ("chg_device_count", "chg_profile_count"):

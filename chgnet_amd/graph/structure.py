@@ -89,6 +89,19 @@ class Structure:
         formula = " ".join(f"{s}{counts[s]}" for s in order)
         return SimpleNamespace(formula=formula)
 
+    @property
+    def site_properties(self) -> dict:
+        """Per-site properties by name (pymatgen's ``Structure.site_properties``; ``StructOptimizer.relax`` sets "magmom")."""
+        return self.__dict__.setdefault("_site_properties", {})
+
+    def add_site_property(self, property_name: str, values) -> None:
+        if len(values) != len(self):
+            raise ValueError(f"site property {property_name!r} has {len(values)} values for {len(self)} sites")
+        self.site_properties[property_name] = list(values)
+
+    def remove_site_property(self, property_name: str) -> None:
+        self.site_properties.pop(property_name, None)
+
     def copy(self) -> "Structure":
         return Structure(Lattice(self.lattice.matrix.copy()), self.atomic_numbers.copy(), self.frac_coords.copy())
 

@@ -1,0 +1,269 @@
+"""``StructOptimizer`` -- batched structure relaxation on the device (reference chgnet/model/dynamics.py:184-400).
+
+The reference relaxes one structure at a time through ASE: ``FIRE(FrechetCellFilter(atoms)).run(fmax, steps)`` with
+``CHGNetCalculator`` evaluating every step.  ASE is absent offline, and one Python round trip per step leaves the batch
+engine idle.  Here the whole optimizer runs behind the C-ABI (``chg_relax_*``, include/chgnet_hip.h): every structure
+is an independent FIRE optimizer whose float64 state stays in HBM, one step kernel (csrc/kernels_relax.h) advances all
+active structures at once, and structures that have stopped drop out of the next graph build.  A batch gives every
+structure the result it would get alone.  The semantics are those of ASE's FIRE and FrechetCellFilter with their
+defaults; tests/relax_ref.py restates them in float64 NumPy / SciPy.
+
+Deviation: a structure whose energy, forces or stress are non-finite even on the engine's wide-range sweep stops with
+status ``NONFINITE`` without moving (ASE would carry the NaN on).
+"""
+
+from __future__ import annotations
+
+import contextlib
+import ctypes
+import io
+import pickle
+import sys
+
+import numpy as np
+
+from chgnet_amd import _lib
+from chgnet_amd.calculator import GPA_TO_EV_A3, CHGNetCalculator, atoms_to_structure
+from chgnet_amd.graph.structure import Lattice, Structure
+
+OPTIMIZERS = ("FIRE",)
+FILTERS = ("FrechetCellFilter",)
+STATUS_NAMES = ("RUNNING", "CONVERGED", "MAX_STEPS", "NONFINITE")
+FIRE_DEFAULTS = {"dt": 0.1, "maxstep": 0.2, "dtmax": 1.0, "Nmin": 5, "finc": 1.1, "fdec": 0.5, "astart": 0.1, "fa": 0.99}
+
+
+def _voigt(s: np.ndarray) -> np.ndarray:
+    """3x3 stress (any leading axes) -> ASE Voigt order xx, yy, zz, yz, xz, xy."""
+    return np.stack([s[..., 0, 0], s[..., 1, 1], s[..., 2, 2], s[..., 1, 2], s[..., 0, 2], s[..., 0, 1]], axis=-1)
+
+
+class TrajectoryObserver:
+    """Frames of one relaxation (reference dynamics.py:349-405): total energy (eV), forces (eV/A), stress (Voigt 6, eV/A^3),
+    magnetic moments, cartesian positions and cells, one per logged evaluation plus the final one once more."""
+
+    def __init__(self, atomic_numbers) -> None:
+        self.atomic_numbers = np.asarray(atomic_numbers)
+        self.energies: list[float] = []
+        self.forces: list[np.ndarray] = []
+        self.stresses: list[np.ndarray] = []
+        self.magmoms: list[np.ndarray] = []
+        self.atom_positions: list[np.ndarray] = []
+        self.cells: list[np.ndarray] = []
+
+    def append(self, energy, forces, stress, magmoms, positions, cell) -> None:
+        self.energies.append(float(energy))
+        self.forces.append(np.asarray(forces))
+        self.stresses.append(np.asarray(stress))
+        self.magmoms.append(np.asarray(magmoms))
+        self.atom_positions.append(np.asarray(positions))
+        self.cells.append(np.asarray(cell))
+
+    def __len__(self) -> int:
+        return len(self.energies)
+
+    def save(self, filename: str) -> None:
+        """Pickle with the reference's keys."""
+        out_pkl = {"energy": self.energies, "forces": self.forces, "stresses": self.stresses, "magmoms": self.magmoms,
+                   "atom_positions": self.atom_positions, "cell": self.cells, "atomic_number": self.atomic_numbers}
+        with open(filename, "wb") as file:
+            pickle.dump(out_pkl, file)
+
+
+class StructOptimizer:
+    """Relax crystal structures with FIRE (through the Frechet cell filter) on the device."""
+
+    def __init__(self, model=None, optimizer_class="FIRE", use_device: str | None = None, stress_weight: float = GPA_TO_EV_A3,
+                 on_isolated_atoms: str = "warn") -> None:
+        name = optimizer_class if isinstance(optimizer_class, str) else getattr(optimizer_class, "__name__", None)
+        if name not in OPTIMIZERS:
+            raise ValueError(f"Optimizer instance not found. Select from {list(OPTIMIZERS)}")
+        self.optimizer_class = name
+        if isinstance(model, CHGNetCalculator):
+            self.calculator = model
+        else:
+            self.calculator = CHGNetCalculator(model=model, stress_weight=stress_weight, use_device=use_device,
+                                               on_isolated_atoms=on_isolated_atoms)
+
+    @property
+    def version(self) -> str | None:
+        return self.calculator.model.version
+
+    @property
+    def n_params(self) -> int:
+        return self.calculator.model.n_params
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _params(fmax, steps, relax_cell, ase_filter, fire_kwargs: dict) -> dict:
+        if ase_filter not in FILTERS:
+            raise ValueError(f"Invalid {ase_filter=}, must be one of {list(FILTERS)}. ")
+        unknown = set(fire_kwargs) - set(FIRE_DEFAULTS) - {"downhill_check"}
+        if unknown:
+            raise TypeError(f"FIRE got unexpected keyword argument(s) {sorted(unknown)}")
+        if fire_kwargs.get("downhill_check"):
+            raise ValueError("FIRE(downhill_check=True) is not supported")
+        fire = {k: fire_kwargs.get(k, v) for k, v in FIRE_DEFAULTS.items()}
+        fmax = 0.1 if fmax is None else float(fmax)
+        steps = 500 if steps is None else int(steps)
+        if fmax < 0 or steps < 0:
+            raise ValueError(f"fmax and steps must be non-negative, got {fmax=}, {steps=}")
+        return {"fmax": fmax, "steps": steps, "relax_cell": bool(relax_cell), **fire}
+
+    def _structures(self, atoms) -> list[Structure]:
+        structs = [atoms_to_structure(a) for a in atoms]
+        for s in structs:
+            if not hasattr(s, "frac_coords") or len(s) == 0:
+                raise ValueError("every structure needs at least one site")
+        return structs
+
+    def _check_isolated(self, structures: list) -> None:
+        """Isolated atoms of the initial structures are reported like ``predict_structure`` does (warn / error / ignore), once per structure."""
+        model = self.calculator.model
+        conv = model.graph_converter
+        if conv.on_isolated_atoms == "ignore":
+            return
+        eng = model.engine
+        batch = eng.build_prepared(eng.prepare_structures(structures), conv.atom_graph_cutoff, conv.bond_graph_cutoff)
+        n_iso = batch.packed.n_isolated
+        batch.free()
+        if n_iso:
+            for s in structures:
+                conv(s)
+
+    def _run(self, structures: list, p: dict, frame_every: int | None, verbose: bool):
+        """Relax ``structures`` together: one ``chg_relax`` handle, frames every ``frame_every`` evaluations (None: none)."""
+        model = self.calculator.model
+        eng, conv = model.engine, model.graph_converter
+        prep = eng.prepare_structures(structures)
+        n_at = np.diff(prep.atom_off)
+        params = _lib.RelaxParams(
+            fmax=p["fmax"], max_steps=p["steps"], relax_cell=int(p["relax_cell"]), dt=p["dt"], maxstep=p["maxstep"], dtmax=p["dtmax"],
+            finc=p["finc"], fdec=p["fdec"], astart=p["astart"], fa=p["fa"], nmin=int(p["Nmin"]), exp_cell_factor=0.0,
+            r_atom=conv.atom_graph_cutoff, r_bond=conv.bond_graph_cutoff, numerical_tol=1e-8, stress_weight=self.calculator.stress_weight)
+        host = _lib.StructsHost(prep.n_struct, int(prep.atom_off[-1]), prep.z.ctypes.data_as(_lib.c_int_p),
+                                prep.frac.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                prep.lattice.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), prep.atom_off.ctypes.data_as(_lib.c_int_p))
+        handle = ctypes.c_void_p()
+        eng._check(eng.lib.chg_relax_create(eng.handle, ctypes.byref(host), ctypes.byref(params), ctypes.byref(handle)))
+        B, N = prep.n_struct, int(prep.atom_off[-1])
+        scale = n_at.astype(np.float64) if model.is_intensive else np.ones(B)
+        trajs = [TrajectoryObserver(prep.z[prep.atom_off[i]:prep.atom_off[i + 1]]) for i in range(B)] if frame_every else None
+
+        def download() -> dict:
+            out = {"frac": np.empty((N, 3)), "lattice": np.empty((B, 3, 3)), "e": np.empty(B, np.float32), "f": np.empty((N, 3), np.float32),
+                   "s": np.empty((B, 3, 3), np.float32), "m": np.empty(N, np.float32), "n_steps": np.empty(B, np.int32),
+                   "status": np.empty(B, np.int32)}
+            o = _lib.RelaxOutHost()
+            dp = ctypes.POINTER(ctypes.c_double)
+            o.frac, o.lattice = out["frac"].ctypes.data_as(dp), out["lattice"].ctypes.data_as(dp)
+            for key, name in (("e", "energy"), ("f", "force"), ("s", "stress"), ("m", "magmom")):
+                setattr(o, name, out[key].ctypes.data_as(_lib.c_float_p))
+            o.n_steps, o.status = out["n_steps"].ctypes.data_as(_lib.c_int_p), out["status"].ctypes.data_as(_lib.c_int_p)
+            eng._check(eng.lib.chg_relax_download(eng.handle, handle, ctypes.byref(o)))
+            return out
+
+        def record(d: dict, which) -> None:
+            for i in which:
+                sl = slice(prep.atom_off[i], prep.atom_off[i + 1])
+                trajs[i].append(d["e"][i] * scale[i], d["f"][sl].astype(np.float64), _voigt(d["s"][i].astype(np.float64)) * self.calculator.stress_weight,
+                                d["m"][sl].astype(np.float64), d["frac"][sl] @ d["lattice"][i], d["lattice"][i].copy())
+
+        def log(d: dict, active_before: np.ndarray) -> None:
+            if not verbose:
+                return
+            for i in np.flatnonzero(active_before):
+                sl = slice(prep.atom_off[i], prep.atom_off[i + 1])
+                fmax_now = float(np.sqrt((d["f"][sl].astype(np.float64) ** 2).sum(1).max()))
+                last = d["n_steps"][i] - (1 if d["status"][i] == 0 else 0)
+                print(f"FIRE[{i}]: {last:4d}  E = {d['e'][i] * scale[i]:.6f} eV  max|f| = {fmax_now:.6f} eV/A  {STATUS_NAMES[d['status'][i]]}")
+
+        n_active = ctypes.c_int32(B)
+        try:
+            active = np.ones(B, bool)
+            # the first call evaluates the initial configurations (frame 0); every later call takes `interval` more evaluations
+            interval = frame_every or max(1, p["steps"] + 1)
+            first = True
+            while n_active.value > 0:
+                eng._check(eng.lib.chg_relax_run(eng.handle, handle, 1 if first else interval, ctypes.byref(n_active)))
+                first = False
+                if trajs is not None or verbose:
+                    d = download()
+                    if trajs is not None:
+                        # the evaluation just taken is frame number n_steps (stopped) or n_steps - 1 (still running)
+                        idx = d["n_steps"] - (d["status"] == 0)
+                        record(d, [i for i in np.flatnonzero(active) if idx[i] % frame_every == 0])
+                    log(d, active)
+                    active = d["status"] == 0
+            d = download()
+            if trajs is not None:
+                record(d, range(B))           # the reference calls obs() once more after run()
+        finally:
+            eng.lib.chg_relax_free(eng.handle, handle)
+        return prep, d, scale, trajs
+
+    def _result(self, prep, d, scale, i: int, assign_magmoms: bool) -> dict:
+        sl = slice(prep.atom_off[i], prep.atom_off[i + 1])
+        struct = Structure(Lattice(d["lattice"][i]), prep.z[sl].copy(), d["frac"][sl].copy())
+        if assign_magmoms:
+            struct.add_site_property("magmom", [float(m) for m in d["m"][sl]])
+        return {"final_structure": struct, "energy": float(d["e"][i] * scale[i]), "forces": d["f"][sl].astype(np.float64),
+                "stress": _voigt(d["s"][i].astype(np.float64)) * self.calculator.stress_weight, "magmoms": d["m"][sl].astype(np.float64),
+                "n_steps": int(d["n_steps"][i]), "status": STATUS_NAMES[d["status"][i]], "converged": bool(d["status"][i] == 1)}
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    def relax(self, atoms, *, fmax: float | None = 0.1, steps: int | None = 500, relax_cell: bool | None = True,
+              ase_filter: str | None = "FrechetCellFilter", save_path: str | None = None, loginterval: int | None = 1,
+              crystal_feas_save_path: str | None = None, verbose: bool = True, assign_magmoms: bool = True, **kwargs) -> dict:
+        """Relax one Structure / Atoms until the largest generalized force is below ``fmax`` (reference dynamics.py:246-346).
+        Returns ``{"final_structure", "trajectory"}``."""
+        if crystal_feas_save_path is not None:
+            raise ValueError("crystal_feas_save_path is not supported by the device relaxation")
+        p = self._params(fmax, steps, relax_cell, ase_filter, kwargs)
+        loginterval = 1 if loginterval is None else int(loginterval)
+        if loginterval < 1:
+            raise ValueError(f"{loginterval=} must be positive")
+        structs = self._structures([atoms])
+        self._check_isolated(structs)
+        stream = sys.stdout if verbose else io.StringIO()
+        with contextlib.redirect_stdout(stream):
+            prep, d, scale, trajs = self._run(structs, p, loginterval, verbose)
+        if save_path is not None:
+            trajs[0].save(save_path)
+        res = self._result(prep, d, scale, 0, assign_magmoms)
+        return {"final_structure": res["final_structure"], "trajectory": trajs[0]}
+
+    def relax_batch(self, structures, *, fmax: float | None = 0.1, steps: int | None = 500, relax_cell: bool | None = True,
+                    ase_filter: str | None = "FrechetCellFilter", loginterval: int | None = 1, verbose: bool = False,
+                    assign_magmoms: bool = True, trajectory: bool = False, **kwargs) -> list[dict]:
+        """Relax many structures at once, each an independent optimizer (same result as ``relax`` on it alone).  Returns one
+        dict per structure: ``final_structure``, ``energy`` (eV), ``forces``, ``stress`` (Voigt, eV/A^3), ``magmoms``, ``n_steps``,
+        ``converged``, ``status`` (and ``trajectory`` when asked).  Chunked by atoms like ``predict_structure``; a chunk whose
+        batch does not fit in device memory is split in two and relaxed again."""
+        from chgnet_amd.model import _plan_chunks, _run_splitting  # noqa: PLC0415
+
+        p = self._params(fmax, steps, relax_cell, ase_filter, kwargs)
+        loginterval = 1 if loginterval is None else int(loginterval)
+        if loginterval < 1:
+            raise ValueError(f"{loginterval=} must be positive")
+        structs = self._structures(list(structures))
+        if not structs:
+            return []
+        model = self.calculator.model
+
+        def run(chunk):
+            stream = sys.stdout if verbose else io.StringIO()
+            with contextlib.redirect_stdout(stream):
+                prep, d, scale, trajs = self._run(chunk, p, loginterval if trajectory else None, verbose)
+            out = []
+            for i in range(len(chunk)):
+                r = self._result(prep, d, scale, i, assign_magmoms)
+                if trajectory:
+                    r["trajectory"] = trajs[i]
+                out.append(r)
+            return out
+
+        results = []
+        for a, b in _plan_chunks([len(s) for s in structs], 1, model.min_atoms_per_batch):
+            self._check_isolated(structs[a:b])
+            results.extend(_run_splitting(run, structs[a:b]))
+        return results

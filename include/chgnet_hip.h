@@ -107,9 +107,9 @@ typedef struct chg_out_host {
 } chg_out_host;
 
 /* Version of this interface: bumped whenever a struct of this header grows or an entry point changes meaning (chg_model_desc gained
- * n_mlp_hidden / mlp_out_bias at 2; chg_batch_build_predict arrived at 3).  A binding compiled against another value must refuse the
+ * n_mlp_hidden / mlp_out_bias at 2; chg_batch_build_predict arrived at 3; the chg_relax_* entry points at 4).  A binding compiled against another value must refuse the
  * library: chg_engine_create COPIES *desc, so an older, shorter chg_model_desc would be read past its end. */
-#define CHG_ABI_VERSION 3
+#define CHG_ABI_VERSION 4
 int chg_abi_version(void);
 int chg_device_count(void);
 /* Length in floats of the weight blob for an n_conv-block model (same table as pack.py:weight_layout). */
@@ -234,6 +234,50 @@ int chg_test_rows_gemm(chg_engine* eng, const float* x, const float* wt, const f
  *   mode 1  Y[rows,64] = X[rows,f]  . W     adjoint operands (rows scaled by a power of two), split image of W^T
  *   mode 2 / 3  the same two products from ONE row-major image (forward ds_read_b64, adjoint ds_read_b64_tr_b16) */
 int chg_test_split_gemm(chg_engine* eng, const float* x, const float* w, float* y, int rows, int f, int mode);
+
+/* ---- structure relaxation: FIRE through the Frechet cell filter, every structure an independent optimizer -------------------
+ * Reference: StructOptimizer.relax (chgnet/model/dynamics.py:184-346), ASE FIRE(FrechetCellFilter(atoms)).run(fmax, steps) with ASE's
+ * defaults.  The state of every structure (generalized coordinates u / X, velocity, dt, a, Nsteps, step count, status) lives in HBM
+ * in float64; one step = graph built on the device from the active structures + prediction (chg_batch_build_predict) + one step
+ * kernel (csrc/kernels_relax.h) + one asynchronous copy of the next coordinates.  Structures that have stopped drop out of the next
+ * build.  DESIGN.md "Structure relaxation" states the semantics; tests/relax_ref.py restates them in float64 NumPy. */
+enum { CHG_RELAX_RUNNING = 0, CHG_RELAX_CONVERGED = 1, CHG_RELAX_MAX_STEPS = 2, CHG_RELAX_NONFINITE = 3 };
+typedef struct chg_relax_params {
+  double fmax;                 /* converged: max over rows |g_row|^2 < fmax^2 (cell rows included)                     */
+  int32_t max_steps, relax_cell;
+  double dt, maxstep, dtmax, finc, fdec, astart, fa;   /* ASE FIRE: 0.1, 0.2, 1.0, 1.1, 0.5, 0.1, 0.99                 */
+  int32_t nmin;                /* 5                                                                                     */
+  double exp_cell_factor;      /* <= 0: atoms of each structure                                                        */
+  double r_atom, r_bond, numerical_tol;                /* graph build (6, 3, 1e-8)                                      */
+  double stress_weight;        /* engine stress (GPa) -> eV/A^3; <= 0: 1 / 160.21766208                                  */
+} chg_relax_params;
+typedef struct chg_relax chg_relax;
+/* Frame of the LAST evaluated configuration of every structure (null pointers are skipped).  Units as chg_batch_download. */
+typedef struct chg_relax_out_host {
+  double* frac;        /* [N,3]   fractional coordinates of the evaluated configuration */
+  double* lattice;     /* [B,3,3] rows a,b,c                                            */
+  float* energy;       /* [B]     eV/atom if is_intensive else eV                       */
+  float* force;        /* [N,3]   eV/A                                                   */
+  float* stress;       /* [B,9]   GPa                                                    */
+  float* magmom;       /* [N]     mu_B                                                   */
+  int32_t* n_steps;    /* [B]     optimizer steps taken                                 */
+  int32_t* status;     /* [B]     CHG_RELAX_*                                           */
+} chg_relax_out_host;
+/* Copies the structures and the parameters; no evaluation yet.  CHG_ENOMEM when the state cannot be allocated. */
+int chg_relax_create(chg_engine* eng, const chg_structs_host* host, const chg_relax_params* params, chg_relax** out);
+/* Up to n_steps evaluations, each followed by a step of every structure still running; *n_active = structures still running
+ * (0: done).  A batch whose results are non-finite is evaluated again on the wide-range sweep (as chg_batch_download does); a
+ * structure that is non-finite even there stops as CHG_RELAX_NONFINITE without moving.  CHG_ENOMEM: the batch arena does not fit. */
+int chg_relax_run(chg_engine* eng, chg_relax* relax, int32_t n_steps, int32_t* n_active);
+int chg_relax_download(chg_engine* eng, chg_relax* relax, const chg_relax_out_host* out);
+int chg_relax_free(chg_engine* eng, chg_relax* relax);
+/* Tests only: ONE step kernel on caller-given state and results (like chg_test_rows_gemm), in place.  Layout of the state (structure o
+ * with atoms atom_off[o]..atom_off[o+1]): q, v [N + 3B, 3] (rows of o start at atom_off[o] + 3 o: atom rows u or r, then 3 cell rows X),
+ * sd [B, 24] doubles (L0[9], L0^-1[9], exp_cell_factor, dt, a, 3 spare), si [B, 4] ints (FIRE Nsteps, steps taken, status, spare).
+ * energy [B], force [N,3], stress [B,9] GPa, magmom [N] or null; out: frac_next [N,3], lat_next [B,9] (the moved structures'). */
+int chg_test_relax_step(chg_engine* eng, const chg_relax_params* params, int32_t n_struct, const int32_t* atom_off, double* q, double* v,
+                        double* sd, int32_t* si, const float* energy, const float* force, const float* stress, const float* magmom,
+                        double* frac_next, double* lat_next);
 
 /* ---- exchange steps of the multi-GPU path, straight on RCCL (one communicator per process = per GPU) ----------
  * The reference is single-device; these carry what SURVEY 8e needs and nothing else: the all-gather of per-structure
