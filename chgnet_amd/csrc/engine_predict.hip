@@ -465,13 +465,18 @@ template <bool HIDDEN, bool BWD, int NW = WAVES>
 int launch_angle(chg_engine* eng, const char* label, chg_batch* b, const AngleArgs& a) {
   LaunchScope ls(eng, label);
   AngleArgs plain = a;
+  // The row-order kernel behind the per-atom / TEAM / blocked-tile ones returns at once while win.flag[0] is 1; it may be left out
+  // only when the graph builder itself emitted the index in use (valid by construction).  An index built from the angle rows by the
+  // k_win_* kernels in prepare_windows (device-built batches of more than 8,191 atoms, or builds that did not expect to need it) can
+  // still clear the flag, and then the row-order kernel is what computes the layer.
+  const bool index_from_builder = b->canonical && (b->win_index_ready || b->blk_ready);
   if (!BWD && !HIDDEN && b->win_built && per_atom_forward()) {
     AngleWArgs w{};
     w.a = a; w.w = b->win;
     w.a.image = eng->img_angle[0][a.slot];
     hipLaunchKernelGGL(k_angleupd_fwd_a, dim3(b->win_grid), dim3(BLOCK), angle_fa_lds(), eng->stream, w);
     HIP_TRY(eng, hipGetLastError());
-    if (b->canonical) return CHG_OK;
+    if (index_from_builder) return CHG_OK;
   } else if (BWD && b->blk_cap > 0) {
     // small batch: self-contained blocked tiles (kernels_angle_blk.h; built on the device: the index is valid by construction)
     AngleBlkArgs w{};
@@ -481,7 +486,7 @@ int launch_angle(chg_engine* eng, const char* label, chg_batch* b, const AngleAr
     const int grid = std::max(1, std::min(eng->num_cus, (b->blk_cap + WAVES - 1) / WAVES));
     hipLaunchKernelGGL((k_angle_bwd_blk<HIDDEN>), dim3(grid), dim3(BLOCK), angle_blk_lds<HIDDEN>(), eng->stream, w);
     HIP_TRY(eng, hipGetLastError());
-    if (b->canonical) return CHG_OK;                      // else the row-order kernel below: it returns at once when the flag says 1
+    if (index_from_builder) return CHG_OK;                // else the row-order kernel below: it returns at once when the flag says 1
   } else if (BWD && b->win_team > 0) {
     // MD-size batch: an atom per team of waves (kernels_angle_w.h TEAM); the row-order kernel below returns at once unless the graph
     // turned out not to have the canonical angle structure
@@ -492,7 +497,7 @@ int launch_angle(chg_engine* eng, const char* label, chg_batch* b, const AngleAr
     else
     hipLaunchKernelGGL((k_angle_bwd_w<HIDDEN, true>), dim3(b->win_grid), dim3(BLOCK), angle_w_lds<HIDDEN>(), eng->stream, w);
     HIP_TRY(eng, hipGetLastError());
-    if (b->canonical) return CHG_OK;    // built on the device: the index is valid by construction (a launch less per layer: ~4.5 us each)
+    if (index_from_builder) return CHG_OK;    // a launch less per layer (~4.5 us each)
   } else if (BWD && b->win_built && per_atom_adjoint(HIDDEN)) {
     // per-atom adjoint (kernels_angle_w.h) when the batch has the canonical angle structure, else the row-order one: both are
     // launched, the device flag picks (no host round trip, and a captured hipGraph stays valid across rebuilt graphs)
@@ -503,7 +508,7 @@ int launch_angle(chg_engine* eng, const char* label, chg_batch* b, const AngleAr
     else
     hipLaunchKernelGGL((k_angle_bwd_w<HIDDEN>), dim3(b->win_grid), dim3(BLOCK), angle_w_lds<HIDDEN>(), eng->stream, w);
     HIP_TRY(eng, hipGetLastError());
-    if (b->canonical) return CHG_OK;
+    if (index_from_builder) return CHG_OK;
   } else {
     plain.skip_flag = nullptr;
   }

@@ -134,7 +134,7 @@ __device__ __forceinline__ void scatter_rows64_add_masked(const float* tile, int
 }
 
 // The index of an UPLOADED graph from its centre-major order (WinIndex: q_a .. q_ab2 after k_win_rows, toff4 after k_win_scan2): row -> slot.
-// blk_a was set to -1, the other slot arrays to 0 (memsets).
+// blk_a was set to -1, the other slot arrays to 0 (memsets).  Any row that cannot be placed clears w.flag[0].
 static __global__ void k_blk_from_q(int A, int N, WinIndex w, int* __restrict__ blk_a, int* __restrict__ blk_b1c, int* __restrict__ blk_b2c,
                                     int* __restrict__ blk_ctr, int* __restrict__ blk_desc, int* __restrict__ blk_tiles, int cap_tiles) {
   const int row = blockIdx.x * blockDim.x + threadIdx.x;
@@ -150,7 +150,11 @@ static __global__ void k_blk_from_q(int A, int N, WinIndex w, int* __restrict__ 
   const long tile = (long)w.toff4[c] + (long)(i >> ps) * nq + (jp >> qs);
   if (tile >= cap_tiles) { w.flag[0] = 0; return; }
   const size_t sl = (size_t)tile * 16 + ((i & ((1 << ps) - 1)) << qs) + (jp & ((1 << qs) - 1));
-  blk_a[sl] = w.q_a[row]; blk_b1c[sl] = w.q_b1c[row]; blk_b2c[sl] = w.q_b2c[row]; blk_ctr[sl] = c;
+  // a graph that repeats a (first bond, second bond) pair of an atom (and so misses another) passes every count check above: two
+  // rows would share this slot and the adjoint would see one of them.  The first row claims the slot; a second one marks the graph
+  // non-canonical (the row-order adjoint launched behind the blocked tiles then does the work)
+  if (atomicCAS(blk_a + sl, -1, w.q_a[row]) != -1) { w.flag[0] = 0; return; }
+  blk_b1c[sl] = w.q_b1c[row]; blk_b2c[sl] = w.q_b2c[row]; blk_ctr[sl] = c;
   blk_desc[tile] = ps | (qs << 4) | ((i >> ps << ps) << 8) | ((jp >> qs << qs) << 16);
 }
 
