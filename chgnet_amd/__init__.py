@@ -34,4 +34,8 @@ def __getattr__(name):  # lazy: keeps `import chgnet_amd` free of the HIP librar
         from chgnet_amd import relax
 
         return getattr(relax, name)
+    if name in ("MolecularDynamics", "MDTrajectory"):
+        from chgnet_amd import dynamics
+
+        return getattr(dynamics, name)
     raise AttributeError(name)

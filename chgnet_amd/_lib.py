@@ -26,6 +26,7 @@ EXPORTED_SYMBOLS = (
     "chg_backward_allreduce", "chg_batch_all_gather_energy", "chg_engine_stream", "chg_engine_device",
     "chg_host_alloc", "chg_host_free",
     "chg_relax_create", "chg_relax_run", "chg_relax_download", "chg_relax_free", "chg_test_relax_step",
+    "chg_md_create", "chg_md_run", "chg_md_download", "chg_md_free", "chg_test_md_step",
 )
 
 
@@ -72,6 +73,22 @@ class RelaxOutHost(ctypes.Structure):
                 ("force", c_float_p), ("stress", c_float_p), ("magmom", c_float_p), ("n_steps", c_int_p), ("status", c_int_p)]
 
 
+class MdParams(ctypes.Structure):
+    _fields_ = [("ensemble", ctypes.c_int32), ("fixcm", ctypes.c_int32), ("dt", ctypes.c_double), ("temperature", ctypes.c_double),
+                ("taut", ctypes.c_double), ("taup", ctypes.c_double), ("pressure", ctypes.c_double), ("compressibility", ctypes.c_double),
+                ("kB", ctypes.c_double), ("stress_weight", ctypes.c_double), ("loginterval", ctypes.c_int32), ("ring_frames", ctypes.c_int32),
+                ("log_stress", ctypes.c_int32), ("log_crystal_fea", ctypes.c_int32), ("r_atom", ctypes.c_double), ("r_bond", ctypes.c_double),
+                ("numerical_tol", ctypes.c_double)]
+
+
+class MdOutHost(ctypes.Structure):
+    _dp = ctypes.POINTER(ctypes.c_double)
+    _fields_ = [("positions", _dp), ("momenta", _dp), ("cell", _dp), ("n_steps", c_int_p), ("status", c_int_p),
+                ("frame_capacity", ctypes.c_int32), ("n_frames", c_int_p), ("frame_step", c_int_p), ("frame_scalars", _dp),
+                ("frame_positions", _dp), ("frame_momenta", _dp), ("frame_cell", _dp), ("frame_force", c_float_p),
+                ("frame_stress", c_float_p), ("frame_crystal_fea", c_float_p)]
+
+
 _LIB = None
 
 
@@ -81,7 +98,7 @@ def hip_lib_path() -> str:
     return os.environ.get("CHGNET_HIP_LIB", HIP_LIB)   # override: kernel timing experiments only
 
 
-ABI_VERSION = 4   # include/chgnet_hip.h CHG_ABI_VERSION
+ABI_VERSION = 5   # include/chgnet_hip.h CHG_ABI_VERSION
 
 
 def load() -> ctypes.CDLL:
@@ -174,6 +191,12 @@ def load() -> ctypes.CDLL:
     lib.chg_relax_free.argtypes = [vp, vp]
     lib.chg_test_relax_step.argtypes = [vp, ctypes.POINTER(RelaxParams), ctypes.c_int32, c_int_p, dp, dp, dp, c_int_p, c_float_p, c_float_p,
                                         c_float_p, c_float_p, dp, dp]
+    lib.chg_md_create.argtypes = [vp, ctypes.POINTER(StructsHost), dp, dp, ctypes.POINTER(MdParams), ctypes.POINTER(vp)]
+    lib.chg_md_run.argtypes = [vp, vp, ctypes.c_int32]
+    lib.chg_md_download.argtypes = [vp, vp, ctypes.POINTER(MdOutHost)]
+    lib.chg_md_free.argtypes = [vp, vp]
+    lib.chg_test_md_step.argtypes = [vp, ctypes.POINTER(MdParams), ctypes.c_int32, c_int_p, ctypes.c_int32, dp, dp, dp, dp, dp, c_int_p,
+                                     c_float_p, c_float_p, c_float_p, dp, dp]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is ctypes.c_int and name not in ("chg_device_count", "chg_profile_count"):

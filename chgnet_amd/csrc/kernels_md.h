@@ -1,0 +1,265 @@
+// kernels_md.h -- one molecular-dynamics step kernel for every replica of a batched MD run (chg_md_*).
+//
+// Reference driver replaced (file:line relative to /root/reference/chgnet):
+//   MolecularDynamics: ASE VelocityVerlet / NVTBerendsen / Inhomogeneous_NPTBerendsen / NPTBerendsen   model/dynamics.py:433-780
+// tests/md_ref.py restates the semantics in float64 NumPy; DESIGN.md "Molecular dynamics" gives the state layout.
+//
+// One workgroup (4 waves) per replica.  Thread 0 does the 3x3 algebra (thermostat factor, barostat scaling, cell inverse); all 256
+// threads stream the atom rows with workgroup reductions.  All state is f64 in HBM.  No synchronisation or allocation: the launch
+// can be graph-captured.  What one launch does is chosen by `flags`:
+//   MD_ABSORB  take the evaluation of the configuration written last (energy, forces, stress): non-finite -> retry / NONFINITE.
+//              Phase 0 (a full step's configuration): MD_KICK2 finishes the step with the second half kick; Ekin, T and the
+//              ideal-gas tensor are formed and a frame is written when the frame pointers are set.
+//              Phase 1 (NPT: the barostat's scaled configuration, which ASE evaluates again because set_cell(scale_atoms=True) moved
+//              the atoms): first half kick with these forces, fixcm, drift.
+//   MD_START   start the next step from the cached forces: thermostat lambda, then NPT: barostat scaling, write the scaled
+//              configuration and go to phase 1; NVE / NVT: first half kick, fixcm, drift.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "kernels_relax.h"   // mm3, det3, inv3, wave_sum_f64
+
+namespace chg {
+
+enum : int { MD_RUNNING = 0, MD_NONFINITE = 1 };
+enum : int { MD_NVE = 0, MD_NVT_BERENDSEN = 1, MD_NPT_BERENDSEN_INHOMOGENEOUS = 2, MD_NPT_BERENDSEN = 3 };
+enum : int { MD_ABSORB = 1, MD_KICK2 = 2, MD_START = 4 };
+constexpr int MD_SD = 40;   // doubles per replica: L[9] L^-1[9] Epot Ekin T stress[9] (eV/A^3, no ideal gas) G[9] (sum p p / m) spare
+constexpr int MD_SI = 4;    // ints per replica: steps completed, status, phase, spare
+constexpr int MD_FRAME_SCAL = 3;   // frame scalars per replica: Epot (engine units), Ekin, T
+
+struct MdStepArgs {
+  // state, replica o owns atom rows aoff[o]..aoff[o+1] (the batch has the same numbering: every replica is evaluated every time)
+  double* r;              // [N, 3] cartesian positions
+  double* p;              // [N, 3] momenta
+  double* f;              // [N, 3] forces of the last absorbed evaluation
+  const double* m;        // [N]    masses
+  double* sd;             // [B, MD_SD]
+  int* si;                // [B, MD_SI]
+  const int* aoff;        // [B + 1]
+  // the evaluation (MD_ABSORB)
+  const float* energy;    // [B]
+  const float* force;     // [N, 3]
+  const float* stress;    // [B, 9] GPa or null (task without stress)
+  const float* cfea;      // [B, fea_dim] or null
+  const int* sel;         // [grid] replicas this launch steps (null: all, grid = B)
+  // frame slot (null fr_scal: no frame this launch)
+  double *fr_scal, *fr_pos, *fr_mom, *fr_cell;
+  float *fr_force, *fr_stress, *fr_cfea;
+  // next configuration to evaluate
+  double* frac_next;      // [N, 3]
+  double* lat_next;       // [B, 9]
+  int* retry;             // [B] set to 1 (state untouched) when the evaluation is non-finite and final_try == 0
+  double dt, temperature, taut, taup, pressure, compressibility, kB, stress_weight;
+  int ensemble, fixcm, flags, final_try, fea_dim;
+};
+
+static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int o = a.sel ? a.sel[blockIdx.x] : blockIdx.x;
+  const int a0 = a.aoff[o], n = a.aoff[o + 1] - a0;
+  double* r = a.r + 3 * (size_t)a0;
+  double* p = a.p + 3 * (size_t)a0;
+  double* f = a.f + 3 * (size_t)a0;
+  const double* m = a.m + a0;
+  double* sd = a.sd + (size_t)MD_SD * o;
+  int* si = a.si + (size_t)MD_SI * o;
+  const bool npt = a.ensemble == MD_NPT_BERENDSEN_INHOMOGENEOUS || a.ensemble == MD_NPT_BERENDSEN;
+  const double hdt = 0.5 * a.dt;
+
+  __shared__ double red[4][9];
+  __shared__ int rfin[4];
+  __shared__ double sLinv[9], sM[9], s_lam, s_mean[3];
+  __shared__ int s_status, s_phase, s_go;
+
+  if (tid == 0) { s_status = si[1]; s_phase = si[2]; }
+  __syncthreads();
+  if (s_status != MD_RUNNING) return;   // frozen (NONFINITE): neither moved nor logged again
+  bool advance = false;                 // first half kick, fixcm, drift follow
+
+  if (a.flags & MD_ABSORB) {
+    int fin = 1;
+    for (int i = tid; i < n; i += 256) {
+      const float* fi = a.force + 3 * ((size_t)a0 + i);
+      fin &= isfinite(fi[0]) && isfinite(fi[1]) && isfinite(fi[2]);
+    }
+    fin = __all(fin);
+    if (lane == 0) rfin[wv] = fin;
+    __syncthreads();
+    if (tid == 0) {
+      int ok = rfin[0] & rfin[1] & rfin[2] & rfin[3] & (int)isfinite(a.energy[o]);
+      if (a.stress)
+        for (int i = 0; i < 9; ++i) ok &= (int)isfinite(a.stress[9 * (size_t)o + i]);
+      if (!ok) {
+        if (a.final_try) si[1] = MD_NONFINITE;
+        else a.retry[o] = 1;
+      }
+      s_go = ok;
+    }
+    __syncthreads();
+    if (!s_go) return;
+
+    if (s_phase == 1) {                 // NPT: forces of the scaled configuration
+      for (int i = tid; i < n; i += 256) {
+        const float* fi = a.force + 3 * ((size_t)a0 + i);
+        f[3 * i] = fi[0]; f[3 * i + 1] = fi[1]; f[3 * i + 2] = fi[2];
+      }
+      if (tid == 0) {
+        sd[18] = a.energy[o];
+        if (a.stress)
+          for (int i = 0; i < 9; ++i) sd[21 + i] = (double)a.stress[9 * (size_t)o + i] * a.stress_weight;
+        si[2] = 0;
+        s_lam = 1.0;
+      }
+      advance = true;
+    } else {
+      const bool kick = a.flags & MD_KICK2;
+      const bool frame = a.fr_scal != nullptr;
+      double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // sum p.p / m, then G xx yy zz yz xz xy
+      for (int i = tid; i < n; i += 256) {
+        const float* fi = a.force + 3 * ((size_t)a0 + i);
+        double pi[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          const double fj = fi[j];
+          f[3 * i + j] = fj;
+          pi[j] = kick ? p[3 * i + j] + hdt * fj : p[3 * i + j];
+          p[3 * i + j] = pi[j];
+        }
+        const double im = 1.0 / m[i];
+        acc[1] += pi[0] * pi[0] * im; acc[2] += pi[1] * pi[1] * im; acc[3] += pi[2] * pi[2] * im;
+        acc[4] += pi[1] * pi[2] * im; acc[5] += pi[0] * pi[2] * im; acc[6] += pi[0] * pi[1] * im;
+        if (frame) {
+          const size_t ro = 3 * ((size_t)a0 + i);
+#pragma unroll
+          for (int j = 0; j < 3; ++j) { a.fr_pos[ro + j] = r[3 * i + j]; a.fr_mom[ro + j] = pi[j]; a.fr_force[ro + j] = fi[j]; }
+        }
+      }
+#pragma unroll
+      for (int k = 1; k < 7; ++k) acc[k] = wave_sum_f64(acc[k]);
+      if (lane == 0)
+        for (int k = 1; k < 7; ++k) red[wv][k] = acc[k];
+      __syncthreads();
+      if (tid == 0) {
+        double G[7];
+        for (int k = 1; k < 7; ++k) G[k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
+        const double ekin = 0.5 * (G[1] + G[2] + G[3]);
+        const double T = 2.0 * ekin / (3.0 * n * a.kB);
+        sd[18] = a.energy[o];
+        sd[19] = ekin;
+        sd[20] = T;
+        if (a.stress)
+          for (int i = 0; i < 9; ++i) sd[21 + i] = (double)a.stress[9 * (size_t)o + i] * a.stress_weight;
+        const double Gm[9] = {G[1], G[6], G[5], G[6], G[2], G[4], G[5], G[4], G[3]};
+        for (int i = 0; i < 9; ++i) sd[30 + i] = Gm[i];
+        if (kick) si[0] += 1;
+        if (frame) {
+          a.fr_scal[MD_FRAME_SCAL * (size_t)o] = a.energy[o];
+          a.fr_scal[MD_FRAME_SCAL * (size_t)o + 1] = ekin;
+          a.fr_scal[MD_FRAME_SCAL * (size_t)o + 2] = T;
+          for (int i = 0; i < 9; ++i) a.fr_cell[9 * (size_t)o + i] = sd[i];
+          for (int i = 0; i < 9; ++i) a.fr_stress[9 * (size_t)o + i] = a.stress ? a.stress[9 * (size_t)o + i] : 0.0f;
+          if (a.cfea && a.fr_cfea)
+            for (int i = 0; i < a.fea_dim; ++i) a.fr_cfea[(size_t)a.fea_dim * o + i] = a.cfea[(size_t)a.fea_dim * o + i];
+        }
+      }
+    }
+  }
+
+  if ((a.flags & MD_START) && !advance) {
+    // thermostat (ASE NVTBerendsen.scale_velocities) and barostat (NPTBerendsen / Inhomogeneous_NPTBerendsen.scale_positions_and_cell)
+    __syncthreads();   // sd written by thread 0 above
+    if (tid == 0) {
+      double lam = 1.0;
+      if (a.ensemble != MD_NVE) {
+        const double T = sd[20];
+        const double ratio = T > 0.0 ? a.temperature / T : (a.temperature > 0.0 ? (double)INFINITY : 1.0);
+        lam = sqrt(1.0 + (ratio - 1.0) * (a.dt / a.taut));
+        if (lam > 1.1) lam = 1.1;
+        if (lam < 0.9) lam = 0.9;
+      }
+      s_lam = lam;
+      if (npt) {
+        double L[9], Ln[9], M[9], st[9];
+        for (int i = 0; i < 9; ++i) L[i] = sd[i];
+        const double iv = 1.0 / fabs(det3(L));
+        for (int i = 0; i < 9; ++i) st[i] = sd[21 + i] - lam * lam * sd[30 + i] * iv;   // stress incl. the ideal-gas term
+        double sc[3];
+        if (a.ensemble == MD_NPT_BERENDSEN_INHOMOGENEOUS) {
+          const double taupscl = a.dt * a.compressibility / a.taup / 3.0;
+          for (int i = 0; i < 3; ++i) sc[i] = 1.0 - taupscl * (a.pressure - (-st[4 * i]));
+        } else {
+          const double taupscl = a.dt / a.taup;
+          const double old_p = -(st[0] + st[4] + st[8]) / 3.0;
+          sc[0] = sc[1] = sc[2] = 1.0 - taupscl * a.compressibility / 3.0 * (a.pressure - old_p);
+        }
+        for (int i = 0; i < 3; ++i)
+          for (int j = 0; j < 3; ++j) Ln[3 * i + j] = sc[i] * L[3 * i + j];
+        mm3(sd + 9, Ln, M);            // positions <- positions . solve(L, L')
+        for (int i = 0; i < 9; ++i) { sM[i] = M[i]; sd[i] = Ln[i]; }
+        inv3(Ln, sd + 9);
+        for (int i = 0; i < 9; ++i) { sLinv[i] = sd[9 + i]; a.lat_next[9 * (size_t)o + i] = Ln[i]; }
+        si[2] = 1;
+      }
+    }
+    __syncthreads();
+    const double lam = s_lam;
+    for (int i = tid; i < n; i += 256) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) p[3 * i + j] *= lam;
+      if (npt) {
+        const double x0 = r[3 * i], x1 = r[3 * i + 1], x2 = r[3 * i + 2];
+        double* fr = a.frac_next + 3 * ((size_t)a0 + i);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) r[3 * i + j] = x0 * sM[j] + x1 * sM[3 + j] + x2 * sM[6 + j];
+        const double y0 = r[3 * i], y1 = r[3 * i + 1], y2 = r[3 * i + 2];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) fr[j] = y0 * sLinv[j] + y1 * sLinv[3 + j] + y2 * sLinv[6 + j];
+      }
+    }
+    if (npt) return;                    // the scaled configuration is evaluated before the half kick
+    advance = true;
+  }
+  if (!advance) return;
+
+  // first half kick with the cached forces, fixcm (mean momentum, not mass-weighted), drift r += dt p / m
+  __syncthreads();
+  double ps[3] = {0.0, 0.0, 0.0};
+  for (int i = tid; i < n; i += 256)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double pj = p[3 * i + j] + hdt * f[3 * i + j];
+      p[3 * i + j] = pj;
+      ps[j] += pj;
+    }
+  if (a.fixcm) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) ps[j] = wave_sum_f64(ps[j]);
+    if (lane == 0)
+      for (int j = 0; j < 3; ++j) red[wv][j] = ps[j];
+  }
+  if (tid == 0)
+    for (int i = 0; i < 9; ++i) sLinv[i] = sd[9 + i];
+  __syncthreads();
+  if (tid == 0) {
+    for (int j = 0; j < 3; ++j) s_mean[j] = a.fixcm ? (red[0][j] + red[1][j] + red[2][j] + red[3][j]) / (double)n : 0.0;
+    for (int i = 0; i < 9; ++i) a.lat_next[9 * (size_t)o + i] = sd[i];
+  }
+  __syncthreads();
+  for (int i = tid; i < n; i += 256) {
+    const double mi = m[i];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double pj = a.fixcm ? p[3 * i + j] - s_mean[j] : p[3 * i + j];
+      p[3 * i + j] = pj;
+      r[3 * i + j] += a.dt * pj / mi;
+    }
+    const double y0 = r[3 * i], y1 = r[3 * i + 1], y2 = r[3 * i + 2];
+    double* fr = a.frac_next + 3 * ((size_t)a0 + i);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) fr[j] = y0 * sLinv[j] + y1 * sLinv[3 + j] + y2 * sLinv[6 + j];
+  }
+}
+
+}  // namespace chg

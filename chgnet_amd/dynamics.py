@@ -1,0 +1,409 @@
+"""``MolecularDynamics`` -- batched molecular dynamics on the device (reference chgnet/model/dynamics.py:433-780).
+
+The reference drives MD through ASE (VelocityVerlet, NVTBerendsen, Inhomogeneous_NPTBerendsen, NPTBerendsen) with
+``CHGNetCalculator`` evaluating every step.  ASE is absent offline, and one host round trip per step leaves the engine idle.  Here
+the integrator runs behind the C-ABI (``chg_md_*``, include/chgnet_hip.h): every replica's float64 state (positions, momenta,
+masses, cell) stays in HBM, and one step kernel (csrc/kernels_md.h) advances all replicas after each device graph build and
+prediction.  ``run_batch`` runs replicas of different sizes as one handle; each gets the trajectory it would get alone.
+tests/md_ref.py restates the semantics in float64 NumPy.
+
+Out of scope, refused with ``ValueError``: the Nose-Hoover thermostat (ASE ``NPT``), and NPT without ``bulk_modulus`` (the
+reference then fits an equation of state).  Deviations from the reference:
+  - ``starting_temperature`` draws from a seeded numpy ``Generator`` (``seed``), not ASE's global RNG: same distribution,
+    different draws;
+  - a replica whose energy or forces are non-finite even on the engine's wide-range sweep stops with status ``NONFINITE`` and
+    its state untouched (ASE carries the NaN on);
+  - there is no ASE ``.traj`` writer: ``trajectory`` names a pickle with ``TrajectoryObserver``'s keys plus ``momenta`` and
+    ``temperature``; ``magmoms`` stay empty (the step evaluates energy and forces, plus stress for NPT).
+"""
+
+from __future__ import annotations
+
+import ctypes
+import pickle
+import sys
+
+import numpy as np
+
+from chgnet_amd import _lib
+from chgnet_amd.calculator import CHGNetCalculator, atoms_to_structure
+from chgnet_amd.graph.structure import Lattice, Structure
+
+# ase.units (CODATA 2014)
+_E, _AMU, _KB_J = 1.6021766208e-19, 1.660539040e-27, 1.38064852e-23
+FS = 1e-15 * (1e10 * np.sqrt(_E / _AMU))   # units.fs = 1e-15 * second
+KB = _KB_J / _E                             # units.kB, eV/K
+GPA = 1e9 * ((1 / _E) / 1e30)               # units.GPa = 1e9 * Pascal, eV/A^3
+
+ENSEMBLE_CODES = {"nve": 0, "nvt": 1, "npt_inhomogeneous": 2, "npt_berendsen": 3}
+STATUS_NAMES = ("RUNNING", "NONFINITE")
+
+# ase.data.atomic_masses (IUPAC 2016 standard atomic weights), Z = 0..94
+ATOMIC_MASSES = np.array([
+    1.0, 1.008, 4.002602, 6.94, 9.0121831, 10.81, 12.011, 14.007, 15.999, 18.998403163, 20.1797, 22.98976928, 24.305, 26.9815385,
+    28.085, 30.973761998, 32.06, 35.45, 39.948, 39.0983, 40.078, 44.955908, 47.867, 50.9415, 51.9961, 54.938044, 55.845, 58.933194,
+    58.6934, 63.546, 65.38, 69.723, 72.630, 74.921595, 78.971, 79.904, 83.798, 85.4678, 87.62, 88.90584, 91.224, 92.90637, 95.95,
+    97.90721, 101.07, 102.90550, 106.42, 107.8682, 112.414, 114.818, 118.710, 121.760, 127.60, 126.90447, 131.293, 132.90545196,
+    137.327, 138.90547, 140.116, 140.90766, 144.242, 144.91276, 150.36, 151.964, 157.25, 158.92535, 162.500, 164.93033, 167.259,
+    168.93422, 173.054, 174.9668, 178.49, 180.94788, 183.84, 186.207, 190.23, 192.217, 195.084, 196.966569, 200.592, 204.38,
+    207.2, 208.98040, 208.98243, 209.98715, 222.01758, 223.01974, 226.02541, 227.02775, 232.0377, 231.03588, 238.02891,
+    237.04817, 244.06421])
+
+
+def _voigt(s: np.ndarray) -> np.ndarray:
+    return np.array([s[0, 0], s[1, 1], s[2, 2], s[1, 2], s[0, 2], s[0, 1]])
+
+
+def maxwell_boltzmann(masses: np.ndarray, temperature_k: float, rng: np.random.Generator) -> np.ndarray:
+    """ASE MaxwellBoltzmannDistribution(force_temp=True) then Stationary (mass-weighted, temperature preserved): momenta [n, 3]."""
+    masses = np.asarray(masses, np.float64)
+    kt = KB * temperature_k
+    p = rng.standard_normal((len(masses), 3)) * np.sqrt(masses * kt)[:, None]
+
+    def force_temperature(p, target_kt):
+        cur = float(np.vdot(p, p / masses[:, None])) / (3 * len(masses))
+        return p * np.sqrt(target_kt / cur) if cur > 0 else p
+
+    p = force_temperature(p, kt)
+    t0_kt = float(np.vdot(p, p / masses[:, None])) / (3 * len(masses))
+    p = p - (p.sum(0) / masses.sum()) * masses[:, None]
+    return force_temperature(p, t0_kt)
+
+
+class MDTrajectory:
+    """Frames of one replica, every ``loginterval`` steps from step 0: potential energy (eV), forces (eV/A), stress (Voigt, eV/A^3,
+    when evaluated), cartesian positions, cells, momenta and temperature (K)."""
+
+    def __init__(self, atomic_numbers) -> None:
+        self.atomic_numbers = np.asarray(atomic_numbers)
+        self.steps: list[int] = []
+        self.energies: list[float] = []
+        self.kinetic_energies: list[float] = []
+        self.forces: list[np.ndarray] = []
+        self.stresses: list[np.ndarray] = []
+        self.magmoms: list[np.ndarray] = []
+        self.atom_positions: list[np.ndarray] = []
+        self.cells: list[np.ndarray] = []
+        self.momenta: list[np.ndarray] = []
+        self.temperatures: list[float] = []
+        self.crystal_feas: list[np.ndarray] = []
+
+    def __len__(self) -> int:
+        return len(self.energies)
+
+    def save(self, filename: str) -> None:
+        """Pickle with TrajectoryObserver's keys (reference dynamics.py:389-405) plus momenta and temperature."""
+        out_pkl = {"energy": self.energies, "forces": self.forces, "stresses": self.stresses, "magmoms": self.magmoms,
+                   "atom_positions": self.atom_positions, "cell": self.cells, "atomic_number": self.atomic_numbers,
+                   "momenta": self.momenta, "temperature": self.temperatures}
+        with open(filename, "wb") as file:
+            pickle.dump(out_pkl, file)
+
+
+class MDLogger:
+    """ASE MDLogger's text format (header, then time in ps, Etot, Epot, Ekin in eV and T in K per logged step)."""
+
+    def __init__(self, logfile: str, natoms: int) -> None:
+        self.logfile = logfile
+        digits = 4 if natoms <= 100 else 3 if natoms <= 1000 else 2
+        self.hdr = "%-9s " % ("Time[ps]",) + "%12s %12s %12s  %6s" % ("Etot[eV]", "Epot[eV]", "Ekin[eV]", "T[K]")
+        self.fmt = "%-10.4f " + 3 * ("%%12.%df " % (digits,)) + " %6.1f\n"
+        self._write(self.hdr + "\n")
+
+    def _write(self, text: str) -> None:
+        if self.logfile == "-":
+            sys.stdout.write(text)
+            return
+        with open(self.logfile, "a") as fh:
+            fh.write(text)
+
+    def rows(self, times_ps, epot, ekin, temp) -> None:
+        self._write("".join(self.fmt % (t, e + k, e, k, tt) for t, e, k, tt in zip(times_ps, epot, ekin, temp)))
+
+
+def _resolve(ensemble: str, thermostat: str, bulk_modulus) -> str:
+    """Reference dynamics.py:598-760 -> the integrator name used here; out-of-scope choices raise ValueError."""
+    ens = ensemble.lower()
+    th = thermostat.lower()
+    if ens == "nve":
+        return "nve"
+    if ens not in ("nvt", "npt"):
+        raise ValueError(f"Ensemble {ensemble!r} not supported, choose in 'nve', 'nvt', 'npt'")
+    if th == "nose-hoover":
+        raise ValueError("thermostat='Nose-Hoover' (ASE NPT, upper-triangular cells) is not supported by the device MD; "
+                         "use 'Berendsen_inhomogeneous', 'Berendsen' (NVT) or 'npt_berendsen' (NPT)")
+    if ens == "nvt":
+        if th.startswith("berendsen"):
+            return "nvt"
+        raise ValueError("Thermostat not supported, choose in 'Nose-Hoover', 'Berendsen', 'Berendsen_inhomogeneous'")
+    if bulk_modulus is None:
+        raise ValueError("NPT without bulk_modulus is not supported by the device MD (the reference fits an equation of state "
+                         "there); pass bulk_modulus in GPa")
+    if th == "berendsen_inhomogeneous":
+        return "npt_inhomogeneous"
+    if th == "npt_berendsen":
+        return "npt_berendsen"
+    raise ValueError("Thermostat not supported, choose in 'Nose-Hoover', 'Berendsen', 'Berendsen_inhomogeneous'")
+
+
+class _DeviceRun:
+    """One ``chg_md`` handle over R replicas; ``run`` returns the frames drained from the device ring."""
+
+    RING = 32
+
+    def __init__(self, calc: CHGNetCalculator, structures: list, masses: np.ndarray, momenta: np.ndarray, kind: str, cfg: dict) -> None:
+        model = calc.model
+        self.eng, self.model, self.calc = model.engine, model, calc
+        conv = model.graph_converter
+        self.prep = prep = self.eng.prepare_structures(structures)
+        self.B, self.N = prep.n_struct, int(prep.atom_off[-1])
+        self.n_at = np.diff(prep.atom_off)
+        self.loginterval = int(cfg["loginterval"])
+        self.cfea = bool(cfg["crystal_fea"])
+        self.stress = kind.startswith("npt") or bool(cfg["log_stress"])
+        self.masses = np.ascontiguousarray(masses, np.float64)
+        mom = np.ascontiguousarray(momenta, np.float64)
+        params = _lib.MdParams(ensemble=ENSEMBLE_CODES[kind], fixcm=1, dt=cfg["dt"], temperature=cfg["temperature"], taut=cfg["taut"],
+                               taup=cfg["taup"], pressure=cfg["pressure"], compressibility=cfg["compressibility"], kB=KB,
+                               stress_weight=calc.stress_weight, loginterval=self.loginterval, ring_frames=self.RING,
+                               log_stress=int(self.stress), log_crystal_fea=int(self.cfea), r_atom=conv.atom_graph_cutoff,
+                               r_bond=conv.bond_graph_cutoff, numerical_tol=1e-8)
+        dp = ctypes.POINTER(ctypes.c_double)
+        host = _lib.StructsHost(self.B, self.N, prep.z.ctypes.data_as(_lib.c_int_p), prep.frac.ctypes.data_as(dp),
+                                prep.lattice.ctypes.data_as(dp), prep.atom_off.ctypes.data_as(_lib.c_int_p))
+        self.handle = ctypes.c_void_p()
+        self.eng._check(self.eng.lib.chg_md_create(self.eng.handle, ctypes.byref(host), self.masses.ctypes.data_as(dp), mom.ctypes.data_as(dp),
+                                                   ctypes.byref(params), ctypes.byref(self.handle)))
+        self.started = False
+        self.step = 0
+
+    def free(self) -> None:
+        if self.handle:
+            self.eng.lib.chg_md_free(self.eng.handle, self.handle)
+            self.handle = ctypes.c_void_p()
+
+    def _download(self) -> dict:
+        B, N, K = self.B, self.N, self.RING
+        d = {"positions": np.empty((N, 3)), "momenta": np.empty((N, 3)), "cell": np.empty((B, 3, 3)), "n_steps": np.empty(B, np.int32),
+             "status": np.empty(B, np.int32), "n_frames": np.zeros(1, np.int32), "frame_step": np.empty(K, np.int32),
+             "frame_scalars": np.empty((K, B, 3)), "frame_positions": np.empty((K, N, 3)), "frame_momenta": np.empty((K, N, 3)),
+             "frame_cell": np.empty((K, B, 3, 3)), "frame_force": np.empty((K, N, 3), np.float32), "frame_stress": np.empty((K, B, 3, 3), np.float32),
+             "frame_crystal_fea": np.empty((K, B, 64), np.float32)}
+        o = _lib.MdOutHost()
+        dp = ctypes.POINTER(ctypes.c_double)
+        for k, v in d.items():
+            ptype = dp if v.dtype == np.float64 else _lib.c_float_p if v.dtype == np.float32 else _lib.c_int_p
+            setattr(o, k, v.ctypes.data_as(ptype))
+        o.frame_capacity = K
+        self.eng._check(self.eng.lib.chg_md_download(self.eng.handle, self.handle, ctypes.byref(o)))
+        return d
+
+    def run(self, steps: int, sink) -> dict:
+        """``steps`` more steps in chunks whose frames fit the ring; every drained frame goes to ``sink(d, k)``.  Returns the final state."""
+        li = self.loginterval
+        left = int(steps)
+        while True:
+            chunk = min(left, li * (self.RING - 1))
+            self.eng._check(self.eng.lib.chg_md_run(self.eng.handle, self.handle, chunk))
+            self.started = True
+            self.step += chunk
+            left -= chunk
+            d = self._download()
+            for k in range(int(d["n_frames"][0])):
+                sink(d, k)
+            if left <= 0:
+                return d
+
+
+class MolecularDynamics:
+    """Molecular dynamics on the device (reference MolecularDynamics: same arguments and defaults, plus ``seed``)."""
+
+    def __init__(self, atoms, *, model=None, ensemble: str = "nvt", thermostat: str = "Berendsen_inhomogeneous", temperature: float = 300,
+                 starting_temperature: float | None = None, timestep: float = 2.0, pressure: float = 1.01325e-4, taut: float | None = None,
+                 taup: float | None = None, bulk_modulus: float | None = None, trajectory: str | None = None, logfile: str | None = None,
+                 loginterval: int = 1, crystal_feas_logfile: str | None = None, append_trajectory: bool = False,  # noqa: ARG002
+                 on_isolated_atoms: str = "warn", return_site_energies: bool = False, use_device: str | None = None,
+                 seed: int | None = None) -> None:
+        self.ensemble, self.thermostat = ensemble, thermostat
+        self.kind = _resolve(ensemble, thermostat, bulk_modulus)
+        if int(loginterval) < 1:
+            raise ValueError(f"{loginterval=} must be positive")
+        if not timestep > 0:
+            raise ValueError(f"{timestep=} must be positive")
+        if isinstance(model, CHGNetCalculator):
+            self.calculator = model
+        else:
+            self.calculator = CHGNetCalculator(model=model, use_device=use_device, on_isolated_atoms=on_isolated_atoms,
+                                               return_site_energies=return_site_energies)
+        taut = 100 * timestep if taut is None else taut
+        taup = 1000 * timestep if taup is None else taup
+        self.bulk_modulus = bulk_modulus
+        compressibility = 0.0 if bulk_modulus is None else 1.0 / (bulk_modulus / 160.2176)
+        self.cfg = {"dt": timestep * FS, "temperature": float(temperature), "taut": taut * FS, "taup": taup * FS, "pressure": pressure * GPA,
+                    "compressibility": compressibility, "loginterval": int(loginterval), "crystal_fea": crystal_feas_logfile is not None,
+                    "log_stress": False}
+        self.trajectory, self.logfile, self.loginterval, self.timestep = trajectory, logfile, int(loginterval), timestep
+        self.crystal_feas_logfile = crystal_feas_logfile
+        self.starting_temperature, self.seed = starting_temperature, seed
+        self._run: _DeviceRun | None = None
+        self.traj: MDTrajectory | None = None
+        self._logger: MDLogger | None = None
+        self.set_atoms(atoms)
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _initial(atoms, starting_temperature, rng):
+        structure = atoms_to_structure(atoms)
+        if not hasattr(structure, "frac_coords") or len(structure) == 0:
+            raise ValueError("the structure needs at least one site")
+        if hasattr(atoms, "get_masses"):
+            masses = np.asarray(atoms.get_masses(), np.float64)
+        else:
+            masses = ATOMIC_MASSES[np.asarray(structure.atomic_numbers)]
+        if starting_temperature is not None:
+            momenta = maxwell_boltzmann(masses, float(starting_temperature), rng)
+        elif hasattr(atoms, "get_momenta"):
+            momenta = np.asarray(atoms.get_momenta(), np.float64)
+        else:
+            momenta = np.zeros((len(structure), 3))      # a Structure starts at 0 K (reference docstring)
+        return structure, masses, momenta
+
+    def set_atoms(self, atoms) -> None:
+        """New atoms for the next ``run`` (the calculator and the integrator settings stay)."""
+        self.close()
+        rng = np.random.default_rng(self.seed)
+        self._structure, self._masses, self._momenta = self._initial(atoms, self.starting_temperature, rng)
+        self._step_offset = getattr(self, "nsteps", 0)
+        self.nsteps = self._step_offset
+        self.traj = MDTrajectory(self._structure.atomic_numbers)
+        self._cfeas: list[np.ndarray] = []
+
+    @property
+    def atoms(self) -> Structure:
+        """The current configuration as a ``Structure`` (unwrapped fractional coordinates)."""
+        return self._structure
+
+    @property
+    def momenta(self) -> np.ndarray:
+        return self._momenta
+
+    def close(self) -> None:
+        if getattr(self, "_run", None) is not None:
+            self._run.free()
+            self._run = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001, S110
+            pass
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    def _sinks(self, run: _DeviceRun, trajs: list[MDTrajectory], cfeas: list[list], step_offset: int):
+        scale = run.n_at.astype(np.float64) if run.model.is_intensive else np.ones(run.B)
+        sw = self.calculator.stress_weight
+        pending = {"t": [], "e": [], "k": [], "T": []}
+
+        def sink(d, k):
+            step = int(d["frame_step"][k])
+            for i in range(run.B):
+                if d["status"][i] != 0 and step > d["n_steps"][i]:
+                    continue                     # NONFINITE replica: no frames after it stopped
+                sl = slice(run.prep.atom_off[i], run.prep.atom_off[i + 1])
+                tr = trajs[i]
+                e = float(d["frame_scalars"][k, i, 0] * scale[i])
+                tr.steps.append(step + step_offset)
+                tr.energies.append(e)
+                tr.kinetic_energies.append(float(d["frame_scalars"][k, i, 1]))
+                tr.temperatures.append(float(d["frame_scalars"][k, i, 2]))
+                tr.forces.append(d["frame_force"][k, sl].astype(np.float64))
+                if run.stress:
+                    tr.stresses.append(_voigt(d["frame_stress"][k, i].astype(np.float64)) * sw)
+                tr.atom_positions.append(d["frame_positions"][k, sl].copy())
+                tr.momenta.append(d["frame_momenta"][k, sl].copy())
+                tr.cells.append(d["frame_cell"][k, i].copy())
+                if run.cfea:
+                    cfeas[i].append(d["frame_crystal_fea"][k, i].copy())
+                if i == 0:
+                    pending["t"].append((step + step_offset) * self.cfg["dt"] / (1000 * FS))
+                    pending["e"].append(e)
+                    pending["k"].append(tr.kinetic_energies[-1])
+                    pending["T"].append(tr.temperatures[-1])
+        return sink, pending
+
+    def run(self, steps: int) -> MDTrajectory:
+        """``steps`` MD steps (reference: ``self.dyn.run(steps)``).  Frames every ``loginterval`` steps (step 0 on the first call)
+        go to the in-memory trajectory, ``logfile``, ``trajectory`` and ``crystal_feas_logfile``; returns the trajectory."""
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError(f"{steps=} must be >= 0")
+        if self._run is None:
+            conv = self.calculator.model.graph_converter
+            if conv.on_isolated_atoms != "ignore":     # isolated atoms are reported like predict_structure does
+                conv(self._structure)
+            self._run = _DeviceRun(self.calculator, [self._structure], self._masses, self._momenta, self.kind, self.cfg)
+            if self.logfile is not None and self._logger is None:
+                self._logger = MDLogger(self.logfile, len(self._structure))
+        run = self._run
+        sink, pending = self._sinks(run, [self.traj], [self._cfeas], self._step_offset)
+        d = run.run(steps, sink)
+        if self._logger is not None and pending["t"]:
+            self._logger.rows(pending["t"], pending["e"], pending["k"], pending["T"])
+        self._update_state(d)
+        self.nsteps = self._step_offset + run.step
+        if d["status"][0] != 0:
+            print(f"MolecularDynamics: the run stopped at step {int(d['n_steps'][0])}: non-finite energy or forces")
+        if self.trajectory is not None:
+            self.traj.save(self.trajectory)
+        if self.crystal_feas_logfile:
+            with open(self.crystal_feas_logfile, "wb") as file:
+                pickle.dump({"crystal_feas": self._cfeas}, file)
+        return self.traj
+
+    def _update_state(self, d: dict) -> None:
+        lat = d["cell"][0]
+        self._structure = Structure(Lattice(lat), self._structure.atomic_numbers, d["positions"] @ np.linalg.inv(lat))
+        self._momenta = d["momenta"].copy()
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    @classmethod
+    def run_batch(cls, structures, steps: int, *, seeds=None, model=None, **kwargs) -> list[dict]:
+        """Run R independent replicas (possibly of different sizes) as one device handle: each gets the trajectory it would get
+        alone with ``MolecularDynamics(structures[i], seed=seeds[i], **kwargs).run(steps)``.  Returns, per replica, ``{"trajectory",
+        "final_structure", "momenta", "status", "n_steps"}``.  ``trajectory`` / ``logfile`` / ``crystal_feas_logfile`` are not
+        written here."""
+        structures = list(structures)
+        if not structures:
+            return []
+        seeds = [None] * len(structures) if seeds is None else list(seeds)
+        if len(seeds) != len(structures):
+            raise ValueError("one seed per structure")
+        for k in ("trajectory", "logfile", "crystal_feas_logfile"):
+            if kwargs.get(k) is not None:
+                raise ValueError(f"run_batch does not write {k}: save each returned trajectory instead")
+        md, calc = [], model
+        for s, sd in zip(structures, seeds):      # one calculator for all replicas
+            md.append(cls(s, model=calc, seed=sd, **kwargs))
+            calc = md[-1].calculator
+        first = md[0]
+        structs = [m._structure for m in md]
+        conv = first.calculator.model.graph_converter
+        if conv.on_isolated_atoms != "ignore":
+            for s in structs:
+                conv(s)
+        run = _DeviceRun(first.calculator, structs, np.concatenate([m._masses for m in md]), np.concatenate([m._momenta for m in md]),
+                         first.kind, first.cfg)
+        try:
+            trajs = [m.traj for m in md]
+            sink, _ = first._sinks(run, trajs, [m._cfeas for m in md], 0)
+            d = run.run(int(steps), sink)
+        finally:
+            run.free()
+        out = []
+        for i, tr in enumerate(trajs):
+            sl = slice(run.prep.atom_off[i], run.prep.atom_off[i + 1])
+            lat = d["cell"][i]
+            fin = Structure(Lattice(lat), structs[i].atomic_numbers, d["positions"][sl] @ np.linalg.inv(lat))
+            out.append({"trajectory": tr, "final_structure": fin, "momenta": d["momenta"][sl].copy(),
+                        "status": STATUS_NAMES[d["status"][i]], "n_steps": int(d["n_steps"][i])})
+        return out

@@ -107,9 +107,9 @@ typedef struct chg_out_host {
 } chg_out_host;
 
 /* Version of this interface: bumped whenever a struct of this header grows or an entry point changes meaning (chg_model_desc gained
- * n_mlp_hidden / mlp_out_bias at 2; chg_batch_build_predict arrived at 3; the chg_relax_* entry points at 4).  A binding compiled against another value must refuse the
+ * n_mlp_hidden / mlp_out_bias at 2; chg_batch_build_predict arrived at 3; the chg_relax_* entry points at 4; the chg_md_* entry points at 5).  A binding compiled against another value must refuse the
  * library: chg_engine_create COPIES *desc, so an older, shorter chg_model_desc would be read past its end. */
-#define CHG_ABI_VERSION 4
+#define CHG_ABI_VERSION 5
 int chg_abi_version(void);
 int chg_device_count(void);
 /* Length in floats of the weight blob for an n_conv-block model (same table as pack.py:weight_layout). */
@@ -278,6 +278,68 @@ int chg_relax_free(chg_engine* eng, chg_relax* relax);
 int chg_test_relax_step(chg_engine* eng, const chg_relax_params* params, int32_t n_struct, const int32_t* atom_off, double* q, double* v,
                         double* sd, int32_t* si, const float* energy, const float* force, const float* stress, const float* magmom,
                         double* frac_next, double* lat_next);
+
+/* ---- molecular dynamics: NVE, NVT Berendsen, NPT Berendsen, every structure an independent replica ---------------------------
+ * Reference: MolecularDynamics (chgnet/model/dynamics.py:433-780) with ASE VelocityVerlet, NVTBerendsen, Inhomogeneous_NPTBerendsen and
+ * NPTBerendsen.  The state of every replica (cartesian positions, momenta, masses, cached forces, cell and its inverse, step count,
+ * status) lives in HBM in float64; one evaluation = graph built on the device from all replicas + prediction (chg_batch_build_predict,
+ * task ef, efs for NPT or logged stress) + one step kernel (csrc/kernels_md.h) + one asynchronous copy of the next coordinates.  NPT
+ * takes two evaluations per step, as ASE does (the barostat moves the atoms before the first half kick).  Units are ASE's: eV, A,
+ * amu, time in A sqrt(amu / eV).  DESIGN.md "Molecular dynamics" states the semantics; tests/md_ref.py restates them in NumPy. */
+enum { CHG_MD_NVE = 0, CHG_MD_NVT_BERENDSEN = 1, CHG_MD_NPT_BERENDSEN_INHOMOGENEOUS = 2, CHG_MD_NPT_BERENDSEN = 3 };
+enum { CHG_MD_RUNNING = 0, CHG_MD_NONFINITE = 1 };
+typedef struct chg_md_params {
+  int32_t ensemble;            /* CHG_MD_*                                                                                 */
+  int32_t fixcm;               /* NVT / NPT: subtract the mean momentum after the first half kick (ASE fixcm=True)         */
+  double dt;                   /* time step, ASE time units                                                                */
+  double temperature;          /* K (NVT / NPT)                                                                            */
+  double taut, taup;           /* ASE time units                                                                           */
+  double pressure;             /* eV/A^3 (NPT)                                                                             */
+  double compressibility;      /* A^3/eV (NPT)                                                                             */
+  double kB;                   /* eV/K; <= 0: 8.6173303e-5 (CODATA 2014, ASE units.kB)                                      */
+  double stress_weight;        /* engine stress (GPa) -> eV/A^3; <= 0: 1 / 160.21766208                                    */
+  int32_t loginterval;         /* a frame every loginterval steps, step 0 included; 0: no frames                           */
+  int32_t ring_frames;         /* frames the device ring holds between two chg_md_download calls                          */
+  int32_t log_stress;          /* evaluate the stress every step (task efs) even without NPT: frames then carry it        */
+  int32_t log_crystal_fea;     /* frames carry crystal_fea [64]                                                            */
+  double r_atom, r_bond, numerical_tol;                /* graph build (6, 3, 1e-8)                                          */
+} chg_md_params;
+typedef struct chg_md chg_md;
+/* Current state (null pointers are skipped) and up to frame_capacity of the oldest frames in the ring, which are removed from it. */
+typedef struct chg_md_out_host {
+  double* positions;           /* [N,3]   cartesian, A (unwrapped)                                                         */
+  double* momenta;             /* [N,3]   amu A / ASE time unit                                                            */
+  double* cell;                /* [B,3,3] rows a,b,c                                                                       */
+  int32_t* n_steps;            /* [B]     steps completed                                                                  */
+  int32_t* status;             /* [B]     CHG_MD_*                                                                         */
+  int32_t frame_capacity;      /* K: frames the arrays below hold                                                          */
+  int32_t* n_frames;           /* out: frames written                                                                      */
+  int32_t* frame_step;         /* [K]                                                                                      */
+  double* frame_scalars;       /* [K,B,3] energy as the engine gives it (eV/atom if is_intensive), Ekin (eV), T (K)        */
+  double* frame_positions;     /* [K,N,3]                                                                                  */
+  double* frame_momenta;       /* [K,N,3]                                                                                  */
+  double* frame_cell;          /* [K,B,3,3]                                                                                */
+  float* frame_force;          /* [K,N,3] eV/A                                                                             */
+  float* frame_stress;         /* [K,B,9] GPa, the model's stress (no ideal-gas term); 0 when not evaluated               */
+  float* frame_crystal_fea;    /* [K,B,64] (log_crystal_fea)                                                               */
+} chg_md_out_host;
+/* Copies the structures, masses [N] (amu) and initial momenta [N,3] (null: zero); no evaluation yet.  CHG_ENOMEM when the state
+ * cannot be allocated. */
+int chg_md_create(chg_engine* eng, const chg_structs_host* host, const double* masses, const double* momenta, const chg_md_params* params,
+                  chg_md** out);
+/* n_steps steps of every replica (the first call evaluates the initial configuration first and writes the frame of step 0).  A batch
+ * whose results are non-finite is evaluated again on the wide-range sweep; a replica that is non-finite even there stops as
+ * CHG_MD_NONFINITE with its state untouched.  CHG_EINVAL (nothing run) when the frames due do not fit the ring. */
+int chg_md_run(chg_engine* eng, chg_md* md, int32_t n_steps);
+int chg_md_download(chg_engine* eng, chg_md* md, const chg_md_out_host* out);
+int chg_md_free(chg_engine* eng, chg_md* md);
+/* Tests only: ONE step kernel launch on caller-given state, in place.  flags: 1 absorb the evaluation (energy [B], force [N,3],
+ * stress [B,9] GPa or null), 2 second half kick, 4 start the next step.  State: r, momenta, forces (cached), masses [N,3] / [N];
+ * sd [B, 40] doubles (L[9], L^-1[9], Epot, Ekin, T, stress[9] eV/A^3, sum p p / m [9], spare); si [B, 4] ints (steps completed,
+ * status, phase (1: NPT scaled configuration awaiting its evaluation), spare); out: frac_next [N,3], lat_next [B,9]. */
+int chg_test_md_step(chg_engine* eng, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
+                     double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy, const float* force,
+                     const float* stress, double* frac_next, double* lat_next);
 
 /* ---- exchange steps of the multi-GPU path, straight on RCCL (one communicator per process = per GPU) ----------
  * The reference is single-device; these carry what SURVEY 8e needs and nothing else: the all-gather of per-structure

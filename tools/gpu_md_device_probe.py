@@ -1,0 +1,75 @@
+"""Throughput of the device molecular dynamics (MolecularDynamics.run_batch, chgnet_amd/dynamics.py) on one GPU: replica-steps/s
+of R = 1, 8, 64 replicas of the 256-atom 2x2x2 Li9Co7O16 cell, NVT Berendsen at 300 K, 2 fs, against the host BerendsenNVT
+(chgnet_amd/md.py) through CHGNetCalculator on the same machine.  One JSON line per leg, appended to --out.
+
+  --leg device --replicas R   one chg_md handle over R replicas (wall clock of run_batch: create, steps, download)
+  --leg host                  one replica, BerendsenNVT + CHGNetCalculator.calculate per step
+
+Weights: the trained-like golden set (tests/golden/weights_trained_like.npz).  Run every leg under its own time limit.
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+
+def _cell(d, seed):
+    from chgnet_amd.graph.structure import Structure, Lattice
+
+    s = Structure(Lattice(d["lattice_f64"]), d["atomic_number"], d["frac_coord_f64"]).make_supercell((2, 2, 2))
+    rng = np.random.default_rng(seed)
+    cart = s.frac_coords @ s.lattice.matrix + 0.02 * rng.normal(size=(len(s), 3))
+    return Structure(s.lattice, s.atomic_numbers, cart @ np.linalg.inv(s.lattice.matrix))
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--leg", choices=("device", "host"), required=True)
+    ap.add_argument("--replicas", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "md_device_probe.jsonl"))
+    args = ap.parse_args()
+
+    from chgnet_amd import CHGNet, CHGNetCalculator
+
+    W = dict(np.load(os.path.join(REPO, "tests", "golden", "weights_trained_like.npz")))
+    lco = np.load(os.path.join(REPO, "tests", "golden", "case_li9co7o16.npz"))
+    calc = CHGNetCalculator(model=CHGNet(state_dict=W))
+    out = {"leg": args.leg, "ensemble": "nvt", "atoms_each": 256, "steps": args.steps, "timestep_fs": 2.0}
+    if args.leg == "device":
+        from chgnet_amd.dynamics import MolecularDynamics
+
+        R = args.replicas
+        cells = [_cell(lco, 100 + i) for i in range(R)]
+        kw = dict(model=calc, ensemble="nvt", temperature=300.0, starting_temperature=300.0, timestep=2.0, loginterval=args.steps)
+        MolecularDynamics.run_batch(cells, 5, seeds=list(range(R)), **kw)          # warm-up: engine creation, first builds
+        t0 = time.perf_counter()
+        res = MolecularDynamics.run_batch(cells, args.steps, seeds=list(range(R)), **kw)
+        wall = time.perf_counter() - t0
+        out.update(replicas=R, wall_s=wall, replica_steps_per_s=R * args.steps / wall, steps_per_s=args.steps / wall,
+                   nonfinite=int(sum(r["status"] != "RUNNING" for r in res)),
+                   final_T_mean=float(np.mean([r["trajectory"].temperatures[-1] for r in res])))
+    else:
+        from chgnet_amd.md import BerendsenNVT
+
+        md = BerendsenNVT(_cell(lco, 100), calc, temperature_K=300.0, timestep_fs=2.0, taut_fs=200.0, seed=0)
+        md.run(5)
+        r = md.run(args.steps)
+        out.update(replicas=1, wall_s=r["wall_s"], replica_steps_per_s=r["steps_per_s"], steps_per_s=r["steps_per_s"])
+    line = json.dumps(out)
+    print(line, flush=True)
+    with open(args.out, "a") as fh:
+        fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
