@@ -89,6 +89,16 @@ class MdOutHost(ctypes.Structure):
                 ("frame_stress", c_float_p), ("frame_crystal_fea", c_float_p)]
 
 
+_POINTER_OF = {"float64": ctypes.POINTER(ctypes.c_double), "float32": c_float_p, "int32": c_int_p}
+
+
+def fill_out(out: ctypes.Structure, arrays: dict) -> ctypes.Structure:
+    """Point the fields of a ``*_out_host`` struct at NumPy arrays named like them (pointer type by dtype); returns ``out``."""
+    for name, a in arrays.items():
+        setattr(out, name, a.ctypes.data_as(_POINTER_OF[a.dtype.name]))
+    return out
+
+
 _LIB = None
 
 

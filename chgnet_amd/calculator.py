@@ -54,6 +54,26 @@ def atoms_to_structure(atoms) -> Structure:
     return Structure(Lattice(cell), np.asarray(atoms.get_atomic_numbers()), np.asarray(atoms.get_scaled_positions(wrap=False)))
 
 
+def voigt(s: np.ndarray) -> np.ndarray:
+    """3x3 stress (any leading axes) -> ASE Voigt order xx, yy, zz, yz, xz, xy."""
+    return np.stack([s[..., 0, 0], s[..., 1, 1], s[..., 2, 2], s[..., 1, 2], s[..., 0, 2], s[..., 0, 1]], axis=-1)
+
+
+def report_isolated_atoms(model: CHGNet, structures: list) -> None:
+    """Isolated atoms of ``structures`` are reported like ``predict_structure`` does (warn / error / ignore), once per structure.
+    The graphs are built on the device to count them; the host converter phrases the report only when there are any."""
+    conv = model.graph_converter
+    if conv.on_isolated_atoms == "ignore":
+        return
+    eng = model.engine
+    batch = eng.build_prepared(eng.prepare_structures(structures), conv.atom_graph_cutoff, conv.bond_graph_cutoff)
+    n_iso = batch.packed.n_isolated
+    batch.free()
+    if n_iso:
+        for s in structures:
+            conv(s)
+
+
 class CHGNetCalculator(Calculator):
     """CHGNet Calculator for ASE applications."""
 

@@ -18,7 +18,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "kernels_relax.h"   // mm3, det3, inv3, wave_sum_f64
+#include "mat3.h"   // mm3, det3, inv3, wave_sum_f64
 
 namespace chg {
 

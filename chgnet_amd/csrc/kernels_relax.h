@@ -13,6 +13,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "mat3.h"   // mm3, det3, inv3, wave_sum_f64, wave_max_f64
+
 namespace chg {
 
 enum : int { RELAX_RUNNING = 0, RELAX_CONVERGED = 1, RELAX_MAX_STEPS = 2, RELAX_NONFINITE = 3 };
@@ -45,23 +47,6 @@ struct RelaxStepArgs {
   double fmax2, maxstep, dtmax, finc, fdec, astart, fa, stress_weight;
   int max_steps, nmin, relax_cell, final_try;
 };
-
-// ---- 3x3 helpers (row-major) -------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void mm3(const double* a, const double* b, double* c) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) c[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
-}
-__device__ __forceinline__ double det3(const double* m) {
-  return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-}
-__device__ __forceinline__ void inv3(const double* m, double* r) {
-  const double id = 1.0 / det3(m);
-  r[0] = (m[4] * m[8] - m[5] * m[7]) * id; r[1] = (m[2] * m[7] - m[1] * m[8]) * id; r[2] = (m[1] * m[5] - m[2] * m[4]) * id;
-  r[3] = (m[5] * m[6] - m[3] * m[8]) * id; r[4] = (m[0] * m[8] - m[2] * m[6]) * id; r[5] = (m[2] * m[3] - m[0] * m[5]) * id;
-  r[6] = (m[3] * m[7] - m[4] * m[6]) * id; r[7] = (m[1] * m[6] - m[0] * m[7]) * id; r[8] = (m[0] * m[4] - m[1] * m[3]) * id;
-}
 
 // expm(M) and, when e != null, the Frechet derivative L(M, E) = top-right block of expm([[M, E], [0, M]]).  The 6x6 block matrix is
 // kept as its two distinct 3x3 blocks ([[P, Q], [0, P]] is closed under products), scaled by 2^-s until ||M||_1 <= 1/4, summed as a
@@ -96,17 +81,6 @@ __device__ inline void expm_frechet3(const double* m, const double* e, double* o
   }
 #pragma unroll
   for (int i = 0; i < 9; ++i) { out_exp[i] = p[i]; if (out_l) out_l[i] = q[i]; }
-}
-
-__device__ __forceinline__ double wave_sum_f64(double x) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-  return x;
-}
-__device__ __forceinline__ double wave_max_f64(double x) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) x = fmax(x, __shfl_xor(x, off));
-  return x;
 }
 
 static __global__ __launch_bounds__(256) void k_relax_step(RelaxStepArgs p) {

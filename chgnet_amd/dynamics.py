@@ -26,7 +26,7 @@ import sys
 import numpy as np
 
 from chgnet_amd import _lib
-from chgnet_amd.calculator import CHGNetCalculator, atoms_to_structure
+from chgnet_amd.calculator import CHGNetCalculator, atoms_to_structure, report_isolated_atoms, voigt
 from chgnet_amd.graph.structure import Lattice, Structure
 
 # ase.units (CODATA 2014)
@@ -48,10 +48,6 @@ ATOMIC_MASSES = np.array([
     168.93422, 173.054, 174.9668, 178.49, 180.94788, 183.84, 186.207, 190.23, 192.217, 195.084, 196.966569, 200.592, 204.38,
     207.2, 208.98040, 208.98243, 209.98715, 222.01758, 223.01974, 226.02541, 227.02775, 232.0377, 231.03588, 238.02891,
     237.04817, 244.06421])
-
-
-def _voigt(s: np.ndarray) -> np.ndarray:
-    return np.array([s[0, 0], s[1, 1], s[2, 2], s[1, 2], s[0, 2], s[0, 1]])
 
 
 def maxwell_boltzmann(masses: np.ndarray, temperature_k: float, rng: np.random.Generator) -> np.ndarray:
@@ -169,8 +165,7 @@ class _DeviceRun:
                                log_stress=int(self.stress), log_crystal_fea=int(self.cfea), r_atom=conv.atom_graph_cutoff,
                                r_bond=conv.bond_graph_cutoff, numerical_tol=1e-8)
         dp = ctypes.POINTER(ctypes.c_double)
-        host = _lib.StructsHost(self.B, self.N, prep.z.ctypes.data_as(_lib.c_int_p), prep.frac.ctypes.data_as(dp),
-                                prep.lattice.ctypes.data_as(dp), prep.atom_off.ctypes.data_as(_lib.c_int_p))
+        host = prep.host()
         self.handle = ctypes.c_void_p()
         self.eng._check(self.eng.lib.chg_md_create(self.eng.handle, ctypes.byref(host), self.masses.ctypes.data_as(dp), mom.ctypes.data_as(dp),
                                                    ctypes.byref(params), ctypes.byref(self.handle)))
@@ -189,11 +184,7 @@ class _DeviceRun:
              "frame_scalars": np.empty((K, B, 3)), "frame_positions": np.empty((K, N, 3)), "frame_momenta": np.empty((K, N, 3)),
              "frame_cell": np.empty((K, B, 3, 3)), "frame_force": np.empty((K, N, 3), np.float32), "frame_stress": np.empty((K, B, 3, 3), np.float32),
              "frame_crystal_fea": np.empty((K, B, 64), np.float32)}
-        o = _lib.MdOutHost()
-        dp = ctypes.POINTER(ctypes.c_double)
-        for k, v in d.items():
-            ptype = dp if v.dtype == np.float64 else _lib.c_float_p if v.dtype == np.float32 else _lib.c_int_p
-            setattr(o, k, v.ctypes.data_as(ptype))
+        o = _lib.fill_out(_lib.MdOutHost(), d)
         o.frame_capacity = K
         self.eng._check(self.eng.lib.chg_md_download(self.eng.handle, self.handle, ctypes.byref(o)))
         return d
@@ -318,7 +309,7 @@ class MolecularDynamics:
                 tr.temperatures.append(float(d["frame_scalars"][k, i, 2]))
                 tr.forces.append(d["frame_force"][k, sl].astype(np.float64))
                 if run.stress:
-                    tr.stresses.append(_voigt(d["frame_stress"][k, i].astype(np.float64)) * sw)
+                    tr.stresses.append(voigt(d["frame_stress"][k, i].astype(np.float64)) * sw)
                 tr.atom_positions.append(d["frame_positions"][k, sl].copy())
                 tr.momenta.append(d["frame_momenta"][k, sl].copy())
                 tr.cells.append(d["frame_cell"][k, i].copy())
@@ -338,9 +329,7 @@ class MolecularDynamics:
         if steps < 0:
             raise ValueError(f"{steps=} must be >= 0")
         if self._run is None:
-            conv = self.calculator.model.graph_converter
-            if conv.on_isolated_atoms != "ignore":     # isolated atoms are reported like predict_structure does
-                conv(self._structure)
+            report_isolated_atoms(self.calculator.model, [self._structure])
             self._run = _DeviceRun(self.calculator, [self._structure], self._masses, self._momenta, self.kind, self.cfg)
             if self.logfile is not None and self._logger is None:
                 self._logger = MDLogger(self.logfile, len(self._structure))
@@ -387,10 +376,7 @@ class MolecularDynamics:
             calc = md[-1].calculator
         first = md[0]
         structs = [m._structure for m in md]
-        conv = first.calculator.model.graph_converter
-        if conv.on_isolated_atoms != "ignore":
-            for s in structs:
-                conv(s)
+        report_isolated_atoms(first.calculator.model, structs)
         run = _DeviceRun(first.calculator, structs, np.concatenate([m._masses for m in md]), np.concatenate([m._momenta for m in md]),
                          first.kind, first.cfg)
         try:

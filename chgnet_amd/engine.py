@@ -28,6 +28,12 @@ class PreparedStructures:
     def __init__(self, n_struct: int, z: np.ndarray, atom_off: np.ndarray, frac: np.ndarray, lattice: np.ndarray) -> None:
         self.n_struct, self.z, self.atom_off, self.frac, self.lattice = n_struct, z, atom_off, frac, lattice
 
+    def host(self) -> _lib.StructsHost:
+        """The ``chg_structs_host`` view of these arrays (it points into them: keep this object alive while it is used)."""
+        dp = ctypes.POINTER(ctypes.c_double)
+        return _lib.StructsHost(self.n_struct, int(self.atom_off[-1]), _ip(self.z), self.frac.ctypes.data_as(dp),
+                                self.lattice.ctypes.data_as(dp), _ip(self.atom_off))
+
 
 class EngineOutOfMemory(RuntimeError):
     """CHG_ENOMEM: the batch arena could not be allocated (or exceeds ``Engine.set_memory_limit``).
@@ -219,8 +225,7 @@ class Engine:
                        numerical_tol: float = 1e-8, predict_task: str | None = None) -> DeviceBatch:
         """Device side of ``build_batch`` (chg_batch_build).  ``predict_task``: the prediction is enqueued by the same native call
         (chg_batch_build_predict) -- a single-structure caller saves the trip back to Python between the two."""
-        host = _lib.StructsHost(prep.n_struct, int(prep.atom_off[-1]), _ip(prep.z), prep.frac.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                prep.lattice.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _ip(prep.atom_off))
+        host = prep.host()
         handle = ctypes.c_void_p()
         counts = np.zeros(6, dtype=np.int32)
         if predict_task is not None:

@@ -23,18 +23,13 @@ import sys
 import numpy as np
 
 from chgnet_amd import _lib
-from chgnet_amd.calculator import GPA_TO_EV_A3, CHGNetCalculator, atoms_to_structure
+from chgnet_amd.calculator import GPA_TO_EV_A3, CHGNetCalculator, atoms_to_structure, report_isolated_atoms, voigt
 from chgnet_amd.graph.structure import Lattice, Structure
 
 OPTIMIZERS = ("FIRE",)
 FILTERS = ("FrechetCellFilter",)
 STATUS_NAMES = ("RUNNING", "CONVERGED", "MAX_STEPS", "NONFINITE")
 FIRE_DEFAULTS = {"dt": 0.1, "maxstep": 0.2, "dtmax": 1.0, "Nmin": 5, "finc": 1.1, "fdec": 0.5, "astart": 0.1, "fa": 0.99}
-
-
-def _voigt(s: np.ndarray) -> np.ndarray:
-    """3x3 stress (any leading axes) -> ASE Voigt order xx, yy, zz, yz, xz, xy."""
-    return np.stack([s[..., 0, 0], s[..., 1, 1], s[..., 2, 2], s[..., 1, 2], s[..., 0, 2], s[..., 0, 1]], axis=-1)
 
 
 class TrajectoryObserver:
@@ -116,20 +111,6 @@ class StructOptimizer:
                 raise ValueError("every structure needs at least one site")
         return structs
 
-    def _check_isolated(self, structures: list) -> None:
-        """Isolated atoms of the initial structures are reported like ``predict_structure`` does (warn / error / ignore), once per structure."""
-        model = self.calculator.model
-        conv = model.graph_converter
-        if conv.on_isolated_atoms == "ignore":
-            return
-        eng = model.engine
-        batch = eng.build_prepared(eng.prepare_structures(structures), conv.atom_graph_cutoff, conv.bond_graph_cutoff)
-        n_iso = batch.packed.n_isolated
-        batch.free()
-        if n_iso:
-            for s in structures:
-                conv(s)
-
     def _run(self, structures: list, p: dict, frame_every: int | None, verbose: bool):
         """Relax ``structures`` together: one ``chg_relax`` handle, frames every ``frame_every`` evaluations (None: none)."""
         model = self.calculator.model
@@ -140,9 +121,7 @@ class StructOptimizer:
             fmax=p["fmax"], max_steps=p["steps"], relax_cell=int(p["relax_cell"]), dt=p["dt"], maxstep=p["maxstep"], dtmax=p["dtmax"],
             finc=p["finc"], fdec=p["fdec"], astart=p["astart"], fa=p["fa"], nmin=int(p["Nmin"]), exp_cell_factor=0.0,
             r_atom=conv.atom_graph_cutoff, r_bond=conv.bond_graph_cutoff, numerical_tol=1e-8, stress_weight=self.calculator.stress_weight)
-        host = _lib.StructsHost(prep.n_struct, int(prep.atom_off[-1]), prep.z.ctypes.data_as(_lib.c_int_p),
-                                prep.frac.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                prep.lattice.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), prep.atom_off.ctypes.data_as(_lib.c_int_p))
+        host = prep.host()
         handle = ctypes.c_void_p()
         eng._check(eng.lib.chg_relax_create(eng.handle, ctypes.byref(host), ctypes.byref(params), ctypes.byref(handle)))
         B, N = prep.n_struct, int(prep.atom_off[-1])
@@ -150,32 +129,27 @@ class StructOptimizer:
         trajs = [TrajectoryObserver(prep.z[prep.atom_off[i]:prep.atom_off[i + 1]]) for i in range(B)] if frame_every else None
 
         def download() -> dict:
-            out = {"frac": np.empty((N, 3)), "lattice": np.empty((B, 3, 3)), "e": np.empty(B, np.float32), "f": np.empty((N, 3), np.float32),
-                   "s": np.empty((B, 3, 3), np.float32), "m": np.empty(N, np.float32), "n_steps": np.empty(B, np.int32),
-                   "status": np.empty(B, np.int32)}
-            o = _lib.RelaxOutHost()
-            dp = ctypes.POINTER(ctypes.c_double)
-            o.frac, o.lattice = out["frac"].ctypes.data_as(dp), out["lattice"].ctypes.data_as(dp)
-            for key, name in (("e", "energy"), ("f", "force"), ("s", "stress"), ("m", "magmom")):
-                setattr(o, name, out[key].ctypes.data_as(_lib.c_float_p))
-            o.n_steps, o.status = out["n_steps"].ctypes.data_as(_lib.c_int_p), out["status"].ctypes.data_as(_lib.c_int_p)
-            eng._check(eng.lib.chg_relax_download(eng.handle, handle, ctypes.byref(o)))
+            out = {"frac": np.empty((N, 3)), "lattice": np.empty((B, 3, 3)), "energy": np.empty(B, np.float32),
+                   "force": np.empty((N, 3), np.float32), "stress": np.empty((B, 3, 3), np.float32), "magmom": np.empty(N, np.float32),
+                   "n_steps": np.empty(B, np.int32), "status": np.empty(B, np.int32)}
+            eng._check(eng.lib.chg_relax_download(eng.handle, handle, ctypes.byref(_lib.fill_out(_lib.RelaxOutHost(), out))))
             return out
 
         def record(d: dict, which) -> None:
             for i in which:
                 sl = slice(prep.atom_off[i], prep.atom_off[i + 1])
-                trajs[i].append(d["e"][i] * scale[i], d["f"][sl].astype(np.float64), _voigt(d["s"][i].astype(np.float64)) * self.calculator.stress_weight,
-                                d["m"][sl].astype(np.float64), d["frac"][sl] @ d["lattice"][i], d["lattice"][i].copy())
+                trajs[i].append(d["energy"][i] * scale[i], d["force"][sl].astype(np.float64),
+                                voigt(d["stress"][i].astype(np.float64)) * self.calculator.stress_weight, d["magmom"][sl].astype(np.float64),
+                                d["frac"][sl] @ d["lattice"][i], d["lattice"][i].copy())
 
         def log(d: dict, active_before: np.ndarray) -> None:
             if not verbose:
                 return
             for i in np.flatnonzero(active_before):
                 sl = slice(prep.atom_off[i], prep.atom_off[i + 1])
-                fmax_now = float(np.sqrt((d["f"][sl].astype(np.float64) ** 2).sum(1).max()))
+                fmax_now = float(np.sqrt((d["force"][sl].astype(np.float64) ** 2).sum(1).max()))
                 last = d["n_steps"][i] - (1 if d["status"][i] == 0 else 0)
-                print(f"FIRE[{i}]: {last:4d}  E = {d['e'][i] * scale[i]:.6f} eV  max|f| = {fmax_now:.6f} eV/A  {STATUS_NAMES[d['status'][i]]}")
+                print(f"FIRE[{i}]: {last:4d}  E = {d['energy'][i] * scale[i]:.6f} eV  max|f| = {fmax_now:.6f} eV/A  {STATUS_NAMES[d['status'][i]]}")
 
         n_active = ctypes.c_int32(B)
         try:
@@ -205,9 +179,9 @@ class StructOptimizer:
         sl = slice(prep.atom_off[i], prep.atom_off[i + 1])
         struct = Structure(Lattice(d["lattice"][i]), prep.z[sl].copy(), d["frac"][sl].copy())
         if assign_magmoms:
-            struct.add_site_property("magmom", [float(m) for m in d["m"][sl]])
-        return {"final_structure": struct, "energy": float(d["e"][i] * scale[i]), "forces": d["f"][sl].astype(np.float64),
-                "stress": _voigt(d["s"][i].astype(np.float64)) * self.calculator.stress_weight, "magmoms": d["m"][sl].astype(np.float64),
+            struct.add_site_property("magmom", [float(m) for m in d["magmom"][sl]])
+        return {"final_structure": struct, "energy": float(d["energy"][i] * scale[i]), "forces": d["force"][sl].astype(np.float64),
+                "stress": voigt(d["stress"][i].astype(np.float64)) * self.calculator.stress_weight, "magmoms": d["magmom"][sl].astype(np.float64),
                 "n_steps": int(d["n_steps"][i]), "status": STATUS_NAMES[d["status"][i]], "converged": bool(d["status"][i] == 1)}
 
     # ------------------------------------------------------------------------------------------------------------------------
@@ -223,7 +197,7 @@ class StructOptimizer:
         if loginterval < 1:
             raise ValueError(f"{loginterval=} must be positive")
         structs = self._structures([atoms])
-        self._check_isolated(structs)
+        report_isolated_atoms(self.calculator.model, structs)
         stream = sys.stdout if verbose else io.StringIO()
         with contextlib.redirect_stdout(stream):
             prep, d, scale, trajs = self._run(structs, p, loginterval, verbose)
@@ -264,6 +238,6 @@ class StructOptimizer:
 
         results = []
         for a, b in _plan_chunks([len(s) for s in structs], 1, model.min_atoms_per_batch):
-            self._check_isolated(structs[a:b])
+            report_isolated_atoms(model, structs[a:b])
             results.extend(_run_splitting(run, structs[a:b]))
         return results

@@ -141,13 +141,15 @@ def test_product_build_defines_no_experiment_switch():
 
 
 def test_ctypes_structs_mirror_the_c_header(tmp_path):
-    """``chg_model_desc`` (with the ``n_mlp_hidden`` field the 0.2.0 head needs) and ``chg_out_host`` as gcc lays them
-    out from include/chgnet_hip.h == the ctypes mirrors in chgnet_amd/_lib.py, field by field."""
+    """``chg_model_desc`` (with the ``n_mlp_hidden`` field the 0.2.0 head needs), ``chg_out_host`` and the other structs of the C-ABI
+    (batches, relaxation, MD) as gcc lays them out from include/chgnet_hip.h == the ctypes mirrors in chgnet_amd/_lib.py, field by field."""
     import subprocess
 
     from chgnet_amd import _lib
 
-    fields = {"chg_model_desc": _lib.ModelDesc, "chg_out_host": _lib.OutHost, "chg_structs_host": _lib.StructsHost, "chg_batch_host": _lib.BatchHost}
+    fields = {"chg_model_desc": _lib.ModelDesc, "chg_out_host": _lib.OutHost, "chg_structs_host": _lib.StructsHost, "chg_batch_host": _lib.BatchHost,
+              "chg_relax_params": _lib.RelaxParams, "chg_relax_out_host": _lib.RelaxOutHost, "chg_md_params": _lib.MdParams,
+              "chg_md_out_host": _lib.MdOutHost}
     lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "chgnet_hip.h"', "int main(void) {"]
     for cname, cls in fields.items():
         lines.append(f'  printf("{cname} %zu\\n", sizeof({cname}));')

@@ -300,3 +300,21 @@ def test_large_batch_64_replicas(calc):
     for o in out:
         assert o["status"] == "RUNNING" and o["n_steps"] == 20
         assert len(o["trajectory"]) == 3 and np.all(np.isfinite(o["final_structure"].frac_coords))
+
+
+# ---- 6. isolated atoms -------------------------------------------------------------------------------------------------------------
+def test_isolated_atoms_reported_once_per_structure(model, capsys):
+    """A batch with one structure holding isolated atoms: the converter's message once on stderr under "warn", ValueError under "error"."""
+    from chgnet_amd.dynamics import MolecularDynamics
+    from chgnet_amd.graph.structure import Lattice, Structure
+
+    lone = Structure(Lattice(np.eye(3) * 20.0), ["H", "O"], [[0, 0, 0], [0.5, 0.5, 0.5]])
+    structs = [_structure("limno2", rattle=0.05, seed=1), lone, _structure("li9co7o16", rattle=0.03, seed=2)]
+    try:
+        capsys.readouterr()
+        MolecularDynamics.run_batch(structs, 2, model=model, on_isolated_atoms="warn", ensemble="nve", starting_temperature=300.0, seeds=[1, 2, 3])
+        assert capsys.readouterr().err.count("has 2 isolated atom") == 1
+        with pytest.raises(ValueError, match="has 2 isolated atom"):
+            MolecularDynamics.run_batch(structs, 2, model=model, on_isolated_atoms="error", ensemble="nve", seeds=[1, 2, 3])
+    finally:
+        model.graph_converter.set_isolated_atom_response("warn")

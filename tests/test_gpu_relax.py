@@ -229,9 +229,7 @@ def test_large_batch_five_steps(model):
     structs = [_structure("limno2", (5, 1, 1), rattle=0.05, strain=0.02, seed=100 + i) for i in range(1024)]
     eng = model.engine
     prep = eng.prepare_structures(structs)
-    host = _lib.StructsHost(prep.n_struct, int(prep.atom_off[-1]), prep.z.ctypes.data_as(_lib.c_int_p),
-                            prep.frac.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                            prep.lattice.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), prep.atom_off.ctypes.data_as(_lib.c_int_p))
+    host = prep.host()
     p = _params(1, 0.1, 5)
     h = ctypes.c_void_p()
     eng._check(eng.lib.chg_relax_create(eng.handle, ctypes.byref(host), ctypes.byref(p), ctypes.byref(h)))
@@ -243,18 +241,32 @@ def test_large_batch_five_steps(model):
             if n_active.value == 0:
                 break
         N, B = int(prep.atom_off[-1]), 1024
-        out = {"frac": np.empty((N, 3)), "lattice": np.empty((B, 3, 3)), "e": np.empty(B, np.float32), "f": np.empty((N, 3), np.float32),
-               "s": np.empty((B, 9), np.float32), "m": np.empty(N, np.float32), "n": np.empty(B, np.int32), "st": np.empty(B, np.int32)}
-        o = _lib.RelaxOutHost()
-        dp = ctypes.POINTER(ctypes.c_double)
-        o.frac, o.lattice = out["frac"].ctypes.data_as(dp), out["lattice"].ctypes.data_as(dp)
-        o.energy, o.force, o.stress, o.magmom = (out[k].ctypes.data_as(_lib.c_float_p) for k in ("e", "f", "s", "m"))
-        o.n_steps, o.status = out["n"].ctypes.data_as(_lib.c_int_p), out["st"].ctypes.data_as(_lib.c_int_p)
-        eng._check(eng.lib.chg_relax_download(eng.handle, h, ctypes.byref(o)))
+        out = {"frac": np.empty((N, 3)), "lattice": np.empty((B, 3, 3)), "energy": np.empty(B, np.float32), "force": np.empty((N, 3), np.float32),
+               "stress": np.empty((B, 9), np.float32), "magmom": np.empty(N, np.float32), "n_steps": np.empty(B, np.int32),
+               "status": np.empty(B, np.int32)}
+        eng._check(eng.lib.chg_relax_download(eng.handle, h, ctypes.byref(_lib.fill_out(_lib.RelaxOutHost(), out))))
     finally:
         eng.lib.chg_relax_free(eng.handle, h)
     assert history[-1] == 0 and len(history) == 6 and all(a >= b for a, b in zip(history, history[1:]))
-    for k in ("frac", "lattice", "e", "f", "s", "m"):
+    for k in ("frac", "lattice", "energy", "force", "stress", "magmom"):
         assert np.all(np.isfinite(out[k])), k
-    assert set(np.unique(out["st"])) <= {1, 2}
-    assert np.all(out["n"][out["st"] == 2] == 5) and np.all(out["n"] <= 5)
+    assert set(np.unique(out["status"])) <= {1, 2}
+    assert np.all(out["n_steps"][out["status"] == 2] == 5) and np.all(out["n_steps"] <= 5)
+
+
+# ---- 6. isolated atoms -------------------------------------------------------------------------------------------------------------
+def test_isolated_atoms_reported_once_per_structure(model, capsys):
+    """A batch with one structure holding isolated atoms: the converter's message once on stderr under "warn", ValueError under "error"."""
+    from chgnet_amd.graph.structure import Lattice, Structure
+    from chgnet_amd.relax import StructOptimizer
+
+    lone = Structure(Lattice(np.eye(3) * 20.0), ["H", "O"], [[0, 0, 0], [0.5, 0.5, 0.5]])
+    structs = [_structure("limno2", rattle=0.05, seed=1), lone, _structure("li9co7o16", rattle=0.03, seed=2)]
+    try:
+        capsys.readouterr()
+        StructOptimizer(model=model, on_isolated_atoms="warn").relax_batch(structs, steps=3)
+        assert capsys.readouterr().err.count("has 2 isolated atom") == 1
+        with pytest.raises(ValueError, match="has 2 isolated atom"):
+            StructOptimizer(model=model, on_isolated_atoms="error").relax_batch(structs, steps=3)
+    finally:
+        model.graph_converter.set_isolated_atom_response("warn")
