@@ -38,4 +38,8 @@ def __getattr__(name):  # lazy: keeps `import chgnet_amd` free of the HIP librar
         from chgnet_amd import dynamics
 
         return getattr(dynamics, name)
+    if name == "gamma_frequencies":
+        from chgnet_amd.phonons import gamma_frequencies
+
+        return gamma_frequencies
     raise AttributeError(name)

@@ -8,6 +8,7 @@
 #include "kernels_train2.h"
 #include "kernels_train2_tile.h"
 #include "kernels_train2_freq.h"
+#include "kernels_hvp.h"
 
 struct Train2 {
   float *ux, *Wst;                                   // direction: [N,3], [B,9]
@@ -27,6 +28,7 @@ struct Train2 {
   float *gP0, *gR0, *gS0;                            // this workspace's own G(P), G(R), G(S) (gP / gR / gS may point into the batch)
   float* ro[26];                                     // readout planes [N,64]
   float *zero_lo, *zero_hi;                          // range cleared at the start of every call
+  float *hvp_gu, *hvp_grk, *hvp_out, *hvp_vir;       // HVP mode: k_edge_force operands [Ed,4] [Eu], H u as its "force" -H u [N,3], virial [B,9]
 };
 
 namespace chgh {
@@ -402,6 +404,7 @@ void layout_train2(chg_batch* b, Train2& t, Carver& c) {
   for (int l = 0; l < L - 1; ++l) t.aggBd[l] = c.take<float>(Eb * D);
   t.bar_b = c.take<float>(Eu * D); t.g_b = c.take<float>(Eu * D); t.bar_wag = c.take<float>(Eu * D); t.g_wag = c.take<float>(Eu * D);
   t.bar_wbg = c.take<float>(Eb * D); t.g_wbg = c.take<float>(Eb * D); t.bar_ang = c.take<float>(A * D); t.g_ang = c.take<float>(A * D);
+  t.hvp_gu = c.take<float>(Ed * 4); t.hvp_grk = c.take<float>(Eu); t.hvp_out = c.take<float>(3 * N); t.hvp_vir = c.take<float>(9 * B);
   t.zero_hi = c.take<float>(0);
   // table gradients: cleared before every layer
   t.barP = c.take<float>(N * 4 * D); t.gP = c.take<float>(N * 4 * D); t.barQ = c.take<float>(Eu * 2 * D); t.gQ = c.take<float>(Eu * 2 * D);
@@ -454,7 +457,7 @@ int ensure_train2_buffers(chg_engine* eng, chg_batch* b) {
 
 inline dim3 wave_rows_grid(chg_engine* eng, int64_t rows) { return dim3((unsigned)wave_grid(eng, rows)); }
 
-int run_backward2(chg_engine* eng, chg_batch* b) {
+int run_backward2(chg_engine* eng, chg_batch* b, bool hvp) {
   const Weights& w = eng->w;
   Train2& t = *b->t2;
   const int L = b->L;
@@ -462,6 +465,7 @@ int run_backward2(chg_engine* eng, chg_batch* b) {
   auto G = [&](const float* wp) { return grad_of(eng, b, wp); };
   const int N = b->N, Ed = b->Ed, Eu = b->Eu, A = b->A, Eb = b->Eb;
   const bool angles = A > 0;
+  const bool wg = !hvp;   // HVP mode (chg_hessian_vector): only the adjoints reach the embeddings, no weight-gradient contraction
   TRY(zero(eng, b->t_grad, sizeof(float) * (size_t)eng->desc.n_weights));
   TRY(zero(eng, t.zero_lo, (size_t)((char*)t.zero_hi - (char*)t.zero_lo)));
   auto gemm = [&](const char* label, int K, int NOUT, const float* X, int ldx, const int* in_idx, const float* Wt, const float* bias,
@@ -504,7 +508,10 @@ int run_backward2(chg_engine* eng, chg_batch* b) {
   }
   if (angles) {
     { LaunchScope ls(eng, "t2_basis");
-      hipLaunchKernelGGL(k2_angle_basis, g1((int64_t)A * KB2), dim3(256), 0, st, b->eu, t.ud4, b->a_d1, b->a_d2, w.freq_ang, t.X4, t.X4d, t.th2, A); }
+      if (hvp)
+        hipLaunchKernelGGL(k_hvp_angle_basis, g1((int64_t)A * KB2), dim3(256), 0, st, b->ev, t.vd4, b->a_d1, b->a_d2, w.freq_ang, t.X4, t.X4d, t.th2, A);
+      else
+        hipLaunchKernelGGL(k2_angle_basis, g1((int64_t)A * KB2), dim3(256), 0, st, b->eu, t.ud4, b->a_d1, b->a_d2, w.freq_ang, t.X4, t.X4d, t.th2, A); }
     LaunchScope ls(eng, "t2_embed_lin");
     hipLaunchKernelGGL(k2_embed_lin, wave_rows_grid(eng, A), dim3(256), 0, st, t.X4d, w.w_ang_emb, t.angd[0], nullptr, A);
   }
@@ -675,22 +682,22 @@ int run_backward2(chg_engine* eng, chg_batch* b) {
     { LaunchScope ls(eng, "t2_readout");
       hipLaunchKernelGGL(k2_readout_seed, g1((int64_t)nd), dim3(256), 0, st, w.mlp_w3, b->t_cot, b->atom_owner, t.ro[sidx[nh]], t.ro[sdidx[nh]], t.ro[BS],
                          t.ro[GS], t.ro[DW3], N); }
-    TRY(colsum(eng, t.ro[DW3], D, nullptr, 0, N, D, G(w.mlp_w3)));
+    if (wg) TRY(colsum(eng, t.ro[DW3], D, nullptr, 0, N, D, G(w.mlp_w3)));
     const float* gW[3] = {G(w.mlp_w0), G(w.mlp_w1), G(w.mlp_w2)};
     const float* gb[3] = {G(w.mlp_b0), G(w.mlp_b1), G(w.mlp_b2)};
     for (int i = nh - 1; i >= 0; --i) {
       { LaunchScope ls(eng, "t2_readout");
         hipLaunchKernelGGL(k2_hidden_b, g1((int64_t)nd), dim3(256), 0, st, t.ro[lidx[i]], t.ro[ldidx[i]], t.ro[BS], t.ro[GS], t.ro[BL], t.ro[GLr], nd); }
-      TRY((xty<4, 4>(eng, "t2_wgrad", t.ro[BL], D, nullptr, t.ro[sidx[i]], D, nullptr, N, 1.0f, (float*)gW[i], D, D, (float*)gb[i])));
-      TRY((xty<4, 4>(eng, "t2_wgrad", t.ro[GLr], D, nullptr, t.ro[sdidx[i]], D, nullptr, N, 1.0f, (float*)gW[i], D, D)));
+      if (wg) TRY((xty<4, 4>(eng, "t2_wgrad", t.ro[BL], D, nullptr, t.ro[sidx[i]], D, nullptr, N, 1.0f, (float*)gW[i], D, D, (float*)gb[i])));
+      if (wg) TRY((xty<4, 4>(eng, "t2_wgrad", t.ro[GLr], D, nullptr, t.ro[sdidx[i]], D, nullptr, N, 1.0f, (float*)gW[i], D, D)));
       TRY(gemm("t2_readout", 64, 64, t.ro[BL], D, nullptr, Wt[i], nullptr, nullptr, 0, t.ro[BS], D, nullptr, N, 0));
       TRY(gemm("t2_readout", 64, 64, t.ro[GLr], D, nullptr, Wt[i], nullptr, nullptr, 0, t.ro[GS], D, nullptr, N, 0));
     }
     { LaunchScope ls(eng, "t2_readout");
       hipLaunchKernelGGL(k2_ln_b, wave_rows_grid(eng, N), dim3(256), 0, st, b->atom[L], t.atomd[L], w.ro_ln_g, t.ro[BS], t.ro[GS], t.bar_a, t.g_a,
                          t.ro[DGAM], t.ro[DBET], N); }
-    TRY(colsum(eng, t.ro[DGAM], D, nullptr, 0, N, D, G(w.ro_ln_g)));
-    TRY(colsum(eng, t.ro[DBET], D, nullptr, 0, N, D, G(w.ro_ln_b)));
+    if (wg) TRY(colsum(eng, t.ro[DGAM], D, nullptr, 0, N, D, G(w.ro_ln_g)));
+    if (wg) TRY(colsum(eng, t.ro[DBET], D, nullptr, 0, N, D, G(w.ro_ln_b)));
   }
   TRY(check());
 
@@ -698,8 +705,8 @@ int run_backward2(chg_engine* eng, chg_batch* b) {
   reverse = true;
   // gated-MLP internals common to the three layer kinds: BCG / GCG -> weight gradients of the second layer, BZ / GZ
   auto hidden_back = [&](const GatedW& g, const float* w2c_t, const float* w2g_t, int rows) -> int {
-    TRY(xty_halves(eng, "t2_wgrad", t.BCG, t.H, rows, G(g.w2c), G(g.w2g), G(g.b2c), G(g.b2g)));
-    TRY(xty_halves(eng, "t2_wgrad", t.GCG, t.Hd, rows, G(g.w2c), G(g.w2g)));
+    if (wg) TRY(xty_halves(eng, "t2_wgrad", t.BCG, t.H, rows, G(g.w2c), G(g.w2g), G(g.b2c), G(g.b2g)));
+    if (wg) TRY(xty_halves(eng, "t2_wgrad", t.GCG, t.Hd, rows, G(g.w2c), G(g.w2g)));
     TRY(gemm_pair(t.BCG, w2c_t, w2g_t, nullptr, nullptr, t.BH, rows));
     TRY(gemm_pair(t.GCG, w2c_t, w2g_t, nullptr, nullptr, t.GH, rows));
     LaunchScope ls(eng, "t2_hidden_b");
@@ -710,8 +717,8 @@ int run_backward2(chg_engine* eng, chg_batch* b) {
   auto atomconv_b = [&](int l) -> int {
     const ACW& aw = w.ac[l];
     // atom[l+1] = agg . Wout^T + b_out + atom[l]
-    TRY((xty<4, 4>(eng, "t2_wgrad", t.bar_a, D, nullptr, b->agg_l[l], D, nullptr, N, 1.0f, G(aw.w_out), D, D, G(aw.b_out))));
-    TRY((xty<4, 4>(eng, "t2_wgrad", t.g_a, D, nullptr, t.aggd[l], D, nullptr, N, 1.0f, G(aw.w_out), D, D)));
+    if (wg) TRY((xty<4, 4>(eng, "t2_wgrad", t.bar_a, D, nullptr, b->agg_l[l], D, nullptr, N, 1.0f, G(aw.w_out), D, D, G(aw.b_out))));
+    if (wg) TRY((xty<4, 4>(eng, "t2_wgrad", t.g_a, D, nullptr, t.aggd[l], D, nullptr, N, 1.0f, G(aw.w_out), D, D)));
     if (Ed == 0) return CHG_OK;
     TRY(gemm("t2_gemm_out", 64, 64, t.bar_a, D, nullptr, aw.w_out_t, nullptr, nullptr, 0, t.bar_agg, D, nullptr, N, 0));
     TRY(gemm("t2_gemm_out", 64, 64, t.g_a, D, nullptr, aw.w_out_t, nullptr, nullptr, 0, t.g_agg, D, nullptr, N, 0));
@@ -723,8 +730,8 @@ int run_backward2(chg_engine* eng, chg_batch* b) {
       { LaunchScope ls(eng, "t2_atom_b");
         hipLaunchKernelGGL(k2_atom<true>, dim3(tile_grid(eng, Ed)), dim3(BLOCK), t2_atom_lds(), st, a);
         HIP_TRY(eng, hipGetLastError()); }
-      TRY(xty_halves(eng, "t2_wgrad", a.BCG, a.H, Ed, G(aw.g.w2c), G(aw.g.w2g), G(aw.g.b2c), G(aw.g.b2g)));
-      TRY(xty_halves(eng, "t2_wgrad", a.GCG, a.Hd, Ed, G(aw.g.w2c), G(aw.g.w2g)));
+      if (wg) TRY(xty_halves(eng, "t2_wgrad", a.BCG, a.H, Ed, G(aw.g.w2c), G(aw.g.w2g), G(aw.g.b2c), G(aw.g.b2g)));
+      if (wg) TRY(xty_halves(eng, "t2_wgrad", a.GCG, a.Hd, Ed, G(aw.g.w2c), G(aw.g.w2g)));
     } else {
     TRY(atom_rows(l));
     {
@@ -745,21 +752,23 @@ int run_backward2(chg_engine* eng, chg_batch* b) {
     }
     }
     // first layer (factorised): table gradients contract with the rows the tables were made from, bar with primal and G with tangent
-    for (int half = 0; half < 2; ++half) {
-      TRY((xty<8, 4>(eng, "t2_wgrad", t.barP + half * 2 * D, 4 * D, nullptr, b->atom[l], D, nullptr, N, 1.0f, G(aw.w_cn) + half * 2 * D * D, D, D,
-                     half == 0 ? G(aw.b1) : nullptr)));
-      TRY((xty<8, 4>(eng, "t2_wgrad", t.gP + half * 2 * D, 4 * D, nullptr, t.atomd[l], D, nullptr, N, 1.0f, G(aw.w_cn) + half * 2 * D * D, D, D)));
-    }
-    TRY((xty<8, 4>(eng, "t2_wgrad", t.barQ, 2 * D, nullptr, b->hb0, D, nullptr, Eu, 1.0f, G(aw.w_bond), D, D)));
-    TRY((xty<8, 4>(eng, "t2_wgrad", t.gQ, 2 * D, nullptr, t.hb0d, D, nullptr, Eu, 1.0f, G(aw.w_bond), D, D)));
-    if (Eb > 0 && b->hbc[l] != b->hbc[0]) {
-      TRY((xty<8, 4>(eng, "t2_wgrad", t.barQ, 2 * D, b->bn_und, b->hbc[l], D, nullptr, Eb, 1.0f, G(aw.w_bond), D, D)));
-      TRY((xty<8, 4>(eng, "t2_wgrad", t.barQ, 2 * D, b->bn_und, b->hb0, D, b->bn_und, Eb, -1.0f, G(aw.w_bond), D, D)));
-      TRY((xty<8, 4>(eng, "t2_wgrad", t.gQ, 2 * D, b->bn_und, t.hbcd[l], D, nullptr, Eb, 1.0f, G(aw.w_bond), D, D)));
-      TRY((xty<8, 4>(eng, "t2_wgrad", t.gQ, 2 * D, b->bn_und, t.hb0d, D, b->bn_und, Eb, -1.0f, G(aw.w_bond), D, D)));
-    }
-    if (eng->desc.mlp_out_bias && angles && l > 0) {   // constant shift of the bonds outside the bond graph: no tangent, bar(Q) only
-      TRY(bond_shift_wgrad(eng, b, t.barQ, aw.q_shift, G(aw.w_bond)));
+    if (wg) {
+      for (int half = 0; half < 2; ++half) {
+        TRY((xty<8, 4>(eng, "t2_wgrad", t.barP + half * 2 * D, 4 * D, nullptr, b->atom[l], D, nullptr, N, 1.0f, G(aw.w_cn) + half * 2 * D * D, D, D,
+                       half == 0 ? G(aw.b1) : nullptr)));
+        TRY((xty<8, 4>(eng, "t2_wgrad", t.gP + half * 2 * D, 4 * D, nullptr, t.atomd[l], D, nullptr, N, 1.0f, G(aw.w_cn) + half * 2 * D * D, D, D)));
+      }
+      TRY((xty<8, 4>(eng, "t2_wgrad", t.barQ, 2 * D, nullptr, b->hb0, D, nullptr, Eu, 1.0f, G(aw.w_bond), D, D)));
+      TRY((xty<8, 4>(eng, "t2_wgrad", t.gQ, 2 * D, nullptr, t.hb0d, D, nullptr, Eu, 1.0f, G(aw.w_bond), D, D)));
+      if (Eb > 0 && b->hbc[l] != b->hbc[0]) {
+        TRY((xty<8, 4>(eng, "t2_wgrad", t.barQ, 2 * D, b->bn_und, b->hbc[l], D, nullptr, Eb, 1.0f, G(aw.w_bond), D, D)));
+        TRY((xty<8, 4>(eng, "t2_wgrad", t.barQ, 2 * D, b->bn_und, b->hb0, D, b->bn_und, Eb, -1.0f, G(aw.w_bond), D, D)));
+        TRY((xty<8, 4>(eng, "t2_wgrad", t.gQ, 2 * D, b->bn_und, t.hbcd[l], D, nullptr, Eb, 1.0f, G(aw.w_bond), D, D)));
+        TRY((xty<8, 4>(eng, "t2_wgrad", t.gQ, 2 * D, b->bn_und, t.hb0d, D, b->bn_und, Eb, -1.0f, G(aw.w_bond), D, D)));
+      }
+      if (eng->desc.mlp_out_bias && angles && l > 0) {   // constant shift of the bonds outside the bond graph: no tangent, bar(Q) only
+        TRY(bond_shift_wgrad(eng, b, t.barQ, aw.q_shift, G(aw.w_bond)));
+      }
     }
     TRY(rows_gemm_in2(eng, "t2_gemm_tab", t.barP, 4 * D, aw.w_cn_t, aw.w_cn_t + 2 * D * D, t.bar_a, nullptr, N, 1));
     TRY(rows_gemm_in2(eng, "t2_gemm_tab", t.gP, 4 * D, aw.w_cn_t, aw.w_cn_t + 2 * D * D, t.g_a, nullptr, N, 1));
@@ -781,14 +790,16 @@ int run_backward2(chg_engine* eng, chg_batch* b) {
       LaunchScope ls(eng, "t2_scatter_z");
       hipLaunchKernelGGL(k2_scatter_z, wave_rows_grid(eng, (A + TILE_ROWS - 1) / TILE_ROWS), dim3(256), scatter_z_lds(), st, a);
     }
-    for (int half = 0; half < 2; ++half) {
-      TRY((xty<8, 4>(eng, "t2_wgrad", t.barR + half * 2 * D, 4 * D, nullptr, hrows, D, nullptr, Eb, 1.0f, G(w_bij) + half * 2 * D * D, D, D)));
-      TRY((xty<8, 4>(eng, "t2_wgrad", t.gR + half * 2 * D, 4 * D, nullptr, hrowsd, D, nullptr, Eb, 1.0f, G(w_bij) + half * 2 * D * D, D, D)));
+    if (wg) {
+      for (int half = 0; half < 2; ++half) {
+        TRY((xty<8, 4>(eng, "t2_wgrad", t.barR + half * 2 * D, 4 * D, nullptr, hrows, D, nullptr, Eb, 1.0f, G(w_bij) + half * 2 * D * D, D, D)));
+        TRY((xty<8, 4>(eng, "t2_wgrad", t.gR + half * 2 * D, 4 * D, nullptr, hrowsd, D, nullptr, Eb, 1.0f, G(w_bij) + half * 2 * D * D, D, D)));
+      }
+      TRY((xty<8, 4>(eng, "t2_wgrad", t.barS, 2 * D, nullptr, atoms, D, nullptr, N, 1.0f, G(w_ctr), D, D, G(b1))));
+      TRY((xty<8, 4>(eng, "t2_wgrad", t.gS, 2 * D, nullptr, atomsd, D, nullptr, N, 1.0f, G(w_ctr), D, D)));
+      TRY((xty<8, 4>(eng, "t2_wgrad", t.BZ, 2 * D, nullptr, angs, D, nullptr, A, 1.0f, G(w_ang), D, D)));
+      TRY((xty<8, 4>(eng, "t2_wgrad", t.GZ, 2 * D, nullptr, angsd, D, nullptr, A, 1.0f, G(w_ang), D, D)));
     }
-    TRY((xty<8, 4>(eng, "t2_wgrad", t.barS, 2 * D, nullptr, atoms, D, nullptr, N, 1.0f, G(w_ctr), D, D, G(b1))));
-    TRY((xty<8, 4>(eng, "t2_wgrad", t.gS, 2 * D, nullptr, atomsd, D, nullptr, N, 1.0f, G(w_ctr), D, D)));
-    TRY((xty<8, 4>(eng, "t2_wgrad", t.BZ, 2 * D, nullptr, angs, D, nullptr, A, 1.0f, G(w_ang), D, D)));
-    TRY((xty<8, 4>(eng, "t2_wgrad", t.GZ, 2 * D, nullptr, angsd, D, nullptr, A, 1.0f, G(w_ang), D, D)));
     TRY(rows_gemm_in2(eng, "t2_gemm_tab", t.barR, 4 * D, w_bij_t, w_bij_t + 2 * D * D, t.bar_b, b->bn_und, Eb, 1));
     TRY(rows_gemm_in2(eng, "t2_gemm_tab", t.gR, 4 * D, w_bij_t, w_bij_t + 2 * D * D, t.g_b, b->bn_und, Eb, 1));
     TRY(gemm("t2_gemm_tab", 128, 64, t.barS, 2 * D, nullptr, w_ctr_t, nullptr, nullptr, 0, t.bar_a, D, nullptr, N, 1));
@@ -830,9 +841,9 @@ int run_backward2(chg_engine* eng, chg_batch* b) {
       }
       const BCW& bw = w.bc[l];
       // hbc[l+1] = aggB . Wout^T + b_out + hbc[l]; its adjoints live in the node rows of bar_b / g_b; b_out reaches every bond (above)
-      if (eng->desc.mlp_out_bias) TRY(colsum(eng, t.bar_b, D, nullptr, 0, Eu, D, G(bw.b_out)));
-      TRY((xty<4, 4>(eng, "t2_wgrad", t.bar_b, D, b->bn_und, b->aggB_l[l], D, nullptr, Eb, 1.0f, G(bw.w_out), D, D)));
-      TRY((xty<4, 4>(eng, "t2_wgrad", t.g_b, D, b->bn_und, t.aggBd[l], D, nullptr, Eb, 1.0f, G(bw.w_out), D, D)));
+      if (wg && eng->desc.mlp_out_bias) TRY(colsum(eng, t.bar_b, D, nullptr, 0, Eu, D, G(bw.b_out)));
+      if (wg) TRY((xty<4, 4>(eng, "t2_wgrad", t.bar_b, D, b->bn_und, b->aggB_l[l], D, nullptr, Eb, 1.0f, G(bw.w_out), D, D)));
+      if (wg) TRY((xty<4, 4>(eng, "t2_wgrad", t.g_b, D, b->bn_und, t.aggBd[l], D, nullptr, Eb, 1.0f, G(bw.w_out), D, D)));
       TRY(gemm("t2_gemm_out", 64, 64, t.bar_b, D, b->bn_und, bw.w_out_t, nullptr, nullptr, 0, t.bar_agg, D, nullptr, Eb, 0));
       TRY(gemm("t2_gemm_out", 64, 64, t.g_b, D, b->bn_und, bw.w_out_t, nullptr, nullptr, 0, t.g_agg, D, nullptr, Eb, 0));
       if (fused) {
@@ -856,6 +867,7 @@ int run_backward2(chg_engine* eng, chg_batch* b) {
                        { LaunchScope ls(eng, "t2_bond_b");
                          hipLaunchKernelGGL((k2_angle<true, true>), angle_grid, dim3(BLOCK), t2_angle_lds<true>(), st, a);
                          HIP_TRY(eng, hipGetLastError()); }
+                       if (!wg) return CHG_OK;
                        TRY(xty_halves(eng, "t2_wgrad", a.BCG, a.H, A, G(bw.g.w2c), G(bw.g.w2g), G(bw.g.b2c), G(bw.g.b2g)));
                        return xty_halves(eng, "t2_wgrad", a.GCG, a.Hd, A, G(bw.g.w2c), G(bw.g.w2g));
                      }));
@@ -863,6 +875,8 @@ int run_backward2(chg_engine* eng, chg_batch* b) {
     TRY(atomconv_b(l));
   }
   TRY(check());
+
+  if (hvp) return CHG_OK;   // hvp_from_adjoints takes bar / G of the embeddings from here
 
   // ---- embeddings: 31 -> 64 linears (bar with basis, G with basis tangent), frequencies, atom embedding table ----
   if (Eu > 0) {
@@ -943,6 +957,8 @@ int train_set_lds(chg_engine* eng) {
   if ((s = set_lds(eng, k2_scatter_z, scatter_z_lds()))) return s;
   if ((s = set_lds(eng, k2_freq_grad_t, freq_grad_lds()))) return s;
   if ((s = set_lds(eng, k2_angle_freq_grad_t, angle_freq_grad_lds()))) return s;
+  if ((s = set_lds(eng, k_hvp_bond_t, hvp_bond_lds()))) return s;
+  if ((s = set_lds(eng, k_hvp_angle_t, hvp_angle_lds()))) return s;
   return CHG_OK;
 }
 
@@ -994,10 +1010,78 @@ int backward_compute(chg_engine* eng, chg_batch* b, const float* energy_cotangen
     for (int l = 0; l < b->L; ++l) TRY(atomconv_q_table(eng, b, l));
     b->q_tables = true;
   }
-  TRY(second_order ? run_backward2(eng, b) : run_backward(eng, b));
+  TRY(second_order ? run_backward2(eng, b, false) : run_backward(eng, b));
   // the b3 slot joins the blob ON THE DEVICE, so that a following all-reduce sums it over the ranks like every other entry (it used
   // to be written into the host copy after the collective: every rank then applied its LOCAL value / world -- ADVICE r03)
   HIP_TRY(eng, hipMemcpyAsync(b->t_grad + (eng->w.mlp_b3 - eng->d_weights), &b->h_g_b3, sizeof(float), hipMemcpyHostToDevice, eng->stream));
+  return CHG_OK;
+}
+
+// HVP mode, after run_backward2(.., hvp = true): bar / G of the embeddings -> adjoints of r, rdot, theta, thetadot (kernels_hvp.h) ->
+// per-edge operands of k_edge_force, whose "force" is -H u
+int hvp_from_adjoints(chg_engine* eng, chg_batch* b) {
+  const Weights& w = eng->w;
+  Train2& t = *b->t2;
+  hipStream_t st = eng->stream;
+  const int Ed = b->Ed, Eu = b->Eu, A = b->A, Eb = b->Eb;
+  if (Ed == 0) return CHG_OK;
+  const double pc = eng->desc.cutoff_coeff;
+  const Envelope env{(float)(-(pc + 1) * (pc + 2) / 2), (float)(pc * (pc + 2)), (float)(-pc * (pc + 1) / 2), eng->desc.cutoff_coeff};
+  const bool fused = t2_fused();   // the fused sweep leaves G(wag), G(wbg) in the batch (the force sweep's first-order adjoints)
+  const float* g_wag = fused ? b->Gwag : t.g_wag;
+  const float* g_wbg = fused ? b->Gwbgc : t.g_wbg;
+  {
+    LaunchScope ls(eng, "hvp_bond");
+    HvpBondArgs a{Eu, nullptr, b->ev, t.vd4, b->u_u2d, w.freq_ag, eng->desc.atom_graph_cutoff, env, t.bar_b, t.g_b, w.w_bond_emb,
+                  t.bar_wag, g_wag, w.w_wag, t.hvp_gu, t.hvp_grk};
+    hipLaunchKernelGGL(k_hvp_bond_t, dim3(grid_for(Eu, 2 * eng->num_cus)), dim3(BLOCK), hvp_bond_lds(), st, a);
+    if (Eb > 0) {
+      HvpBondArgs c{Eb, b->bn_und, b->ev, t.vd4, b->u_u2d, w.freq_bg, eng->desc.bond_graph_cutoff, env, t.bar_wbg, g_wbg, w.w_wbg,
+                    nullptr, nullptr, nullptr, t.hvp_gu, t.hvp_grk};
+      hipLaunchKernelGGL(k_hvp_bond_t, dim3(grid_for(Eb, 2 * eng->num_cus)), dim3(BLOCK), hvp_bond_lds(), st, c);
+    }
+    HIP_TRY(eng, hipGetLastError());
+  }
+  if (A > 0) {
+    LaunchScope ls(eng, "hvp_angle");
+    hipLaunchKernelGGL(k_hvp_angle_t, dim3(grid_for(A, 2 * eng->num_cus)), dim3(BLOCK), hvp_angle_lds(), st, t.bar_ang, t.g_ang, w.w_ang_emb,
+                       t.th2, w.freq_ang, b->ev, t.vd4, b->a_d1, b->a_d2, b->e_d2u, t.hvp_gu, t.hvp_grk, A);
+    HIP_TRY(eng, hipGetLastError());
+  }
+  ForceArgs f{};
+  f.ev = b->ev; f.eu = b->eu; f.Gu = t.hvp_gu; f.Grk = t.hvp_grk;
+  f.e_center = b->e_center; f.e_d2u = b->e_d2u; f.e_owner = b->e_owner; f.e_rev = b->e_rev; f.u_u2d = b->u_u2d;
+  f.n_edges = Ed; f.force = t.hvp_out; f.virial = t.hvp_vir;
+  LaunchScope ls(eng, "hvp_scatter");
+  hipLaunchKernelGGL(k_edge_force, g1(Ed, EF_EDGES_PER_BLOCK), dim3(256), 0, st, f);
+  HIP_TRY(eng, hipGetLastError());
+  return CHG_OK;
+}
+
+// H u of every structure's total energy (fixed graph, fixed cell) along direction [N,3] -> hvp [N,3], both host
+int hvp_compute(chg_engine* eng, chg_batch* b, const float* direction, float* hvp) {
+  if (b->last_task == 0) { eng->err = "chg_hessian_vector: run chg_predict on this batch first (the sweep reuses its activations)"; return CHG_EINVAL; }
+  if ((int)b->h_atom_off.size() != b->B + 1) { eng->err = "chg_hessian_vector: batch has no host atom offsets"; return CHG_EINVAL; }
+#ifndef CHG_WIDE_RANGE
+  if (b->wide_range) return chgh_wide::hvp_compute(eng, b, direction, hvp);
+#endif
+  TRY(ensure_train_buffers(eng, b));
+  // seeds: no energy or magmom cotangent, ux = u, Wst = 0.  The sweep reuses the first-order adjoints of the force sweep (chg_backward)
+  if (!b->seed1_adjoints) TRY(run_predict(eng, b, b->last_task | CHG_TASK_F));
+  TRY(ensure_train2_buffers(eng, b));
+  TRY(zero(eng, b->t_cot, sizeof(float) * b->B));
+  b->t_has_mcot = false;
+  HIP_TRY(eng, hipMemcpyAsync(b->t2->ux, direction, sizeof(float) * 3 * (size_t)b->N, hipMemcpyHostToDevice, eng->stream));
+  TRY(zero(eng, b->t2->Wst, sizeof(float) * 9 * (size_t)b->B));
+  if (b->Ed > 0 && !b->q_tables) {
+    for (int l = 0; l < b->L; ++l) TRY(atomconv_q_table(eng, b, l));
+    b->q_tables = true;
+  }
+  TRY(run_backward2(eng, b, true));
+  TRY(hvp_from_adjoints(eng, b));
+  HIP_TRY(eng, hipMemcpyAsync(hvp, b->t2->hvp_out, sizeof(float) * 3 * (size_t)b->N, hipMemcpyDeviceToHost, eng->stream));
+  HIP_TRY(eng, hipStreamSynchronize(eng->stream));
+  for (size_t i = 0; i < (size_t)3 * b->N; ++i) hvp[i] = -hvp[i];   // k_edge_force forms -dEdot/dx
   return CHG_OK;
 }
 
@@ -1054,6 +1138,22 @@ int chg_backward(chg_engine* eng, chg_batch* b, const float* energy_cotangent, c
 int chg_backward_allreduce(chg_engine* eng, chg_batch* b, const float* energy_cotangent, const float* magmom_cotangent,
                            const float* force_cotangent, const float* stress_cotangent, chg_comm* comm, float* grad_blob) {
   return backward_impl(eng, b, energy_cotangent, magmom_cotangent, force_cotangent, stress_cotangent, comm, grad_blob);
+}
+
+int chg_hessian_vector(chg_engine* eng, chg_batch* b, const float* direction, float* hvp) {
+  if (!eng || !b || !direction || !hvp) return CHG_EINVAL;
+  HIP_TRY(eng, hipSetDevice(eng->device));
+  const int status = hvp_compute(eng, b, direction, hvp);
+  if (status != CHG_OK) return status;
+  // a product sweep that left the f16 operand range gives non-finite rows: the batch moves to the wide-range sweeps (as at
+  // chg_batch_download) and the product is formed again there
+  bool finite = true;
+  for (int64_t i = 0; i < 3 * (int64_t)b->N && finite; ++i) finite = std::isfinite(hvp[i]);
+  if (finite || b->wide_range) return CHG_OK;
+  b->wide_range = true;
+  if (b->graph_exec) { hipGraphExecDestroy(b->graph_exec); b->graph_exec = nullptr; }
+  TRY(chgh_wide::run_predict(eng, b, b->last_task | CHG_TASK_F));
+  return chgh_wide::hvp_compute(eng, b, direction, hvp);
 }
 
 }  // extern "C"

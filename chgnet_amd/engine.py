@@ -290,6 +290,18 @@ class Engine:
             self._check(self.lib.chg_backward(self.handle, batch.handle, ptr(cot), ptr(mcot), ptr(fcot), ptr(scot), _fp(grad)))
         return grad
 
+    def hessian_vector(self, batch: DeviceBatch, direction) -> np.ndarray:
+        """H u for every structure of ``batch`` (chg_hessian_vector): ``direction`` [N,3] (A) over all atoms of the batch ->
+        [N,3] float32 (eV/A^2), the second derivative of each structure's total energy on the batch's fixed graph and cell.
+        Needs a preceding ``predict`` on ``batch``; overwrites its gradient workspace."""
+        n = batch.packed.n_atoms
+        u = np.ascontiguousarray(direction, np.float32)
+        if u.shape != (n, 3):
+            raise ValueError(f"direction has shape {u.shape}; the batch has {n} atoms: expected ({n}, 3)")
+        out = np.empty((n, 3), np.float32)
+        self._check(self.lib.chg_hessian_vector(self.handle, batch.handle, _fp(u), _fp(out)))
+        return out
+
     def all_gather_energy(self, batch: DeviceBatch, comm, width: int) -> np.ndarray:
         """[nranks, width] table of the per-structure energies of every rank's batch (zero-padded to ``width``), gathered
         from HBM on the engine's stream (chg_batch_all_gather_energy).  After ``predict``."""

@@ -376,6 +376,74 @@ class CHGNet:
         predictions = _run_pipelined(chunks, pack_pinned, launch, collect, run)   # the next chunk is packed during the sweep
         return predictions[0] if len(graphs) == 1 else predictions
 
+    # ---- second derivatives: Hessian-vector products and force constants (csrc/kernels_hvp.h) ----------------
+    def _graph_of(self, item):
+        if _is_graph(item):
+            return item
+        if not _is_structure(item):
+            raise TypeError(f"{type(item)=}: expected a Structure or a CrystalGraph")
+        if self.graph_converter is None:
+            raise ValueError("graph_converter cannot be None!")
+        return self.graph_converter(item)     # isolated atoms: the converter's error / warning, as in predict_structure
+
+    def _hvp_graphs(self, graphs: list, directions: list, batch_size: int, min_atoms: int) -> list[np.ndarray]:
+        eng = self.engine
+
+        def run(idx):
+            batch = eng.upload(pack_batch([graphs[i] for i in idx]))
+            try:
+                eng.predict(batch, "ef")
+                h = eng.hessian_vector(batch, np.concatenate([directions[i] for i in idx]))
+                off = batch.packed.atom_off
+            finally:
+                batch.free()
+            return [h[off[k]:off[k + 1]].copy() for k in range(len(idx))]
+
+        out: list[np.ndarray] = []
+        for a, b in _plan_chunks([len(g.atomic_number) for g in graphs], batch_size, min_atoms):
+            out.extend(_run_splitting(run, list(range(a, b))))
+        return out
+
+    def hessian_vector_product(self, structures_or_graphs, directions, *, batch_size: int = 16):
+        """Exact H u per structure: ``sum_j d2 E / (dx_i dx_j) u_j`` with E the structure's TOTAL energy (eV; for an intensive
+        model the per-atom energy times n), x the cartesian positions at fixed cell, on the fixed graph (no neighbour-list
+        rebuild) -- the second derivative of the function whose gradient gives the forces.  ``directions``: one [n,3] array (A)
+        per structure.  Returns one [n,3] float32 array (eV/A^2) per structure (a bare array for a single structure or graph).
+        ``batch_size`` as in ``predict_structure``."""
+        single = _is_structure(structures_or_graphs) or _is_graph(structures_or_graphs)
+        items = [structures_or_graphs] if single else list(structures_or_graphs)
+        dirs = [directions] if single else list(directions)
+        if len(dirs) != len(items):
+            raise ValueError(f"{len(items)} structures but {len(dirs)} directions")
+        graphs = [self._graph_of(x) for x in items]
+        for i, (g, d) in enumerate(zip(graphs, dirs)):
+            n = len(g.atomic_number)
+            dirs[i] = np.asarray(d, np.float32)
+            if dirs[i].shape != (n, 3):
+                raise ValueError(f"direction {i} has shape {dirs[i].shape}; its structure has {n} atoms: expected ({n}, 3)")
+        out = self._hvp_graphs(graphs, dirs, batch_size, self.min_atoms_per_batch)
+        return out[0] if single else out
+
+    def predict_hessian(self, structure, *, symmetrize: bool = True, max_atoms_per_batch: int = 16384):
+        """Force constants ``d2 E / (dx_i dx_j)`` (eV/A^2, float64 [3n,3n], indexed 3i+alpha) of each structure, from 3n exact
+        Hessian-vector products along the unit directions (same semantics as ``hessian_vector_product``).  The 3n replicas run
+        in device batches of at most ``max_atoms_per_batch`` atoms.  ``symmetrize``: return (H + H^T) / 2.  A list in, a list out."""
+        single = _is_structure(structure) or _is_graph(structure)
+        items = [structure] if single else list(structure)
+        out = []
+        for g in [self._graph_of(x) for x in items]:
+            n = len(g.atomic_number)
+            eye = np.eye(3 * n, dtype=np.float32).reshape(3 * n, n, 3)
+            h = np.zeros((3 * n, 3 * n), np.float64)
+            per = max(1, int(max_atoms_per_batch) // max(n, 1))
+            for c0 in range(0, 3 * n, per):
+                cols = range(c0, min(3 * n, c0 + per))
+                res = self._hvp_graphs([g] * len(cols), [eye[c] for c in cols], len(cols), 0)
+                for c, r in zip(cols, res):
+                    h[:, c] = r.reshape(-1)
+            out.append(0.5 * (h + h.T) if symmetrize else h)
+        return out[0] if single else out
+
     # ---- (de)serialisation (model.py:667-745) ----------------------------------------------------------
     def as_dict(self) -> dict:
         return {"state_dict": self._state_dict, "model_args": self.model_args}

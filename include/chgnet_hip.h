@@ -107,7 +107,8 @@ typedef struct chg_out_host {
 } chg_out_host;
 
 /* Version of this interface: bumped whenever a struct of this header grows or an entry point changes meaning (chg_model_desc gained
- * n_mlp_hidden / mlp_out_bias at 2; chg_batch_build_predict arrived at 3; the chg_relax_* entry points at 4; the chg_md_* entry points at 5).  A binding compiled against another value must refuse the
+ * n_mlp_hidden / mlp_out_bias at 2; chg_batch_build_predict arrived at 3; the chg_relax_* entry points at 4; the chg_md_* entry points at 5;
+ * chg_hessian_vector was added at 5 without a bump: a new entry point only, no struct or signature changed).  A binding compiled against another value must refuse the
  * library: chg_engine_create COPIES *desc, so an older, shorter chg_model_desc would be read past its end. */
 #define CHG_ABI_VERSION 5
 int chg_abi_version(void);
@@ -196,6 +197,12 @@ int chg_backward(chg_engine* eng, chg_batch* batch, const float* energy_cotangen
 struct chg_comm;
 int chg_backward_allreduce(chg_engine* eng, chg_batch* batch, const float* energy_cotangent, const float* magmom_cotangent,
                            const float* force_cotangent, const float* stress_cotangent, struct chg_comm* comm, float* grad_blob);
+/* H u per structure: hvp[i] = sum_j d2 E_b / (dx_i dx_j) u_j over the atoms j of i's structure (E_b the total energy, eV; fixed
+ * neighbour list; cartesian positions, cell fixed).  direction: host [N,3] (A); hvp: host [N,3] (eV/A^2).  After chg_predict on
+ * `batch` (runs the force prediction first if the last one was energy-only).  Overwrites the gradient workspace.  Synchronous.
+ * The tangent + two-adjoint sweep of chg_backward without its weight-gradient contractions, then the adjoints of the bond lengths
+ * and angles (csrc/kernels_hvp.h) scattered to the atoms. */
+int chg_hessian_vector(chg_engine* eng, chg_batch* batch, const float* direction, float* hvp);
 /* All-gather of the batch's per-structure energies (after chg_predict) from HBM on the engine's stream: every rank
  * contributes `width` floats (its n_struct energies, zero-padded), table: host [nranks * width] in rank order. */
 int chg_batch_all_gather_energy(chg_engine* eng, chg_batch* batch, struct chg_comm* comm, int64_t width, float* table);
