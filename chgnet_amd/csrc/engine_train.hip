@@ -16,16 +16,10 @@ struct Train2 {
   float *X6, *X6d, *X3, *X3d, *X4, *X4d, *th2;       // bases + tangents [Eu,32] x4, [A,32] x2, [A,2]
   float *hb0d, *wagd, *wbgcd;                        // tangent embeddings [Eu,64] x2, [Eb,64]
   float *atomd[MAX_CONV + 1], *hbcd[MAX_CONV + 1], *angd[MAX_CONV], *aggd[MAX_CONV], *aggBd[MAX_CONV];
-  float *Pd, *Qd, *Rd, *Sd, *ZA, *ZAd;               // tangent tables [N,256] [Eu,128] [Eb,256] [N,128]; W_ang . ang [A,128] x2
-  float *Z, *Zd, *H, *Hd, *CG, *CGd, *BCG, *GCG, *BH, *GH, *BZ, *GZ;   // [R,128]  (Z..CGd: the CURRENT layer's rows, see cache)
-  float* scratch6[6];                                // one shared set of Z, Zd, H, Hd, CG, CGd (recompute mode)
-  // per-layer rows kept from the tangent forward for the reverse sweep when device memory allows (layer ids: AtomConv l -> l,
-  // BondConv l -> L + l, AngleUpdate l -> 2L + l); otherwise the reverse sweep recomputes them into scratch6
-  float* cache[3 * MAX_CONV][6];
-  bool cached = false;
-  float *bar_a, *g_a, *bar_b, *g_b, *bar_wag, *g_wag, *bar_wbg, *g_wbg, *bar_ang, *g_ang, *bar_agg, *g_agg;
-  float *barP, *gP, *barQ, *gQ, *barR, *gR, *barS, *gS;
-  float *gP0, *gR0, *gS0;                            // this workspace's own G(P), G(R), G(S) (gP / gR / gS may point into the batch)
+  float *Pd, *Qd, *Rd, *Sd;                          // tangent tables [N,256] [Eu,128] [Eb,256] [N,128]
+  float *H, *Hd, *BCG, *GCG, *BZ, *GZ;               // [R,128] rows the tile kernels leave for the weight-gradient contractions
+  float *bar_a, *g_a, *bar_b, *g_b, *bar_wag, *bar_wbg, *bar_ang, *g_ang, *bar_agg, *g_agg;
+  float *barP, *barQ, *gQ, *barR, *barS;             // table adjoints of the layer being swept
   float* ro[26];                                     // readout planes [N,64]
   float *zero_lo, *zero_hi;                          // range cleared at the start of every call
   float *hvp_gu, *hvp_grk, *hvp_out, *hvp_vir;       // HVP mode: k_edge_force operands [Ed,4] [Eu], H u as its "force" -H u [N,3], virial [B,9]
@@ -351,15 +345,7 @@ int run_backward(chg_engine* eng, chg_batch* b) {
   return CHG_OK;
 }
 
-
-
 void free_train2(chg_batch* b) { delete b->t2; b->t2 = nullptr; }
-
-// fused tile kernels (kernels_train2_tile.h); CHGNET_T2_UNFUSED=1 keeps the row-array pipeline of kernels_train2.h (A/B, debugging)
-bool t2_fused() {
-  static const bool fused = !std::getenv("CHGNET_T2_UNFUSED");
-  return fused;
-}
 
 void layout_train2(chg_batch* b, Train2& t, Carver& c) {
   const size_t B = b->B, N = b->N, Ed = b->Ed, Eu = b->Eu, A = b->A, Eb = b->Eb, R = std::max(Ed, A);
@@ -373,28 +359,9 @@ void layout_train2(chg_batch* b, Train2& t, Carver& c) {
   for (int l = 0; l < L; ++l) t.hbcd[l] = c.take<float>(Eb * D);
   for (int l = 0; l < L - 1; ++l) t.angd[l] = c.take<float>(A * D);
   t.Pd = c.take<float>(N * 4 * D); t.Qd = c.take<float>(Eu * 2 * D); t.Rd = c.take<float>(Eb * 4 * D); t.Sd = c.take<float>(N * 2 * D);
-  // the fused sweep keeps six [rows,128] arrays (the operands of the weight-gradient contractions); the row-array pipeline sixteen
-  // here and, when memory allows, a cache of six per layer
-  const bool fused = t2_fused();
-  t.ZA = t.ZAd = t.BH = t.GH = nullptr;
-  if (!fused) { t.ZA = c.take<float>(A * 2 * D); t.ZAd = c.take<float>(A * 2 * D); }
-  for (int q = 0; q < 6; ++q) t.scratch6[q] = (!fused || q == 2 || q == 3) ? c.take<float>(R * 2 * D) : nullptr;   // fused: H, Hd dumps
-  float** rows[] = {&t.BCG, &t.GCG, &t.BZ, &t.GZ};
+  // the six [rows,128] arrays the tile kernels leave for the weight-gradient contractions
+  float** rows[] = {&t.H, &t.Hd, &t.BCG, &t.GCG, &t.BZ, &t.GZ};
   for (float** r : rows) *r = c.take<float>(R * 2 * D);
-  if (!fused) { t.BH = c.take<float>(R * 2 * D); t.GH = c.take<float>(R * 2 * D); }
-  if (fused) t.cached = false;
-  for (int id = 0; id < 3 * MAX_CONV; ++id)
-    for (int q = 0; q < 6; ++q) t.cache[id][q] = nullptr;
-  if (t.cached) {
-    for (int l = 0; l < L; ++l)
-      for (int q = 0; q < 6; ++q) t.cache[l][q] = c.take<float>(Ed * 2 * D);
-    if (A > 0) {
-      for (int l = 0; l < L - 1; ++l)
-        for (int q = 0; q < 6; ++q) t.cache[L + l][q] = c.take<float>(A * 2 * D);
-      for (int l = 0; l < L - 2; ++l)
-        for (int q = 4; q < 6; ++q) t.cache[2 * L + l][q] = c.take<float>(A * 2 * D);   // single layer: only c|g (= z) and its tangent
-    }
-  }
   t.bar_agg = c.take<float>(std::max(N, Eb) * D); t.g_agg = c.take<float>(std::max(N, Eb) * D);
   t.bar_a = c.take<float>(N * D); t.g_a = c.take<float>(N * D);
   for (int i = 0; i < 26; ++i) t.ro[i] = c.take<float>(N * D);
@@ -402,39 +369,22 @@ void layout_train2(chg_batch* b, Train2& t, Carver& c) {
   t.zero_lo = c.take<float>(0);
   for (int l = 0; l < L; ++l) t.aggd[l] = c.take<float>(N * D);
   for (int l = 0; l < L - 1; ++l) t.aggBd[l] = c.take<float>(Eb * D);
-  t.bar_b = c.take<float>(Eu * D); t.g_b = c.take<float>(Eu * D); t.bar_wag = c.take<float>(Eu * D); t.g_wag = c.take<float>(Eu * D);
-  t.bar_wbg = c.take<float>(Eb * D); t.g_wbg = c.take<float>(Eb * D); t.bar_ang = c.take<float>(A * D); t.g_ang = c.take<float>(A * D);
+  t.bar_b = c.take<float>(Eu * D); t.g_b = c.take<float>(Eu * D); t.bar_wag = c.take<float>(Eu * D);
+  t.bar_wbg = c.take<float>(Eb * D); t.bar_ang = c.take<float>(A * D); t.g_ang = c.take<float>(A * D);
   t.hvp_gu = c.take<float>(Ed * 4); t.hvp_grk = c.take<float>(Eu); t.hvp_out = c.take<float>(3 * N); t.hvp_vir = c.take<float>(9 * B);
   t.zero_hi = c.take<float>(0);
-  // table gradients: cleared before every layer
-  t.barP = c.take<float>(N * 4 * D); t.gP = c.take<float>(N * 4 * D); t.barQ = c.take<float>(Eu * 2 * D); t.gQ = c.take<float>(Eu * 2 * D);
-  t.barR = c.take<float>(Eb * 4 * D); t.gR = c.take<float>(Eb * 4 * D); t.barS = c.take<float>(N * 2 * D); t.gS = c.take<float>(N * 2 * D);
-  t.gP0 = t.gP; t.gR0 = t.gR; t.gS0 = t.gS;
+  // table adjoints of the layer being swept (G(P), G(R), G(S) are the force sweep's, in the batch)
+  t.barP = c.take<float>(N * 4 * D); t.barQ = c.take<float>(Eu * 2 * D); t.gQ = c.take<float>(Eu * 2 * D);
+  t.barR = c.take<float>(Eb * 4 * D); t.barS = c.take<float>(N * 2 * D);
 }
 
 int ensure_train2_buffers(chg_engine* eng, chg_batch* b) {
   if (b->t2) return CHG_OK;
   Train2* t = new (std::nothrow) Train2();
   if (!t) return CHG_ENOMEM;
-  // keep the per-layer rows of the tangent forward for the reverse sweep if that still leaves a quarter of the free memory
-  size_t total = 0;
-  {
-    size_t free_b = 0, total_b = 0;
-    hipMemGetInfo(&free_b, &total_b);
-    {
-      std::lock_guard<std::mutex> lk(eng->pool_mu);
-      for (auto& a : eng->work_pool) free_b += a.second;
-    }
-    t->cached = true;
-    Carver cc{nullptr};
-    layout_train2(b, *t, cc);
-    const size_t want = (cc.pos + 255) & ~size_t(255);
-    const size_t budget = eng->memory_limit ? std::min(free_b, eng->memory_limit) : free_b;
-    if (std::getenv("CHGNET_TRAIN_NO_CACHE") || want > budget - budget / 4) t->cached = false;
-  }
   Carver c{nullptr};
   layout_train2(b, *t, c);
-  total = (c.pos + 255) & ~size_t(255);
+  const size_t total = (c.pos + 255) & ~size_t(255);
   if (eng->memory_limit && total + b->arena_bytes + b->train_bytes > eng->memory_limit) {
     delete t;
     eng->err = "chg_backward: second-order training workspace of " + std::to_string(total) + " bytes exceeds the engine's memory limit";
@@ -472,22 +422,9 @@ int run_backward2(chg_engine* eng, chg_batch* b, bool hvp) {
                   const float* resid, int ldr, float* Y, int ldy, const int* out_idx, int rows, int acc) {
     return rows_gemm(eng, label, K, NOUT, X, ldx, in_idx, Wt, bias, resid, ldr, Y, ldy, out_idx, rows, acc);
   };
-  // Y[:, 0:64 | 64:128] = X[:, 0:64 | 64:128] . [Wc ; Wg]^T   (the two 64 x 64 second-layer blocks of a gated MLP)
-  auto gemm_pair = [&](const float* X, const float* Wc, const float* Wg, const float* bc, const float* bg, float* Y, int rows) -> int {
-    TRY(gemm("t2_gemm_w2", 64, 64, X, 2 * D, nullptr, Wc, bc, nullptr, 0, Y, 2 * D, nullptr, rows, 0));
-    return gemm("t2_gemm_w2", 64, 64, X + D, 2 * D, nullptr, Wg, bg, nullptr, 0, Y + D, 2 * D, nullptr, rows, 0);
-  };
   auto check = [&]() -> int { HIP_TRY(eng, hipGetLastError()); return CHG_OK; };
-  // The fused sweep (t2_fused) does not re-form the G adjoints (seed 1) of quantities that only leave it: those are the first-order adjoints the
-  // force sweep of chg_predict left in the batch (chg_backward makes sure that sweep has run): Gwag, Gwbgc and, per layer, GP / GR / GS.
-  const bool fused = t2_fused();
-  const float* g_wag = fused ? b->Gwag : t.g_wag;
-  const float* g_wbg = fused ? b->Gwbgc : t.g_wbg;
-  auto table_adjoints_of = [&](int atom_layer, int angle_slot) {   // where G(P) / G(R), G(S) of the layer being swept live
-    t.gP = (fused && atom_layer >= 0) ? b->GP_l[atom_layer] : t.gP0;
-    t.gR = (fused && angle_slot >= 0) ? b->GR_l[angle_slot] : t.gR0;
-    t.gS = (fused && angle_slot >= 0) ? b->GS_l[angle_slot] : t.gS0;
-  };
+  // The sweep does not re-form the G adjoints (seed 1) of quantities that only leave it: those are the first-order adjoints the force
+  // sweep of chg_predict left in the batch (chg_backward makes sure that sweep has run): Gwag, Gwbgc and, per layer, GP / GR / GS.
 
   // ---- direction -> tangent of geometry, bases, embeddings ---------------------------------------------
   if (Ed > 0) {
@@ -522,13 +459,6 @@ int run_backward2(chg_engine* eng, chg_batch* b, bool hvp) {
   }
   TRY(check());
 
-  // rows of the layer being worked on: its cache slot (filled by the tangent forward, reused by the reverse sweep) or the scratch set
-  bool reverse = false;
-  auto select_rows = [&](int id) -> bool {      // returns true when the rows are already there (reverse sweep, cached)
-    float** dst[6] = {&t.Z, &t.Zd, &t.H, &t.Hd, &t.CG, &t.CGd};
-    for (int q = 0; q < 6; ++q) *dst[q] = (t.cached && t.cache[id][q]) ? t.cache[id][q] : t.scratch6[q];
-    return t.cached && reverse;
-  };
   // ---- per-layer pieces ------------------------------------------------------------------------------------
   // tangent tables of AtomConv l:  Pd = atomd . [Wc;Wn]^T,  Qd = hbd . Wb^T  (node rows from hbcd[l])
   auto atom_tables_t = [&](int l) -> int {
@@ -539,39 +469,6 @@ int run_backward2(chg_engine* eng, chg_batch* b, bool hvp) {
       TRY(gemm("t2_gemm_tab", 64, 128, t.hbcd[l], D, nullptr, aw.w_bond, nullptr, nullptr, 0, t.Qd, 2 * D, b->bn_und, Eb, 0));
     return CHG_OK;
   };
-  // z, zd (and the hidden activations) of AtomConv l for every directed edge (centre-major order), then c|g and tangents
-  auto atom_rows = [&](int l) -> int {
-    const ACW& aw = w.ac[l];
-    if (select_rows(l)) return CHG_OK;
-    TRY(atom_tables_t(l));
-    GatherZArgs a{};
-    a.rows = Ed; a.t0 = b->Pl[l]; a.t1 = b->Pl[l]; a.t2 = b->Ql[l]; a.d0 = t.Pd; a.d1 = t.Pd; a.d2 = t.Qd;
-    a.ld0 = 4 * D; a.ld1 = 4 * D; a.ld2 = 2 * D; a.off0 = 0; a.off1 = 2 * D; a.off2 = 0;
-    a.i0 = b->e_center; a.i1 = b->e_nbr; a.i2 = b->e_d2u; a.hidden = 1; a.Z = t.Z; a.Zd = t.Zd; a.H = t.H; a.Hd = t.Hd;
-    { LaunchScope ls(eng, "t2_gather_z");
-      hipLaunchKernelGGL(k2_gather_z, wave_rows_grid(eng, Ed), dim3(256), 0, st, a); }
-    TRY(gemm_pair(t.H, aw.g.w2c, aw.g.w2g, aw.g.b2c, aw.g.b2g, t.CG, Ed));
-    return gemm_pair(t.Hd, aw.g.w2c, aw.g.w2g, nullptr, nullptr, t.CGd, Ed);
-  };
-  // the same for BondConv (hidden) / AngleUpdate (single layer) of slot; hrows / atoms / angs are the layer's inputs
-  auto angle_rows = [&](int slot, bool hidden, const float* w_bij, const float* w_ctr, const float* w_ang, const GatedW& g, const float* hrowsd,
-                        const float* atomsd, const float* angs, const float* angsd) -> int {
-    if (select_rows(slot < L ? L + slot : 2 * L + (slot - L))) return CHG_OK;
-    TRY(rows_gemm_out2(eng, "t2_gemm_tab", hrowsd, nullptr, w_bij, w_bij + 2 * D * D, nullptr, t.Rd, 4 * D, Eb));
-    TRY(gemm("t2_gemm_tab", 64, 128, atomsd, D, nullptr, w_ctr, nullptr, nullptr, 0, t.Sd, 2 * D, nullptr, N, 0));
-    TRY(gemm("t2_gemm_ang", 64, 128, angs, D, nullptr, w_ang, nullptr, nullptr, 0, t.ZA, 2 * D, nullptr, A, 0));
-    TRY(gemm("t2_gemm_ang", 64, 128, angsd, D, nullptr, w_ang, nullptr, nullptr, 0, t.ZAd, 2 * D, nullptr, A, 0));
-    GatherZArgs a{};
-    a.rows = A; a.t0 = b->Rl[slot]; a.t1 = b->Rl[slot]; a.t2 = b->Sl[slot]; a.d0 = t.Rd; a.d1 = t.Rd; a.d2 = t.Sd;
-    a.ld0 = 4 * D; a.ld1 = 4 * D; a.ld2 = 2 * D; a.off0 = 0; a.off1 = 2 * D; a.off2 = 0;
-    a.i0 = b->a_b1c; a.i1 = b->a_b2c; a.i2 = b->a_ctr; a.add = t.ZA; a.addd = t.ZAd; a.hidden = hidden ? 1 : 0;
-    a.Z = hidden ? t.Z : t.CG; a.Zd = hidden ? t.Zd : t.CGd; a.H = t.H; a.Hd = t.Hd;   // single layer: c|g IS z
-    { LaunchScope ls(eng, "t2_gather_z");
-      hipLaunchKernelGGL(k2_gather_z, wave_rows_grid(eng, A), dim3(256), 0, st, a); }
-    if (!hidden) return CHG_OK;
-    TRY(gemm_pair(t.H, g.w2c, g.w2g, g.b2c, g.b2g, t.CG, A));
-    return gemm_pair(t.Hd, g.w2c, g.w2g, nullptr, nullptr, t.CGd, A);
-  };
 
   // ---- tangent forward ---------------------------------------------------------------------------------------
   auto atom2_args = [&](int l) {
@@ -579,7 +476,7 @@ int run_backward2(chg_engine* eng, chg_batch* b, bool hvp) {
     a.n_edges = Ed; a.e_center = b->p_center; a.e_nbr = b->p_nbr;
     a.P = b->Pl[l]; a.Q = b->Ql[l]; a.Pd = t.Pd; a.Qd = t.Qd; a.gw = w.ac[l].g; a.wag = b->wag; a.wagd = t.wagd;
     a.aggd = t.aggd[l]; a.bar_agg = t.bar_agg; a.g_agg = t.g_agg; a.bar_w = t.bar_wag;
-    a.H = t.scratch6[2]; a.Hd = t.scratch6[3]; a.BCG = t.BCG; a.GCG = t.GCG; a.park0 = t.BZ; a.park1 = t.GZ;
+    a.H = t.H; a.Hd = t.Hd; a.BCG = t.BCG; a.GCG = t.GCG; a.park0 = t.BZ; a.park1 = t.GZ;
     a.barP = t.barP; a.barQ = t.barQ; a.gQ = t.gQ; a.g_ln = G(w.ac[l].g.ln1_g);
     return a;
   };
@@ -594,25 +491,18 @@ int run_backward2(chg_engine* eng, chg_batch* b, bool hvp) {
     a.R = b->Rl[slot]; a.S = b->Sl[slot]; a.Rd = t.Rd; a.Sd = t.Sd; a.ang = angs; a.angd = angsd; a.w_ang = w_ang; a.gw = g;
     a.w = b->wbgc; a.wd = t.wbgcd; a.bar_agg = t.bar_agg; a.g_agg = t.g_agg; a.bar_w = t.bar_wbg;
     a.bar_ang = t.bar_ang; a.g_ang = t.g_ang;
-    a.H = t.scratch6[2]; a.Hd = t.scratch6[3]; a.BCG = t.BCG; a.GCG = t.GCG; a.BZ = t.BZ; a.GZ = t.GZ;
+    a.H = t.H; a.Hd = t.Hd; a.BCG = t.BCG; a.GCG = t.GCG; a.BZ = t.BZ; a.GZ = t.GZ;
     a.barR = t.barR; a.barS = t.barS; a.g_ln = G(g.ln1_g);
     return a;
   };
   const dim3 angle_grid(tile_grid(eng, std::max(A, 1)));
   auto atomconv_t = [&](int l) -> int {
     const ACW& aw = w.ac[l];
-    if (Ed > 0 && fused) {
+    if (Ed > 0) {
       TRY(atom_tables_t(l));
       LaunchScope ls(eng, "t2_atom_t");
       hipLaunchKernelGGL(k2_atom<false>, dim3(tile_grid(eng, Ed)), dim3(BLOCK), t2_atom_lds(), st, atom2_args(l));
       HIP_TRY(eng, hipGetLastError());
-    } else if (Ed > 0) {
-      TRY(atom_rows(l));
-      GatedTArgs a{};
-      a.rows = Ed; a.mode = T2_ATOM; a.CG = t.CG; a.CGd = t.CGd; a.ln = aw.g.ln1_g; a.i_dst = b->e_center; a.i_w1 = b->e_d2u;
-      a.w = b->wag; a.wd = t.wagd; a.aggd = t.aggd[l];
-      LaunchScope ls(eng, "t2_gated_t");
-      hipLaunchKernelGGL(k2_gated_t, wave_rows_grid(eng, Ed), dim3(256), 0, st, a);
     }
     return gemm("t2_gemm_out", 64, 64, t.aggd[l], D, nullptr, aw.w_out, nullptr, t.atomd[l], D, t.atomd[l + 1], D, nullptr, N, 0);
   };
@@ -620,25 +510,16 @@ int run_backward2(chg_engine* eng, chg_batch* b, bool hvp) {
     TRY(atomconv_t(l));
     if (angles) {
       const BCW& bw = w.bc[l];
-      if (fused) {
+      {
         TRY(angle_tables_t(bw.w_bij, bw.w_ctr, t.hbcd[l], t.atomd[l + 1]));
         Angle2Args a = angle2_args(l, bw.w_ang, bw.g, b->ang[l], t.angd[l]);
         a.aggd = t.aggBd[l];
         LaunchScope ls(eng, "t2_bond_t");
         hipLaunchKernelGGL((k2_angle<true, false>), angle_grid, dim3(BLOCK), t2_angle_lds<true>(), st, a);
         HIP_TRY(eng, hipGetLastError());
-      } else {
-      TRY(angle_rows(l, true, bw.w_bij, bw.w_ctr, bw.w_ang, bw.g, t.hbcd[l], t.atomd[l + 1], b->ang[l], t.angd[l]));
-      {
-        GatedTArgs a{};
-        a.rows = A; a.mode = T2_BOND; a.CG = t.CG; a.CGd = t.CGd; a.ln = bw.g.ln1_g; a.i_dst = b->a_b1c; a.i_w1 = b->a_b1c; a.i_w2 = b->a_b2c;
-        a.w = b->wbgc; a.wd = t.wbgcd; a.aggd = t.aggBd[l];
-        LaunchScope ls(eng, "t2_gated_t");
-        hipLaunchKernelGGL(k2_gated_t, wave_rows_grid(eng, A), dim3(256), 0, st, a);
-      }
       }
       TRY(gemm("t2_gemm_out", 64, 64, t.aggBd[l], D, nullptr, bw.w_out, nullptr, t.hbcd[l], D, t.hbcd[l + 1], D, nullptr, Eb, 0));
-      if (l < L - 2 && fused) {
+      if (l < L - 2) {
         const AUW& uw = w.au[l];
         TRY(angle_tables_t(uw.w_bij, uw.w_ctr, t.hbcd[l + 1], t.atomd[l + 1]));
         Angle2Args a = angle2_args(L + l, uw.w_ang, uw.g, b->ang[l], t.angd[l]);
@@ -646,13 +527,6 @@ int run_backward2(chg_engine* eng, chg_batch* b, bool hvp) {
         LaunchScope ls(eng, "t2_angle_t");
         hipLaunchKernelGGL((k2_angle<false, false>), angle_grid, dim3(BLOCK), t2_angle_lds<false>(), st, a);
         HIP_TRY(eng, hipGetLastError());
-      } else if (l < L - 2) {
-        const AUW& uw = w.au[l];
-        TRY(angle_rows(L + l, false, uw.w_bij, uw.w_ctr, uw.w_ang, uw.g, t.hbcd[l + 1], t.atomd[l + 1], b->ang[l], t.angd[l]));
-        GatedTArgs a{};
-        a.rows = A; a.mode = T2_ANGLE; a.CG = t.CG; a.CGd = t.CGd; a.ln = uw.g.ln1_g; a.angd_in = t.angd[l]; a.angd_out = t.angd[l + 1];
-        LaunchScope ls(eng, "t2_gated_t");
-        hipLaunchKernelGGL(k2_gated_t, wave_rows_grid(eng, A), dim3(256), 0, st, a);
       }
     } else if (Eb > 0) {
       HIP_TRY(eng, hipMemcpyAsync(t.hbcd[l + 1], t.hbcd[l], sizeof(float) * (size_t)Eb * D, hipMemcpyDeviceToDevice, st));
@@ -702,18 +576,6 @@ int run_backward2(chg_engine* eng, chg_batch* b, bool hvp) {
   TRY(check());
 
   // ---- reverse sweep with two adjoints -----------------------------------------------------------------------
-  reverse = true;
-  // gated-MLP internals common to the three layer kinds: BCG / GCG -> weight gradients of the second layer, BZ / GZ
-  auto hidden_back = [&](const GatedW& g, const float* w2c_t, const float* w2g_t, int rows) -> int {
-    if (wg) TRY(xty_halves(eng, "t2_wgrad", t.BCG, t.H, rows, G(g.w2c), G(g.w2g), G(g.b2c), G(g.b2g)));
-    if (wg) TRY(xty_halves(eng, "t2_wgrad", t.GCG, t.Hd, rows, G(g.w2c), G(g.w2g)));
-    TRY(gemm_pair(t.BCG, w2c_t, w2g_t, nullptr, nullptr, t.BH, rows));
-    TRY(gemm_pair(t.GCG, w2c_t, w2g_t, nullptr, nullptr, t.GH, rows));
-    LaunchScope ls(eng, "t2_hidden_b");
-    hipLaunchKernelGGL(k2_hidden_b, g1((int64_t)rows * 2 * D), dim3(256), 0, st, t.Z, t.Zd, t.BH, t.GH, t.BZ, t.GZ, (size_t)rows * 2 * D);
-    return check();
-  };
-
   auto atomconv_b = [&](int l) -> int {
     const ACW& aw = w.ac[l];
     // atom[l+1] = agg . Wout^T + b_out + atom[l]
@@ -722,41 +584,21 @@ int run_backward2(chg_engine* eng, chg_batch* b, bool hvp) {
     if (Ed == 0) return CHG_OK;
     TRY(gemm("t2_gemm_out", 64, 64, t.bar_a, D, nullptr, aw.w_out_t, nullptr, nullptr, 0, t.bar_agg, D, nullptr, N, 0));
     TRY(gemm("t2_gemm_out", 64, 64, t.g_a, D, nullptr, aw.w_out_t, nullptr, nullptr, 0, t.g_agg, D, nullptr, N, 0));
-    table_adjoints_of(l, -1);
-    if (fused) {
-      TRY(atom_tables_t(l));
-      TRY(zero(eng, t.barP, sizeof(float) * (size_t)N * 4 * D));
-      const Atom2Args a = atom2_args(l);
-      { LaunchScope ls(eng, "t2_atom_b");
-        hipLaunchKernelGGL(k2_atom<true>, dim3(tile_grid(eng, Ed)), dim3(BLOCK), t2_atom_lds(), st, a);
-        HIP_TRY(eng, hipGetLastError()); }
-      if (wg) TRY(xty_halves(eng, "t2_wgrad", a.BCG, a.H, Ed, G(aw.g.w2c), G(aw.g.w2g), G(aw.g.b2c), G(aw.g.b2g)));
-      if (wg) TRY(xty_halves(eng, "t2_wgrad", a.GCG, a.Hd, Ed, G(aw.g.w2c), G(aw.g.w2g)));
-    } else {
-    TRY(atom_rows(l));
-    {
-      GatedBArgs a{};
-      a.rows = Ed; a.mode = T2_ATOM; a.CG = t.CG; a.CGd = t.CGd; a.ln = aw.g.ln1_g; a.i_dst = b->e_center; a.i_w1 = b->e_d2u;
-      a.w = b->wag; a.wd = t.wagd; a.bar_agg = t.bar_agg; a.g_agg = t.g_agg; a.bar_w = t.bar_wag; a.g_w = t.g_wag;
-      a.BCG = t.BCG; a.GCG = t.GCG; a.g_ln = G(aw.g.ln1_g);
-      LaunchScope ls(eng, "t2_gated_b");
-      hipLaunchKernelGGL(k2_gated_b, wave_rows_grid(eng, Ed), dim3(256), 0, st, a);
-    }
-    TRY(hidden_back(aw.g, aw.w2c_t, aw.w2g_t, Ed));
-    TRY(zero(eng, t.barP, sizeof(float) * (size_t)N * 4 * D)); TRY(zero(eng, t.gP, sizeof(float) * (size_t)N * 4 * D));
-    TRY(zero(eng, t.barQ, sizeof(float) * (size_t)Eu * 2 * D)); TRY(zero(eng, t.gQ, sizeof(float) * (size_t)Eu * 2 * D));
-    {
-      ScatterZArgs a{Ed, t.BZ, t.GZ, t.barP, t.barP, t.barQ, t.gP, t.gP, t.gQ, 4 * D, 4 * D, 2 * D, 0, 2 * D, 0, b->e_center, b->e_nbr, b->e_d2u};
-      LaunchScope ls(eng, "t2_scatter_z");
-      hipLaunchKernelGGL(k2_scatter_z, wave_rows_grid(eng, (Ed + TILE_ROWS - 1) / TILE_ROWS), dim3(256), scatter_z_lds(), st, a);
-    }
-    }
+    TRY(atom_tables_t(l));
+    TRY(zero(eng, t.barP, sizeof(float) * (size_t)N * 4 * D));
+    const Atom2Args a = atom2_args(l);
+    { LaunchScope ls(eng, "t2_atom_b");
+      hipLaunchKernelGGL(k2_atom<true>, dim3(tile_grid(eng, Ed)), dim3(BLOCK), t2_atom_lds(), st, a);
+      HIP_TRY(eng, hipGetLastError()); }
+    const float* gP = b->GP_l[l];
     // first layer (factorised): table gradients contract with the rows the tables were made from, bar with primal and G with tangent
     if (wg) {
+      TRY(xty_halves(eng, "t2_wgrad", a.BCG, a.H, Ed, G(aw.g.w2c), G(aw.g.w2g), G(aw.g.b2c), G(aw.g.b2g)));
+      TRY(xty_halves(eng, "t2_wgrad", a.GCG, a.Hd, Ed, G(aw.g.w2c), G(aw.g.w2g)));
       for (int half = 0; half < 2; ++half) {
         TRY((xty<8, 4>(eng, "t2_wgrad", t.barP + half * 2 * D, 4 * D, nullptr, b->atom[l], D, nullptr, N, 1.0f, G(aw.w_cn) + half * 2 * D * D, D, D,
                        half == 0 ? G(aw.b1) : nullptr)));
-        TRY((xty<8, 4>(eng, "t2_wgrad", t.gP + half * 2 * D, 4 * D, nullptr, t.atomd[l], D, nullptr, N, 1.0f, G(aw.w_cn) + half * 2 * D * D, D, D)));
+        TRY((xty<8, 4>(eng, "t2_wgrad", gP + half * 2 * D, 4 * D, nullptr, t.atomd[l], D, nullptr, N, 1.0f, G(aw.w_cn) + half * 2 * D * D, D, D)));
       }
       TRY((xty<8, 4>(eng, "t2_wgrad", t.barQ, 2 * D, nullptr, b->hb0, D, nullptr, Eu, 1.0f, G(aw.w_bond), D, D)));
       TRY((xty<8, 4>(eng, "t2_wgrad", t.gQ, 2 * D, nullptr, t.hb0d, D, nullptr, Eu, 1.0f, G(aw.w_bond), D, D)));
@@ -771,42 +613,41 @@ int run_backward2(chg_engine* eng, chg_batch* b, bool hvp) {
       }
     }
     TRY(rows_gemm_in2(eng, "t2_gemm_tab", t.barP, 4 * D, aw.w_cn_t, aw.w_cn_t + 2 * D * D, t.bar_a, nullptr, N, 1));
-    TRY(rows_gemm_in2(eng, "t2_gemm_tab", t.gP, 4 * D, aw.w_cn_t, aw.w_cn_t + 2 * D * D, t.g_a, nullptr, N, 1));
+    TRY(rows_gemm_in2(eng, "t2_gemm_tab", gP, 4 * D, aw.w_cn_t, aw.w_cn_t + 2 * D * D, t.g_a, nullptr, N, 1));
     TRY(gemm("t2_gemm_tab", 128, 64, t.barQ, 2 * D, nullptr, aw.w_bond_t, nullptr, nullptr, 0, t.bar_b, D, nullptr, Eu, 1));
     return gemm("t2_gemm_tab", 128, 64, t.gQ, 2 * D, nullptr, aw.w_bond_t, nullptr, nullptr, 0, t.g_b, D, nullptr, Eu, 1);
   };
 
-  // tail shared by BondConv / AngleUpdate: BZ / GZ [A,128] -> table gradients, weight gradients, adjoints of the inputs
-  auto angle_back = [&](const float* w_bij, const float* w_ctr, const float* b1, const float* w_ang, const float* w_bij_t, const float* w_ctr_t,
-                        const float* w_ang_t, const float* hrows, const float* hrowsd, const float* atoms, const float* atomsd,
-                        const float* angs, const float* angsd, const std::function<int()>& fused_kernel) -> int {
+  // reverse kernel of BondConv (HIDDEN) / AngleUpdate of slot: its first-layer adjoints are scattered to the tables bar(R), bar(S)
+  // and contracted back to the angle features in the kernel
+  auto angle_b = [&](auto hidden, const char* label, const Angle2Args& a) -> int {
+    constexpr bool HIDDEN = decltype(hidden)::value;
     TRY(zero(eng, t.barR, sizeof(float) * (size_t)Eb * 4 * D));
     TRY(zero(eng, t.barS, sizeof(float) * (size_t)N * 2 * D));
-    if (!fused) { TRY(zero(eng, t.gR, sizeof(float) * (size_t)Eb * 4 * D)); TRY(zero(eng, t.gS, sizeof(float) * (size_t)N * 2 * D)); }
-    if (fused) {
-      TRY(fused_kernel());     // first-layer adjoints scattered to the tables and contracted back to the angle features in the kernel
-    } else {
-      ScatterZArgs a{A, t.BZ, t.GZ, t.barR, t.barR, t.barS, t.gR, t.gR, t.gS, 4 * D, 4 * D, 2 * D, 0, 2 * D, 0, b->a_b1c, b->a_b2c, b->a_ctr};
-      LaunchScope ls(eng, "t2_scatter_z");
-      hipLaunchKernelGGL(k2_scatter_z, wave_rows_grid(eng, (A + TILE_ROWS - 1) / TILE_ROWS), dim3(256), scatter_z_lds(), st, a);
-    }
+    LaunchScope ls(eng, label);
+    hipLaunchKernelGGL((k2_angle<HIDDEN, true>), angle_grid, dim3(BLOCK), t2_angle_lds<HIDDEN>(), st, a);
+    HIP_TRY(eng, hipGetLastError());
+    return CHG_OK;
+  };
+  // tail shared by BondConv / AngleUpdate: table adjoints of slot -> weight gradients, adjoints of the inputs
+  auto angle_back = [&](int slot, const float* w_bij, const float* w_ctr, const float* b1, const float* w_ang, const float* w_bij_t,
+                        const float* w_ctr_t, const float* hrows, const float* hrowsd, const float* atoms, const float* atomsd,
+                        const float* angs, const float* angsd) -> int {
+    const float *gR = b->GR_l[slot], *gS = b->GS_l[slot];
     if (wg) {
       for (int half = 0; half < 2; ++half) {
         TRY((xty<8, 4>(eng, "t2_wgrad", t.barR + half * 2 * D, 4 * D, nullptr, hrows, D, nullptr, Eb, 1.0f, G(w_bij) + half * 2 * D * D, D, D)));
-        TRY((xty<8, 4>(eng, "t2_wgrad", t.gR + half * 2 * D, 4 * D, nullptr, hrowsd, D, nullptr, Eb, 1.0f, G(w_bij) + half * 2 * D * D, D, D)));
+        TRY((xty<8, 4>(eng, "t2_wgrad", gR + half * 2 * D, 4 * D, nullptr, hrowsd, D, nullptr, Eb, 1.0f, G(w_bij) + half * 2 * D * D, D, D)));
       }
       TRY((xty<8, 4>(eng, "t2_wgrad", t.barS, 2 * D, nullptr, atoms, D, nullptr, N, 1.0f, G(w_ctr), D, D, G(b1))));
-      TRY((xty<8, 4>(eng, "t2_wgrad", t.gS, 2 * D, nullptr, atomsd, D, nullptr, N, 1.0f, G(w_ctr), D, D)));
+      TRY((xty<8, 4>(eng, "t2_wgrad", gS, 2 * D, nullptr, atomsd, D, nullptr, N, 1.0f, G(w_ctr), D, D)));
       TRY((xty<8, 4>(eng, "t2_wgrad", t.BZ, 2 * D, nullptr, angs, D, nullptr, A, 1.0f, G(w_ang), D, D)));
       TRY((xty<8, 4>(eng, "t2_wgrad", t.GZ, 2 * D, nullptr, angsd, D, nullptr, A, 1.0f, G(w_ang), D, D)));
     }
     TRY(rows_gemm_in2(eng, "t2_gemm_tab", t.barR, 4 * D, w_bij_t, w_bij_t + 2 * D * D, t.bar_b, b->bn_und, Eb, 1));
-    TRY(rows_gemm_in2(eng, "t2_gemm_tab", t.gR, 4 * D, w_bij_t, w_bij_t + 2 * D * D, t.g_b, b->bn_und, Eb, 1));
+    TRY(rows_gemm_in2(eng, "t2_gemm_tab", gR, 4 * D, w_bij_t, w_bij_t + 2 * D * D, t.g_b, b->bn_und, Eb, 1));
     TRY(gemm("t2_gemm_tab", 128, 64, t.barS, 2 * D, nullptr, w_ctr_t, nullptr, nullptr, 0, t.bar_a, D, nullptr, N, 1));
-    TRY(gemm("t2_gemm_tab", 128, 64, t.gS, 2 * D, nullptr, w_ctr_t, nullptr, nullptr, 0, t.g_a, D, nullptr, N, 1));
-    if (fused) return CHG_OK;
-    TRY(gemm("t2_gemm_ang", 128, 64, t.BZ, 2 * D, nullptr, w_ang_t, nullptr, nullptr, 0, t.bar_ang, D, nullptr, A, 1));
-    return gemm("t2_gemm_ang", 128, 64, t.GZ, 2 * D, nullptr, w_ang_t, nullptr, nullptr, 0, t.g_ang, D, nullptr, A, 1);
+    return gemm("t2_gemm_tab", 128, 64, gS, 2 * D, nullptr, w_ctr_t, nullptr, nullptr, 0, t.g_a, D, nullptr, N, 1);
   };
 
   TRY(atomconv_b(L - 1));
@@ -819,25 +660,10 @@ int run_backward2(chg_engine* eng, chg_batch* b, bool hvp) {
     if (angles) {
       if (l < L - 2) {
         const AUW& uw = w.au[l];
-        if (fused) {
-          TRY(angle_tables_t(uw.w_bij, uw.w_ctr, t.hbcd[l + 1], t.atomd[l + 1]));
-        } else {
-        TRY(angle_rows(L + l, false, uw.w_bij, uw.w_ctr, uw.w_ang, uw.g, t.hbcd[l + 1], t.atomd[l + 1], b->ang[l], t.angd[l]));
-        GatedBArgs a{};
-        a.rows = A; a.mode = T2_ANGLE; a.CG = t.CG; a.CGd = t.CGd; a.ln = uw.g.ln1_g; a.bar_agg = t.bar_ang; a.g_agg = t.g_ang;
-        a.BCG = t.BZ; a.GCG = t.GZ; a.g_ln = G(uw.g.ln1_g);      // single layer: bar(c|g) IS bar(z)
-        { LaunchScope ls(eng, "t2_gated_b");
-          hipLaunchKernelGGL(k2_gated_b, wave_rows_grid(eng, A), dim3(256), 0, st, a); }
-        }
-        table_adjoints_of(-1, L + l);
-        TRY(angle_back(uw.w_bij, uw.w_ctr, uw.b1, uw.w_ang, uw.w_bij_t, uw.w_ctr_t, uw.w_ang_t, b->hbc[l + 1], t.hbcd[l + 1], b->atom[l + 1],
-                       t.atomd[l + 1], b->ang[l], t.angd[l], [&]() -> int {
-                         LaunchScope ls(eng, "t2_angle_b");
-                         hipLaunchKernelGGL((k2_angle<false, true>), angle_grid, dim3(BLOCK), t2_angle_lds<false>(), st,
-                                            angle2_args(L + l, uw.w_ang, uw.g, b->ang[l], t.angd[l]));
-                         HIP_TRY(eng, hipGetLastError());
-                         return CHG_OK;
-                       }));
+        TRY(angle_tables_t(uw.w_bij, uw.w_ctr, t.hbcd[l + 1], t.atomd[l + 1]));
+        TRY(angle_b(std::false_type{}, "t2_angle_b", angle2_args(L + l, uw.w_ang, uw.g, b->ang[l], t.angd[l])));
+        TRY(angle_back(L + l, uw.w_bij, uw.w_ctr, uw.b1, uw.w_ang, uw.w_bij_t, uw.w_ctr_t, b->hbc[l + 1], t.hbcd[l + 1], b->atom[l + 1],
+                       t.atomd[l + 1], b->ang[l], t.angd[l]));
       }
       const BCW& bw = w.bc[l];
       // hbc[l+1] = aggB . Wout^T + b_out + hbc[l]; its adjoints live in the node rows of bar_b / g_b; b_out reaches every bond (above)
@@ -846,31 +672,13 @@ int run_backward2(chg_engine* eng, chg_batch* b, bool hvp) {
       if (wg) TRY((xty<4, 4>(eng, "t2_wgrad", t.g_b, D, b->bn_und, t.aggBd[l], D, nullptr, Eb, 1.0f, G(bw.w_out), D, D)));
       TRY(gemm("t2_gemm_out", 64, 64, t.bar_b, D, b->bn_und, bw.w_out_t, nullptr, nullptr, 0, t.bar_agg, D, nullptr, Eb, 0));
       TRY(gemm("t2_gemm_out", 64, 64, t.g_b, D, b->bn_und, bw.w_out_t, nullptr, nullptr, 0, t.g_agg, D, nullptr, Eb, 0));
-      if (fused) {
-        TRY(angle_tables_t(bw.w_bij, bw.w_ctr, t.hbcd[l], t.atomd[l + 1]));
-      } else {
-      TRY(angle_rows(l, true, bw.w_bij, bw.w_ctr, bw.w_ang, bw.g, t.hbcd[l], t.atomd[l + 1], b->ang[l], t.angd[l]));
-      {
-        GatedBArgs a{};
-        a.rows = A; a.mode = T2_BOND; a.CG = t.CG; a.CGd = t.CGd; a.ln = bw.g.ln1_g; a.i_dst = b->a_b1c; a.i_w1 = b->a_b1c; a.i_w2 = b->a_b2c;
-        a.w = b->wbgc; a.wd = t.wbgcd; a.bar_agg = t.bar_agg; a.g_agg = t.g_agg; a.bar_w = t.bar_wbg; a.g_w = t.g_wbg;
-        a.BCG = t.BCG; a.GCG = t.GCG; a.g_ln = G(bw.g.ln1_g);
-        LaunchScope ls(eng, "t2_gated_b");
-        hipLaunchKernelGGL(k2_gated_b, wave_rows_grid(eng, A), dim3(256), 0, st, a);
-      }
-      TRY(hidden_back(bw.g, bw.w2c_t, bw.w2g_t, A));
-      }
-      table_adjoints_of(-1, l);
-      TRY(angle_back(bw.w_bij, bw.w_ctr, bw.b1, bw.w_ang, bw.w_bij_t, bw.w_ctr_t, bw.w_ang_t, b->hbc[l], t.hbcd[l], b->atom[l + 1], t.atomd[l + 1],
-                     b->ang[l], t.angd[l], [&]() -> int {
-                       const Angle2Args a = angle2_args(l, bw.w_ang, bw.g, b->ang[l], t.angd[l]);
-                       { LaunchScope ls(eng, "t2_bond_b");
-                         hipLaunchKernelGGL((k2_angle<true, true>), angle_grid, dim3(BLOCK), t2_angle_lds<true>(), st, a);
-                         HIP_TRY(eng, hipGetLastError()); }
-                       if (!wg) return CHG_OK;
-                       TRY(xty_halves(eng, "t2_wgrad", a.BCG, a.H, A, G(bw.g.w2c), G(bw.g.w2g), G(bw.g.b2c), G(bw.g.b2g)));
-                       return xty_halves(eng, "t2_wgrad", a.GCG, a.Hd, A, G(bw.g.w2c), G(bw.g.w2g));
-                     }));
+      TRY(angle_tables_t(bw.w_bij, bw.w_ctr, t.hbcd[l], t.atomd[l + 1]));
+      const Angle2Args a = angle2_args(l, bw.w_ang, bw.g, b->ang[l], t.angd[l]);
+      TRY(angle_b(std::true_type{}, "t2_bond_b", a));
+      if (wg) TRY(xty_halves(eng, "t2_wgrad", a.BCG, a.H, A, G(bw.g.w2c), G(bw.g.w2g), G(bw.g.b2c), G(bw.g.b2g)));
+      if (wg) TRY(xty_halves(eng, "t2_wgrad", a.GCG, a.Hd, A, G(bw.g.w2c), G(bw.g.w2g)));
+      TRY(angle_back(l, bw.w_bij, bw.w_ctr, bw.b1, bw.w_ang, bw.w_bij_t, bw.w_ctr_t, b->hbc[l], t.hbcd[l], b->atom[l + 1], t.atomd[l + 1],
+                     b->ang[l], t.angd[l]));
     }
     TRY(atomconv_b(l));
   }
@@ -883,47 +691,29 @@ int run_backward2(chg_engine* eng, chg_batch* b, bool hvp) {
     TRY((xty<4, 2>(eng, "t2_wgrad", t.bar_b, D, nullptr, t.X6, KB2, nullptr, Eu, 1.0f, G(w.w_bond_emb), NRAD, NRAD)));
     TRY((xty<4, 2>(eng, "t2_wgrad", t.g_b, D, nullptr, t.X6d, KB2, nullptr, Eu, 1.0f, G(w.w_bond_emb), NRAD, NRAD)));
     TRY((xty<4, 2>(eng, "t2_wgrad", t.bar_wag, D, nullptr, t.X6, KB2, nullptr, Eu, 1.0f, G(w.w_wag), NRAD, NRAD)));
-    TRY((xty<4, 2>(eng, "t2_wgrad", g_wag, D, nullptr, t.X6d, KB2, nullptr, Eu, 1.0f, G(w.w_wag), NRAD, NRAD)));
+    TRY((xty<4, 2>(eng, "t2_wgrad", b->Gwag, D, nullptr, t.X6d, KB2, nullptr, Eu, 1.0f, G(w.w_wag), NRAD, NRAD)));
     TRY((xty<4, 2>(eng, "t2_wgrad", t.bar_wbg, D, nullptr, t.X3, KB2, b->bn_und, Eb, 1.0f, G(w.w_wbg), NRAD, NRAD)));
-    TRY((xty<4, 2>(eng, "t2_wgrad", g_wbg, D, nullptr, t.X3d, KB2, b->bn_und, Eb, 1.0f, G(w.w_wbg), NRAD, NRAD)));
-    // frequency gradients on 16-row tiles (kernels_train2_freq.h; CHGNET_T2_FREQ_ROWS=1 keeps the one-row-per-wave kernels for A/B runs)
-    static const bool freq_rows = [] { const char* e = std::getenv("CHGNET_T2_FREQ_ROWS"); return e && std::atoi(e) != 0; }();
+    TRY((xty<4, 2>(eng, "t2_wgrad", b->Gwbgc, D, nullptr, t.X3d, KB2, b->bn_und, Eb, 1.0f, G(w.w_wbg), NRAD, NRAD)));
+    // frequency gradients on 16-row tiles (kernels_train2_freq.h)
     {
       LaunchScope ls(eng, "t2_freq");
-      if (freq_rows) {
-        FreqGradArgs a{Eu, nullptr, b->ev, t.vd4, b->u_u2d, w.freq_ag, eng->desc.atom_graph_cutoff, env, t.bar_b, t.g_b, w.w_bond_emb,
-                       t.bar_wag, g_wag, w.w_wag, G(w.freq_ag)};
-        hipLaunchKernelGGL(k2_freq_grad, wave_rows_grid(eng, Eu), dim3(256), 0, st, a);
-      } else {
-        FreqGradTArgs a{Eu, nullptr, b->ev, t.vd4, b->u_u2d, w.freq_ag, eng->desc.atom_graph_cutoff, env, t.bar_b, t.g_b, w.w_bond_emb,
-                        t.bar_wag, g_wag, w.w_wag, G(w.freq_ag)};
-        hipLaunchKernelGGL(k2_freq_grad_t, dim3(grid_for(Eu, 2 * eng->num_cus)), dim3(BLOCK), freq_grad_lds(), st, a);
-      }
+      FreqGradTArgs a{Eu, nullptr, b->ev, t.vd4, b->u_u2d, w.freq_ag, eng->desc.atom_graph_cutoff, env, t.bar_b, t.g_b, w.w_bond_emb,
+                      t.bar_wag, b->Gwag, w.w_wag, G(w.freq_ag)};
+      hipLaunchKernelGGL(k2_freq_grad_t, dim3(grid_for(Eu, 2 * eng->num_cus)), dim3(BLOCK), freq_grad_lds(), st, a);
     }
     if (Eb > 0) {
       LaunchScope ls(eng, "t2_freq");
-      if (freq_rows) {
-        FreqGradArgs a{Eb, b->bn_und, b->ev, t.vd4, b->u_u2d, w.freq_bg, eng->desc.bond_graph_cutoff, env, t.bar_wbg, g_wbg, w.w_wbg,
-                       nullptr, nullptr, nullptr, G(w.freq_bg)};
-        hipLaunchKernelGGL(k2_freq_grad, wave_rows_grid(eng, Eb), dim3(256), 0, st, a);
-      } else {
-        FreqGradTArgs a{Eb, b->bn_und, b->ev, t.vd4, b->u_u2d, w.freq_bg, eng->desc.bond_graph_cutoff, env, t.bar_wbg, g_wbg, w.w_wbg,
-                        nullptr, nullptr, nullptr, G(w.freq_bg)};
-        hipLaunchKernelGGL(k2_freq_grad_t, dim3(grid_for(Eb, 2 * eng->num_cus)), dim3(BLOCK), freq_grad_lds(), st, a);
-      }
+      FreqGradTArgs a{Eb, b->bn_und, b->ev, t.vd4, b->u_u2d, w.freq_bg, eng->desc.bond_graph_cutoff, env, t.bar_wbg, b->Gwbgc, w.w_wbg,
+                      nullptr, nullptr, nullptr, G(w.freq_bg)};
+      hipLaunchKernelGGL(k2_freq_grad_t, dim3(grid_for(Eb, 2 * eng->num_cus)), dim3(BLOCK), freq_grad_lds(), st, a);
     }
   }
   if (angles) {
     TRY((xty<4, 2>(eng, "t2_wgrad", t.bar_ang, D, nullptr, t.X4, KB2, nullptr, A, 1.0f, G(w.w_ang_emb), NANG, NANG)));
     TRY((xty<4, 2>(eng, "t2_wgrad", t.g_ang, D, nullptr, t.X4d, KB2, nullptr, A, 1.0f, G(w.w_ang_emb), NANG, NANG)));
     LaunchScope ls(eng, "t2_freq");
-    static const bool freq_rows_a = [] { const char* e = std::getenv("CHGNET_T2_FREQ_ROWS"); return e && std::atoi(e) != 0; }();
-    if (freq_rows_a)
-      hipLaunchKernelGGL(k2_angle_freq_grad, wave_rows_grid(eng, A), dim3(256), 0, st, t.bar_ang, t.g_ang, w.w_ang_emb, t.th2, w.freq_ang,
-                         G(w.freq_ang), A);
-    else
-      hipLaunchKernelGGL(k2_angle_freq_grad_t, dim3(grid_for(A, 2 * eng->num_cus)), dim3(BLOCK), angle_freq_grad_lds(), st, t.bar_ang, t.g_ang,
-                         w.w_ang_emb, t.th2, w.freq_ang, G(w.freq_ang), A);
+    hipLaunchKernelGGL(k2_angle_freq_grad_t, dim3(grid_for(A, 2 * eng->num_cus)), dim3(BLOCK), angle_freq_grad_lds(), st, t.bar_ang, t.g_ang,
+                       w.w_ang_emb, t.th2, w.freq_ang, G(w.freq_ang), A);
   }
   {
     LaunchScope ls(eng, "wgrad_atom_embed");
@@ -954,7 +744,6 @@ int train_set_lds(chg_engine* eng) {
   if ((s = set_lds(eng, (k_xty3<8, 8, true>), (xty3_lds<8, 8, true>())))) return s;
   if ((s = set_lds(eng, (k_xty<4, 4>), (xty_lds<4, 4>())))) return s;
   if ((s = set_lds(eng, (k_xty<4, 2>), (xty_lds<4, 2>())))) return s;
-  if ((s = set_lds(eng, k2_scatter_z, scatter_z_lds()))) return s;
   if ((s = set_lds(eng, k2_freq_grad_t, freq_grad_lds()))) return s;
   if ((s = set_lds(eng, k2_angle_freq_grad_t, angle_freq_grad_lds()))) return s;
   if ((s = set_lds(eng, k_hvp_bond_t, hvp_bond_lds()))) return s;
@@ -1027,16 +816,13 @@ int hvp_from_adjoints(chg_engine* eng, chg_batch* b) {
   if (Ed == 0) return CHG_OK;
   const double pc = eng->desc.cutoff_coeff;
   const Envelope env{(float)(-(pc + 1) * (pc + 2) / 2), (float)(pc * (pc + 2)), (float)(-pc * (pc + 1) / 2), eng->desc.cutoff_coeff};
-  const bool fused = t2_fused();   // the fused sweep leaves G(wag), G(wbg) in the batch (the force sweep's first-order adjoints)
-  const float* g_wag = fused ? b->Gwag : t.g_wag;
-  const float* g_wbg = fused ? b->Gwbgc : t.g_wbg;
   {
     LaunchScope ls(eng, "hvp_bond");
     HvpBondArgs a{Eu, nullptr, b->ev, t.vd4, b->u_u2d, w.freq_ag, eng->desc.atom_graph_cutoff, env, t.bar_b, t.g_b, w.w_bond_emb,
-                  t.bar_wag, g_wag, w.w_wag, t.hvp_gu, t.hvp_grk};
+                  t.bar_wag, b->Gwag, w.w_wag, t.hvp_gu, t.hvp_grk};   // G(wag), G(wbg): the force sweep's, in the batch
     hipLaunchKernelGGL(k_hvp_bond_t, dim3(grid_for(Eu, 2 * eng->num_cus)), dim3(BLOCK), hvp_bond_lds(), st, a);
     if (Eb > 0) {
-      HvpBondArgs c{Eb, b->bn_und, b->ev, t.vd4, b->u_u2d, w.freq_bg, eng->desc.bond_graph_cutoff, env, t.bar_wbg, g_wbg, w.w_wbg,
+      HvpBondArgs c{Eb, b->bn_und, b->ev, t.vd4, b->u_u2d, w.freq_bg, eng->desc.bond_graph_cutoff, env, t.bar_wbg, b->Gwbgc, w.w_wbg,
                     nullptr, nullptr, nullptr, t.hvp_gu, t.hvp_grk};
       hipLaunchKernelGGL(k_hvp_bond_t, dim3(grid_for(Eb, 2 * eng->num_cus)), dim3(BLOCK), hvp_bond_lds(), st, c);
     }

@@ -9,11 +9,10 @@
 // adjoints per activation: G(y) = dE/dy (seed 1) and bar(y) = d Phi / dy (seed ce), with
 //   bar(x) = J^T bar(y) + d/dx [G(y) . J(x) xdot],    bar(W) += bar(y) x^T + G(y) xdot^T.
 //
-// This first device version keeps the sweep UNFUSED: every Linear runs through the engine's row GEMMs
-// (k_rows_gemm) on primal, tangent, bar and G rows alike, every weight gradient is a k_xty contraction, and the
-// kernels here are the row-local nonlinear pieces in between -- one wave per row, lane f = feature f of the core
-// branch and of the gate branch ([rows][128] arrays: columns 0..63 core, 64..127 gate).  It is HBM-bound by
-// construction (a dozen [rows,128] arrays per layer); fusing it like the first-order kernels is later work.
+// Per layer the sweep runs as fused tile kernels (kernels_train2_tile.h, kernels_train2_freq.h).  What is here: the row-local
+// nonlinear pieces those kernels share -- LayerNorm statistics and the gated-MLP tail with its tangent and two-adjoint backward, one
+// row at a time, lane f = feature f of the core branch and of the gate branch ([rows][128] rows: columns 0..63 core, 64..127 gate) --
+// and the row-parallel kernels of the geometry tangent, the bases, the embedding linears and the readout.
 #pragma once
 
 #include "kernels_geom.h"
@@ -44,45 +43,22 @@ __device__ __forceinline__ float ln_proj(float a, float xh, float& m_ax) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// gather of the first-layer pre-activation z (and its tangent) from the per-layer tables
-// ---------------------------------------------------------------------------------------------------------
-struct GatherZArgs {
-  int rows;
-  // three table gathers:  z = T0[i0][off0 + .] + T1[i1][off1 + .] + T2[i2][off2 + .]  (+ add[row][.])
-  const float *t0, *t1, *t2;     // primal tables
-  const float *d0, *d1, *d2;     // tangent tables (same shapes)
-  int ld0, ld1, ld2, off0, off1, off2;
-  const int *i0, *i1, *i2;
-  const float *add, *addd;       // optional [rows,128] addends (W_ang . angle features), primal and tangent
-  int hidden;                    // 1: also write H = silu(z), Hd = silu'(z) zd
-  float *Z, *Zd, *H, *Hd;        // [rows,128]
-};
-
-static __global__ __launch_bounds__(256) void k2_gather_z(GatherZArgs p) {
-  const int lane = threadIdx.x & 63;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
-  for (int r = wave; r < p.rows; r += nwaves) {
-    const size_t a0 = (size_t)p.i0[r] * p.ld0 + p.off0, a1 = (size_t)p.i1[r] * p.ld1 + p.off1, a2 = (size_t)p.i2[r] * p.ld2 + p.off2;
-    const size_t o = (size_t)r * 2 * D;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {   // core, gate
-      const int f = 64 * h + lane;
-      float z = p.t0[a0 + f] + p.t1[a1 + f] + p.t2[a2 + f];
-      float zd = p.d0[a0 + f] + p.d1[a1 + f] + p.d2[a2 + f];
-      if (p.add) { z += p.add[o + f]; zd += p.addd[o + f]; }
-      p.Z[o + f] = z;
-      p.Zd[o + f] = zd;
-      if (p.hidden) {
-        p.H[o + f] = siluf_(z);
-        p.Hd[o + f] = dsiluf_(z) * zd;
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------
 // gated MLP tail:  (c, g) -> y = silu(LN1 c) * sigmoid(LN2 g), forward with tangent and the two-adjoint backward
 // ---------------------------------------------------------------------------------------------------------
+// Per layer (pre-activations from the layer's tables, kernels_train2_tile.h; tangents alike, Pd / Qd / Rd / Sd):
+//   AtomConv    z = P[centre][0:128] + P[nbr][128:256] + Q[bond],  h = silu(z), hd = silu'(z) zd,  c|g = h . [W2c | W2g]^T + b2
+//   BondConv    z = R[b1][0:128] + R[b2][128:256] + S[ctr] + ang . W_ang^T, then as AtomConv
+//   AngleUpdate c|g = z of BondConv's form (a single layer)
+// and y = silu(LN1 c) * sigmoid(LN2 g) (gated_row_fwd) leaves the row as
+//   AtomConv    m = y wag[k], summed into the aggregate of the centre:  md = yd wag + y wagd
+//   BondConv    u = y wbg[b1] wbg[b2], summed into the aggregate of bond b1:  ud = yd w1 w2 + y (w1d w2 + w1 w2d)
+//   AngleUpdate ang' = ang + y
+// The two adjoints of y that gated_row_bwd takes, from those of the aggregate row a (bar(a), G(a)):
+//   AtomConv    bar(y) = wag bar(a) + wagd G(a),  G(y) = wag G(a);   bar(wag) += y bar(a) + yd G(a)
+//   BondConv    bar(y) = w1 w2 bar(a) + (w1d w2 + w1 w2d) G(a),  G(y) = w1 w2 G(a);
+//               bar(w1) += y w2 bar(a) + (yd w2 + y w2d) G(a),  bar(w2) += y w1 bar(a) + (yd w1 + y w1d) G(a)
+//   AngleUpdate bar(y) = bar(ang'),  G(y) = G(ang')
+// (G(wag), G(wbg) are first-order adjoints: the force sweep leaves them in the batch.)
 struct GatedRow {       // everything the backward needs of one row, this lane's feature
   float xh1, r1, xh2, r2, xh1d, xh2d, n1d, n2d, a1, a2, a1d, a2d, da1, da2, s1, n1;
   float pt1, pt2, mt1, mt2;   // P(cd), P(gd), mean(cd xh1), mean(gd xh2)
@@ -146,144 +122,6 @@ __device__ __forceinline__ void gated_row_bwd(const GatedRow& s, float bar_y, fl
   }
 }
 
-enum { T2_ATOM = 0, T2_BOND = 1, T2_ANGLE = 2 };
-
-struct GatedTArgs {
-  int rows, mode;
-  const float *CG, *CGd;                 // [rows,128] second-layer pre-activations (c | g) and tangents
-  const float *ln;                       // [4][64] ln1_g, ln1_b, ln2_g, ln2_b
-  // ATOM: m = y * wag[k] scattered by centre;  BOND: u = y * wbg[b1] * wbg[b2] scattered by b1;  ANGLE: ang' = ang + y
-  const int *i_dst, *i_w1, *i_w2;        // ATOM: centre, d2u, -;  BOND: b1c, b1c, b2c;  ANGLE: -, -, -
-  const float *w, *wd;                   // ATOM: wag / wagd [Eu,64];  BOND: wbgc / wbgcd [Eb,64]
-  float* aggd;                           // ATOM / BOND: tangent of the aggregate (zeroed), atomics
-  const float* angd_in;                  // ANGLE: [rows,64]
-  float* angd_out;
-};
-
-// Rows are centre-major (edges) / sorted by owning bond (angles): each wave takes a CONTIGUOUS block of rows, keeps what
-// depends only on the run's key in registers (weights of the owning bond) and sends one atomic row per run instead of one
-// per row.
-static __global__ __launch_bounds__(256) void k2_gated_t(GatedTArgs p) {
-  const int lane = threadIdx.x & 63;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
-  const float g1 = p.ln[lane], b1 = p.ln[D + lane], g2 = p.ln[2 * D + lane], b2 = p.ln[3 * D + lane];
-  const int per = (p.rows + nwaves - 1) / nwaves;
-  const int rb = min(p.rows, wave * per), re = min(p.rows, rb + per);
-  int cur = -1;
-  float acc = 0.f, w1 = 0.f, w1d = 0.f;
-  float in[4] = {0.f, 0.f, 0.f, 0.f};   // the next row's inputs are requested before this row's results are stored
-  if (rb < re) { const size_t o = (size_t)rb * 2 * D; in[0] = p.CG[o + lane]; in[1] = p.CG[o + D + lane]; in[2] = p.CGd[o + lane]; in[3] = p.CGd[o + D + lane]; }
-  for (int r = rb; r < re; ++r) {
-    const float c0 = in[0], c1 = in[1], c2 = in[2], c3 = in[3];
-    if (r + 1 < re) { const size_t o = (size_t)(r + 1) * 2 * D; in[0] = p.CG[o + lane]; in[1] = p.CG[o + D + lane]; in[2] = p.CGd[o + lane]; in[3] = p.CGd[o + D + lane]; }
-    const GatedRow s = gated_row_fwd(c0, c1, c2, c3, g1, b1, g2, b2);
-    if (p.mode == T2_ANGLE) {
-      p.angd_out[(size_t)r * D + lane] = p.angd_in[(size_t)r * D + lane] + s.yd;
-      continue;
-    }
-    const int dst = p.i_dst[r];
-    if (dst != cur) {
-      if (cur >= 0) atomicAdd(p.aggd + (size_t)cur * D + lane, acc);
-      cur = dst;
-      acc = 0.f;
-      if (p.mode == T2_BOND) {          // i_w1 == i_dst: the owning bond's weight row
-        w1 = p.w[(size_t)dst * D + lane];
-        w1d = p.wd[(size_t)dst * D + lane];
-      }
-    }
-    if (p.mode == T2_ATOM) {
-      const size_t k = (size_t)p.i_w1[r] * D + lane;
-      acc += s.yd * p.w[k] + s.y * p.wd[k];
-    } else {
-      const size_t k2 = (size_t)p.i_w2[r] * D + lane;
-      const float w2 = p.w[k2];
-      acc += s.yd * w1 * w2 + s.y * (w1d * w2 + w1 * p.wd[k2]);
-    }
-  }
-  if (cur >= 0) atomicAdd(p.aggd + (size_t)cur * D + lane, acc);
-}
-
-struct GatedBArgs {
-  int rows, mode;
-  const float *CG, *CGd, *ln;
-  const int *i_dst, *i_w1, *i_w2;
-  const float *w, *wd;
-  const float *bar_agg, *g_agg;          // ATOM: [N,64] adjoints of the aggregate (gathered by centre); BOND: [Eb,64] by b1; ANGLE: bar_ang / g_ang [rows,64]
-  float *bar_w, *g_w;                    // ATOM: bar / G of wag [Eu,64]; BOND: of wbgc [Eb,64]  (atomics)
-  float *BCG, *GCG;                      // out [rows,128]: bar(c|g), G(c|g)
-  float* g_ln;                           // [4][64] LayerNorm-affine gradients (atomics)
-};
-
-static __global__ __launch_bounds__(256) void k2_gated_b(GatedBArgs p) {
-  const int lane = threadIdx.x & 63;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
-  const float g1 = p.ln[lane], b1 = p.ln[D + lane], g2 = p.ln[2 * D + lane], b2 = p.ln[3 * D + lane];
-  float lnacc[4] = {0.f, 0.f, 0.f, 0.f};
-  const int per = (p.rows + nwaves - 1) / nwaves;          // contiguous rows per wave: see k2_gated_t
-  const int rb = min(p.rows, wave * per), re = min(p.rows, rb + per);
-  int cur = -1;
-  float bar_a = 0.f, g_a = 0.f;                            // adjoints of the run's aggregate row
-  float w1 = 0.f, w1d = 0.f, acc_bw = 0.f, acc_gw = 0.f;   // BOND: the owning bond's weight row and its gradient sums
-  float in[4] = {0.f, 0.f, 0.f, 0.f};                      // next row's inputs in flight over this row's work (see k2_gated_t)
-  if (rb < re) { const size_t o = (size_t)rb * 2 * D; in[0] = p.CG[o + lane]; in[1] = p.CG[o + D + lane]; in[2] = p.CGd[o + lane]; in[3] = p.CGd[o + D + lane]; }
-  for (int r = rb; r < re; ++r) {
-    const size_t o = (size_t)r * 2 * D;
-    const float c0 = in[0], c1 = in[1], c2 = in[2], c3 = in[3];
-    if (r + 1 < re) { const size_t o1 = o + 2 * D; in[0] = p.CG[o1 + lane]; in[1] = p.CG[o1 + D + lane]; in[2] = p.CGd[o1 + lane]; in[3] = p.CGd[o1 + D + lane]; }
-    const GatedRow s = gated_row_fwd(c0, c1, c2, c3, g1, b1, g2, b2);
-    float bar_y, g_y;
-    if (p.mode == T2_ANGLE) {
-      bar_y = p.bar_agg[(size_t)r * D + lane];
-      g_y = p.g_agg[(size_t)r * D + lane];
-    } else {
-      const int dst = p.i_dst[r];
-      if (dst != cur) {
-        if (p.mode == T2_BOND && cur >= 0) {
-          atomicAdd(p.bar_w + (size_t)cur * D + lane, acc_bw);
-          atomicAdd(p.g_w + (size_t)cur * D + lane, acc_gw);
-        }
-        cur = dst;
-        bar_a = p.bar_agg[(size_t)dst * D + lane];
-        g_a = p.g_agg[(size_t)dst * D + lane];
-        if (p.mode == T2_BOND) {        // i_w1 == i_dst
-          w1 = p.w[(size_t)dst * D + lane];
-          w1d = p.wd[(size_t)dst * D + lane];
-          acc_bw = acc_gw = 0.f;
-        }
-      }
-      if (p.mode == T2_ATOM) {
-        const size_t k = (size_t)p.i_w1[r] * D + lane;
-        const float w = p.w[k], wd = p.wd[k];
-        atomicAdd(p.bar_w + k, s.y * bar_a + s.yd * g_a);
-        atomicAdd(p.g_w + k, s.y * g_a);
-        bar_y = w * bar_a + wd * g_a;
-        g_y = w * g_a;
-      } else {
-        const size_t k2 = (size_t)p.i_w2[r] * D + lane;
-        const float w2 = p.w[k2], w2d = p.wd[k2];
-        acc_bw += s.y * w2 * bar_a + (s.yd * w2 + s.y * w2d) * g_a;
-        acc_gw += s.y * w2 * g_a;
-        atomicAdd(p.bar_w + k2, s.y * w1 * bar_a + (s.yd * w1 + s.y * w1d) * g_a);
-        atomicAdd(p.g_w + k2, s.y * w1 * g_a);
-        bar_y = w1 * w2 * bar_a + (w1d * w2 + w1 * w2d) * g_a;
-        g_y = w1 * w2 * g_a;
-      }
-    }
-    float bar_c, bar_g, g_c, g_g;
-    gated_row_bwd(s, bar_y, g_y, g1, g2, lnacc, bar_c, bar_g, g_c, g_g);
-    p.BCG[o + lane] = bar_c;
-    p.BCG[o + D + lane] = bar_g;
-    p.GCG[o + lane] = g_c;
-    p.GCG[o + D + lane] = g_g;
-  }
-  if (p.mode == T2_BOND && cur >= 0) {
-    atomicAdd(p.bar_w + (size_t)cur * D + lane, acc_bw);
-    atomicAdd(p.g_w + (size_t)cur * D + lane, acc_gw);
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) atomicAdd(p.g_ln + q * D + lane, lnacc[q]);
-}
-
 // hidden layer:  bar(z) = silu'(z) bar(H) + silu''(z) zd G(H),   G(z) = silu'(z) G(H)      (elementwise over [rows,128])
 static __global__ void k2_hidden_b(const float* __restrict__ Z, const float* __restrict__ Zd, const float* __restrict__ BH,
                             const float* __restrict__ GH, float* __restrict__ BZ, float* __restrict__ GZ, size_t n) {
@@ -292,54 +130,6 @@ static __global__ void k2_hidden_b(const float* __restrict__ Z, const float* __r
   const float z = Z[i], d1 = dsiluf_(z), gh = GH[i];
   BZ[i] = d1 * BH[i] + ddsiluf_(z) * Zd[i] * gh;
   GZ[i] = d1 * gh;
-}
-
-// scatter of the first-layer adjoints back to the tables: three destinations per row, bar and G together
-struct ScatterZArgs {
-  int rows;
-  const float *BZ, *GZ;           // [rows,128]
-  float *b0, *b1, *b2;            // bar table gradients (zeroed)
-  float *g0, *g1, *g2;            // G table gradients
-  int ld0, ld1, ld2, off0, off1, off2;
-  const int *i0, *i1, *i2;
-};
-
-// One wave = 16 consecutive rows staged in LDS; each destination leaves the tile as run sums over equal adjacent keys
-// (mfma_tile.h:seg_colsum_atomic): the rows are centre-major (edges) / sorted by owning bond (angles), so the first key is one
-// long run, and keys that are not sorted simply make 16 runs of one row -- one 256-B atomic row per run and 64 columns.
-constexpr int SZ_TS = 2 * D + PAD;
-constexpr size_t scatter_z_lds() { return sizeof(float) * 4 * 2 * TILE_ROWS * SZ_TS; }
-
-static __global__ __launch_bounds__(256) void k2_scatter_z(ScatterZArgs p) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  float* TB = smem + wv * 2 * TILE_ROWS * SZ_TS;
-  float* TG = TB + TILE_ROWS * SZ_TS;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
-  const int ntiles = (p.rows + TILE_ROWS - 1) / TILE_ROWS;
-  const int hw = lane >> 5, t4 = lane & 31;     // half-wave per row, 32 lanes x float4 = one 512-B row
-  for (int tile = wave; tile < ntiles; tile += nwaves) {
-    const int row0 = tile * TILE_ROWS, nvalid = min(TILE_ROWS, p.rows - row0);
-    const int j = lane & 15;
-    const int r = row0 + (j < nvalid ? j : 0);
-    const int k0 = j < nvalid ? p.i0[r] : -1, k1 = j < nvalid ? p.i1[r] : -1, k2 = j < nvalid ? p.i2[r] : -1;
-#pragma unroll
-    for (int it = 0; it < TILE_ROWS / 2; ++it) {
-      const int rr = 2 * it + hw;
-      if (rr < nvalid) {
-        *reinterpret_cast<f32x4*>(TB + rr * SZ_TS + 4 * t4) = *reinterpret_cast<const f32x4*>(p.BZ + (size_t)(row0 + rr) * 2 * D + 4 * t4);
-        *reinterpret_cast<f32x4*>(TG + rr * SZ_TS + 4 * t4) = *reinterpret_cast<const f32x4*>(p.GZ + (size_t)(row0 + rr) * 2 * D + 4 * t4);
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-    seg_colsum_atomic<2 * D>(TB, SZ_TS, k0, nvalid, p.b0 + p.off0, p.ld0, lane);
-    seg_colsum_atomic<2 * D>(TB, SZ_TS, k1, nvalid, p.b1 + p.off1, p.ld1, lane);
-    seg_colsum_atomic<2 * D>(TB, SZ_TS, k2, nvalid, p.b2 + p.off2, p.ld2, lane);
-    seg_colsum_atomic<2 * D>(TG, SZ_TS, k0, nvalid, p.g0 + p.off0, p.ld0, lane);
-    seg_colsum_atomic<2 * D>(TG, SZ_TS, k1, nvalid, p.g1 + p.off1, p.ld1, lane);
-    seg_colsum_atomic<2 * D>(TG, SZ_TS, k2, nvalid, p.g2 + p.off2, p.ld2, lane);
-    __builtin_amdgcn_wave_barrier();
-  }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -428,54 +218,6 @@ static __global__ __launch_bounds__(256) void k2_embed_lin(const float* __restri
   }
 }
 
-// frequency gradients of the radial bases:  d f_j += sum_k [ bar(rbf)_kj d rbf/df + G(rbf)_kj d2 rbf/(dr df) rdot_k ]
-// with bar(rbf) = bar(hb0) Wbe + bar(wag) Wag (cutoff r_atom) or bar(wbg) Wbg (cutoff r_bond): lane j = basis index
-struct FreqGradArgs {
-  int rows;                       // bonds (atom-graph cutoff: all Eu; bond-graph cutoff: the Eb node bonds)
-  const int* row_und;             // null: row k is undirected bond k; else undirected index of row
-  const f32x4 *ev, *vd4;
-  const int* u_u2d;
-  const float* freq;
-  float rc;
-  Envelope env;
-  const float *barA, *gA, *WA;    // adjoint rows [rows,64] and their [64][31] weight
-  const float *barB, *gB, *WB;    // optional second pair (null)
-  float* g_freq;                  // [31]
-};
-
-static __global__ __launch_bounds__(256) void k2_freq_grad(FreqGradArgs p) {
-  __shared__ float WAs[D * NRAD], WBs[D * NRAD];
-  for (int i = threadIdx.x; i < D * NRAD; i += blockDim.x) {
-    WAs[i] = p.WA[i];
-    WBs[i] = p.WB ? p.WB[i] : 0.f;
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
-  const float fj = lane < NRAD ? p.freq[lane] : 0.f;
-  float acc = 0.f;
-  for (int r = wave; r < p.rows; r += nwaves) {
-    const int k = p.row_und ? p.row_und[r] : r;
-    const int e = p.u_u2d[k];
-    const float rr = p.ev[e][3], rd = p.vd4[e][3];
-    const size_t o = (size_t)r * D + lane;
-    const float ba = p.barA[o], ga = p.gA[o], bb = p.barB ? p.barB[o] : 0.f, gb = p.gB ? p.gB[o] : 0.f;
-    float bar_x = 0.f, g_x = 0.f;      // this lane's basis index j = lane: sum over the 64 features (broadcast from every lane)
-#pragma unroll 8
-    for (int f = 0; f < D; ++f) {
-      const float wa = lane < NRAD ? WAs[f * NRAD + lane] : 0.f, wb = lane < NRAD ? WBs[f * NRAD + lane] : 0.f;
-      bar_x += bcast(ba, f) * wa + bcast(bb, f) * wb;
-      g_x += bcast(ga, f) * wa + bcast(gb, f) * wb;
-    }
-    if (lane < NRAD) {
-      float v, dr, df, drdf;
-      rbf_all(rr, p.rc, fj, p.env, v, dr, df, drdf);
-      acc += bar_x * df + g_x * drdf * rd;
-    }
-  }
-  if (lane < NRAD) atomicAdd(p.g_freq + lane, acc);
-}
-
 // Fourier basis of every angle with tangent:  X [A,32], Xd [A,32];  also theta and thetadot (for the frequency gradient)
 static __global__ void k2_angle_basis(const f32x4* __restrict__ eu, const f32x4* __restrict__ ud4, const int* __restrict__ a_d1,
                                const int* __restrict__ a_d2, const float* __restrict__ freq, float* __restrict__ X, float* __restrict__ Xd,
@@ -502,38 +244,6 @@ static __global__ void k2_angle_basis(const f32x4* __restrict__ eu, const f32x4*
   X[t] = x;
   Xd[t] = dx * thd;
   if (j == 0) { th2[2 * a] = theta; th2[2 * a + 1] = thd; }
-}
-
-// d g_q += sum_a [ bar(four) d four/dg + G(four) d2 four/(d theta dg) thetadot ],  bar(four) = bar(ang0) Wae
-static __global__ __launch_bounds__(256) void k2_angle_freq_grad(const float* __restrict__ bar_ang, const float* __restrict__ g_ang,
-                                                          const float* __restrict__ Wae, const float* __restrict__ th2,
-                                                          const float* __restrict__ freq, float* __restrict__ g_freq, int n_angles) {
-  __shared__ float Ws[D * NANG];
-  for (int i = threadIdx.x; i < D * NANG; i += blockDim.x) Ws[i] = Wae[i];
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
-  // lane j in 1..15: sin column of frequency j-1; lane j in 16..30: cos column of frequency j-16
-  const bool is_sin = lane >= 1 && lane <= NFREQ, is_cos = lane > NFREQ && lane < NANG;
-  const int q = is_sin ? lane - 1 : (is_cos ? lane - 1 - NFREQ : 0);
-  const float gq = freq[q];
-  float acc = 0.f;
-  for (int a = wave; a < n_angles; a += nwaves) {
-    const float ba = bar_ang[(size_t)a * D + lane], ga = g_ang[(size_t)a * D + lane];
-    float bar_x = 0.f, g_x = 0.f;
-#pragma unroll 8
-    for (int f = 0; f < D; ++f) {
-      const float w = lane < NANG ? Ws[f * NANG + lane] : 0.f;
-      bar_x += bcast(ba, f) * w;
-      g_x += bcast(ga, f) * w;
-    }
-    const float theta = th2[2 * a], thd = th2[2 * a + 1];
-    float sn, cs;
-    sincos_cw(gq * theta, sn, cs);
-    if (is_sin) acc += (bar_x * theta * cs + g_x * (cs - gq * theta * sn) * thd) * INV_SQRT_PI;
-    if (is_cos) acc += (-bar_x * theta * sn + g_x * (-sn - gq * theta * cs) * thd) * INV_SQRT_PI;
-  }
-  if (is_sin || is_cos) atomicAdd(g_freq + q, acc);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -598,12 +308,6 @@ static __global__ void k2_readout_seed(const float* __restrict__ w3, const float
   bar_s[t] = c * w3[f];
   g_s[t] = w3[f];
   dw3_rows[t] = c * s3[t] + s3d[t];
-}
-
-// out[i] = a[i] + b[i]   /   magmom head handled by k_magmom_bwd (kernels_train.h)
-static __global__ void k2_add(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, size_t n) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = a[i] + b[i];
 }
 
 }  // namespace chg

@@ -3,7 +3,7 @@
 //   d f_j += sum_k [ bar(basis)_kj  d basis_j / d f  +  G(basis)_kj  d2 basis_j / (d x d f)  xdot_k ]
 //   bar(basis) = bar(h) W_emb (+ bar(w) W_w),   G(basis) likewise        (x = bond length r / angle theta)
 //
-// kernels_train2.h did this one ROW per wave with lane = basis index (31 of 64 lanes busy, a 64-step loop of four lane broadcasts and
+// Their first form took one ROW per wave with lane = basis index (31 of 64 lanes busy, a 64-step loop of four lane broadcasts and
 // two LDS reads per row: 640 vector instructions per row, 6.5 ms of a 1024-structure training step).  Here a wave owns 16 rows like
 // every tile kernel of the engine: the adjoint rows are contracted with W^T on the matrix pipe (`embed_adjoint`: split-precision,
 // rows scaled per row by a power of two -- gradients of any magnitude), which leaves lane (row j, g) with the 8 basis indices

@@ -1,12 +1,13 @@
 // kernels_train2_tile.h -- the second-order fine-tuning sweep (kernels_train2.h: derivation, reference lines) FUSED per layer:
-// one tile kernel per layer kind and direction instead of the chain  gather_z -> 4 row GEMMs -> gated_t | gated_b -> 4 row GEMMs
-// -> hidden_b -> scatter_z  over [rows,128] arrays in HBM (a dozen array passes per layer visit; the sweep was HBM-bound at
-// ~3.5 TB/s for 215 ms per 1024-structure step).
+// one tile kernel per layer kind and direction instead of a chain of row kernels and row GEMMs over [rows,128] arrays in HBM
+// (gather of z, the two GEMMs of the hidden layer, the gated tail, its adjoint, the hidden layer's adjoint, scatter of the adjoints
+// to the tables: a dozen array passes per layer visit; that form of the sweep was HBM-bound at ~3.5 TB/s for 215 ms per
+// 1024-structure step).
 //
 // One wave = 16 rows, as in the first-order kernels (mfma_tile.h).  Linear pieces run on the matrix pipe in the accumulator
 // layout (split-precision contractions against row-major weight images in LDS, mfma_split.h: one image serves W and W^T); the
 // row-local nonlinear piece -- LayerNorm, activations, their tangents and the two-adjoint backward -- reuses gated_row_fwd /
-// gated_row_bwd of the unfused sweep verbatim in their layout (one row at a time, lane = feature): the tile goes through the
+// gated_row_bwd (kernels_train2.h) verbatim in their layout (one row at a time, lane = feature): the tile goes through the
 // wave's LDS tile eight rows at a time.  Only what the weight-gradient contractions (k_xty) need leaves the kernel as rows:
 // H, Hd, bar(c|g), G(c|g).  Nothing of the tangent forward is kept: the reverse kernel recomputes it from the tables.
 #pragma once
@@ -15,10 +16,6 @@
 
 #include "kernels_conv.h"
 #include "kernels_train2.h"
-
-#ifndef CHG_T2_SB
-#define CHG_T2_SB 0
-#endif
 
 namespace chg {
 
@@ -130,11 +127,7 @@ __device__ __forceinline__ void ln2_backward(V64& bn, V64& gn, const float* gamm
   }
 }
 
-// k2_atom<reverse> keeps the one-row-at-a-time form of its row-local part (t2_rows below: why); CHG_T2_ROWS=1: the tangent forward as well
-#ifndef CHG_T2_ROWS
-#define CHG_T2_ROWS 0
-#endif
-constexpr bool t2_rows_atom(bool reverse) { return CHG_T2_ROWS != 0 || reverse; }
+// k2_atom<true> (reverse) keeps the one-row-at-a-time form of its row-local part: why, above k2_angle
 
 struct Atom2Args {
   int n_edges;
@@ -234,7 +227,7 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k2_atom(Atom2Args p) {
         gemm_rm<VT, VT, true, false>(cdg.t, I2g, D, D, hd.t, j, g, lane_t);
       }
     }
-    if constexpr (t2_rows_atom(REVERSE)) {
+    if constexpr (REVERSE) {
     // ---- row-local part, eight rows at a time through the tile (lane_t = feature) ----
     // Rolled loops: unrolled, the sixteen copies of the row math cost 175 spilled registers.  One bond (two rows) per step; what the
     // next bond needs from memory (adjoints of its two atoms' aggregates, its weight row, the old rows of the weight adjoints) is
@@ -314,8 +307,8 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k2_atom(Atom2Args p) {
       continue;
     }
     } else {
-    // ---- row-local part in the accumulator layout, sixteen rows at once (tangent forward only: t2_rows_atom) ----
-    static_assert(!REVERSE, "the AtomConv reverse kernel keeps the one-row-at-a-time form (t2_rows_atom)");
+    // ---- row-local part in the accumulator layout, sixteen rows at once (tangent forward only) ----
+    static_assert(!REVERSE, "the AtomConv reverse kernel keeps the one-row-at-a-time form");
     float r1, r2, mt1, mt2;
     ln2_forward(cc, cdc, r1, mt1);            // cc = xhat1, cdc = P(cd)
     ln2_forward(cg, cdg, r2, mt2);
@@ -450,16 +443,12 @@ constexpr size_t t2_angle_lds() {
 // WITH a hidden layer (BondConv here, AtomConv above).  Next to the hidden layer's state and six gathered rows per angle the two passes
 // of the accumulator-layout form do not fit 256 registers (225-270 spilled registers: 40 ms instead of 29 per step), and a form that
 // parks the row state in the dump rows and streams it back slice by slice waits for its own loads behind the scatter's atomics (57 ms);
-// profiles/r05_experiments.md section 13.  CHG_T2_ROWS=1: every instantiation (A/B builds).
-// CHG_T2_BOND_ACC=1 (A/B builds): the BondConv reverse kernel in the accumulator layout as well -- three passes over the slices, the
-// first of which forms bar(y), G(y) from the six bond rows and keeps them in 32 registers, so that the other two read nothing.  Round 6,
-// same box: 84 spilled registers (56 scratch stores, 77 loads per tile against 25 / 25), t2_bond_b 31.2 ms against 29.7 in the
+// profiles/r05_experiments.md section 13.
+// The BondConv reverse kernel in the accumulator layout as well was tried in round 6 -- three passes over the slices, the
+// first of which formed bar(y), G(y) from the six bond rows and kept them in 32 registers, so that the other two read nothing:
+// 84 spilled registers (56 scratch stores, 77 loads per tile against 25 / 25), t2_bond_b 31.2 ms against 29.7 in the
 // one-row-at-a-time form.  The passes themselves are the spill source: the same kernel cut off behind the BCG / GCG dump (the
 // "recompute + adjoint of the tail" half of a two-kernel split) spills 169.
-#ifndef CHG_T2_BOND_ACC
-#define CHG_T2_BOND_ACC 0
-#endif
-constexpr bool t2_rows(bool hidden, bool reverse) { return CHG_T2_ROWS != 0 || (hidden && reverse && !CHG_T2_BOND_ACC); }
 
 template <bool HIDDEN, bool REVERSE>
 __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k2_angle(Angle2Args p) {
@@ -549,7 +538,7 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k2_angle(Angle2Args p) {
         }
       }
     }
-    if constexpr (t2_rows(HIDDEN, REVERSE)) {
+    if constexpr (HIDDEN && REVERSE) {
     // ---- row-local part, eight rows at a time through the tile (lane_t = feature); what the next row needs from memory is
     //      requested a row ahead ----
     float acc = 0.f, acc_bw = 0.f;                    // BondConv: run sums over the owning bond
@@ -651,7 +640,6 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k2_angle(Angle2Args p) {
     // ---- row-local part in the accumulator layout: sixteen rows at once (the helpers above) ----
     const bool valid = j < nvalid;
     const int kb1 = valid ? b1 : -1;
-    [[maybe_unused]] const int kb2 = valid ? b2 : -1;
     float r1, r2, mt1, mt2;
     ln2_forward(cc, cdc, r1, mt1);            // cc = xhat1, cdc = P(cd): what the way back needs of the first LayerNorm
     ln2_forward(cg, cdg, r2, mt2);
@@ -660,18 +648,11 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k2_angle(Angle2Args p) {
     int sb1 = b1, sb2 = b2, srow = row, sg = g;   // the slices' row indices and column group (made opaque between the two reverse passes)
     // what a slice reads from memory, requested one slice ahead
     struct SliceIn { f32x4 w1, w1d, w2, w2d, a, b; };
-    // BondConv reverse: bar(y), G(y) of the tile, formed once (pass 3, which reads the six bond rows anyway) and kept for passes 1 and 2,
-    // which then read nothing from memory: 32 registers instead of 2 x 24 of slice inputs in flight and 2 x 24 loads per pass
-    [[maybe_unused]] V64 by, gy;
-    auto slice_in = [&](int ft, auto pass_c) {
-      constexpr int PASS = decltype(pass_c)::value;
+    auto slice_in = [&](int ft) {
       SliceIn in;
       in.w1 = in.w1d = in.w2 = in.w2d = in.a = in.b = zero4();
       if (HIDDEN) {                          // BondConv: u = y wbg[b1] wbg[b2] summed over the angles of bond b1
-        if (PASS == 0 || PASS == 3) {
-          in.w1 = rd4(p.w, sb1, ft, sg); in.w1d = rd4(p.wd, sb1, ft, sg); in.w2 = rd4(p.w, sb2, ft, sg); in.w2d = rd4(p.wd, sb2, ft, sg);
-        }
-        if (PASS == 3) { in.a = rd4(p.bar_agg, sb1, ft, sg); in.b = rd4(p.g_agg, sb1, ft, sg); }     // the two adjoints of the owning bond's aggregate
+        in.w1 = rd4(p.w, sb1, ft, sg); in.w1d = rd4(p.wd, sb1, ft, sg); in.w2 = rd4(p.w, sb2, ft, sg); in.w2d = rd4(p.wd, sb2, ft, sg);
       } else if (!REVERSE) {                 // AngleUpdate: ang' = ang + y
         in.a = rd4(p.angd, srow, ft, sg);
       } else {
@@ -695,19 +676,9 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k2_angle(Angle2Args p) {
         if (PASS == 0) {
           if (HIDDEN) o0[r] = e.yd * in.w1[r] * in.w2[r] + e.y * (in.w1d[r] * in.w2[r] + in.w1[r] * in.w2d[r]);
           else o0[r] += e.yd;
-        } else if (PASS == 3) {
-          // BondConv reverse: bar adjoints of the two bond weights (first bond: a run sum over the tile's rows, second bond: a row each)
-          o0[r] = e.y * in.w2[r] * in.a[r] + (e.yd * in.w2[r] + e.y * in.w2d[r]) * in.b[r];
-          o1[r] = e.y * in.w1[r] * in.a[r] + (e.yd * in.w1[r] + e.y * in.w1d[r]) * in.b[r];
-          // y enters u = y w1 w2: bar(y) = w1 w2 bar(u) + (w1 w2)_d G(u), G(y) = w1 w2 G(u)
-          const float w12 = in.w1[r] * in.w2[r], w12d = in.w1d[r] * in.w2[r] + in.w1[r] * in.w2d[r];
-          by.t[ft][r] = w12 * in.a[r] + w12d * in.b[r];
-          gy.t[ft][r] = w12 * in.b[r];
         } else {
-          float bar_y = in.a[r], g_y = in.b[r];
-          if (HIDDEN) { bar_y = by.t[ft][r]; g_y = gy.t[ft][r]; }
           float bn1, gn1, bn2, gn2;
-          gate1_bwd(e, bar_y, g_y, bn1, gn1, bn2, gn2);
+          gate1_bwd(e, in.a[r], in.b[r], bn1, gn1, bn2, gn2);
           const float h1 = gn1 * ga1[r], p1 = bn1 * ga1[r], h2 = gn2 * ga2[r], p2 = bn2 * ga2[r];
           if (PASS == 1) {
             sum[0] += h1; sum[1] += h1 * xh1; sum[2] += h1 * pt1; sum[3] += p1; sum[4] += p1 * xh1;
@@ -732,9 +703,9 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k2_angle(Angle2Args p) {
     };
     auto sweep = [&](auto pass_c) {
       __builtin_amdgcn_wave_barrier();
-      SliceIn cur = slice_in(0, pass_c);
+      SliceIn cur = slice_in(0);
       CHG_EV(ft) {
-        const SliceIn nxt = slice_in(ft + 1 < VT ? ft + 1 : ft, pass_c);
+        const SliceIn nxt = slice_in(ft + 1 < VT ? ft + 1 : ft);
         slice(ft, cur, pass_c);
         cur = nxt;
       }
@@ -757,12 +728,6 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k2_angle(Angle2Args p) {
       if (HIDDEN) seg_colsum_atomic<D>(T, TS, kb1, nvalid, p.aggd, D, lane_t);
       __builtin_amdgcn_wave_barrier();
       continue;
-    }
-    if (HIDDEN) {                               // (before pass 2 overwrites xhat / P(cd))
-      sweep(std::integral_constant<int, 3>{});
-      seg_colsum_atomic<D>(T, TS, kb1, nvalid, p.bar_w, D, lane_t);
-      row_atomic_add<D>(T + D, TS, kb2, nvalid, p.bar_w, D, lane_t);
-      __builtin_amdgcn_wave_barrier();
     }
     sweep(std::integral_constant<int, 1>{});
     tile_colsums(lnacc[2], lnacc[3]);
