@@ -34,15 +34,7 @@ using namespace chg;
 
 constexpr int MAX_CONV = 8;
 constexpr float F16_OPERAND_LIMIT = 65504.0f;   // largest finite f16: forward operands of the split contractions are not rescaled
-#ifndef CHG_FWD_WAVES
-#define CHG_FWD_WAVES 8
-#endif
-#ifdef CHG_PHASE_TIMING
-constexpr size_t PHASE_FLOATS = (size_t)8 * 2 * 10 * PH_WAVES;   // kernels_conv.h PH_FLUSH
-#else
-constexpr size_t PHASE_FLOATS = 64;
-#endif
-constexpr int FWD_WAVES = CHG_FWD_WAVES;   // waves per workgroup of the light forward kernels (12 = 3 per SIMD measured no better: profiles notes)
+constexpr int FWD_WAVES = 8;   // waves per workgroup of the light forward kernels (12 = 3 per SIMD measured no better: profiles notes)
 
 struct ACW { const float *w_cn, *w_bond, *b1, *q_bias, *q_shift; GatedW g; const float *w2c_t, *w2g_t, *w_out, *b_out, *w_out_t, *w_cn_t, *w_bond_t; };
 struct BCW { const float *w_bij, *w_ang, *w_ctr, *b1; GatedW g; const float *w2c_t, *w2g_t, *w_out, *b_out, *w_out_t, *w_bij_t, *w_ang_t, *w_ctr_t; };
@@ -93,7 +85,6 @@ struct chg_engine {
   float* d_images = nullptr;
   const float* p_elem = nullptr;               // [94][256] P table of the first AtomConv per element (k_prologue; rebuilt with the images)
   const float* img_ac_fwd[2][MAX_CONV] = {};   // [without / with q_bias][layer]
-  const float* img_ac_bwd[MAX_CONV] = {};
   const float* img_ac_bwd_rm[MAX_CONV] = {};   // row-major block of the fused adjoint (k_atomconv_image_rm)
   const float* img_angle[2][2 * MAX_CONV] = {};   // [fwd / bwd][slot: BondConv l | L + AngleUpdate l]
   ErrText err;                // last failure text of the calling thread
@@ -166,7 +157,6 @@ struct chg_batch {
   float *energy, *site_energy, *site_raw, *magmom, *crystal_fea, *force, *virial, *volume;
   // reverse sweep
   float *Ga, *GA, *Gb, *Gwag, *Gwbgc, *Gang, *GQ, *Gagg, *Grk, *Gu;
-  float* phase = nullptr;   // CHG_PHASE_TIMING builds: per-phase shader-clock totals of the angle kernels
   WinIndex win{};           // centre-major row order + window slots of the angle adjoints (kernels_angle_w.h), built by prepare_windows
   int *win_tmp = nullptr, *win_scan = nullptr;
   int win_grid = 64;        // workgroups of the per-atom kernels (a multiple of 64: the atom schedule is built for it, k_win_schedule)

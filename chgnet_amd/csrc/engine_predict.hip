@@ -100,11 +100,8 @@ int collect_profile(chg_engine* eng) {
   return CHG_OK;
 }
 
-// workgroups per CU launched for the tile kernels (CHGNET_GRID_MULT, timing experiments; default 2)
-static int tile_grid_mult() {
-  static const int m = [] { const char* e = std::getenv("CHGNET_GRID_MULT"); const int v = e ? std::atoi(e) : 2; return v > 0 ? v : 2; }();
-  return m;
-}
+constexpr int TILE_GRID_MULT = 2;    // workgroups per CU launched for the tile kernels
+constexpr int EMBED_GRID_MULT = 2;   // ... and for the angle basis expansion
 
 int grid_for(int rows, int max_blocks, int block_rows) {
   int ntiles = (rows + block_rows - 1) / block_rows;
@@ -113,22 +110,15 @@ int grid_for(int rows, int max_blocks, int block_rows) {
   return std::max(g, 1);
 }
 
-// grid of a tile kernel: CHGNET_GRID_MULT workgroups per CU -- one per CU when that already gives every workgroup no more than a few
+// grid of a tile kernel: TILE_GRID_MULT workgroups per CU -- one per CU when that already gives every workgroup no more than a few
 // tiles (small batches: the second workgroup of a CU would stage the weights again for one or two tiles; MD replay 1.478 -> 1.437 ms)
 int tile_grid(chg_engine* eng, int rows, int block_rows) {
   const int ntiles = (rows + block_rows - 1) / block_rows;
-  const int mult = ntiles <= 4 * eng->num_cus ? 1 : tile_grid_mult();
+  const int mult = ntiles <= 4 * eng->num_cus ? 1 : TILE_GRID_MULT;
   // rounded UP to a multiple of 8 (tile_range's XCD mapping): rounding 221 blocks down to 216 left 42 waves of a 256-atom cell's
   // AtomConv kernels with a second tile, i.e. doubled the kernel's time; a workgroup without tiles costs nothing
   return std::max(1, std::min((ntiles + 7) & ~7, mult * eng->num_cus));
 }
-
-#ifdef CHG_EXPERIMENTS
-static int exp_nw() {
-  static const int v = [] { const char* e = std::getenv("CHGNET_EXP_NW"); return e ? std::atoi(e) : 0; }();
-  return v;
-}
-#endif
 
 template <int K, int NOUT, int PARTS = 1>
 int launch_rows_gemm(chg_engine* eng, const char* label, const RowsGemm& p) {
@@ -223,12 +213,12 @@ int zero(chg_engine* eng, void* p, size_t bytes) {
 // Prebuilt weight blocks (see stage_image, mfma_tile.h): one per tile kernel and layer, laid out by the kernels' own staging code.
 int build_images(chg_engine* eng) {
   const int L = eng->desc.n_conv;
-  constexpr size_t AF = ac_fwd_image_floats(), AB = ac_bwd_image_floats();
+  constexpr size_t AF = ac_fwd_image_floats(), AB = ac_bwd_rm_image_floats();
   constexpr size_t BF = AngleLds<true, false>::tiles, BB = AngleLds<true, true>::tiles, UF = AngleLds<false, false>::tiles,
                    UB = AngleLds<false, true>::tiles;
   static_assert(AF % 4 == 0 && AB % 4 == 0 && BF % 4 == 0 && BB % 4 == 0 && UF % 4 == 0 && UB % 4 == 0, "images are copied in 16-byte units");
   constexpr size_t PE = (size_t)94 * 4 * D;     // per-element P table of AtomConv 0 (k_prologue)
-  const size_t total = (size_t)L * (2 * AF + AB + ac_bwd_rm_image_floats()) + (size_t)(L - 1) * (BF + BB + UF + UB) + PE;
+  const size_t total = (size_t)L * (2 * AF + AB) + (size_t)(L - 1) * (BF + BB + UF + UB) + PE;
   if (!eng->d_images) {
     HIP_TRY(eng, hipMalloc(&eng->d_images, total * sizeof(float)));
     HIP_TRY(eng, hipMemsetAsync(eng->d_images, 0, total * sizeof(float), eng->stream));   // slots no staging writes (unused vectors)
@@ -242,12 +232,9 @@ int build_images(chg_engine* eng) {
       a.q_bias = qb ? eng->w.ac[l].q_bias : nullptr;
       float* img = take(AF);
       eng->img_ac_fwd[qb][l] = img;
-      hipLaunchKernelGGL(k_atomconv_image<false>, dim3(1), dim3(BLOCK), 0, eng->stream, a, img);
+      hipLaunchKernelGGL(k_atomconv_image<>, dim3(1), dim3(BLOCK), 0, eng->stream, a, img);
     }
     float* img = take(AB);
-    eng->img_ac_bwd[l] = img;
-    hipLaunchKernelGGL(k_atomconv_image<true>, dim3(1), dim3(BLOCK), 0, eng->stream, a, img);
-    img = take(ac_bwd_rm_image_floats());
     eng->img_ac_bwd_rm[l] = img;
     hipLaunchKernelGGL(k_atomconv_image_rm, dim3(1), dim3(BLOCK), 0, eng->stream, a, img);
   }
@@ -305,14 +292,6 @@ int atomconv_q_table(chg_engine* eng, chg_batch* b, int l) {
   return CHG_OK;
 }
 
-// Tile order per kernel: bit k of CHGNET_TILE_INTERLEAVE (default 31 = every kernel; A/B switch) -- 1 atomconv_fwd, 2 atomconv_bwd,
-// 4 bondconv_fwd, 8 angleupd_fwd, 16 row-order angle adjoints.  Same-box A/B (profiles/r04_experiments.md): the interleaved sweep cuts
-// the fabric traffic of every kernel by 20-30 %; their times move by 0-3 % (they are bound by vector-ALU issue, not by bytes).
-static int interleave_mask() {
-  static const int m = [] { const char* e = std::getenv("CHGNET_TILE_INTERLEAVE"); return e ? std::atoi(e) : 31; }();
-  return m;
-}
-
 AtomConvArgs atomconv_args(chg_engine* eng, chg_batch* b, int l) {
   AtomConvArgs a{};
   a.P = b->Pl[l]; a.Q = b->Ql[l]; a.wag = b->wag;
@@ -320,7 +299,6 @@ AtomConvArgs atomconv_args(chg_engine* eng, chg_batch* b, int l) {
   a.gw = eng->w.ac[l].g;
   a.agg = b->agg_l[l]; a.GA = b->GA; a.GP = b->GP_l[l]; a.GQ = b->GQ; a.Gwag = b->Gwag;
   a.first_wag = l == b->L - 1;   // the reverse sweep starts with the last AtomConv
-  a.phase = b->phase;
   a.hb0 = b->hb0;
   a.hbc = (b->Eb > 0 && b->hbc[l] != b->hbc[0]) ? b->hbc[l] : nullptr;   // bond-graph nodes carry layer-l features
   a.u_bnode = b->u_bnode;
@@ -338,13 +316,6 @@ int atomconv_fwd_kernel(chg_engine* eng, chg_batch* b, int l, bool keep_q) {
     a.image = eng->img_ac_fwd[a.q_bias ? 1 : 0][l];
     a.e_nbr = b->p_nbr;
     a.Qout = keep_q ? b->Ql[l] : nullptr;   // the reverse sweep gathers the bond partial as a table
-    a.interleave = interleave_mask() & 1;
-#ifdef CHG_EXPERIMENTS
-    if (exp_nw() == 4) {
-      const size_t lds4 = std::max(atomconv_lds<4, false, true>(), (size_t)100 << 10);
-      hipLaunchKernelGGL((k_atomconv_fwd<4>), dim3(tile_grid(eng, b->Ed, TILE_ROWS * 4)), dim3(64 * 4), lds4, eng->stream, a);
-    } else
-#endif
     hipLaunchKernelGGL((k_atomconv_fwd<FWD_WAVES>), dim3(tile_grid(eng, b->Ed, TILE_ROWS * FWD_WAVES)), dim3(64 * FWD_WAVES), lds, eng->stream, a);
     HIP_TRY(eng, hipGetLastError());
   }
@@ -361,30 +332,21 @@ int atomconv_fwd(chg_engine* eng, chg_batch* b, int l, bool keep_q) {
   return rows_gemm(eng, "gemm_out", 64, 64, b->agg_l[l], D, nullptr, w.w_out, w.b_out, b->atom[l], D, b->atom[l + 1], D, nullptr, b->N, 0);
 }
 
-// The adjoint with the dE/d h_bond update in its tiles (k_atomconv_bwd<false, true>: no dE/dQ table, no gemm_GQ).
+// The adjoint with the dE/d h_bond update in its tiles (k_atomconv_bwd<false>: no dE/dQ table, no gemm_GQ).
 // Same box, ms per headline step: table + gemm_GQ 4.52 + 1.38; fused 5.23: -0.6 ms, and one launch fewer per layer for MD-size
-// batches.  CHGNET_FUSE_GQ=0 switches back for A/B timing.
+// batches.
 constexpr size_t acb_fused_lds() { return sizeof(float) * ((size_t)ac_bwd_rm_image_floats() + WAVES * TILE_FLOATS); }
-static bool fuse_gq() {
-  static const bool on = [] { const char* e = std::getenv("CHGNET_FUSE_GQ"); return !e || std::atoi(e) != 0; }();
-  return on;
-}
 
-int atomconv_bwd_kernel(chg_engine* eng, chg_batch* b, int l, bool fused) {
-  {  // pair-ordered edge list: GQ (or, fused, Gb) and Gwag rows are owned by one tile each (no zeroing, no atomics)
+int atomconv_bwd_kernel(chg_engine* eng, chg_batch* b, int l) {
+  {  // pair-ordered edge list: Gb and Gwag rows are owned by one tile each (no zeroing, no atomics)
     AtomConvArgs a = atomconv_args(eng, b, l);
     a.e_center = b->p_center;
     a.e_nbr = b->p_nbr;
-    a.image = eng->img_ac_bwd[l];
-    a.interleave = (interleave_mask() >> 1) & 1;
+    a.image = eng->img_ac_bwd_rm[l];
     a.Gb = b->Gb;
     a.gb_accumulate = l == b->L - 1 ? 0 : 1;
     LaunchScope ls(eng, "atomconv_bwd");
-    if (fused) {
-      a.image = eng->img_ac_bwd_rm[l];
-      hipLaunchKernelGGL((k_atomconv_bwd<false, true>), dim3(tile_grid(eng, b->Ed)), dim3(BLOCK), acb_fused_lds(), eng->stream, a);
-    } else
-      hipLaunchKernelGGL(k_atomconv_bwd<false>, dim3(tile_grid(eng, b->Ed)), dim3(BLOCK), (atomconv_lds<WAVES, true>()), eng->stream, a);
+    hipLaunchKernelGGL(k_atomconv_bwd<false>, dim3(tile_grid(eng, b->Ed)), dim3(BLOCK), acb_fused_lds(), eng->stream, a);
     HIP_TRY(eng, hipGetLastError());
   }
   return CHG_OK;
@@ -394,22 +356,10 @@ int atomconv_bwd(chg_engine* eng, chg_batch* b, int l) {
   const ACW& w = eng->w.ac[l];
   if (b->Ed == 0) return CHG_OK;  // agg == 0: only the residual path, already in Ga
   TRY(rows_gemm(eng, "gemm_Gagg", 64, 64, b->Ga, D, nullptr, w.w_out_t, nullptr, nullptr, 0, b->GA, D, nullptr, b->N, 0));
-  const bool fused = fuse_gq();
-  TRY(atomconv_bwd_kernel(eng, b, l, fused));
-  if (fused) {
-    if (l > 0) TRY(rows_gemm_in2(eng, "gemm_GP", b->GP_l[l], 4 * D, w.w_cn_t, w.w_cn_t + 2 * D * D, b->Ga, nullptr, b->N, 1));
-    return CHG_OK;
-  }
-  if (l > 0 && small_rows(b->N) && small_rows(b->Eu)) {   // small batch: both in one launch (targets: atom rows, bond rows)
-    MultiGemm m;
-    m.add(RowsGemm{b->GP_l[l], 4 * D, nullptr, w.w_cn_t, nullptr, nullptr, 0, b->Ga, D, nullptr, b->N, 1, w.w_cn_t + 2 * D * D, 2 * D, 0, 0, 0}, D, D);
-    m.add(RowsGemm{b->GQ, 2 * D, nullptr, w.w_bond_t, nullptr, nullptr, 0, b->Gb, D, nullptr, b->Eu, l == b->L - 1 ? 0 : 1, nullptr, 0, 0, 0, 0}, D, D);
-    return launch_rows_gemm_multi<128>(eng, "gemm_GPQ", m);
-  }
-  if (l > 0) {  // dE/d atom[l] += GPc . Wc + GPn . Wn   (atom[0] is an embedding: no position dependence)
-    TRY(rows_gemm_in2(eng, "gemm_GP", b->GP_l[l], 4 * D, w.w_cn_t, w.w_cn_t + 2 * D * D, b->Ga, nullptr, b->N, 1));
-  }
-  return rows_gemm(eng, "gemm_GQ", 128, 64, b->GQ, 2 * D, nullptr, w.w_bond_t, nullptr, nullptr, 0, b->Gb, D, nullptr, b->Eu, l == b->L - 1 ? 0 : 1);
+  TRY(atomconv_bwd_kernel(eng, b, l));
+  // dE/d atom[l] += GPc . Wc + GPn . Wn   (atom[0] is an embedding: no position dependence)
+  if (l > 0) TRY(rows_gemm_in2(eng, "gemm_GP", b->GP_l[l], 4 * D, w.w_cn_t, w.w_cn_t + 2 * D * D, b->Ga, nullptr, b->N, 1));
+  return CHG_OK;
 }
 
 // ---- BondConv / AngleUpdate ----------------------------------------------------------------------------
@@ -438,21 +388,12 @@ AngleArgs angle_args(chg_batch* b, int slot, const float* ang, const float* w_an
   a.R = b->Rl[slot]; a.S = b->Sl[slot]; a.ang = ang; a.wbgc = b->wbgc;
   a.a_ctr = b->a_ctr; a.a_b1c = b->a_b1c; a.a_b2c = b->a_b2c; a.n_angles = b->A;
   a.w_ang = w_ang; a.gw = g; a.out = out; a.slot = slot;
-  a.Gagg = b->Gagg; a.Gang = b->Gang; a.GR = b->GR_l[slot]; a.GS = b->GS_l[slot]; a.Gwbgc = b->Gwbgc; a.phase = b->phase;
+  a.Gagg = b->Gagg; a.Gang = b->Gang; a.GR = b->GR_l[slot]; a.GS = b->GS_l[slot]; a.Gwbgc = b->Gwbgc;
   a.first_gang = slot == b->L - 2;   // slot l < L is BondConv l; the sweep's first angle kernel is BondConv L-2
   a.skip_flag = b->win.flag;
   // the forward keeps z for the adjoint only when an adjoint that reads it follows (per-atom / TEAM kernels, kernels_angle_w.h)
   a.zsave = (b->zsave_now && (b->win_built || b->win_team > 0)) ? b->zsave_l[slot] : nullptr;
   return a;
-}
-
-// Which adjoints run per atom (kernels_angle_w.h): both.  AngleUpdate 2.23 -> 1.60 ms; BondConv 3.44 -> 3.03 ms once all of its
-// contractions run in split precision from row-major images.  CHGNET_PER_ATOM_BONDCONV=0 / CHGNET_PER_ATOM_ANGLEUPD=0 switch back to
-// the plain kernels for A/B timing.
-static bool per_atom_adjoint(bool hidden) {
-  static const bool bc = [] { const char* e = std::getenv("CHGNET_PER_ATOM_BONDCONV"); return !e || std::atoi(e) != 0; }();
-  static const bool au = [] { const char* e = std::getenv("CHGNET_PER_ATOM_ANGLEUPD"); return !e || std::atoi(e) != 0; }();
-  return hidden ? bc : au;
 }
 
 // AngleUpdate forward per atom, table rows in LDS (kernels_angle_fa.h).  CHGNET_PER_ATOM_FWD=0 switches back to the row-order kernel.
@@ -498,9 +439,11 @@ int launch_angle(chg_engine* eng, const char* label, chg_batch* b, const AngleAr
     hipLaunchKernelGGL((k_angle_bwd_w<HIDDEN, true>), dim3(b->win_grid), dim3(BLOCK), angle_w_lds<HIDDEN>(), eng->stream, w);
     HIP_TRY(eng, hipGetLastError());
     if (index_from_builder) return CHG_OK;    // a launch less per layer (~4.5 us each)
-  } else if (BWD && b->win_built && per_atom_adjoint(HIDDEN)) {
+  } else if (BWD && b->win_built) {
     // per-atom adjoint (kernels_angle_w.h) when the batch has the canonical angle structure, else the row-order one: both are
-    // launched, the device flag picks (no host round trip, and a captured hipGraph stays valid across rebuilt graphs)
+    // launched, the device flag picks (no host round trip, and a captured hipGraph stays valid across rebuilt graphs).  Per atom
+    // against row order: AngleUpdate 2.23 -> 1.60 ms; BondConv 3.44 -> 3.03 ms once all of its contractions run in split precision
+    // from row-major images.
     AngleWArgs w{};
     w.a = a; w.w = b->win;
     w.a.image = eng->img_angle[1][a.slot];
@@ -513,17 +456,6 @@ int launch_angle(chg_engine* eng, const char* label, chg_batch* b, const AngleAr
     plain.skip_flag = nullptr;
   }
   plain.image = eng->img_angle[BWD ? 1 : 0][a.slot];
-  plain.interleave = (interleave_mask() >> (BWD ? 4 : HIDDEN ? 2 : 3)) & 1;
-#ifdef CHG_EXPERIMENTS
-  // occupancy probe (profiles/r05_experiments.md): the same kernel with FOUR waves per workgroup and the LDS request padded so that
-  // one workgroup fits per CU -> one wave per SIMD.  t(1 wave) / t(2 waves) says how much of a wave's time the SIMD is free.
-  if (exp_nw() == 4 && !BWD && NW == WAVES) {
-    const size_t lds4 = std::max(angle_lds<HIDDEN, 4, BWD>(), (size_t)100 << 10);
-    hipLaunchKernelGGL((k_angle<HIDDEN, BWD, 4>), dim3(tile_grid(eng, b->A, TILE_ROWS * 4)), dim3(64 * 4), lds4, eng->stream, plain);
-    HIP_TRY(eng, hipGetLastError());
-    return CHG_OK;
-  }
-#endif
   const size_t lds = angle_lds<HIDDEN, NW, BWD>();
   hipLaunchKernelGGL((k_angle<HIDDEN, BWD, NW>), dim3(tile_grid(eng, b->A, TILE_ROWS * NW)), dim3(64 * NW), lds, eng->stream, plain);
   HIP_TRY(eng, hipGetLastError());
@@ -589,11 +521,6 @@ AngleEmbedTArgs angle_embed_args(chg_engine* eng, chg_batch* b) {
   a.freq = eng->w.freq_ang; a.w_emb = eng->w.w_ang_emb;
   a.ang0 = b->ang[0]; a.Gang = b->Gang; a.Gu = b->Gu;
   return a;
-}
-
-static int embed_grid_mult() {
-  static const int m = [] { const char* e = std::getenv("CHGNET_EMBED_GRID_MULT"); return e ? std::atoi(e) : 2; }();
-  return m;
 }
 
 // ---- MD-size batches: the row GEMMs between two tile kernels as ONE chained launch (kernels_chain.h) -------------------------------
@@ -696,7 +623,7 @@ int reverse_tiny(chg_engine* eng, chg_batch* b) {
   const Weights& w = eng->w;
   const int L = b->L;
   TRY(rows_gemm(eng, "gemm_Gagg", 64, 64, b->Ga, D, nullptr, w.ac[L - 1].w_out_t, nullptr, nullptr, 0, b->GA, D, nullptr, b->N, 0));
-  TRY(atomconv_bwd_kernel(eng, b, L - 1, true));
+  TRY(atomconv_bwd_kernel(eng, b, L - 1));
   for (int l = L - 2; l >= 0; --l) {
     const bool au = l < L - 2;
     if (au) TRY((launch_angle<false, true>(eng, "angleupd_bwd", b, angle_args(b, L + l, b->ang[l], w.au[l].w_ang, w.au[l].g, nullptr))));
@@ -732,7 +659,7 @@ int reverse_tiny(chg_engine* eng, chg_batch* b) {
       q.add = b->Gb; q.add_idx = b->bn_und; q.lda = D; q.Y1 = b->Gb; q.y1_idx = b->bn_und; q.ldy1 = D;
       TRY(launch_chain(eng, "chain_At", cb));
     }
-    TRY(atomconv_bwd_kernel(eng, b, l, true));
+    TRY(atomconv_bwd_kernel(eng, b, l));
   }
   return CHG_OK;
 }
@@ -743,9 +670,6 @@ int run_predict(chg_engine* eng, chg_batch* b, uint32_t task) {
   const bool want_f = task & CHG_TASK_F, want_s = task & CHG_TASK_S, want_m = task & CHG_TASK_M;
   const bool want_grad = want_f || want_s;
   hipStream_t st = eng->stream;
-#ifdef CHG_PHASE_TIMING
-  HIP_TRY(eng, hipMemsetAsync(b->phase, 0, sizeof(float) * PHASE_FLOATS, st));
-#endif
 
   // ---- geometry, bases, embeddings (model.py:826-871, 432-439) ----
   const bool tiny = tiny_batch(b);
@@ -771,23 +695,17 @@ int run_predict(chg_engine* eng, chg_batch* b, uint32_t task) {
       hipLaunchKernelGGL(k_edge_geom, g1(b->Ed), dim3(256), 0, st, b->cart, b->lattice, b->e_center, b->e_nbr, b->e_image, b->e_owner, b->ev, b->eu, b->Ed); }
     if (tiny) {   // both parts of the bond expansion and the angle expansion: one launch
       EmbedAllArgs ea{bond_embed_args(eng, b), angle_embed_args(eng, b), grid_for(b->Eu, 2 * eng->num_cus),
-                      b->Eb > 0 ? grid_for(b->Eb, 2 * eng->num_cus) : 0, b->A > 0 ? grid_for(b->A, embed_grid_mult() * eng->num_cus) : 0};
+                      b->Eb > 0 ? grid_for(b->Eb, 2 * eng->num_cus) : 0, b->A > 0 ? grid_for(b->A, EMBED_GRID_MULT * eng->num_cus) : 0};
       LaunchScope ls(eng, "embed_fwd");
       hipLaunchKernelGGL(k_embed_all<false>, dim3(ea.g_bond1 + ea.g_bond2 + ea.g_angle), dim3(BLOCK), bond_embed_lds(), st, ea);
     } else { LaunchScope ls(eng, "bond_embed_fwd");   // atom-graph expansion for every bond, bond-graph expansion for the bond-graph nodes only
-      static const int o4 = [] { const char* e = std::getenv("CHGNET_EMBED_O4"); return e ? std::atoi(e) : 1; }();
-      if (o4) hipLaunchKernelGGL((k_bond_embed_fwd_o4<1>), dim3(grid_for(b->Eu, o4 * 2 * eng->num_cus)), dim3(BLOCK), bond_embed_lds(), st, bond_embed_args(eng, b));
-      else
-      hipLaunchKernelGGL((k_bond_embed_t<false, false, 1>), dim3(grid_for(b->Eu, 2 * eng->num_cus)), dim3(BLOCK), bond_embed_lds(), st, bond_embed_args(eng, b));
+      hipLaunchKernelGGL((k_bond_embed_fwd_o4<1>), dim3(grid_for(b->Eu, 2 * eng->num_cus)), dim3(BLOCK), bond_embed_lds(), st, bond_embed_args(eng, b));
       if (b->Eb > 0)
         hipLaunchKernelGGL((k_bond_embed_t<false, false, 2>), dim3(grid_for(b->Eb, 2 * eng->num_cus)), dim3(BLOCK), bond_embed_lds(), st, bond_embed_args(eng, b)); }
   }
   if (b->A > 0 && !(tiny && b->Ed > 0)) {
     LaunchScope ls(eng, "angle_embed_fwd");
-    static const int o4 = [] { const char* e = std::getenv("CHGNET_EMBED_O4"); return e ? std::atoi(e) : 1; }();
-    if (o4) hipLaunchKernelGGL((k_angle_embed_fwd_o4<0>), dim3(grid_for(b->A, o4 * embed_grid_mult() * eng->num_cus)), dim3(BLOCK), angle_embed_lds(), st, angle_embed_args(eng, b));
-    else
-    hipLaunchKernelGGL((k_angle_embed_t<false>), dim3(grid_for(b->A, embed_grid_mult() * eng->num_cus)), dim3(BLOCK), angle_embed_lds(), st, angle_embed_args(eng, b));
+    hipLaunchKernelGGL((k_angle_embed_fwd_o4<0>), dim3(grid_for(b->A, EMBED_GRID_MULT * eng->num_cus)), dim3(BLOCK), angle_embed_lds(), st, angle_embed_args(eng, b));
   }
   if (!tiny) { LaunchScope ls(eng, "atom_embed");
     hipLaunchKernelGGL(k_atom_embed, g1((int64_t)b->N * (D / 4)), dim3(256), 0, st, b->z, w.emb, b->atom[0], b->N); }
@@ -800,7 +718,7 @@ int run_predict(chg_engine* eng, chg_batch* b, uint32_t task) {
   // small batches with bonds and angles: the chained schedule (forward_tiny / reverse_tiny); CHGNET_TINY_CHAIN=0 keeps the launch
   // sequence of the large batches
   static const bool chain_on = [] { const char* e = std::getenv("CHGNET_TINY_CHAIN"); return !e || std::atoi(e) != 0; }();
-  const bool chained = tiny && chain_on && fuse_gq() && L >= 2 && b->Ed > 0 && b->A > 0 && b->Eb > 0 && b->p_table_done == 0;
+  const bool chained = tiny && chain_on && L >= 2 && b->Ed > 0 && b->A > 0 && b->Eb > 0 && b->p_table_done == 0;
   if (chained) {
     TRY(forward_tiny(eng, b, want_grad, want_m));
   } else {
@@ -852,7 +770,7 @@ int run_predict(chg_engine* eng, chg_batch* b, uint32_t task) {
     if (b->Ed > 0) {
       if (tiny) {
         EmbedAllArgs ea{bond_embed_args(eng, b), angle_embed_args(eng, b), grid_for(b->Eu, 2 * eng->num_cus),
-                        b->Eb > 0 ? grid_for(b->Eb, 2 * eng->num_cus) : 0, b->A > 0 ? grid_for(b->A, embed_grid_mult() * eng->num_cus) : 0};
+                        b->Eb > 0 ? grid_for(b->Eb, 2 * eng->num_cus) : 0, b->A > 0 ? grid_for(b->A, EMBED_GRID_MULT * eng->num_cus) : 0};
         LaunchScope ls(eng, "embed_bwd");
         hipLaunchKernelGGL(k_embed_all<true>, dim3(ea.g_bond1 + ea.g_bond2 + ea.g_angle), dim3(BLOCK), bond_embed_lds(), st, ea);
       } else { LaunchScope ls(eng, "bond_embed_bwd");
@@ -861,7 +779,7 @@ int run_predict(chg_engine* eng, chg_batch* b, uint32_t task) {
           hipLaunchKernelGGL((k_bond_embed_t<true, false, 2>), dim3(grid_for(b->Eb, 2 * eng->num_cus)), dim3(BLOCK), bond_embed_lds(), st, bond_embed_args(eng, b)); }
       if (b->A > 0 && !tiny) {
         LaunchScope ls(eng, "angle_embed_bwd");
-        hipLaunchKernelGGL((k_angle_embed_t<true>), dim3(grid_for(b->A, embed_grid_mult() * eng->num_cus)), dim3(BLOCK), angle_embed_lds(), st, angle_embed_args(eng, b));
+        hipLaunchKernelGGL((k_angle_embed_t<true>), dim3(grid_for(b->A, EMBED_GRID_MULT * eng->num_cus)), dim3(BLOCK), angle_embed_lds(), st, angle_embed_args(eng, b));
       }
       ForceArgs f{};
       f.ev = b->ev; f.eu = b->eu; f.Gu = b->Gu; f.Grk = b->Grk;
@@ -938,12 +856,11 @@ void carve(chg_batch* b, char* base, size_t& total) {
     b->GS_l[t] = used ? c.take<float>(N * 2 * D) : nullptr;
   }
   b->zero2_end = c.take<float>(0);
-  // first written by a plain store in every sweep (AtomConv L-1: Gwag, its gemm_GQ: Gb; BondConv L-2: Gang): never zeroed
+  // first written by a plain store in every sweep (AtomConv L-1: Gwag and Gb; BondConv L-2: Gang): never zeroed
   b->Gb = c.take<float>(Eu * D); b->Gwag = c.take<float>(Eu * D); b->Gang = c.take<float>(A * D);
   b->Ga = c.take<float>(N * D); b->GA = c.take<float>(N * D);
   b->GQ = c.take<float>(Eu * 2 * D);
   b->Gagg = c.take<float>(Eb * D);
-  b->phase = c.take<float>(PHASE_FLOATS);
   {   // windowed angle adjoints (kernels_angle_w.h)
     WinIndex& w = b->win;
     w.flag = c.take<int>(4); w.na = c.take<int>(N + 1); w.boff = c.take<int>(N + 1); w.aoff = c.take<int>(N + 1); w.toff = c.take<int>(N + 1); w.toff4 = c.take<int>(N + 1);
@@ -1074,7 +991,7 @@ void register_names(chg_batch* b) {
   m["Ga"] = {b->Ga, N * D}; m["GA"] = {b->GA, N * D}; m["Gb"] = {b->Gb, Eu * D}; m["Gwag"] = {b->Gwag, Eu * D};
   m["Gwbgc"] = {b->Gwbgc, Eb * D}; m["Gang"] = {b->Gang, A * D}; m["GP"] = {b->GP_l[0], N * 4 * D}; m["GQ"] = {b->GQ, Eu * 2 * D};
   m["GR"] = {b->GR_l[0], Eb * 4 * D}; m["GS"] = {b->GS_l[0], N * 2 * D}; m["Grk"] = {b->Grk, Eu}; m["Gu"] = {b->Gu, 4 * Ed};
-  m["virial"] = {b->virial, 9 * B}; m["volume"] = {b->volume, B}; m["phase"] = {b->phase, PHASE_FLOATS};
+  m["virial"] = {b->virial, 9 * B}; m["volume"] = {b->volume, B};
   m["frac"] = {b->frac, 3 * N}; m["lattice"] = {b->lattice, 9 * B}; m["e_image"] = {b->e_image, 3 * Ed};
   auto& mi = b->named_i32;
   mi.clear();
@@ -1107,8 +1024,7 @@ int predict_set_lds(chg_engine* eng) {
   if ((s = set_lds(eng, (k_rows_gemm<64, 128, 2>), (rows_gemm_lds<64, 128, 2>())))) return s;
   if ((s = set_lds(eng, (k_rows_gemm<128, 64, 2>), (rows_gemm_lds<128, 64, 2>())))) return s;
   if ((s = set_lds(eng, k_atomconv_fwd<FWD_WAVES>, (atomconv_lds<FWD_WAVES, false, true>())))) return s;
-  if ((s = set_lds(eng, k_atomconv_bwd<false>, (atomconv_lds<WAVES, true>())))) return s;
-  if ((s = set_lds(eng, (k_atomconv_bwd<false, true>), acb_fused_lds()))) return s;
+  if ((s = set_lds(eng, k_atomconv_bwd<false>, acb_fused_lds()))) return s;
   if ((s = set_lds(eng, k_angleupd_fwd_a, angle_fa_lds()))) return s;
   if ((s = set_lds(eng, k_angle_bwd_blk<true>, angle_blk_lds<true>()))) return s;
   if ((s = set_lds(eng, k_angle_bwd_blk<false>, angle_blk_lds<false>()))) return s;
@@ -1122,17 +1038,10 @@ int predict_set_lds(chg_engine* eng) {
   if ((s = set_lds(eng, k_angle<true, true>, (angle_lds<true, WAVES, true>())))) return s;
   if ((s = set_lds(eng, k_angle<false, true>, (angle_lds<false, WAVES, true>())))) return s;
   if ((s = set_lds(eng, k_angle<false, false, FWD_WAVES>, (angle_lds<false, FWD_WAVES>())))) return s;
-#ifdef CHG_EXPERIMENTS
-  if ((s = set_lds(eng, (k_angle<true, false, 4>), (size_t)100 << 10))) return s;
-  if ((s = set_lds(eng, (k_angle<false, false, 4>), (size_t)100 << 10))) return s;
-  if ((s = set_lds(eng, k_atomconv_fwd<4>, (size_t)100 << 10))) return s;
-#endif
   if ((s = set_lds(eng, k_readout<false>, readout_lds()))) return s;
-  if ((s = set_lds(eng, (k_bond_embed_t<false, false, 1>), bond_embed_lds()))) return s;
   if ((s = set_lds(eng, (k_bond_embed_t<false, false, 2>), bond_embed_lds()))) return s;
   if ((s = set_lds(eng, (k_bond_embed_t<true, false, 1>), bond_embed_lds()))) return s;
   if ((s = set_lds(eng, (k_bond_embed_t<true, false, 2>), bond_embed_lds()))) return s;
-  if ((s = set_lds(eng, k_angle_embed_t<false>, angle_embed_lds()))) return s;
   if ((s = set_lds(eng, k_angle_embed_fwd_o4<0>, angle_embed_lds()))) return s;
   if ((s = set_lds(eng, k_bond_embed_fwd_o4<1>, bond_embed_lds()))) return s;
   if ((s = set_lds(eng, k_angle_embed_t<true>, angle_embed_lds()))) return s;

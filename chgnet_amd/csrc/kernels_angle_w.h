@@ -341,7 +341,6 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
   const AngleArgs& p = pw.a;
   const WinIndex& w = pw.w;
   if (w.flag[0] != 1) return;                   // this batch runs the plain adjoint (k_angle<.., true>)
-  PH_START
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int NS = win_ns<HIDDEN>(), PST = win_pst<HIDDEN>();
   // AngleUpdate: split images of W_ang and W_ang^T.  BondConv: row-major images of W_ang, W2c, W2g (each serves both directions).
@@ -378,7 +377,6 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
   float* T = tiles + wave * TILE64_FLOATS;
   float* Trow = T + j * TS64;
   float* pacc = paccs + wave * NS * PST;
-  PH_DECL
   // TEAM: this workgroup's tiles [t_lo, t_hi) of the centre-major tile sequence; c_team: the atom that holds tile t_lo
   int t_lo = 0, t_hi = 0, c_team = 0;
   if (TEAM) {
@@ -451,7 +449,6 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
         // (requesting the NEXT tile's rows a tile ahead -- 32 loop-carried registers -- spilled 11-13 and cost 2.06 -> 2.24 ms, like every
         // other attempt to pipeline this kernel)
         read_dl_g_nt<2 * VT>(p.zsave, (unsigned)a, 2 * D, g, z);
-        PH(0)
         if (!HIDDEN) rows64_issue(gy_rows, p.Gang, a, lane_t);
         if (HIDDEN) {
           read_dl_g<VT>(p.wbgc, (unsigned)b1, D, g, w1.t);
@@ -475,7 +472,6 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
       __builtin_amdgcn_wave_barrier();
       read_dl<VT>(Trow, g, *reinterpret_cast<f32x4(*)[VT]>(&z[VT]));
       __builtin_amdgcn_wave_barrier();
-      PH(0)   // indices + gathers
       if (!HIDDEN) rows64_issue(gy_rows, p.Gang, a, lane_t);
       if (HIDDEN) {
         read_dl_g<VT>(p.wbgc, (unsigned)b1, D, g, w1.t);
@@ -490,7 +486,6 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
       V64 y;
       constexpr bool SLIM = HIDDEN;
       gated_forward<HIDDEN, SLIM, false, MODE>(zc, zg, W2c, W2g, vecs, j, g, s, y);
-      PH(7)   // forward recomputation
       V64 gy;
       if (HIDDEN) {
         V64 g1, g2;
@@ -507,15 +502,8 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
           to_columns(g1, T, Trow, g, lane_t, c1);
           to_columns(g2, T, Trow, g, lane_t, c2[0]);
           run_sum64(c1, nvalid, b1, rg, curg, p.Gwbgc, D, lane_t);
-#if defined(CHG_EXPERIMENTS) && defined(CHG_EXP_NO_G2_ATOMICS)
-          // TIMING-ONLY (wrong results; profiles/r06_experiments.md): the second bond's weight gradient is dropped -- the upper bound of
-          // what ANY scheme that takes these per-angle atomic rows out of the kernel (private rows, a deferred reduction) can gain
-          asm volatile("" :: "v"(c2[0].v[0]));
-#else
           row_add64(c2[0], nvalid, p.Gwbgc, b2, D, lane_t);
-#endif
         }
-        PH(6)   // bond-weight gradient scatter
       } else {
         rows64_commit(gy_rows, T, TS64, lane_t);
         __builtin_amdgcn_wave_barrier();
@@ -524,7 +512,6 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
       }
       V64 gzc, gzg;
       gated_backward<HIDDEN, SLIM, false, MODE>(gy, zc, zg, W2c, W2g, vecs, j, g, s, gzc, gzg);
-      PH(1)   // contractions + gated MLP, forward and adjoint
       // ---- dE/d(angle in) += W_ang^T gz ----
       {
         f32x4 gz[2 * VT] = {gzc.t[0], gzc.t[1], gzc.t[2], gzc.t[3], gzg.t[0], gzg.t[1], gzg.t[2], gzg.t[3]};
@@ -539,13 +526,11 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
         }
         if (HIDDEN) gemm_rm<2 * VT, VT, true, true>(ga.t, reinterpret_cast<const _Float16*>(Wang), 2 * D, D, gz, j, g, lane_t);
         else gemm_split<2 * VT, VT, true>(ga.t, reinterpret_cast<const h16x8*>(WangT), D, gz, j, g);
-        PH(5)   // W_ang^T contraction
         write_dl<VT>(Trow, g, ga.t);
         __builtin_amdgcn_wave_barrier();
         scatter_rows64_add<HIDDEN>(T, TS64, p.Gang, a, nvalid, lane_t, gang_old);
         __builtin_amdgcn_wave_barrier();
       }
-      PH(2)   // W_ang^T contraction + Gang update
       // ---- scatter: first bond and centre as carried run sums, second bond into the private rows ----
       {
         Cols64 cc[2];
@@ -568,7 +553,6 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
         }
         __builtin_amdgcn_wave_barrier();
       }
-      PH(3)   // scatter
     }
     // ---- the atom is done: runs, centre sum, private second-bond rows ----
     int lane_f = lane;
@@ -590,7 +574,6 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
         atomicAdd(grow<float>(p.GR, (unsigned)bond, 4 * D, 3 * D + lane_f), v1);
       }
     }
-    PH(4)   // per-atom flush
     }   // active
     if (TEAM) {
       // the workgroup's eight copies of the private rows, summed and sent out: row sl by wave sl mod 8
@@ -614,7 +597,6 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
       __syncthreads();
     }
   }
-  PH_FLUSH(HIDDEN ? 40 : 50)
 }
 
 }  // namespace chg

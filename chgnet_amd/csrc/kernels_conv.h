@@ -452,31 +452,6 @@ constexpr size_t rows_gemm_lds() {
   return sizeof(float) * (PARTS * NOUT * (K + PAD) + NOUT + WAVES * TILE_ROWS * ((K > NOUT ? K : NOUT) + PAD));
 }
 
-// Phase timing (diagnostic builds, -DCHG_PHASE_TIMING): s_memtime deltas between the phases of a tile,
-// summed per wave and added to p.phase[base + i] at the end; read back with chg_debug_fetch("phase")
-// (tests/gpu_phase_probe.py).
-#ifdef CHG_PHASE_TIMING
-#define PH_DECL unsigned long long ph_t = __builtin_amdgcn_s_memtime(); bool ph_first = true; float ph_acc[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, ph_acc1[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#define PH_TILE(first) ph_first = (first);
-#define PH(i) { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (ph_first) ph_acc1[i] += (float)(t_ - ph_t); else ph_acc[i] += (float)(t_ - ph_t); ph_t = t_; __builtin_amdgcn_sched_barrier(0); }
-// p.phase[kernel 0..3][later / first tile][slot 0..9][wave 0..PH_WAVES): every wave adds to its own floats (plain read-modify-write: the
-// first version met in 20 shared addresses, and 2048 waves' same-address atomics -- ~110 ns each -- cost more than the kernel)
-constexpr int PH_WAVES = 4096;
-// PH_START (first statement of a kernel) / PH_FLUSH: the wave's entry and exit stamps (low 32 bits, bit pattern) of the LAST launch of a kernel
-// go to the otherwise unused kernel slot 6: stamps[kernel][entry / exit][wave] -- when the waves of a launch really start and end.
-#define PH_START const unsigned long long ph_t0 = __builtin_amdgcn_s_memtime();
-#define PH_FLUSH(base) { const int gw_ = blockIdx.x * (blockDim.x >> 6) + wave; if (lane == 0 && gw_ < PH_WAVES) { for (int i_ = 0; i_ < 10; ++i_) { \
-  p.phase[((size_t)((base) / 10 * 2 + 0) * 10 + i_) * PH_WAVES + gw_] += ph_acc[i_]; p.phase[((size_t)((base) / 10 * 2 + 1) * 10 + i_) * PH_WAVES + gw_] += ph_acc1[i_]; } \
-  p.phase[((size_t)6 * 20 + (base) / 10 * 2 + 0) * PH_WAVES + gw_] = __uint_as_float((unsigned)ph_t0); \
-  p.phase[((size_t)6 * 20 + (base) / 10 * 2 + 1) * PH_WAVES + gw_] = __uint_as_float((unsigned)__builtin_amdgcn_s_memtime()); } }
-#else
-#define PH_DECL
-#define PH_START
-#define PH_TILE(first)
-#define PH(i)
-#define PH_FLUSH(base)
-#endif
-
 // =============================================================================================
 // AtomConv
 // =============================================================================================
@@ -486,7 +461,6 @@ struct AtomConvArgs {
   const float* wag;    // [Eu,64]  smooth bond weights (atom graph)
   const int *e_center, *e_nbr, *e_d2u;
   int n_edges;
-  int interleave;      // XCD-local interleaved tile sequence (mfma_tile.h wave_tile_seq) or contiguous per-wave ranges
   GatedW gw;
   // forward: bond partial contracted in the kernel (no gemm_Q / gemm_Qnode launches):  Q[k] = hb[k] . W_bond^T (+ q_bias)
   const float *hb0, *hbc;      // [Eu,64] embedding rows; [Eb,64] layer features of the bond-graph nodes (null: every bond uses hb0)
@@ -501,8 +475,7 @@ struct AtomConvArgs {
   float* GQ;           // [Eu,128] zeroed
   float* Gwag;         // [Eu,64] accumulated over layers
   int first_wag;       // this launch is the first writer of Gwag in the sweep: store, do not read (the buffer is not zeroed)
-  float* phase;        // CHG_PHASE_TIMING builds only (kernel slots 6 = forward, 7 = adjoint)
-  float* Gb;           // fused form of the adjoint (k_atomconv_bwd<false, NW, true>): dE/d h_bond rows [Eu,64], owned by the tile
+  float* Gb;           // inference adjoint (k_atomconv_bwd<false>): dE/d h_bond rows [Eu,64], owned by the tile
   int gb_accumulate;   // ... += (layers below the last) or = (the sweep's first AtomConv)
   // training (k_atomconv_bwd<true>) only
   float* dumpG;        // [Ed,128] pair order: adjoint of the second-layer pre-activations (core | gate)
@@ -523,7 +496,6 @@ constexpr size_t atomconv_lds() {
 // The weight block at the start of the AtomConv kernels' LDS, as a function of the weights alone: staged in the kernel, or built once
 // per weight upload into global memory (k_atomconv_image) and copied (stage_image).
 constexpr int ac_fwd_image_floats() { return 4 * (2 * IMG64 + IMG128) + AC_VEC_SLOTS * D; }
-constexpr int ac_bwd_image_floats() { return 4 * 4 * IMG64 + VEC_SLOTS * D; }
 __device__ __forceinline__ void atomconv_fwd_stage(float* base, const AtomConvArgs& p, int tid, int nthreads) {
   h16x8* I2c = reinterpret_cast<h16x8*>(base);
   h16x8* I2g = I2c + IMG64;
@@ -547,7 +519,7 @@ __device__ __forceinline__ void atomconv_bwd_stage(float* base, const AtomConvAr
   stage_split<true>(I2gT, p.gw.w2g, D, D, tid, nthreads);
   stage_gated_vecs(vecs, p.gw, true, tid);
 }
-// Block of the fused adjoint (k_atomconv_bwd<false, true>): ONE row-major image per hidden matrix serves both directions
+// Block of the inference adjoint (k_atomconv_bwd<false>): ONE row-major image per hidden matrix serves both directions
 // (mfma_split.h gemm_rm), which leaves room for the W_bond^T image next to eight waves' tiles:
 // [W2c rm | W2g rm | vectors | W_bond^T split].
 constexpr int AC_RM_IMG = (int)(rm_image_bytes(D, D) / 4);                                       // floats
@@ -559,13 +531,9 @@ __device__ __forceinline__ void atomconv_bwd_stage_rm(float* base, const AtomCon
   stage_gated_vecs(vecs, p.gw, true, tid);
   stage_split<true>(reinterpret_cast<h16x8*>(vecs + VEC_SLOTS * D), p.w_bond, 2 * D, D, tid, nthreads);
 }
+template <int UNUSED = 0>   // (a template: emitted only by the unit that launches it)
+__global__ __launch_bounds__(BLOCK) void k_atomconv_image(AtomConvArgs p, float* out) { atomconv_fwd_stage(out, p, threadIdx.x, BLOCK); }
 static __global__ __launch_bounds__(BLOCK) void k_atomconv_image_rm(AtomConvArgs p, float* out) { atomconv_bwd_stage_rm(out, p, threadIdx.x, BLOCK); }
-
-template <bool BWD>
-__global__ __launch_bounds__(BLOCK) void k_atomconv_image(AtomConvArgs p, float* out) {
-  if (BWD) atomconv_bwd_stage(out, p, threadIdx.x, BLOCK);
-  else atomconv_fwd_stage(out, p, threadIdx.x, BLOCK);
-}
 
 // Row of h_bond that feeds bond k's partial, as an offset from hb0 (floats).  bn = bond_node(k) >= 0: the row carries layer features
 // (no q_bias).  In two steps: the node index is REQUESTED two tiles ahead and only turned into an offset when the gather is issued --
@@ -592,7 +560,7 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_atomconv_fwd(AtomConv
   float* T = tiles + wave * TILE_FLOATS;
   float* Trow = T + j * TS;
   const int ntiles = (p.n_edges + TILE_ROWS - 1) / TILE_ROWS;     // wave-tiles: this wave's own sequence (mfma_tile.h wave_tile_seq)
-  const TileSeq ts = wave_tile_seq(ntiles, NW, wave, p.interleave);
+  const TileSeq ts = wave_tile_seq<true>(ntiles, NW, wave);
   // Software pipeline over tiles: the row gather of tile t+1 is issued before tile t's MFMA / VALU phase and committed to LDS
   // after it; the indices run two tiles ahead.  (SQ_WAIT_ANY was 37 % of wave time with the gather issued and awaited in place.)
   const int tstride = TILE_ROWS;
@@ -751,15 +719,14 @@ __device__ __forceinline__ void acbwd_scatter(const float* T, int c, int nvalid,
   tile_atomic_add(d2, a2[0]); tile_atomic_add(d2 + 64, a2[1]); tile_atomic_add(d2 + 128, a2[2]); tile_atomic_add(d2 + 192, a2[3]);
 }
 
-// FUSE_GQ: the tile also contracts its dE/dQ rows with W_bond (128 -> 64, split form) and updates the dE/d h_bond rows of its bonds
-// itself -- the rows are in registers (the pair sum is one lane swap), so the [Eu,128] table is neither written nor read back by a
-// row GEMM (gemm_GQ: 1.4 ms per headline step at the HBM rate).  The 32 KB image of W_bond^T fits because the hidden layer then
-// uses the row-major images (18 KB per matrix for both directions instead of 32 KB; with the split images and 7 waves per workgroup
+// Inference (FUSE_GQ = !TRAIN): the tile also contracts its dE/dQ rows with W_bond (128 -> 64, split form) and updates the dE/d h_bond
+// rows of its bonds itself -- the rows are in registers (the pair sum is one lane swap), so the [Eu,128] table is neither written nor
+// read back by a row GEMM (gemm_GQ: 1.4 ms per headline step at the HBM rate).  The 32 KB image of W_bond^T fits because the hidden
+// layer then uses the row-major images (18 KB per matrix for both directions instead of 32 KB; with the split images and 7 waves per workgroup
 // the kernel was 8 % slower: profiles/r04_experiments.md section 12).
-template <bool TRAIN, bool FUSE_GQ = false>
+template <bool TRAIN>
 __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_atomconv_bwd(AtomConvArgs p) {
-  static_assert(!(TRAIN && FUSE_GQ), "the training sweep keeps the dE/dQ table (its weight gradients contract it)");
-  PH_START
+  constexpr bool FUSE_GQ = !TRAIN;   // the training sweep keeps the dE/dQ table (its weight gradients contract it)
   constexpr int NW = WAVES;
   constexpr bool RM = FUSE_GQ;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -776,7 +743,7 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_atomconv_bwd(AtomConvAr
   float* T = tiles + wave * TILE_FLOATS;
   float* Trow = T + j * TS;
   const int ntiles = (p.n_edges + TILE_ROWS - 1) / TILE_ROWS;   // wave-tiles: this wave's own sequence (mfma_tile.h wave_tile_seq)
-  const TileSeq ts = wave_tile_seq(ntiles, NW, wave, p.interleave);
+  const TileSeq ts = wave_tile_seq<!TRAIN>(ntiles, NW, wave);
   const int last_row = p.n_edges - 1;
   int c, n, k;
   {   // the first tile's indices and gather land under the staging of the weights (see k_atomconv_fwd)
@@ -785,15 +752,13 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_atomconv_bwd(AtomConvAr
     GatherRegs gr;
     gather_issue128(gr, p.P, c, p.P + 2 * D, n, p.Q, k, 4 * D, 4 * D, 2 * D, lane);
     if (TRAIN) atomconv_bwd_stage(smem, p, tid, 64 * NW);   // fine-tuning: the weights change every step
-    else stage_image<(RM ? ac_bwd_rm_image_floats() : ac_bwd_image_floats()) / 4, 64 * NW>(smem, p.image, tid);
+    else stage_image<ac_bwd_rm_image_floats() / 4, 64 * NW>(smem, p.image, tid);
     gather_commit128(gr, T, TS, lane);
   }
   __syncthreads();
   TrainTile tt{};
   tt.T = T; tt.lane = lane;
-  PH_DECL
   for (int v = 0; v < ts.count; ++v) {
-    PH_TILE(v == 0)
     const int row0 = ts.at(v) * TILE_ROWS;
     const int nvalid = min(TILE_ROWS, p.n_edges - row0);   // even: Ed = 2 Eu and tiles are 16 rows
     if (TRAIN) {
@@ -820,9 +785,7 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_atomconv_bwd(AtomConvAr
     read_dl<VT>(Trow + D, g, zg.t);
     GatedState s;
     V64 y;
-    PH(0)   // next indices, weights / aggregate adjoint rows, old Gwag rows requested; table sums read
     gated_forward<true, false, TRAIN, HMODE>(zc, zg, W2c, W2g, vecs, j, g, s, y, &tt);
-    PH(1)   // forward recomputation
     asm volatile("" : "+v"(cn), "+v"(nn));   // take the index loads here (landed long ago), not behind later stores
     V64 gy, gw, gzc, gzg;
     CHG_EV(ft) {
@@ -845,9 +808,7 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_atomconv_bwd(AtomConvAr
           if (b < nb) dst[(size_t)b * D] = prev[b];
       }
     }
-    PH(2)   // bond-weight gradient rows
     gated_backward<true, false, TRAIN, HMODE>(gy, zc, zg, W2cT, W2gT, vecs, j, g, s, gzc, gzg, &tt);
-    PH(3)   // gated adjoint
     if (FUSE_GQ) {
       // dE/d h_bond[k] (+)= (gz(2b) + gz(2b+1)) . W_bond: contracted per direction (linear), the pair summed by a lane swap; the
       // even lane of a pair owns the bond's row (four 64-byte segments), plain read-modify-write: the tile owns bonds k0 .. k0 + 7
@@ -874,20 +835,14 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_atomconv_bwd(AtomConvAr
     if (v + 1 < ts.count) {  // the next tile's gathers fly while this tile's run sums are formed and sent
       GatherRegs gr;
       gather_issue128(gr, p.P, cn, p.P + 2 * D, nn, p.Q, kn, 4 * D, 4 * D, 2 * D, lane);
-      PH(4)   // next tile's gathers issued
       acbwd_scatter<!FUSE_GQ>(T, c, nvalid, k0, p, lane);
-      PH(5)   // scatter: GQ rows, run sums of the two atoms
       __builtin_amdgcn_wave_barrier();
       gather_commit128(gr, T, TS, lane);
-      PH(6)   // next tile's gathers landed
     } else {   // the wave's last tile (MD-size batches: its only one) does not wait for rows nobody reads: 5.6k of 47k clocks per wave
-      PH(4)
       acbwd_scatter<!FUSE_GQ>(T, c, nvalid, k0, p, lane);
-      PH(5)
     }
     c = cn; n = nn; k = kn;
   }
-  PH_FLUSH(70)
   if (TRAIN) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) atomicAdd(p.g_ln + q * D + lane, tt.ln[q]);
@@ -904,7 +859,6 @@ struct AngleArgs {
   const float* wbgc;   // [Eb,64]  smooth bond weights (bond graph), compact rows (BondConv only)
   const int *a_ctr, *a_b1c, *a_b2c;
   int n_angles;
-  int interleave;      // XCD-local interleaved tile sequence (mfma_tile.h wave_tile_seq) or contiguous per-wave ranges
   const float* w_ang;  // [128][64] angle block of the first layer (global)
   GatedW gw;
   const float* image;  // prebuilt weight block of the kernel's LDS (k_angle_image); the TRAIN adjoints stage from the fp32 weights
@@ -917,7 +871,6 @@ struct AngleArgs {
   float* GS;           // [N,128] zeroed
   float* Gwbgc;        // [Eb,64] accumulated over layers (BondConv only)
   int first_gang;      // BondConv adjoint of the last layer: first writer of Gang in the sweep (store, do not read: not zeroed)
-  float* phase;        // CHG_PHASE_TIMING builds only: per-phase shader-clock totals (40 floats)
   const int* skip_flag; // row-order kernels (not TRAIN): return at once when *skip_flag == 1 (a per-atom kernel of kernels_angle_w.h / _fa.h runs)
   float* zsave;        // [A + 16,128] or null (large batches, round 6): the forward kernel leaves the first layer's pre-activations z = W_ang x +
                        // R_i + R_j + S behind, the adjoint reads them back instead of gathering four rows per angle and contracting W_ang
@@ -981,8 +934,6 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_angle(AngleArgs p) {
   static_assert(!TRAIN || BWD, "TRAIN is a variant of the adjoint kernels");
   if (!TRAIN && p.skip_flag && *p.skip_flag == 1) return;   // a per-atom kernel does this launch's work (kernels_angle_w.h / kernels_angle_fa.h)
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  PH_START
-  PH_DECL
   constexpr int SPLIT = angle_split(HIDDEN, BWD);
   using L = AngleLds<HIDDEN, BWD>;
   float* Wang = smem;
@@ -995,7 +946,7 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_angle(AngleArgs p) {
   float* T = tiles + wave * TILE_FLOATS;
   float* Trow = T + j * TS;
   const int ntiles = (p.n_angles + TILE_ROWS - 1) / TILE_ROWS;   // wave-tiles: this wave's own sequence (mfma_tile.h wave_tile_seq)
-  const TileSeq ts = wave_tile_seq(ntiles, NW, wave, p.interleave);
+  const TileSeq ts = wave_tile_seq<!TRAIN>(ntiles, NW, wave);
   const int tstride = TILE_ROWS;
   auto row_of = [&](int v) { return max(0, min(ts.at(v) * tstride + j, p.n_angles - 1)); };   // v-th tile of this wave (clamped past its end)
   // Forward: software-pipelined gathers -- the table rows and angle rows of tile t+1 are in flight
@@ -1023,7 +974,6 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_angle(AngleArgs p) {
   if (TRAIN) angle_stage<HIDDEN, BWD>(smem, p.w_ang, p.gw, tid, 64 * NW);   // fine-tuning: the weights change every step
   else stage_image<L::tiles / 4, 64 * NW>(smem, p.image, tid);
   __syncthreads();
-  PH(9)   // prologue: first indices (forward: first gathers issued), weight images, barrier
   TrainTile tt{};
   tt.T = T; tt.lane = lane;
   for (int v = 0; v < ts.count; ++v) {
@@ -1032,7 +982,6 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_angle(AngleArgs p) {
     // behind the tile's atomics (kernels_angle_w.h, same measure)
     int lane_t = lane;
     if (BWD && HIDDEN) asm volatile("" : "+v"(lane_t));
-    PH_TILE(v == 0)
     const int row0 = ts.at(v) * tstride;
     const int nvalid = min(TILE_ROWS, p.n_angles - row0);
     const int ctr = ctr_nx, b1 = b1_nx, b2 = b2_nx;
@@ -1055,7 +1004,6 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_angle(AngleArgs p) {
       x = x_p;
       __builtin_amdgcn_wave_barrier();
       read_dl<2 * VT>(Trow, g, z);
-      PH(0)
       if (v + 1 < ts.count) {
         const int a1 = row_of(v + 1);
         gather_issue128(gr_p, p.R, b1_n2, p.R + 2 * D, b2_n2, p.S, ctr_n2, 4 * D, 4 * D, 2 * D, lane_t);
@@ -1076,12 +1024,10 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_angle(AngleArgs p) {
       __builtin_amdgcn_wave_barrier();
       read_dl<VT>(Trow, g, x.t);
       __builtin_amdgcn_wave_barrier();
-      PH(0)   // indices + angle rows
       gather_sum128(T, TS, p.R, b1, p.R + 2 * D, b2, p.S, ctr, 4 * D, 4 * D, 2 * D, lane_t);
       __builtin_amdgcn_wave_barrier();
       read_dl<2 * VT>(Trow, g, z);
     }
-    PH(1)   // table gather
     Rows64 gy_rows;
     if (BWD && !HIDDEN) rows64_issue(gy_rows, p.Gang, a, lane_t);   // AngleUpdate adjoint: dE/d(new angle), read under the first contraction
     if (SPLIT == 2) gemm_rm<VT, 2 * VT, false, false>(z, reinterpret_cast<const _Float16*>(Wang), 2 * D, D, x.t, j, g, lane_t);
@@ -1095,13 +1041,11 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_angle(AngleArgs p) {
     // way they are issued: conditional or not, non-temporal or not; as whole 512-byte rows through the wave's LDS tile 1.28 ms.)
     if (!BWD && p.zsave) write_dl_g_nt<2 * VT>(p.zsave, (unsigned)(valid ? a : p.n_angles + j), 2 * D, g, z);
     V64 zc{{z[0], z[1], z[2], z[3]}}, zg{{z[4], z[5], z[6], z[7]}};
-    PH(2)   // W_ang contraction
     GatedState s;
     V64 y;
     constexpr bool SLIM = HIDDEN && BWD;   // the BondConv adjoint is the one kernel that spills otherwise (3.41 -> 3.36 ms)
     gated_forward<HIDDEN, SLIM, TRAIN, SPLIT, !BWD>(zc, zg, W2c, W2g, vecs, j, g, s, y, &tt);
     __builtin_amdgcn_wave_barrier();
-    PH(3)   // gated forward
     V64 w1, w2;   // small L2-resident tables: loaded after the MFMA phase to keep its register pressure low
     if (HIDDEN) {
       read_dl_g<VT>(p.wbgc, (unsigned)b1, D, g, w1.t);
@@ -1116,7 +1060,6 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_angle(AngleArgs p) {
       __builtin_amdgcn_wave_barrier();
       if (HIDDEN) seg_colsum_atomic<D>(T, TS, valid ? b1 : -1, nvalid, p.out, D, lane_t);
       else scatter_rows64<false>(T, TS, p.out, a, nvalid, lane_t);
-      PH(4)   // forward output
     } else {
       V64 gy, gzc, gzg;
       if (HIDDEN) {
@@ -1139,9 +1082,7 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_angle(AngleArgs p) {
         read_dl<VT>(Trow, g, gy.t);
       }
       __builtin_amdgcn_wave_barrier();
-      PH(4)   // weight rows / Gang rows, dE/dy, (BondConv) Gwbgc scatter
       gated_backward<HIDDEN, SLIM, TRAIN, SPLIT>(gy, zc, zg, W2c, W2g, vecs, j, g, s, gzc, gzg, &tt);
-      PH(5)   // gated backward
       // dE/d(angle in) += W_ang^T gz   (the residual identity is already in Gang)
       f32x4 gz[2 * VT] = {gzc.t[0], gzc.t[1], gzc.t[2], gzc.t[3], gzg.t[0], gzg.t[1], gzg.t[2], gzg.t[3]};
       if (TRAIN && HIDDEN && valid) write_dl_g<2 * VT>(p.dumpZ, (unsigned)a, 2 * D, g, gz);
@@ -1160,27 +1101,22 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_angle(AngleArgs p) {
         gemm_rm<2 * VT, VT, true, true>(ga.t, reinterpret_cast<const _Float16*>(Wang), 2 * D, D, gz, j, g, lane_t);
         write_dl<VT>(Trow, g, ga.t);
         __builtin_amdgcn_wave_barrier();
-        PH(6)   // W_ang^T contraction
         scatter_rows64_add(T, TS, p.Gang, a, nvalid, lane_t, gang_old);
       } else {
         gemm_split<2 * VT, VT, true>(ga.t, reinterpret_cast<const h16x8*>(WangT), D, gz, j, g);
         write_dl<VT>(Trow, g, ga.t);
         __builtin_amdgcn_wave_barrier();
-        PH(6)   // W_ang^T contraction
         scatter_rows64<true>(T, TS, p.Gang, a, nvalid, lane_t);
       }
       __builtin_amdgcn_wave_barrier();
-      PH(7)   // Gang update
       write_dl<2 * VT>(Trow, g, gz);
       __builtin_amdgcn_wave_barrier();
       seg_colsum_atomic<2 * D>(T, TS, valid ? b1 : -1, nvalid, p.GR, 4 * D, lane_t);
       row_atomic_add<2 * D>(T, TS, valid ? b2 : -1, nvalid, p.GR + 2 * D, 4 * D, lane_t);
       seg_colsum_atomic<2 * D>(T, TS, valid ? ctr : -1, nvalid, p.GS, 2 * D, lane_t);
-      PH(8)   // GR / GS scatter
     }
     __builtin_amdgcn_wave_barrier();
   }
-  PH_FLUSH((HIDDEN ? 0 : 20) + (BWD ? 10 : 0))
   if (TRAIN) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) atomicAdd(p.g_ln + q * D + lane, tt.ln[q]);

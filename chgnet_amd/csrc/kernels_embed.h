@@ -19,10 +19,6 @@
 
 namespace chg {
 
-#ifndef CHG_EMBED_WAVES
-#define CHG_EMBED_WAVES CHG_TWO_WAVES
-#endif
-
 constexpr int KB = 32;            // basis count padded to a multiple of 16
 constexpr int WSB = KB + PAD;     // LDS row stride of a [64][32] embedding weight
 constexpr int ETS = D + PAD;      // LDS tile row stride (64-wide rows)
@@ -475,7 +471,7 @@ __device__ __forceinline__ void angle_embed_body(const AngleEmbedTArgs& p, int v
 }
 
 template <bool BWD, bool TRAIN = false>
-__global__ __launch_bounds__(BLOCK) CHG_EMBED_WAVES void k_angle_embed_t(AngleEmbedTArgs p) {
+__global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_embed_t(AngleEmbedTArgs p) {
   angle_embed_body<BWD, TRAIN>(p, gridDim.x, blockIdx.x);
 }
 

@@ -247,17 +247,9 @@ struct ForceArgs {
 // Each wave takes EF_IT consecutive 64-edge chunks with all their loads in flight together (one edge per thread left the wave
 // slots waiting 95 % of their cycles: two dependent memory round trips and nothing to overlap them with), and the nine virial
 // sums are formed once per wave over the chunks when they belong to one structure.
-#ifndef CHG_EF_IT
-#define CHG_EF_IT 4
-#endif
-#ifdef CHG_EF_WAVES
-#define CHG_EF_ATTR __attribute__((amdgpu_waves_per_eu(CHG_EF_WAVES, CHG_EF_WAVES)))
-#else
-#define CHG_EF_ATTR
-#endif
-constexpr int EF_IT = CHG_EF_IT;    // measured: 2 -> 0.157 ms, 4 -> 0.145, 8 -> 0.190 (one edge per thread: 0.180)
+constexpr int EF_IT = 4;    // measured: 2 -> 0.157 ms, 4 -> 0.145, 8 -> 0.190 (one edge per thread: 0.180)
 constexpr int EF_EDGES_PER_BLOCK = 4 * 64 * EF_IT;
-static __global__ __launch_bounds__(256) CHG_EF_ATTR void k_edge_force(ForceArgs p) {
+static __global__ __launch_bounds__(256) void k_edge_force(ForceArgs p) {
   __shared__ float vir[4][9];
   __shared__ int vown[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

@@ -41,17 +41,13 @@ namespace chg {
 typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
 
-#ifndef CHG_SPLIT_LO_SEPARATE
-#define CHG_SPLIT_LO_SEPARATE 1
-#endif
 // CHG_WIDE_RANGE (engine_predict_wide.hip): EVERY operand row is scaled by a power of two before the split, not only the adjoint rows
 #ifdef CHG_WIDE_RANGE
 constexpr bool WIDE_RANGE = true;
 #else
 constexpr bool WIDE_RANGE = false;
 #endif
-constexpr bool LO_SEPARATE = CHG_SPLIT_LO_SEPARATE;   // low planes scaled by 2^11 in their own accumulator (see above)
-constexpr float LO_SCALE = LO_SEPARATE ? 2048.0f : 1.0f, LO_UNSCALE = 1.0f / LO_SCALE;
+constexpr float LO_SCALE = 2048.0f, LO_UNSCALE = 1.0f / LO_SCALE;   // low planes scaled by 2^11 in their own accumulator (see above)
 
 // bytes of one split image of a [F][K] matrix (both planes)
 constexpr size_t split_image_bytes(int F, int K) { return (size_t)F * K * 4; }
@@ -148,19 +144,7 @@ __device__ __forceinline__ void split_row(SplitRow<KT / 2>& s, const f32x4 (&x)[
   }
 }
 
-// TIMING-ONLY (wrong results; -DCHG_EXPERIMENTS -DCHG_EXP_NO_OPERAND_READS, profiles/r05_experiments.md section 5): the weight operands
-// come out of a register instead of LDS -- what the LDS operand supply of the contractions costs
-#if defined(CHG_EXPERIMENTS) && defined(CHG_EXP_NO_OPERAND_READS)
-#define CHG_OPERAND(expr, salt) fake_operand(salt)
-__device__ __forceinline__ h16x8 fake_operand(int salt) {
-  const _Float16 v = (_Float16)(0.001f * (float)(salt & 7));
-  return h16x8{v, v, v, v, v, v, v, v};
-}
-#else
-#define CHG_OPERAND(expr, salt) (expr)
-#endif
-
-// four output tiles fo0 .. fo0+3 from an already split row.  LO_SEPARATE: the cross products (low planes scaled by 2^11) and the
+// four output tiles fo0 .. fo0+3 from an already split row: the cross products (low planes scaled by 2^11) and the
 // main product go to separate accumulators, the former are scaled back -- a power of two, exact -- and added once; every operand is
 // read from LDS once.  LEAN: the same two tiles at a time (half the accumulator / operand registers in flight): the forward kernels,
 // which carry the next tile's gathered rows in registers and spill with the wide form (same-box A/B: atomconv_fwd +8 %, bondconv_fwd
@@ -169,14 +153,14 @@ template <int MK, bool SCALED, bool LEAN = false>
 __device__ __forceinline__ void gemm_split4(f32x4* acc, const h16x8* img, int F, const SplitRow<MK>& s, int fo0, int i, int g) {
   const int nchunks = MK * 4 * F;
   const h16x8* base0 = img + g * F + 16 * fo0 + i;
-  // LO_SEPARATE: the cross products (hi x lo, lo x hi, carried at 2^11) and the main product in separate accumulators, so that
+  // The cross products (hi x lo, lo x hi, carried at 2^11) and the main product in separate accumulators, so that
   // every operand is read from LDS ONCE (a second sweep over the high plane cost a third more LDS reads than the contraction needs;
   // the tile kernels' weight reads are a large share of their LDS traffic)
   // LEAN (the forward kernels, which sit at the register limit): TWO output tiles at a time with both accumulators (cross products at
   // 2^11 | main product) -- every operand read from LDS once, like the wide form below, at 16 accumulator + 16 operand registers.
   // (Rounds 3-4 used a two-sweep form here -- four tiles, one accumulator set, the high plane read twice: a third more LDS operand
   // reads; same-box A/B of round 5: atomconv_fwd -2 %, bondconv_fwd -2.5 %, profiles/r05_experiments.md section 6.)
-  if constexpr (LEAN && LO_SEPARATE) {
+  if constexpr (LEAN) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       f32x4 t[2], u[2];
@@ -187,7 +171,7 @@ __device__ __forceinline__ void gemm_split4(f32x4* acc, const h16x8* img, int F,
         const h16x8* base = base0 + mk * 4 * F + 32 * h;
         h16x8 wh[2], wl[2];
 #pragma unroll
-        for (int q = 0; q < 2; ++q) { wh[q] = CHG_OPERAND(base[16 * q], q + mk); wl[q] = CHG_OPERAND(base[nchunks + 16 * q], q + mk + 1); }
+        for (int q = 0; q < 2; ++q) { wh[q] = base[16 * q]; wl[q] = base[nchunks + 16 * q]; }
 #pragma unroll
         for (int q = 0; q < 2; ++q) t[q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[q], s.lo[mk], t[q], 0, 0, 0);
 #pragma unroll
@@ -206,29 +190,23 @@ __device__ __forceinline__ void gemm_split4(f32x4* acc, const h16x8* img, int F,
   }
   f32x4 t[4], u[4];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) { t[q] = (SCALED || LO_SEPARATE) ? zero4() : acc[q]; u[q] = SCALED ? zero4() : acc[q]; }
+  for (int q = 0; q < 4; ++q) { t[q] = zero4(); u[q] = SCALED ? zero4() : acc[q]; }
 #pragma unroll
   for (int mk = 0; mk < MK; ++mk) {
     const h16x8* base = base0 + mk * 4 * F;
     h16x8 wh[4], wl[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) { wh[q] = CHG_OPERAND(base[16 * q], q + mk); wl[q] = CHG_OPERAND(base[nchunks + 16 * q], q + mk + 1); }
+    for (int q = 0; q < 4; ++q) { wh[q] = base[16 * q]; wl[q] = base[nchunks + 16 * q]; }
 #pragma unroll
     for (int q = 0; q < 4; ++q) t[q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[q], s.lo[mk], t[q], 0, 0, 0);
-    if (LO_SEPARATE) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) u[q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[q], s.hi[mk], u[q], 0, 0, 0);
-    }
+    for (int q = 0; q < 4; ++q) u[q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[q], s.hi[mk], u[q], 0, 0, 0);
 #pragma unroll
     for (int q = 0; q < 4; ++q) t[q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[q], s.hi[mk], t[q], 0, 0, 0);
-    if (!LO_SEPARATE) {   // the matrix pipe keeps f16 subnormals (tools/split_lab.hip T2): one pass for all three products
-#pragma unroll
-      for (int q = 0; q < 4; ++q) t[q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[q], s.hi[mk], t[q], 0, 0, 0);
-    }
   }
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    const f32x4 r = LO_SEPARATE ? u[q] + t[q] * LO_UNSCALE : t[q];
+    const f32x4 r = u[q] + t[q] * LO_UNSCALE;
     if (SCALED) {
       acc[q] += r * s.up;
     } else {
@@ -340,7 +318,7 @@ __device__ __forceinline__ void gemm_rm4(f32x4* acc, const _Float16* img, int F,
   for (int m = 0; m < MS; ++m) {
     h16x8 wh[4], wl[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) { wh[q] = CHG_OPERAND(rm_operand<ADJOINT>(img, F, K, 0, o0 + q, m, i, g, lane), q + m); wl[q] = CHG_OPERAND(rm_operand<ADJOINT>(img, F, K, 1, o0 + q, m, i, g, lane), q + m + 1); }
+    for (int q = 0; q < 4; ++q) { wh[q] = rm_operand<ADJOINT>(img, F, K, 0, o0 + q, m, i, g, lane); wl[q] = rm_operand<ADJOINT>(img, F, K, 1, o0 + q, m, i, g, lane); }
 #pragma unroll
     for (int q = 0; q < 4; ++q) t[q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[q], s.lo[m], t[q], 0, 0, 0);
 #pragma unroll
@@ -363,7 +341,6 @@ __device__ __forceinline__ void gemm_rm4(f32x4* acc, const _Float16* img, int F,
 template <int KT, int NOT, bool SCALED_, bool ADJOINT>
 __device__ __forceinline__ void gemm_rm(f32x4 (&acc)[NOT], const _Float16* img, int F, int K, const f32x4 (&x)[KT], int i, int g, int lane) {
   static_assert(NOT % 4 == 0 && KT % 2 == 0, "widths are multiples of 64 / 32");
-  static_assert(LO_SEPARATE, "row-major images carry the low plane scaled");
   constexpr bool SCALED = SCALED_ || WIDE_RANGE;
   SplitRow<KT / 2> s;
   split_row<KT, SCALED>(s, x);

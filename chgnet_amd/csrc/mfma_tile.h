@@ -24,13 +24,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// The one diagnostic build switch left: -DCHG_PHASE_TIMING (s_memtime stamps between the phases of the angle kernels, right results,
-// slower).  It needs -DCHG_EXPERIMENTS next to it (chgnet_amd/build.py:build_variant adds it; tests/test_abi.py checks that the product
-// flags define neither).  The wrong-result timing switches of rounds 1-3 (dropped atomics, a quarter of the MFMAs, ...) are gone from the
-// sources; what they measured is in profiles/r01_sq_counters.md, r02_experiments.md, r03_experiments.md.
-#if defined(CHG_PHASE_TIMING) && !defined(CHG_EXPERIMENTS)
-#error "CHG_PHASE_TIMING is a diagnostic build: define CHG_EXPERIMENTS as well (never in a product build)"
-#endif
+// No build switches: the timing-only builds of rounds 1-6 (dropped atomics, a quarter of the MFMAs, stubbed transcendentals, per-phase
+// shader clocks, ...) are gone from the sources (tests/test_abi.py checks); what they measured is in profiles/r01_sq_counters.md and
+// profiles/r02_experiments.md .. r06_experiments.md.
 
 namespace chg {
 
@@ -58,18 +54,8 @@ __device__ __forceinline__ V64 zero64() { return V64{{zero4(), zero4(), zero4(),
 // sigmoid(x) = 1 / (1 + 2^(-x log2 e)) on the hardware transcendentals (v_exp_f32, v_rcp_f32: 1 ulp
 // each) -- 4 VALU instructions instead of ~22 for expf + IEEE division, which made the conv kernels
 // VALU-bound (profiles/r01 notes).  Saturates correctly: x -> -inf gives rcp(inf) = 0, x -> +inf gives 1.
-#if defined(CHG_EXPERIMENTS) && defined(CHG_EXP_NO_TRANS)
-// TIMING-ONLY variant build (wrong results; profiles/r05_experiments.md): the two quarter-rate transcendentals of every sigmoid replaced
-// by full-rate arithmetic, to measure what share of a tile kernel's time they are
-__device__ __forceinline__ float exp_rcp_stub(float t) { return 0.5f + 0.1f * t; }
-#define CHG_EXP2(t) (1.0f + 0.05f * (t))
-#define CHG_RCP(t) (2.0f - (t))
-#else
-#define CHG_EXP2(t) __builtin_amdgcn_exp2f(t)
-#define CHG_RCP(t) __builtin_amdgcn_rcpf(t)
-#endif
 __device__ __forceinline__ float sigmoidf_(float x) {
-  return CHG_RCP(1.0f + CHG_EXP2(-1.4426950408889634f * x));
+  return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
 }
 __device__ __forceinline__ float siluf_(float x) { return x * sigmoidf_(x); }
 // d/dx silu(x) = s (1 + x (1 - s))
@@ -83,9 +69,9 @@ __device__ __forceinline__ float dsiluf_(float x) {
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 sigmoid2(f32x2 x) {
   f32x2 t = x * -1.4426950408889634f;
-  t[0] = CHG_EXP2(t[0]); t[1] = CHG_EXP2(t[1]);
+  t[0] = __builtin_amdgcn_exp2f(t[0]); t[1] = __builtin_amdgcn_exp2f(t[1]);
   t = t + 1.0f;
-  t[0] = CHG_RCP(t[0]); t[1] = CHG_RCP(t[1]);
+  t[0] = __builtin_amdgcn_rcpf(t[0]); t[1] = __builtin_amdgcn_rcpf(t[1]);
   return t;
 }
 __device__ __forceinline__ f32x4 sigmoid4(f32x4 x) {   // pair by pair: four values at once cost the forward kernels ~10 spilled registers
@@ -99,29 +85,18 @@ __device__ __forceinline__ float hsum4(f32x4 v) { return (v[0] + v[1]) + (v[2] +
 #define CHG_EW(ft, r) _Pragma("unroll") for (int ft = 0; ft < VT; ++ft) _Pragma("unroll") for (int r = 0; r < 4; ++r)
 
 // ---- global row addressing ------------------------------------------------------------------------------------------------
-// Row `r` of a row-major float table with `ld` floats per row, at float column `c`.  CHG_ADDR32=1 forms the byte offset in 32 bits
+// Row `r` of a row-major float table with `ld` floats per row, at float column `c`, with a 64-bit offset.  A 32-bit byte offset
 // against the uniform table base (`global_load ... v_off, s[base:base+1]`: one 32-bit multiply-add and one VGPR per address instead
-// of three 64-bit vector instructions and a register pair).  Measured (profiles/r05_experiments.md section 7): 231 -> 99 64-bit
+// of three 64-bit vector instructions and a register pair) measured (profiles/r05_experiments.md section 7): 231 -> 99 64-bit
 // address instructions in the BondConv adjoint, -1.5 % of its vector instructions, -1 % of the step -- not worth the 4 GiB-per-table
-// limit it brings (a 4096-structure batch has 4.2 GB of angle rows): the product keeps 64-bit offsets.
-#ifndef CHG_ADDR32
-#define CHG_ADDR32 0
-#endif
+// limit it brings (a 4096-structure batch has 4.2 GB of angle rows).
 template <class T>
 __device__ __forceinline__ const T* grow(const float* __restrict__ base, unsigned r, int ld, int c) {
-#if CHG_ADDR32
-  return reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + (r * (unsigned)(ld * 4) + (unsigned)(c * 4)));
-#else
   return reinterpret_cast<const T*>(base + (size_t)r * ld + c);
-#endif
 }
 template <class T>
 __device__ __forceinline__ T* grow(float* __restrict__ base, unsigned r, int ld, int c) {
-#if CHG_ADDR32
-  return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + (r * (unsigned)(ld * 4) + (unsigned)(c * 4)));
-#else
   return reinterpret_cast<T*>(base + (size_t)r * ld + c);
-#endif
 }
 
 // ---- D-layout loads / stores ---------------------------------------------------------------
@@ -314,19 +289,19 @@ __device__ __forceinline__ void wave_tile_range(int n_wave_tiles, int waves_per_
 // profiles/r03_l2_counters.csv).  Here XCD x (= blockIdx & 7, the observed dispatch: speed only) owns the x-th eighth of the tiles and
 // its waves walk it side by side: wave lw takes tiles xb + lw, xb + lw + WX, ... (WX = waves of the XCD), the eight waves of a
 // workgroup on eight consecutive tiles.  At any moment an XCD then works inside one or two structures; every table row is fetched
-// from the fabric once.  Small batches (a few tiles per wave: MD) keep the evenly spaced contiguous ranges of wave_tile_range.
-#ifndef CHG_TILE_INTERLEAVE
-#define CHG_TILE_INTERLEAVE 1
-#endif
+// from the fabric once.  Small batches (a few tiles per wave: MD) keep the evenly spaced contiguous ranges of wave_tile_range, and so
+// do the training sweep's kernels (INTERLEAVE = false).  Same-box A/B (profiles/r04_experiments.md): the interleaved sweep cuts the
+// fabric traffic of every kernel by 20-30 %; their times move by 0-3 % (they are bound by vector-ALU issue, not by bytes).
 constexpr int INTERLEAVE_MIN_TILES = 6;      // per wave
 struct TileSeq {
   int first, stride, count;
   __device__ __forceinline__ int at(int v) const { return first + v * stride; }
 };
-__device__ __forceinline__ TileSeq wave_tile_seq(int n_wave_tiles, int waves_per_block, int wave, int interleave = 1) {
+template <bool INTERLEAVE>
+__device__ __forceinline__ TileSeq wave_tile_seq(int n_wave_tiles, int waves_per_block, int wave) {
   const int G = gridDim.x, b = blockIdx.x;
   TileSeq s;
-  if (CHG_TILE_INTERLEAVE && interleave && (G & 7) == 0 && (long)n_wave_tiles >= (long)INTERLEAVE_MIN_TILES * G * waves_per_block) {
+  if (INTERLEAVE && (G & 7) == 0 && (long)n_wave_tiles >= (long)INTERLEAVE_MIN_TILES * G * waves_per_block) {
     const int x = b & 7, WX = (G >> 3) * waves_per_block, lw = (b >> 3) * waves_per_block + wave;
     const int xb = (int)((long)n_wave_tiles * x / 8), xe = (int)((long)n_wave_tiles * (x + 1) / 8);
     s.first = xb + lw;

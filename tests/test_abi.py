@@ -125,19 +125,32 @@ def test_unsupported_architectures_are_rejected(golden_weights):
         pack_weights(golden_weights, {"gMLP_norm": "batch"})
 
 
-def test_product_build_defines_no_experiment_switch():
-    """The wrong-result timing switches of rounds 1-3 (CHG_EXP_*) are gone from the sources; the one diagnostic build switch left,
-    CHG_PHASE_TIMING, is refused without CHG_EXPERIMENTS, and the product flags define neither."""
+# runtime A/B switches retired with their losing paths: the engine must not read them any more
+RETIRED_ENV = ("CHGNET_FUSE_GQ", "CHGNET_EMBED_O4", "CHGNET_TILE_INTERLEAVE", "CHGNET_GRID_MULT", "CHGNET_EMBED_GRID_MULT",
+               "CHGNET_PER_ATOM_BONDCONV", "CHGNET_PER_ATOM_ANGLEUPD", "CHGNET_EXP_NW")
+
+
+def test_sources_carry_no_experiment_build_or_retired_switch():
+    """The timing-only builds (CHG_EXPERIMENTS, CHG_EXP_*, CHG_PHASE_TIMING) and their runtime switch (CHGNET_EXP_*) are gone from the
+    shipping sources and the build script, and the retired A/B switches are gone from the engine -- by plain token search, whatever the
+    preprocessor spelling around them."""
     from chgnet_amd import build
 
-    assert not any("CHG_EXP" in f or "CHG_PHASE_TIMING" in f for f in build.HIP_FLAGS)
-    hdr = open(os.path.join(REPO, "chgnet_amd", "csrc", "mfma_tile.h")).read()
-    used = set()
-    for root, _, files in os.walk(os.path.join(REPO, "chgnet_amd", "csrc")):
-        for f in files:
-            used |= set(re.findall(r"#\s*if(?:def|ndef)?\s+(?:defined\()?(CHG_EXP_[A-Z0-9_]+)", open(os.path.join(root, f)).read()))
-    assert not used, f"experiment switches in the shipping sources: {used}"
-    assert "#if defined(CHG_PHASE_TIMING) && !defined(CHG_EXPERIMENTS)" in hdr and "#error" in hdr
+    experiment = re.compile(r"CHG_EXPERIMENTS|CHG_EXP_|CHG_PHASE_TIMING|CHGNET_EXP_")
+    retired = re.compile(r"\b(?:" + "|".join(RETIRED_ENV) + r")\b")
+    assert not any(experiment.search(f) for f in build.HIP_FLAGS)
+    files = [os.path.join(REPO, "chgnet_amd", "build.py")]
+    for sub in (("chgnet_amd", "csrc"), ("include",)):
+        for root, _, names in os.walk(os.path.join(REPO, *sub)):
+            files += [os.path.join(root, f) for f in names]
+    csrc = os.path.join(REPO, "chgnet_amd", "csrc")
+    hits = []
+    for path in files:
+        text = open(path, errors="replace").read()
+        hits += [f"{os.path.relpath(path, REPO)}: {m.group(0)}" for m in experiment.finditer(text)]
+        if path.startswith(csrc + os.sep):
+            hits += [f"{os.path.relpath(path, REPO)}: {m.group(0)}" for m in retired.finditer(text)]
+    assert len(files) > 30 and not hits, hits
 
 
 def test_ctypes_structs_mirror_the_c_header(tmp_path):
