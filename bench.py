@@ -1,6 +1,6 @@
 """bench.py -- structures/s (energy + force + stress) of the HIP engine on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -18,7 +18,10 @@ no data-path collective); with N > 1 the per-structure energies are all-gathered
 ``--dump-outputs DIR`` (e.g. bench_outputs/, git-ignored) writes rank 0's E / F / S of the last timed step as DIR/e.npy,
 f.npy, s.npy: the inputs are seeded, so two builds run with the same arguments compare output for output.
 
-Prints ONE JSON line (rank 0):
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps, dumps and prints the headline figure (value,
+ms_per_step, the workload's sizes); ``--full`` then measures the rest in runs of their own and adds it to the line:
+  device_ms_per_step / kernel_ms_per_step: the step without its download, whole / per kernel (HIP events on the engine stream)
+  end_to_end     host structures -> graph built on the device -> E/F/S on the host
   roofline       the kernel with the largest share of the step (fp32-MFMA-bound), HIP events on the engine stream
   roofline_hbm   the HBM-bound kernels of the path against a STREAM-like copy measured in this process
   configs        the other BASELINE.json configs: C1 (single LiMnO2 cell + x1024), C3 (ragged 10-100-atom sweep
@@ -1099,8 +1102,11 @@ def main() -> None:
     ap.add_argument("--sweep-chunk", type=int, default=1000, help="C3: batch_size handed to predict_structure")
     ap.add_argument("--md-steps", type=int, default=1000, help="C4: timed MD steps (BASELINE: 1000)")
     ap.add_argument("--train-structures", type=int, default=10240, help="C5: structures in the fine-tuning epoch (all ranks together); 0 = skip")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="headline workload only")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also measure the device-only step, the per-kernel split and both rooflines, the "
+                         "host-to-host end-to-end path, the other BASELINE.json configs and the CPU baseline (off: the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: leave out the other BASELINE.json configs")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: process-group plumbing only (gloo)")
     ap.add_argument("--comm", choices=("auto", "torch", "rccl"), default="auto",
                     help="exchange steps: 'rccl' = the engine library's own RCCL entry points, failing if the communicator cannot be "
@@ -1178,6 +1184,39 @@ def main() -> None:
     energies_in_gather = int(np.isfinite(gathered).sum()) if gathered is not None else args.structures
     dumped = dump_outputs(args.dump_outputs, res, packed.atom_off) if args.dump_outputs and rank == 0 else None
 
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "structures/s (energy+force+stress) on batched ~50-atom crystals",
+            "value": round(value, 2), "unit": "structures/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "strong" if args.total_structures else "weak",
+            "vs_baseline": None,
+            "per_rank_ms_per_step": {"min": round(float(per_rank_ms.min()), 3), "median": round(float(np.median(per_rank_ms)), 3),
+                                     "max": round(float(per_rank_ms.max()), 3)},
+            "dtype": "f32", "data": "synthetic",
+            "arithmetic": "f32 storage, f32 accumulation; contractions of the six tile kernels as 3 x f16 MFMA on split f32 operands "
+                          "(error of the split contraction <= the f32 MFMA's, profiles/r03_split_lab.txt; E/F/S parity unchanged)",
+            "config": {"workload": (f"{args.total_structures} x LiMnO2 5x1x1 (40 atoms, sigma=0.01 frac perturbation) in total, split evenly over the GPUs, task efs"
+                                    if args.total_structures else
+                                    f"{args.structures} x LiMnO2 5x1x1 (40 atoms, sigma=0.01 frac perturbation) per GPU, task efs"),
+                       "structures_per_gpu": args.structures, "atoms": int(packed.n_atoms), "directed_bonds": int(packed.n_directed),
+                       "angles": int(packed.n_angles), "bond_graph_nodes": int(packed.n_bnodes),
+                       "weights": "random-init 0.3.0 architecture (tests/golden/weights_seed0.npz)",
+                       "parallelism": f"structures sharded over {world} GPU(s), RCCL all-gather of energies only",
+                       "process_group_ranks": world, "energies_in_all_gather": energies_in_gather, "cpu_affinity_rank0": ranks.cpu_affinity,
+                       "comm": ranks.backend if world > 1 else "none (single rank)", "rccl": ranks.rccl_info, "comm_note": ranks.comm_note},
+            "device_bytes": batch.device_bytes,
+        }
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+    if not args.full:      # the headline figure is complete: everything below takes runs of its own
+        batch.free()
+        eng.close()
+        ranks.close()
+        if line is not None:
+            emit(line)
+        return
+
     # device-only time of one step and the per-kernel split (HIP events on the engine stream)
     eng.timer_start()
     for _ in range(args.steps):
@@ -1217,7 +1256,6 @@ def main() -> None:
         checks["C2_headline"] = ([graphs[i] for i in sample],
                                  [{"e": res["e"][i], "f": res["f"][o[i]:o[i + 1]], "s": res["s"][i]} for i in sample])
 
-    line = None
     if rank == 0:
         total_ms = sum(ms for _, ms in prof.values()) or 1.0
         ranked = sorted(prof.items(), key=lambda kv: -kv[1][1])
@@ -1335,36 +1373,15 @@ def main() -> None:
             hbm["sq_counters_unit"] = sqc["unit"]
         except (OSError, ValueError, KeyError):
             pass
-        line = {
-            "metric": "structures/s (energy+force+stress) on batched ~50-atom crystals",
-            "value": round(value, 2), "unit": "structures/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "strong" if args.total_structures else "weak",
-            "vs_baseline": None,
-            "per_rank_ms_per_step": {"min": round(float(per_rank_ms.min()), 3), "median": round(float(np.median(per_rank_ms)), 3),
-                                     "max": round(float(per_rank_ms.max()), 3)},
-            "dtype": "f32", "data": "synthetic",
-            "arithmetic": "f32 storage, f32 accumulation; contractions of the six tile kernels as 3 x f16 MFMA on split f32 operands "
-                          "(error of the split contraction <= the f32 MFMA's, profiles/r03_split_lab.txt; E/F/S parity unchanged)",
-            "config": {"workload": (f"{args.total_structures} x LiMnO2 5x1x1 (40 atoms, sigma=0.01 frac perturbation) in total, split evenly over the GPUs, task efs"
-                                    if args.total_structures else
-                                    f"{args.structures} x LiMnO2 5x1x1 (40 atoms, sigma=0.01 frac perturbation) per GPU, task efs"),
-                       "structures_per_gpu": args.structures, "atoms": int(packed.n_atoms), "directed_bonds": int(packed.n_directed),
-                       "angles": int(packed.n_angles), "bond_graph_nodes": int(packed.n_bnodes),
-                       "weights": "random-init 0.3.0 architecture (tests/golden/weights_seed0.npz)",
-                       "parallelism": f"structures sharded over {world} GPU(s), RCCL all-gather of energies only",
-                       "process_group_ranks": world, "energies_in_all_gather": energies_in_gather, "cpu_affinity_rank0": ranks.cpu_affinity,
-                       "comm": ranks.backend if world > 1 else "none (single rank)", "rccl": ranks.rccl_info, "comm_note": ranks.comm_note},
+        line.update({
             "device_ms_per_step": round(dev_ms, 3),
             "end_to_end": {"what": "host structures -> device graph build (chg_batch_build) -> predict -> E/F/S on host, per GPU",
                            "ms": round(e2e_ms, 3), "structures_per_s": round(args.structures / (e2e_ms * 1e-3), 1)},
-            "device_bytes": batch.device_bytes,
             "roofline": roofline,
             "roofline_hbm": hbm,
             "kernel_ms_per_step": {k: round(v[1] / prof_steps, 3) for k, v in ranked},
             "configs": configs,
-        }
-        if dumped is not None:
-            line["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+        })
         if not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"], parity = cpu_leg(weights, graphs[:128], checks)
             try:    # the reference ITSELF, timed where it exists: the build container (tools/cpu_reference_baseline.py; it does not travel here)

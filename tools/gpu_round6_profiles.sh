@@ -3,10 +3,10 @@
 # L2 hit counters and SQ counters of the SAME command; kernel stats of one training step and of the MD loop.
 #   tools/gpu_round6_profiles.sh [tag]  ->  gpurun_out/<tag>/...;  afterwards: python profiles/summarize.py <tag>
 TAG=${1:-r06}; R=$PWD; O=$R/gpurun_out/$TAG; mkdir -p $O/prof
-timeout 600 python bench.py > $O/bench_line.json 2> $O/bench.err; tail -c 400 $O/bench_line.json; echo
+timeout 600 python bench.py --full > $O/bench_line.json 2> $O/bench.err; tail -c 400 $O/bench_line.json; echo
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-configs"
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o ktrace -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-configs > $O/rocprof_ktrace.log 2>&1; echo "ktrace exit $?"
+B="python $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-configs"
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o ktrace -- python $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-configs > $O/rocprof_ktrace.log 2>&1; echo "ktrace exit $?"
 timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/prof -o pmc_fetch -- $B > $O/rocprof_fetch.log 2>&1; echo "pmc fetch exit $?"
 timeout 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/prof -o pmc_write -- $B > $O/rocprof_write.log 2>&1; echo "pmc write exit $?"
 timeout 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_READ_sum TCC_ATOMIC_sum --output-format csv -d $O/prof -o l2a -- $B > $O/rocprof_l2a.log 2>&1; echo "l2a exit $?"
