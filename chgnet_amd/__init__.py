@@ -42,4 +42,8 @@ def __getattr__(name):  # lazy: keeps `import chgnet_amd` free of the HIP librar
         from chgnet_amd.phonons import gamma_frequencies
 
         return gamma_frequencies
+    if name == "elastic_moduli":
+        from chgnet_amd.elastic import elastic_moduli
+
+        return elastic_moduli
     raise AttributeError(name)

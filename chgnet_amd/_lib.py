@@ -27,7 +27,7 @@ EXPORTED_SYMBOLS = (
     "chg_host_alloc", "chg_host_free",
     "chg_relax_create", "chg_relax_run", "chg_relax_download", "chg_relax_free", "chg_test_relax_step",
     "chg_md_create", "chg_md_run", "chg_md_download", "chg_md_free", "chg_test_md_step",
-    "chg_hessian_vector",
+    "chg_hessian_vector", "chg_hessian_vector_strain",
 )
 
 
@@ -180,6 +180,7 @@ def load() -> ctypes.CDLL:
     lib.chg_backward.argtypes = [vp, vp, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p]
     lib.chg_backward_allreduce.argtypes = [vp, vp, c_float_p, c_float_p, c_float_p, c_float_p, vp, c_float_p]
     lib.chg_hessian_vector.argtypes = [vp, vp, c_float_p, c_float_p]
+    lib.chg_hessian_vector_strain.argtypes = [vp, vp, c_float_p, c_float_p, c_float_p, c_float_p]
     lib.chg_batch_all_gather_energy.argtypes = [vp, vp, vp, ctypes.c_int64, c_float_p]
     lib.chg_engine_stream.argtypes = [vp]
     lib.chg_engine_stream.restype = ctypes.c_void_p

@@ -347,7 +347,7 @@ int predict_set_lds(chg_engine* eng);
 int backward_compute(chg_engine* eng, chg_batch* b, const float* energy_cotangent, const float* magmom_cotangent, const float* force_cotangent,
                      const float* stress_cotangent);
 int train_set_lds(chg_engine* eng);
-int hvp_compute(chg_engine* eng, chg_batch* b, const float* direction, float* hvp);
+int hvp_compute(chg_engine* eng, chg_batch* b, const float* direction, const float* strain, float* hvp, float* hvp_strain);
 }  // namespace chgh_wide
 
 using namespace chgh;

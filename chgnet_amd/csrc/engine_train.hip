@@ -807,8 +807,9 @@ int backward_compute(chg_engine* eng, chg_batch* b, const float* energy_cotangen
 }
 
 // HVP mode, after run_backward2(.., hvp = true): bar / G of the embeddings -> adjoints of r, rdot, theta, thetadot (kernels_hvp.h) ->
-// per-edge operands of k_edge_force, whose "force" is -H u
-int hvp_from_adjoints(chg_engine* eng, chg_batch* b) {
+// per-edge operands of k_edge_force, whose "force" is -H u.  strain: the direction has a strain part (Wst), and the scatter is
+// k_hvp_strain_scatter's (-hx into hvp_out, hs into hvp_vir)
+int hvp_from_adjoints(chg_engine* eng, chg_batch* b, bool strain) {
   const Weights& w = eng->w;
   Train2& t = *b->t2;
   hipStream_t st = eng->stream;
@@ -834,40 +835,53 @@ int hvp_from_adjoints(chg_engine* eng, chg_batch* b) {
                        t.th2, w.freq_ang, b->ev, t.vd4, b->a_d1, b->a_d2, b->e_d2u, t.hvp_gu, t.hvp_grk, A);
     HIP_TRY(eng, hipGetLastError());
   }
-  ForceArgs f{};
-  f.ev = b->ev; f.eu = b->eu; f.Gu = t.hvp_gu; f.Grk = t.hvp_grk;
-  f.e_center = b->e_center; f.e_d2u = b->e_d2u; f.e_owner = b->e_owner; f.e_rev = b->e_rev; f.u_u2d = b->u_u2d;
-  f.n_edges = Ed; f.force = t.hvp_out; f.virial = t.hvp_vir;
   LaunchScope ls(eng, "hvp_scatter");
-  hipLaunchKernelGGL(k_edge_force, g1(Ed, EF_EDGES_PER_BLOCK), dim3(256), 0, st, f);
+  if (strain) {
+    HvpScatterArgs f{b->ev, b->eu, t.hvp_gu, t.hvp_grk, b->Gu, b->Grk, t.ux, t.Wst,
+                     b->e_center, b->e_nbr, b->e_d2u, b->e_owner, b->e_rev, b->u_u2d, Ed, t.hvp_out, t.hvp_vir};
+    hipLaunchKernelGGL(k_hvp_strain_scatter, g1(Ed, HVS_EDGES_PER_BLOCK), dim3(256), 0, st, f);
+  } else {
+    ForceArgs f{};
+    f.ev = b->ev; f.eu = b->eu; f.Gu = t.hvp_gu; f.Grk = t.hvp_grk;
+    f.e_center = b->e_center; f.e_d2u = b->e_d2u; f.e_owner = b->e_owner; f.e_rev = b->e_rev; f.u_u2d = b->u_u2d;
+    f.n_edges = Ed; f.force = t.hvp_out; f.virial = t.hvp_vir;
+    hipLaunchKernelGGL(k_edge_force, g1(Ed, EF_EDGES_PER_BLOCK), dim3(256), 0, st, f);
+  }
   HIP_TRY(eng, hipGetLastError());
   return CHG_OK;
 }
 
-// H u of every structure's total energy (fixed graph, fixed cell) along direction [N,3] -> hvp [N,3], both host
-int hvp_compute(chg_engine* eng, chg_batch* b, const float* direction, float* hvp) {
+// H u of every structure's total energy (fixed graph, fixed cell) along direction [N,3] -> hvp [N,3], both host.  strain [B,9] (null:
+// fixed cell): the full (x, eps) Hessian along (u, W) instead, hvp = hx and hvp_strain [B,9] = hs (kernels_hvp.h, strain blocks)
+int hvp_compute(chg_engine* eng, chg_batch* b, const float* direction, const float* strain, float* hvp, float* hvp_strain) {
   if (b->last_task == 0) { eng->err = "chg_hessian_vector: run chg_predict on this batch first (the sweep reuses its activations)"; return CHG_EINVAL; }
   if ((int)b->h_atom_off.size() != b->B + 1) { eng->err = "chg_hessian_vector: batch has no host atom offsets"; return CHG_EINVAL; }
 #ifndef CHG_WIDE_RANGE
-  if (b->wide_range) return chgh_wide::hvp_compute(eng, b, direction, hvp);
+  if (b->wide_range) return chgh_wide::hvp_compute(eng, b, direction, strain, hvp, hvp_strain);
 #endif
   TRY(ensure_train_buffers(eng, b));
-  // seeds: no energy or magmom cotangent, ux = u, Wst = 0.  The sweep reuses the first-order adjoints of the force sweep (chg_backward)
+  // seeds: no energy or magmom cotangent, ux = u, Wst = W (0 at fixed cell).  The sweep reuses the first-order adjoints of the force
+  // sweep (chg_backward); the strain scatter reads its bond-vector operands (b->Gu, b->Grk), which the HVP mode does not write
   if (!b->seed1_adjoints) TRY(run_predict(eng, b, b->last_task | CHG_TASK_F));
   TRY(ensure_train2_buffers(eng, b));
   TRY(zero(eng, b->t_cot, sizeof(float) * b->B));
   b->t_has_mcot = false;
   HIP_TRY(eng, hipMemcpyAsync(b->t2->ux, direction, sizeof(float) * 3 * (size_t)b->N, hipMemcpyHostToDevice, eng->stream));
-  TRY(zero(eng, b->t2->Wst, sizeof(float) * 9 * (size_t)b->B));
+  if (strain)
+    HIP_TRY(eng, hipMemcpyAsync(b->t2->Wst, strain, sizeof(float) * 9 * (size_t)b->B, hipMemcpyHostToDevice, eng->stream));
+  else
+    TRY(zero(eng, b->t2->Wst, sizeof(float) * 9 * (size_t)b->B));
   if (b->Ed > 0 && !b->q_tables) {
     for (int l = 0; l < b->L; ++l) TRY(atomconv_q_table(eng, b, l));
     b->q_tables = true;
   }
   TRY(run_backward2(eng, b, true));
-  TRY(hvp_from_adjoints(eng, b));
+  TRY(hvp_from_adjoints(eng, b, strain != nullptr));
   HIP_TRY(eng, hipMemcpyAsync(hvp, b->t2->hvp_out, sizeof(float) * 3 * (size_t)b->N, hipMemcpyDeviceToHost, eng->stream));
+  if (strain)
+    HIP_TRY(eng, hipMemcpyAsync(hvp_strain, b->t2->hvp_vir, sizeof(float) * 9 * (size_t)b->B, hipMemcpyDeviceToHost, eng->stream));
   HIP_TRY(eng, hipStreamSynchronize(eng->stream));
-  for (size_t i = 0; i < (size_t)3 * b->N; ++i) hvp[i] = -hvp[i];   // k_edge_force forms -dEdot/dx
+  for (size_t i = 0; i < (size_t)3 * b->N; ++i) hvp[i] = -hvp[i];   // the scatter forms -dEdot/dx
   return CHG_OK;
 }
 
@@ -929,7 +943,7 @@ int chg_backward_allreduce(chg_engine* eng, chg_batch* b, const float* energy_co
 int chg_hessian_vector(chg_engine* eng, chg_batch* b, const float* direction, float* hvp) {
   if (!eng || !b || !direction || !hvp) return CHG_EINVAL;
   HIP_TRY(eng, hipSetDevice(eng->device));
-  const int status = hvp_compute(eng, b, direction, hvp);
+  const int status = hvp_compute(eng, b, direction, nullptr, hvp, nullptr);
   if (status != CHG_OK) return status;
   // a product sweep that left the f16 operand range gives non-finite rows: the batch moves to the wide-range sweeps (as at
   // chg_batch_download) and the product is formed again there
@@ -939,7 +953,23 @@ int chg_hessian_vector(chg_engine* eng, chg_batch* b, const float* direction, fl
   b->wide_range = true;
   if (b->graph_exec) { hipGraphExecDestroy(b->graph_exec); b->graph_exec = nullptr; }
   TRY(chgh_wide::run_predict(eng, b, b->last_task | CHG_TASK_F));
-  return chgh_wide::hvp_compute(eng, b, direction, hvp);
+  return chgh_wide::hvp_compute(eng, b, direction, nullptr, hvp, nullptr);
+}
+
+int chg_hessian_vector_strain(chg_engine* eng, chg_batch* b, const float* direction, const float* strain, float* hvp, float* hvp_strain) {
+  if (!eng || !b || !direction || !strain || !hvp || !hvp_strain) return CHG_EINVAL;
+  HIP_TRY(eng, hipSetDevice(eng->device));
+  const int status = hvp_compute(eng, b, direction, strain, hvp, hvp_strain);
+  if (status != CHG_OK) return status;
+  // the wide-range fallback of chg_hessian_vector, on both outputs
+  bool finite = true;
+  for (int64_t i = 0; i < 3 * (int64_t)b->N && finite; ++i) finite = std::isfinite(hvp[i]);
+  for (int64_t i = 0; i < 9 * (int64_t)b->B && finite; ++i) finite = std::isfinite(hvp_strain[i]);
+  if (finite || b->wide_range) return CHG_OK;
+  b->wide_range = true;
+  if (b->graph_exec) { hipGraphExecDestroy(b->graph_exec); b->graph_exec = nullptr; }
+  TRY(chgh_wide::run_predict(eng, b, b->last_task | CHG_TASK_F));
+  return chgh_wide::hvp_compute(eng, b, direction, strain, hvp, hvp_strain);
 }
 
 }  // extern "C"

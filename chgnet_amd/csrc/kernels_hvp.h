@@ -13,9 +13,14 @@
 // either of its directed edges: the reverse edge's radial part equals the representative's), Gu[e] += r_e x (transverse adjoint of v_e),
 // so that kernel's  gv_e = Grk u_e + (I - u u^T) Gu_e / r_e  is the adjoint of the bond vector v_e = x_c - x_n and its "force" is -H u.
 // The contractions with W^T run on the matrix pipe on 16-row tiles (embed_adjoint), the layout of kernels_train2_freq.h.
+//
+// Strain blocks (chg_hessian_vector_strain): E(x, eps) with every bond vector v_e = v0_e (I + eps) (lattice L (I + eps), fixed
+// fractional coordinates), direction (u, W).  The tangent sweep already takes W (k2_geom_t: vd_e = u_c - u_n + v_e W), so the
+// second-order adjoint gv2_e above is the same; what differs is the chain back to (x, eps) -- k_hvp_strain_scatter.
 #pragma once
 
 #include "kernels_embed.h"
+#include "kernels_geom.h"
 #include "kernels_train2.h"
 
 namespace chg {
@@ -289,6 +294,154 @@ static __global__ __launch_bounds__(BLOCK) void k_hvp_angle_t(const float* __res
       bond_adjoint(q.u1, q.v1d, q.r1, q.rd1, a1, b1, d1);
       bond_adjoint(q.u2, q.v2d, q.r2, q.rd2, a2, b2, d2);
     }
+  }
+}
+
+// ---- strain blocks: (x, eps)-adjoints of Edot = sum_e g_e . (u_c - u_n + v_e W) -> -hx [N,3] and hs [B,9] -------------------------------
+// With g_e = dE/dv_e (the force sweep's operands, b->Gu / b->Grk) and gv2_e the second-order adjoint above (t.hvp_gu / t.hvp_grk):
+//   x-adjoint of bond vector e:   gx_e = gv2_e + W g_e                   (the tangent's v0_e W term, chained through v0_e)
+//   strain adjoint of owner b:    sum_e v_e (x) gv2_e + (u_c - u_n) (x) g_e
+// d v_e / d eps . W = v0_e W does not depend on eps, so the virial has no v_e (x) W g_e term: the force and the virial see different
+// per-edge operands, which k_edge_force cannot express.  Otherwise this is k_edge_force: the same centre-major segmented scatter of
+// gx_rev(e) - gx_e (DPP scan, one atomic per run end) and the same per-wave / per-workgroup virial reduction, in fewer chunks per wave
+// (twice the operands per edge).
+struct HvpScatterArgs {
+  const f32x4 *ev, *eu;
+  const float *Gu2, *Grk2;    // second-order operands [Ed,4] [Eu]
+  const float *Gu1, *Grk1;    // first-order operands of the force sweep [Ed,4] [Eu]
+  const float *ux, *Wst;      // direction [N,3], [B,9]
+  const int *e_center, *e_nbr, *e_d2u, *e_owner, *e_rev, *u_u2d;
+  int n_edges;
+  float* force;               // [N,3] zeroed: -hx
+  float* virial;              // [B,9] zeroed: hs
+};
+
+constexpr int HVS_IT = 2;
+constexpr int HVS_EDGES_PER_BLOCK = 4 * 64 * HVS_IT;
+
+// dE/dv of edge e from k_edge_force's operands: gr u + (I - u u^T) gu / r  (gr: the bond's radial adjoint if e carries it, sign of u)
+__device__ __forceinline__ void edge_grad(const f32x4& uu, float inv_r, float gr, const f32x4& gu, float (&gv)[3]) {
+  const float dot = gu[0] * uu[0] + gu[1] * uu[1] + gu[2] * uu[2];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) gv[k] = gr * uu[k] + (gu[k] - dot * uu[k]) * inv_r;
+}
+
+static __global__ __launch_bounds__(256) void k_hvp_strain_scatter(HvpScatterArgs p) {
+  __shared__ float vir[4][9];
+  __shared__ int vown[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int base = (blockIdx.x * 4 + wave) * (64 * HVS_IT);
+  int owner[HVS_IT];
+#pragma unroll
+  for (int it = 0; it < HVS_IT; ++it) {
+    const int e = base + 64 * it + lane;
+    owner[it] = e < p.n_edges ? p.e_owner[e] : -1;
+  }
+  float tv[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const int first = __builtin_amdgcn_readfirstlane(owner[0]);
+  bool uniform = first >= 0;
+#pragma unroll
+  for (int it = 0; it < HVS_IT; ++it) uniform = uniform && __all(owner[it] == first || owner[it] < 0) != 0;
+#pragma unroll
+  for (int it = 0; it < HVS_IT; ++it) {
+    const int e = base + 64 * it + lane;
+    const bool valid = e < p.n_edges;
+    const int ec = valid ? e : 0;
+    float d[3] = {0.f, 0.f, 0.f}, t9[9];
+    int kcur = -1;
+    {
+      const f32x4 vr = p.ev[ec], uu = p.eu[ec];
+      const int kk = p.e_d2u[ec], er = p.e_rev[ec], c = p.e_center[ec], n = p.e_nbr[ec];
+      const bool rep = p.u_u2d[kk] == e;                    // lengths enter only via the representative edge of the bond
+      const float g2r = p.Grk2[kk], g1r = p.Grk1[kk], inv_r = 1.0f / vr[3];
+      const f32x4 mu = f32x4{-uu[0], -uu[1], -uu[2], 0.f}; // u_rev = -u
+      float gv2[3], gv2r[3], g1[3], g1rv[3];
+      edge_grad(uu, inv_r, rep ? g2r : 0.f, *reinterpret_cast<const f32x4*>(p.Gu2 + 4 * (size_t)ec), gv2);
+      edge_grad(mu, inv_r, rep ? 0.f : g2r, *reinterpret_cast<const f32x4*>(p.Gu2 + 4 * (size_t)er), gv2r);
+      edge_grad(uu, inv_r, rep ? g1r : 0.f, *reinterpret_cast<const f32x4*>(p.Gu1 + 4 * (size_t)ec), g1);
+      edge_grad(mu, inv_r, rep ? 0.f : g1r, *reinterpret_cast<const f32x4*>(p.Gu1 + 4 * (size_t)er), g1rv);
+      const float* W = p.Wst + 9 * (size_t)(valid ? owner[it] : 0);
+      float du[3], dg[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { du[k] = p.ux[3 * c + k] - p.ux[3 * n + k]; dg[k] = g1rv[k] - g1[k]; }
+#pragma unroll
+      for (int a = 0; a < 3; ++a) d[a] = gv2r[a] - gv2[a] + W[3 * a] * dg[0] + W[3 * a + 1] * dg[1] + W[3 * a + 2] * dg[2];
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) t9[3 * a + b] = valid ? vr[a] * gv2[b] + du[a] * g1[b] : 0.f;
+      if (!valid) d[0] = d[1] = d[2] = 0.f;
+      kcur = valid ? c : -1;
+    }
+    // segmented inclusive scan over runs of equal centre (k_edge_force's)
+    const int kprev = __builtin_amdgcn_update_dpp(-2, kcur, 0x138, 0xF, 0xF, false);    // wave_shr:1
+    const unsigned long long heads = __ballot(lane == 0 || kprev != kcur);
+    const int start = 63 - __builtin_clzll(heads & (~0ull >> (63 - lane)));
+#define CHG_SEG_STEP(ctrl, rmask, cond)                                                                                  \
+    {                                                                                                                      \
+      const float t0 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(d[0]), (ctrl), (rmask), 0xF, true)); \
+      const float t1 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(d[1]), (ctrl), (rmask), 0xF, true)); \
+      const float t2 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(d[2]), (ctrl), (rmask), 0xF, true)); \
+      if (cond) {                                                                                                          \
+        d[0] += t0;                                                                                                        \
+        d[1] += t1;                                                                                                        \
+        d[2] += t2;                                                                                                        \
+      }                                                                                                                    \
+    }
+    const int row_lane = lane & 15, row_base = lane & ~15;
+    CHG_SEG_STEP(0x111, 0xF, row_lane >= 1 && lane - 1 >= start)     // row_shr:1
+    CHG_SEG_STEP(0x112, 0xF, row_lane >= 2 && lane - 2 >= start)     // row_shr:2
+    CHG_SEG_STEP(0x114, 0xF, row_lane >= 4 && lane - 4 >= start)     // row_shr:4
+    CHG_SEG_STEP(0x118, 0xF, row_lane >= 8 && lane - 8 >= start)     // row_shr:8
+    CHG_SEG_STEP(0x142, 0xA, (row_base & 16) && start < row_base)    // row_bcast:15
+    CHG_SEG_STEP(0x143, 0xC, row_base >= 32 && start < 32)           // row_bcast:31
+#undef CHG_SEG_STEP
+    const int knext = __builtin_amdgcn_update_dpp(-2, kcur, 0x130, 0xF, 0xF, false);    // wave_shl:1
+    if (valid && (lane == 63 || knext != kcur)) {
+#pragma unroll
+      for (int k3 = 0; k3 < 3; ++k3) atomicAdd(p.force + 3 * (size_t)kcur + k3, d[k3]);
+    }
+    if (uniform) {
+#pragma unroll
+      for (int c = 0; c < 9; ++c) tv[c] += t9[c];
+    } else {
+      unsigned long long rem = __ballot(valid);
+      while (rem) {
+        const int o = __builtin_amdgcn_readlane(owner[it], __builtin_ctzll(rem));
+        const bool mine = valid && owner[it] == o;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) {
+          const float sck = wave_sum(mine ? t9[c] : 0.f);
+          if (lane == 0) atomicAdd(p.virial + 9 * (size_t)o + c, sck);
+        }
+        rem &= ~__ballot(mine);
+      }
+    }
+  }
+  if (lane == 0) vown[wave] = uniform ? first : -2;
+  if (uniform) {
+#pragma unroll
+    for (int c = 0; c < 9; ++c) {
+      const float s = wave_sum(tv[c]);
+      if (lane == 0) vir[wave][c] = s;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 9) {
+    const int c = threadIdx.x;
+    int cur = -2;
+    float s = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int o = vown[w];
+      if (o != cur) {
+        if (cur >= 0) atomicAdd(p.virial + 9 * (size_t)cur + c, s);
+        s = 0.f;
+        cur = o;
+      }
+      if (o >= 0) s += vir[w][c];
+    }
+    if (cur >= 0) atomicAdd(p.virial + 9 * (size_t)cur + c, s);
   }
 }
 

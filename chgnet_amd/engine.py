@@ -302,6 +302,23 @@ class Engine:
         self._check(self.lib.chg_hessian_vector(self.handle, batch.handle, _fp(u), _fp(out)))
         return out
 
+    def hessian_vector_strain(self, batch: DeviceBatch, direction, strain) -> tuple[np.ndarray, np.ndarray]:
+        """The full Hessian of each structure's total energy E(x, eps) (lattice L (I + eps), atoms at fixed fractional coordinates)
+        at eps = 0 along (u, W) (chg_hessian_vector_strain): ``direction`` [N,3] (A), ``strain`` [B,3,3] or [B,9] (W per
+        structure) -> ``(hx [N,3] eV/A^2, hs [B,3,3] eV)`` float32, with hs[b][a][c] the derivative along d/d eps[a][c] (the
+        virial's convention).  Needs a preceding ``predict`` on ``batch``; overwrites its gradient workspace."""
+        n, nb = batch.packed.n_atoms, batch.packed.n_struct
+        u = np.ascontiguousarray(direction, np.float32)
+        if u.shape != (n, 3):
+            raise ValueError(f"direction has shape {u.shape}; the batch has {n} atoms: expected ({n}, 3)")
+        w = np.ascontiguousarray(strain, np.float32)
+        if w.shape not in ((nb, 3, 3), (nb, 9)):
+            raise ValueError(f"strain has shape {w.shape}; the batch has {nb} structures: expected ({nb}, 3, 3)")
+        hx = np.empty((n, 3), np.float32)
+        hs = np.empty((nb, 3, 3), np.float32)
+        self._check(self.lib.chg_hessian_vector_strain(self.handle, batch.handle, _fp(u), _fp(w), _fp(hx), _fp(hs)))
+        return hx, hs
+
     def all_gather_energy(self, batch: DeviceBatch, comm, width: int) -> np.ndarray:
         """[nranks, width] table of the per-structure energies of every rank's batch (zero-padded to ``width``), gathered
         from HBM on the engine's stream (chg_batch_all_gather_energy).  After ``predict``."""

@@ -386,18 +386,25 @@ class CHGNet:
             raise ValueError("graph_converter cannot be None!")
         return self.graph_converter(item)     # isolated atoms: the converter's error / warning, as in predict_structure
 
-    def _hvp_graphs(self, graphs: list, directions: list, batch_size: int, min_atoms: int) -> list[np.ndarray]:
+    def _hvp_graphs(self, graphs: list, directions: list, batch_size: int, min_atoms: int, strains: list | None = None) -> list:
+        """H u per graph ([n,3] arrays); with ``strains`` (one 3x3 W per graph) the strain-block products (hx, hs) instead."""
         eng = self.engine
 
         def run(idx):
             batch = eng.upload(pack_batch([graphs[i] for i in idx]))
             try:
                 eng.predict(batch, "ef")
-                h = eng.hessian_vector(batch, np.concatenate([directions[i] for i in idx]))
+                u = np.concatenate([directions[i] for i in idx])
+                if strains is None:
+                    h = eng.hessian_vector(batch, u)
+                else:
+                    h, hs = eng.hessian_vector_strain(batch, u, np.stack([strains[i] for i in idx]))
                 off = batch.packed.atom_off
             finally:
                 batch.free()
-            return [h[off[k]:off[k + 1]].copy() for k in range(len(idx))]
+            if strains is None:
+                return [h[off[k]:off[k + 1]].copy() for k in range(len(idx))]
+            return [(h[off[k]:off[k + 1]].copy(), hs[k].copy()) for k in range(len(idx))]
 
         out: list[np.ndarray] = []
         for a, b in _plan_chunks([len(g.atomic_number) for g in graphs], batch_size, min_atoms):
@@ -410,6 +417,11 @@ class CHGNet:
         rebuild) -- the second derivative of the function whose gradient gives the forces.  ``directions``: one [n,3] array (A)
         per structure.  Returns one [n,3] float32 array (eV/A^2) per structure (a bare array for a single structure or graph).
         ``batch_size`` as in ``predict_structure``."""
+        single, graphs, dirs = self._hvp_args(structures_or_graphs, directions)
+        out = self._hvp_graphs(graphs, dirs, batch_size, self.min_atoms_per_batch)
+        return out[0] if single else out
+
+    def _hvp_args(self, structures_or_graphs, directions):
         single = _is_structure(structures_or_graphs) or _is_graph(structures_or_graphs)
         items = [structures_or_graphs] if single else list(structures_or_graphs)
         dirs = [directions] if single else list(directions)
@@ -421,7 +433,25 @@ class CHGNet:
             dirs[i] = np.asarray(d, np.float32)
             if dirs[i].shape != (n, 3):
                 raise ValueError(f"direction {i} has shape {dirs[i].shape}; its structure has {n} atoms: expected ({n}, 3)")
-        out = self._hvp_graphs(graphs, dirs, batch_size, self.min_atoms_per_batch)
+        return single, graphs, dirs
+
+    def hessian_vector_product_with_strain(self, structures_or_graphs, directions, strains, *, batch_size: int = 16):
+        """Exact products with the full Hessian of E(x, eps) at eps = 0, the strain blocks included: E the structure's TOTAL energy
+        (as in ``hessian_vector_product``), the lattice L (I + eps) and the atoms at fixed fractional coordinates (every bond vector
+        v0 (I + eps)), on the fixed graph.  Along a direction ``u`` [n,3] (A) and a strain ``W`` [3,3] per structure it returns
+        ``(hx, hs)``: ``hx = d2E/dx dx . u + d2E/dx deps : W`` ([n,3] float32, eV/A^2) and ``hs = d2E/deps dx . u +
+        d2E/deps deps : W`` ([3,3] float32, eV; hs[a][b] along d/d eps[a][b], the index convention of the stress).  A tuple for a
+        single structure or graph, else a list of them.  ``W = 0`` gives ``hessian_vector_product``'s H u."""
+        single, graphs, dirs = self._hvp_args(structures_or_graphs, directions)
+        ws = [strains] if single else list(strains)
+        if len(ws) != len(graphs):
+            raise ValueError(f"{len(graphs)} structures but {len(ws)} strains")
+        for i, w in enumerate(ws):
+            ws[i] = np.asarray(w, np.float32)
+            if ws[i].shape not in ((3, 3), (9,)):
+                raise ValueError(f"strain {i} has shape {ws[i].shape}: expected (3, 3)")
+            ws[i] = ws[i].reshape(3, 3)
+        out = self._hvp_graphs(graphs, dirs, batch_size, self.min_atoms_per_batch, ws)
         return out[0] if single else out
 
     def predict_hessian(self, structure, *, symmetrize: bool = True, max_atoms_per_batch: int = 16384):
@@ -442,6 +472,69 @@ class CHGNet:
                 for c, r in zip(cols, res):
                     h[:, c] = r.reshape(-1)
             out.append(0.5 * (h + h.T) if symmetrize else h)
+        return out[0] if single else out
+
+    def predict_elastic_tensor(self, structure, *, relaxed_ion: bool = True, max_atoms_per_batch: int = 16384):
+        """Elastic constants of each structure from the strain blocks of its exact Hessian (``chgnet_amd.elastic``): 6 strain
+        products (u = 0, W = the Voigt unit strains) and, for ``relaxed_ion``, the 3n force-constant columns, run in device batches
+        of at most ``max_atoms_per_batch`` atoms (the replicas of several structures share batches).  Same semantics as
+        ``hessian_vector_product_with_strain``.  Returns per structure a dict:
+
+        - ``clamped_ion``: 6x6 (GPa, Voigt order xx, yy, zz, yz, xz, xy), (1/V) W_i : d2E/deps deps : W_j, symmetrised
+        - ``relaxed_ion``: 6x6 (GPa), clamped minus (1/V) Lambda^T Phi^+ Lambda (translations projected out); None if not asked for
+        - ``internal_strain``: Lambda = d2E/dx deps : W_j, [3n,6] (eV/A)
+        - ``force_constants``: Phi [3n,3n] (eV/A^2, symmetrised), only with ``relaxed_ion``
+        - ``stress``: the residual stress in Voigt order (GPa), ``volume`` (A^3)
+        - ``min_phonon_eigenvalue``: lowest eigenvalue of Phi off the translations (eV/A^2); None without ``relaxed_ion``
+
+        These are elastic constants only at a stress-free, force-free configuration: relax the structure first
+        (``StructOptimizer().relax(..., fmax=1e-3)`` or tighter) and check ``stress`` and ``min_phonon_eigenvalue`` (a negative
+        one: not a minimum).  A list in, a list out."""
+        from chgnet_amd import elastic  # noqa: PLC0415
+
+        single = _is_structure(structure) or _is_graph(structure)
+        graphs = [self._graph_of(x) for x in ([structure] if single else list(structure))]
+        wv = elastic.voigt_strains().astype(np.float32)
+        zero_w = np.zeros((3, 3), np.float32)
+        jobs = []                                   # (structure, column, direction, strain)
+        for s, g in enumerate(graphs):
+            n = len(g.atomic_number)
+            jobs += [(s, j, np.zeros((n, 3), np.float32), wv[j]) for j in range(6)]
+            if relaxed_ion:
+                eye = np.eye(3 * n, dtype=np.float32).reshape(3 * n, n, 3)
+                jobs += [(s, 6 + k, eye[k], zero_w) for k in range(3 * n)]
+        cols = [{} for _ in graphs]
+        cap = max(1, int(max_atoms_per_batch))
+        start = 0
+        while start < len(jobs):                   # consecutive replicas up to the atom cap per device batch
+            stop, atoms = start, 0
+            while stop < len(jobs) and (stop == start or atoms + len(graphs[jobs[stop][0]].atomic_number) <= cap):
+                atoms += len(graphs[jobs[stop][0]].atomic_number)
+                stop += 1
+            chunk = jobs[start:stop]
+            res = self._hvp_graphs([graphs[j[0]] for j in chunk], [j[2] for j in chunk], len(chunk), 0, [j[3] for j in chunk])
+            for (s, c, _, _), r in zip(chunk, res):
+                cols[s][c] = r
+            start = stop
+        pred = self.predict_graph(graphs, task="efs")
+        pred = [pred] if len(graphs) == 1 else pred
+        out = []
+        for s, g in enumerate(graphs):
+            n = len(g.atomic_number)
+            volume = abs(float(np.linalg.det(np.asarray(g.lattice, np.float64).reshape(3, 3))))
+            hs = np.stack([np.asarray(cols[s][j][1], np.float64) for j in range(6)])              # [6,3,3]
+            c = np.einsum("iab,jab->ij", wv.astype(np.float64), hs) * (elastic.EV_A3_TO_GPA / volume)
+            clamped = 0.5 * (c + c.T)
+            lam = np.stack([np.asarray(cols[s][j][0], np.float64).reshape(-1) for j in range(6)], axis=1)
+            r = {"clamped_ion": clamped, "relaxed_ion": None, "internal_strain": lam,
+                 "stress": elastic.to_voigt(pred[s]["s"]), "volume": volume, "min_phonon_eigenvalue": None}
+            if relaxed_ion:
+                phi = np.stack([np.asarray(cols[s][6 + k][0], np.float64).reshape(-1) for k in range(3 * n)], axis=1)
+                phi = 0.5 * (phi + phi.T)
+                relaxed = elastic.relaxed_ion_tensor(clamped, lam, phi, volume)
+                r.update(relaxed_ion=0.5 * (relaxed + relaxed.T), force_constants=phi,
+                         min_phonon_eigenvalue=elastic.min_phonon_eigenvalue(phi))
+            out.append(r)
         return out[0] if single else out
 
     # ---- (de)serialisation (model.py:667-745) ----------------------------------------------------------

@@ -108,7 +108,7 @@ typedef struct chg_out_host {
 
 /* Version of this interface: bumped whenever a struct of this header grows or an entry point changes meaning (chg_model_desc gained
  * n_mlp_hidden / mlp_out_bias at 2; chg_batch_build_predict arrived at 3; the chg_relax_* entry points at 4; the chg_md_* entry points at 5;
- * chg_hessian_vector was added at 5 without a bump: a new entry point only, no struct or signature changed).  A binding compiled against another value must refuse the
+ * chg_hessian_vector and chg_hessian_vector_strain were added at 5 without a bump: new entry points only, no struct or signature changed).  A binding compiled against another value must refuse the
  * library: chg_engine_create COPIES *desc, so an older, shorter chg_model_desc would be read past its end. */
 #define CHG_ABI_VERSION 5
 int chg_abi_version(void);
@@ -203,6 +203,14 @@ int chg_backward_allreduce(chg_engine* eng, chg_batch* batch, const float* energ
  * The tangent + two-adjoint sweep of chg_backward without its weight-gradient contractions, then the adjoints of the bond lengths
  * and angles (csrc/kernels_hvp.h) scattered to the atoms. */
 int chg_hessian_vector(chg_engine* eng, chg_batch* batch, const float* direction, float* hvp);
+/* The same with strain blocks: the full Hessian of E_b(x, eps) at eps = 0 along (u, W), with the lattice L (I + eps) and the atoms at
+ * fixed fractional coordinates (every bond vector v0 (I + eps)):  hvp = d2E/dx dx . u + d2E/dx deps : W  [N,3] (eV/A^2),
+ * hvp_strain[b] = d2E/deps dx . u + d2E/deps deps : W  [B,9] (eV, row-major [a][b] = d/d eps[a][b], the virial's convention).
+ * direction: host [N,3] (A); strain: host [B,9] (dimensionless W per structure).  Preconditions and the wide-range fallback (on either
+ * output) of chg_hessian_vector; strain = 0 gives its hvp.  The (x, eps) adjoints are scattered by k_hvp_strain_scatter
+ * (csrc/kernels_hvp.h).  Added at 5 without a bump, as chg_hessian_vector. */
+int chg_hessian_vector_strain(chg_engine* eng, chg_batch* batch, const float* direction, const float* strain, float* hvp,
+                              float* hvp_strain);
 /* All-gather of the batch's per-structure energies (after chg_predict) from HBM on the engine's stream: every rank
  * contributes `width` floats (its n_struct energies, zero-padded), table: host [nranks * width] in rank order. */
 int chg_batch_all_gather_energy(chg_engine* eng, chg_batch* batch, struct chg_comm* comm, int64_t width, float* table);
