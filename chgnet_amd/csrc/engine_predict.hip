@@ -719,6 +719,11 @@ int run_predict(chg_engine* eng, chg_batch* b, uint32_t task) {
   // sequence of the large batches
   static const bool chain_on = [] { const char* e = std::getenv("CHGNET_TINY_CHAIN"); return !e || std::atoi(e) != 0; }();
   const bool chained = tiny && chain_on && L >= 2 && b->Ed > 0 && b->A > 0 && b->Eb > 0 && b->p_table_done == 0;
+  b->route[0] = tiny;
+  b->route[1] = chained;
+  b->route[2] = want_grad && b->zsave_l[0] && (b->win_built || b->win_team > 0);   // (angle_args: AngleArgs::zsave)
+  b->route[3] = b->win_built;
+  b->route[4] = b->win_team > 0;
   if (chained) {
     TRY(forward_tiny(eng, b, want_grad, want_m));
   } else {

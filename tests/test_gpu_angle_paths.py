@@ -22,7 +22,7 @@ from conftest import GOLDEN, REPO
 pytestmark = pytest.mark.gpu
 
 KNOBS = ("CHGNET_BLK_MAX_ANGLES", "CHGNET_TEAM_MIN_ANGLES", "CHGNET_WIN_MIN_ATOMS_PER_WAVE", "CHGNET_PER_ATOM_FWD",
-         "CHGNET_TINY_FUSE", "CHGNET_TINY_CHAIN")
+         "CHGNET_TINY_FUSE", "CHGNET_TINY_CHAIN", "CHGNET_ZSAVE")
 PER_ATOM = {"CHGNET_BLK_MAX_ANGLES": "0", "CHGNET_TEAM_MIN_ANGLES": "-1", "CHGNET_WIN_MIN_ATOMS_PER_WAVE": "0"}
 CONFIGS = {
     "default": {},                                                           # blocked tiles (the suite may switch them off)
