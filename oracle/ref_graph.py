@@ -44,6 +44,13 @@ def reference_graph(n_atoms, center, neighbor, image, distance, r_bond: float) -
                             image.ctypes.data_as(ip), distance.ctypes.data_as(dp), ctypes.c_double(r_bond),
                             ag.ctypes.data_as(i32), d2u.ctypes.data_as(i32), u2d.ctypes.data_as(i32), bg.ctypes.data_as(i32),
                             ctypes.c_int64(cap), counts.ctypes.data_as(ip))
+    if st == 0 and counts[1] > cap:       # more angles than the guess (dense or thin cells): only the count is valid, so once more
+        cap = int(counts[1])
+        bg = np.zeros((cap, 5), np.int32)
+        st = lib.ref_graph_flat(ctypes.c_int64(n_atoms), ctypes.c_int64(E), center.ctypes.data_as(ip), neighbor.ctypes.data_as(ip),
+                                image.ctypes.data_as(ip), distance.ctypes.data_as(dp), ctypes.c_double(r_bond),
+                                ag.ctypes.data_as(i32), d2u.ctypes.data_as(i32), u2d.ctypes.data_as(i32), bg.ctypes.data_as(i32),
+                                ctypes.c_int64(cap), counts.ctypes.data_as(ip))
     if st != 0:
         raise ValueError(f"reference create_graph: status {st}")
     return {"atom_graph": ag, "directed2undirected": d2u, "undirected2directed": u2d[: counts[0]].copy(),

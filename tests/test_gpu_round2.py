@@ -162,6 +162,7 @@ def test_device_graph_build_against_the_compiled_reference(hip_engine):
     import json
 
     from chgnet_amd.graph.converter import build_graph_arrays
+    from device_graph import fetch_device_graph
     from golden.make_golden_helpers import array_digest
 
     with open(os.path.join(GOLDEN, "ref_graph_c.json")) as fh:
@@ -169,34 +170,20 @@ def test_device_graph_build_against_the_compiled_reference(hip_engine):
     structs = _structures_for_graph_tests()
     for j, (r_atom, r_bond) in enumerate(((6.0, 3.0), (5.0, 3.0), (4.0, 4.0))):
         batch = hip_engine.build_batch(structs, r_atom, r_bond)
-        pb = batch.packed
-        f = lambda name, n: hip_engine.debug_fetch_i32(batch, name, n)  # noqa: E731
-        ec, en, d2u, eo = (f(k, pb.n_directed) for k in ("e_center", "e_nbr", "e_d2u", "e_owner"))
-        img = hip_engine.debug_fetch(batch, "e_image", (pb.n_directed, 3)).astype(np.int64)
-        u2d = f("u_u2d", pb.n_undirected)
-        bn = f("bn_und", pb.n_bnodes)
-        a_ctr, a_b1c, a_b2c, a_d1, a_d2 = (f(k, pb.n_angles) for k in ("a_ctr", "a_b1c", "a_b2c", "a_d1", "a_d2"))
+        per_struct = fetch_device_graph(hip_engine, batch)          # packed indices made local to each structure
         batch.free()
-        a_off = pb.atom_off
-        e_off = np.searchsorted(eo, np.arange(len(structs) + 1))
-        a_owner = np.searchsorted(a_off, a_ctr, side="right") - 1 if pb.n_angles else np.zeros(0, np.int64)
-        u_off = e_off // 2
-        for b, s in enumerate(structs):
-            sl = slice(e_off[b], e_off[b + 1])
-            if e_off[b] == e_off[b + 1]:
+        for b, (s, g) in enumerate(zip(structs, per_struct)):
+            if len(g["center"]) == 0:
                 continue                                               # isolated atoms only: nothing to index
             host = build_graph_arrays(np.asarray(s.frac_coords, np.float64), np.asarray(s.lattice.matrix, np.float64), r_atom, r_bond)
-            assert np.array_equal(host["atom_graph"], np.stack([ec[sl] - a_off[b], en[sl] - a_off[b]], 1)) and np.array_equal(host["image"], img[sl])
+            assert np.array_equal(host["atom_graph"], np.stack([g["center"], g["neighbor"]], 1)) and np.array_equal(host["image"], g["image"])
             ref = fx[f"gpu_{b}_{j}"]
-            fed = {"center": ec[sl] - a_off[b], "neighbor": en[sl] - a_off[b], "image": img[sl], "distance": host["distance"]}
+            fed = {"center": g["center"], "neighbor": g["neighbor"], "image": g["image"], "distance": host["distance"]}
             for key, v in fed.items():                                 # the list the reference was fed
                 assert array_digest(v) == ref[key], (b, key)
-            assert array_digest(d2u[sl] - u_off[b]) == ref["directed2undirected"], (b, "d2u")
-            assert array_digest(u2d[u_off[b]:u_off[b + 1]] - e_off[b]) == ref["undirected2directed"], (b, "u2d")
-            rows = np.flatnonzero(a_owner == b)
-            got_bg = np.stack([a_ctr[rows] - a_off[b], bn[a_b1c[rows]] - u_off[b], a_d1[rows] - e_off[b], bn[a_b2c[rows]] - u_off[b],
-                               a_d2[rows] - e_off[b]], 1) if len(rows) else np.zeros((0, 5), np.int32)
-            assert array_digest(got_bg) == ref["bond_graph"], (b, "bond_graph")
+            assert array_digest(g["directed2undirected"]) == ref["directed2undirected"], (b, "d2u")
+            assert array_digest(g["undirected2directed"]) == ref["undirected2directed"], (b, "u2d")
+            assert array_digest(g["bond_graph"]) == ref["bond_graph"], (b, "bond_graph")
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -207,7 +207,9 @@ def test_cutoff_boundary_rules_known_answer():
     is never the second bond of an angle (a neighbour qualifies only when dist < cutoff).  Atom-graph boundary:
     the neighbour list keeps d < r_atom strictly (host_graph.cpp: d2 < r2); pymatgen's own inequality at
     exactly d == r cannot be pinned offline (pymatgen is not installed) and cannot change E/F/S because the
-    envelope and its derivative vanish at the cutoff (basis.py:197-205)."""
+    envelope and its derivative vanish at the cutoff (basis.py:197-205).  Our own strict ``<`` is pinned by exact integer
+    arithmetic on the tie cases of tests/graph_hard_cases.py (a shell exactly on the cutoff is out: test_neighbor_oracle_cpu.py,
+    test_gpu_graph_oracle.py)."""
     # triangle A(0) B(1) C(2): |AB| = 3.0 (== cutoff), |AC| = 2.0, |BC| = 2.5
     center = [0, 0, 1, 1, 2, 2]
     nbr = [1, 2, 0, 2, 0, 1]
