@@ -27,6 +27,7 @@ EXPORTED_SYMBOLS = (
     "chg_host_alloc", "chg_host_free",
     "chg_relax_create", "chg_relax_run", "chg_relax_download", "chg_relax_free", "chg_test_relax_step",
     "chg_md_create", "chg_md_run", "chg_md_download", "chg_md_free", "chg_test_md_step",
+    "chg_md_create_langevin", "chg_test_md_step_langevin",
     "chg_hessian_vector", "chg_hessian_vector_strain",
 )
 
@@ -210,6 +211,9 @@ def load() -> ctypes.CDLL:
     lib.chg_md_free.argtypes = [vp, vp]
     lib.chg_test_md_step.argtypes = [vp, ctypes.POINTER(MdParams), ctypes.c_int32, c_int_p, ctypes.c_int32, dp, dp, dp, dp, dp, c_int_p,
                                      c_float_p, c_float_p, c_float_p, dp, dp]
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    lib.chg_md_create_langevin.argtypes = [*lib.chg_md_create.argtypes[:5], ctypes.c_double, u64p, ctypes.POINTER(vp)]
+    lib.chg_test_md_step_langevin.argtypes = [*lib.chg_test_md_step.argtypes, ctypes.c_double, u64p]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is ctypes.c_int and name not in ("chg_device_count", "chg_profile_count"):

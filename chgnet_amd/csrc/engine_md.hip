@@ -1,5 +1,6 @@
-// engine_md.hip -- batched molecular dynamics (chg_md_*): NVE, NVT Berendsen, NPT Berendsen (inhomogeneous and isotropic), one
-// independent replica per structure, state in HBM (kernels_md.h).  Reference: MolecularDynamics, chgnet/model/dynamics.py:433-780.
+// engine_md.hip -- batched molecular dynamics (chg_md_*): NVE, NVT Berendsen, NPT Berendsen (inhomogeneous and isotropic), NVT
+// Langevin (BAOAB with counter-based noise, chg_md_create_langevin; not in the reference), one independent replica per structure,
+// state in HBM (kernels_md.h).  Reference: MolecularDynamics, chgnet/model/dynamics.py:433-780.
 //
 // One evaluation of chg_md_run is one evaluate_and_step of the shared driver (engine_stepper.h) on ALL replicas, with k_md_step as
 // the step launch (one workgroup per replica: finish the step, frame, start the next one).  Every replica runs the same number of
@@ -11,11 +12,13 @@
 
 struct chg_md : chgh::Stepper {
   chg_md_params p{};
+  double friction = 0.0;     // MD_NVT_LANGEVIN, inverse ASE time units
   bool started = false;      // the initial configuration has been evaluated (frame of step 0 written)
   int step = 0;              // steps completed (all replicas; a NONFINITE replica stops counting)
   // device: state + per-evaluation buffers
   double *r, *pm, *f, *m, *sd;
   int *si, *d_aoff;
+  unsigned long long* seeds = nullptr;   // [B] noise keys (MD_NVT_LANGEVIN)
   // frame ring: K slots
   int K = 0, ring_head = 0, ring_count = 0;
   std::vector<int> ring_step;
@@ -37,6 +40,7 @@ void carve_md(chg_md* d, Carver& c) {
   d->frac_next = c.take<double>(3 * N);
   d->lat_next = c.take<double>(9 * B);
   d->si = c.take<int>(MD_SI * B);
+  d->seeds = c.take<unsigned long long>(d->p.ensemble == MD_NVT_LANGEVIN ? B : 0);
   d->d_aoff = c.take<int>(B + 1);
   d->d_sel = c.take<int>(B);
   d->retry = c.take<int>(B);
@@ -51,10 +55,18 @@ void carve_md(chg_md* d, Carver& c) {
 
 bool is_npt(int e) { return e == MD_NPT_BERENDSEN_INHOMOGENEOUS || e == MD_NPT_BERENDSEN; }
 
-const char* bad_params(const chg_md_params* p) {
-  if (p->ensemble < MD_NVE || p->ensemble > MD_NPT_BERENDSEN) return "unknown ensemble";
+// langevin: the caller is an entry point that carries friction and seeds (the only ones that may run MD_NVT_LANGEVIN)
+const char* bad_params(const chg_md_params* p, bool langevin = false, double friction = 0.0) {
+  if (langevin) {
+    if (p->ensemble != MD_NVT_LANGEVIN) return "ensemble must be CHG_MD_NVT_LANGEVIN";
+    if (!(friction >= 0.0) || !std::isfinite(friction)) return "friction must be >= 0 and finite";
+    if (!(p->temperature >= 0.0) || !std::isfinite(p->temperature)) return "temperature must be >= 0";
+  } else if (p->ensemble == MD_NVT_LANGEVIN) {
+    return "CHG_MD_NVT_LANGEVIN needs friction and seeds: use chg_md_create_langevin";
+  }
+  if (p->ensemble < MD_NVE || p->ensemble > MD_NVT_LANGEVIN) return "unknown ensemble";
   if (!(p->dt > 0.0) || !std::isfinite(p->dt)) return "dt must be > 0";
-  if (p->ensemble != MD_NVE && (!(p->taut > 0.0) || !(p->temperature >= 0.0))) return "taut must be > 0 and temperature >= 0";
+  if (!langevin && p->ensemble != MD_NVE && (!(p->taut > 0.0) || !(p->temperature >= 0.0))) return "taut must be > 0 and temperature >= 0";
   if (is_npt(p->ensemble) && (!(p->taup > 0.0) || !(p->compressibility > 0.0) || !std::isfinite(p->pressure)))
     return "taup and compressibility must be > 0 and pressure finite";
   if (p->loginterval < 0 || p->ring_frames < 0) return "loginterval and ring_frames must be >= 0";
@@ -72,6 +84,11 @@ chg::MdStepArgs base_args(chg_md* d) {
   a.compressibility = p.compressibility; a.kB = p.kB > 0.0 ? p.kB : 8.6173303e-5;
   a.stress_weight = p.stress_weight > 0.0 ? p.stress_weight : 1.0 / 160.21766208;
   a.ensemble = p.ensemble; a.fixcm = p.ensemble != MD_NVE && p.fixcm; a.fea_dim = FEA;
+  if (p.ensemble == MD_NVT_LANGEVIN) {
+    a.lg_c1 = std::exp(-d->friction * p.dt);
+    a.lg_sig = std::sqrt((1.0 - a.lg_c1 * a.lg_c1) * a.kB * p.temperature);
+    a.seeds = d->seeds;
+  }
   return a;
 }
 
@@ -107,23 +124,20 @@ void set_frame(chg_md* d, MdStepArgs& a, int step) {
 
 bool frame_due(const chg_md* d, int step) { return d->p.loginterval > 0 && step % d->p.loginterval == 0; }
 
-}  // namespace
-
-extern "C" {
-
-int chg_md_create(chg_engine* eng, const chg_structs_host* h, const double* masses, const double* momenta, const chg_md_params* params,
-                  chg_md** out) {
+// chg_md_create (seeds null) and chg_md_create_langevin
+int create(chg_engine* eng, const char* fn, const chg_structs_host* h, const double* masses, const double* momenta, const chg_md_params* params,
+           double friction, const uint64_t* seeds, chg_md** out) {
   if (!eng || !h || !masses || !params || !out) return CHG_EINVAL;
   *out = nullptr;
-  const char* fn = "chg_md_create";
-  if (const char* bad = bad_params(params)) { eng->err = std::string(fn) + ": " + bad; return CHG_EINVAL; }
+  if (const char* bad = bad_params(params, seeds != nullptr, friction)) { eng->err = std::string(fn) + ": " + bad; return CHG_EINVAL; }
   TRY(check_structs(eng, fn, h));
   const int B = h->n_struct, N = h->n_atoms;
   for (int i = 0; i < N; ++i)
-    if (!(masses[i] > 0.0)) { eng->err = "chg_md_create: masses must be > 0"; return CHG_EINVAL; }
+    if (!(masses[i] > 0.0)) { eng->err = std::string(fn) + ": masses must be > 0"; return CHG_EINVAL; }
   HIP_TRY(eng, hipSetDevice(eng->device));
   chg_md* d = new chg_md();
   d->p = *params;
+  d->friction = friction;
   d->K = params->loginterval > 0 ? params->ring_frames : 0;
   d->ring_step.assign(std::max(d->K, 1), 0);
   d->task = CHG_TASK_E | CHG_TASK_F | ((is_npt(params->ensemble) || params->log_stress) ? CHG_TASK_S : 0u);
@@ -139,6 +153,7 @@ int chg_md_create(chg_engine* eng, const chg_structs_host* h, const double* mass
   up(d->m, masses, sizeof(double) * N);
   up(d->sd, sd.data(), sizeof(double) * sd.size());
   up(d->si, si.data(), sizeof(int) * si.size());
+  if (seeds) up(d->seeds, seeds, sizeof(uint64_t) * B);
   up(d->d_aoff, h->atom_off, sizeof(int) * (B + 1));
   up(d->frac_next, h->frac, sizeof(double) * 3 * N);
   up(d->lat_next, h->lattice, sizeof(double) * 9 * B);
@@ -148,6 +163,21 @@ int chg_md_create(chg_engine* eng, const chg_structs_host* h, const double* mass
   if ((s = up.finish()) != CHG_OK) { chg_md_free(eng, d); return s; }
   *out = d;
   return CHG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int chg_md_create(chg_engine* eng, const chg_structs_host* h, const double* masses, const double* momenta, const chg_md_params* params,
+                  chg_md** out) {
+  return create(eng, "chg_md_create", h, masses, momenta, params, 0.0, nullptr, out);
+}
+
+int chg_md_create_langevin(chg_engine* eng, const chg_structs_host* h, const double* masses, const double* momenta,
+                           const chg_md_params* params, double friction, const uint64_t* seeds, chg_md** out) {
+  if (!seeds) return CHG_EINVAL;
+  return create(eng, "chg_md_create_langevin", h, masses, momenta, params, friction, seeds, out);
 }
 
 int chg_md_run(chg_engine* eng, chg_md* d, int32_t n_steps) {
@@ -235,14 +265,19 @@ int chg_md_free(chg_engine* eng, chg_md* d) {
   return CHG_OK;
 }
 
-int chg_test_md_step(chg_engine* eng, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
-                     double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy, const float* force,
-                     const float* stress, double* frac_next, double* lat_next) {
+}  // extern "C"
+
+namespace {
+
+// chg_test_md_step (seeds null) and chg_test_md_step_langevin
+int test_step(chg_engine* eng, const char* fn, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
+              double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy, const float* force,
+              const float* stress, double* frac_next, double* lat_next, double friction, const uint64_t* seeds) {
   if (!eng || !params || n_struct <= 0 || !atom_off || !r || !momenta || !forces || !masses || !sd || !si || !frac_next || !lat_next)
     return CHG_EINVAL;
   if ((flags & MD_ABSORB) && (!energy || !force)) return CHG_EINVAL;
   if (flags & ~(MD_ABSORB | MD_KICK2 | MD_START)) return CHG_EINVAL;
-  if (const char* bad = bad_params(params)) { eng->err = std::string("chg_test_md_step: ") + bad; return CHG_EINVAL; }
+  if (const char* bad = bad_params(params, seeds != nullptr, friction)) { eng->err = std::string(fn) + ": " + bad; return CHG_EINVAL; }
   const size_t B = n_struct, N = atom_off[n_struct];
   if (atom_off[0] != 0) return CHG_EINVAL;
   for (size_t o = 0; o < B; ++o)
@@ -251,10 +286,13 @@ int chg_test_md_step(chg_engine* eng, const chg_md_params* params, int32_t n_str
                     {masses, nullptr, sizeof(double) * N}, {sd, sd, sizeof(double) * MD_SD * B}, {si, si, sizeof(int) * MD_SI * B},
                     {atom_off, nullptr, sizeof(int) * (B + 1)}, {energy, nullptr, sizeof(float) * B}, {force, nullptr, sizeof(float) * 3 * N},
                     {stress, nullptr, sizeof(float) * 9 * B}, {frac_next, frac_next, sizeof(double) * 3 * N},
-                    {lat_next, lat_next, sizeof(double) * 9 * B}, {nullptr, nullptr, sizeof(int) * B}};
-  return run_test_step(eng, "chg_test_md_step", bufs, [&] {
+                    {lat_next, lat_next, sizeof(double) * 9 * B}, {nullptr, nullptr, sizeof(int) * B},
+                    {seeds, nullptr, sizeof(uint64_t) * B}};
+  return run_test_step(eng, fn, bufs, [&] {
     chg_md tmp;
     tmp.p = *params;
+    tmp.friction = friction;
+    tmp.seeds = (unsigned long long*)bufs[13].d;
     MdStepArgs a = base_args(&tmp);
     a.r = (double*)bufs[0].d; a.p = (double*)bufs[1].d; a.f = (double*)bufs[2].d; a.m = (const double*)bufs[3].d;
     a.sd = (double*)bufs[4].d; a.si = (int*)bufs[5].d; a.aoff = (const int*)bufs[6].d;
@@ -265,6 +303,26 @@ int chg_test_md_step(chg_engine* eng, const chg_md_params* params, int32_t n_str
     a.final_try = 1;
     launch_step(eng, a, (int)B);
   });
+}
+
+}  // namespace
+
+extern "C" {
+
+int chg_test_md_step(chg_engine* eng, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
+                     double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy, const float* force,
+                     const float* stress, double* frac_next, double* lat_next) {
+  return test_step(eng, "chg_test_md_step", params, n_struct, atom_off, flags, r, momenta, forces, masses, sd, si, energy, force, stress,
+                   frac_next, lat_next, 0.0, nullptr);
+}
+
+int chg_test_md_step_langevin(chg_engine* eng, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
+                              double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy,
+                              const float* force, const float* stress, double* frac_next, double* lat_next, double friction,
+                              const uint64_t* seeds) {
+  if (!seeds) return CHG_EINVAL;
+  return test_step(eng, "chg_test_md_step_langevin", params, n_struct, atom_off, flags, r, momenta, forces, masses, sd, si, energy, force,
+                   stress, frac_next, lat_next, friction, seeds);
 }
 
 }  // extern "C"

@@ -14,16 +14,20 @@
 //              the atoms): first half kick with these forces, fixcm, drift.
 //   MD_START   start the next step from the cached forces: thermostat lambda, then NPT: barostat scaling, write the scaled
 //              configuration and go to phase 1; NVE / NVT: first half kick, fixcm, drift.
+//              MD_NVT_LANGEVIN (no reference counterpart; BAOAB, Leimkuhler & Matthews 2013): half kick, half drift, the
+//              Ornstein-Uhlenbeck step p <- c1 p + sqrt((1 - c1^2) m kB T) xi with counter-based noise (philox.h), mass-weighted
+//              fixcm, half drift.  tests/langevin_ref.py restates it.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include "mat3.h"   // mm3, det3, inv3, wave_sum_f64
+#include "philox.h"
 
 namespace chg {
 
 enum : int { MD_RUNNING = 0, MD_NONFINITE = 1 };
-enum : int { MD_NVE = 0, MD_NVT_BERENDSEN = 1, MD_NPT_BERENDSEN_INHOMOGENEOUS = 2, MD_NPT_BERENDSEN = 3 };
+enum : int { MD_NVE = 0, MD_NVT_BERENDSEN = 1, MD_NPT_BERENDSEN_INHOMOGENEOUS = 2, MD_NPT_BERENDSEN = 3, MD_NVT_LANGEVIN = 4 };
 enum : int { MD_ABSORB = 1, MD_KICK2 = 2, MD_START = 4 };
 constexpr int MD_SD = 40;   // doubles per replica: L[9] L^-1[9] Epot Ekin T stress[9] (eV/A^3, no ideal gas) G[9] (sum p p / m) spare
 constexpr int MD_SI = 4;    // ints per replica: steps completed, status, phase, spare
@@ -53,6 +57,9 @@ struct MdStepArgs {
   int* retry;             // [B] set to 1 (state untouched) when the evaluation is non-finite and final_try == 0
   double dt, temperature, taut, taup, pressure, compressibility, kB, stress_weight;
   int ensemble, fixcm, flags, final_try, fea_dim;
+  // MD_NVT_LANGEVIN: c1 = exp(-friction dt), sig = sqrt((1 - c1^2) kB T), one noise key per replica
+  double lg_c1, lg_sig;
+  const unsigned long long* seeds;   // [B]
 };
 
 static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
@@ -71,7 +78,7 @@ static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
   __shared__ double red[4][9];
   __shared__ int rfin[4];
   __shared__ double sLinv[9], sM[9], s_lam, s_mean[3];
-  __shared__ int s_status, s_phase, s_go;
+  __shared__ int s_status, s_phase, s_go, s_steps;
 
   if (tid == 0) { s_status = si[1]; s_phase = si[2]; }
   __syncthreads();
@@ -165,6 +172,62 @@ static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
         }
       }
     }
+  }
+
+  if ((a.flags & MD_START) && a.ensemble == MD_NVT_LANGEVIN) {
+    // BAOAB up to the evaluation: B A O A.  The noise counter is the number of steps this replica has completed (thread 0 has
+    // just counted the step that MD_KICK2 finished)
+    __syncthreads();
+    if (tid == 0) {
+      s_steps = si[0];
+      for (int i = 0; i < 9; ++i) { sLinv[i] = sd[9 + i]; a.lat_next[9 * (size_t)o + i] = sd[i]; }
+    }
+    __syncthreads();
+    const unsigned long long seed = a.seeds[o];
+    const unsigned step = (unsigned)s_steps;
+    const bool noisy = a.lg_sig > 0.0;
+    double ps[4] = {0.0, 0.0, 0.0, 0.0};   // sum p, sum m
+    for (int i = tid; i < n; i += 256) {
+      const double mi = m[i];
+      double xi[3] = {0.0, 0.0, 0.0};
+      if (noisy) philox_normal3(seed, (unsigned)i, step, xi);
+      const double sg = a.lg_sig * sqrt(mi);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        double pj = p[3 * i + j] + hdt * f[3 * i + j];
+        r[3 * i + j] += hdt * pj / mi;
+        pj = a.lg_c1 * pj + sg * xi[j];
+        p[3 * i + j] = pj;
+        ps[j] += pj;
+      }
+      ps[3] += mi;
+    }
+    if (a.fixcm) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ps[j] = wave_sum_f64(ps[j]);
+      if (lane == 0)
+        for (int j = 0; j < 4; ++j) red[wv][j] = ps[j];
+      __syncthreads();
+      if (tid == 0) {
+        const double im = 1.0 / (red[0][3] + red[1][3] + red[2][3] + red[3][3]);
+        for (int j = 0; j < 3; ++j) s_mean[j] = (red[0][j] + red[1][j] + red[2][j] + red[3][j]) * im;   // centre-of-mass velocity
+      }
+      __syncthreads();
+    }
+    for (int i = tid; i < n; i += 256) {
+      const double mi = m[i];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const double pj = a.fixcm ? p[3 * i + j] - mi * s_mean[j] : p[3 * i + j];
+        p[3 * i + j] = pj;
+        r[3 * i + j] += hdt * pj / mi;
+      }
+      const double y0 = r[3 * i], y1 = r[3 * i + 1], y2 = r[3 * i + 2];
+      double* fr = a.frac_next + 3 * ((size_t)a0 + i);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) fr[j] = y0 * sLinv[j] + y1 * sLinv[3 + j] + y2 * sLinv[6 + j];
+    }
+    return;
   }
 
   if ((a.flags & MD_START) && !advance) {

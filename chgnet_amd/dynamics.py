@@ -7,6 +7,16 @@ masses, cell) stays in HBM, and one step kernel (csrc/kernels_md.h) advances all
 prediction.  ``run_batch`` runs replicas of different sizes as one handle; each gets the trajectory it would get alone.
 tests/md_ref.py restates the semantics in float64 NumPy.
 
+Beyond the reference: ``ensemble="nvt", thermostat="Langevin"`` samples the canonical ensemble (Berendsen rescaling gives the right
+mean temperature and the wrong fluctuations).  The integrator is BAOAB (half kick, half drift, p <- c1 p + sqrt((1 - c1^2) m kB T) xi
+with c1 = exp(-friction dt), half drift, evaluation, half kick): one evaluation per step, fixed cell, ``friction`` in 1/fs.  The
+noise is generated in the step kernel (csrc/philox.h, Philox4x32-10 + Box-Muller) as a pure function of (``thermostat_seed``, atom
+index, steps completed in the device handle): nothing random is stored, so ``run(10); run(10)`` equals ``run(20)`` and a replica of
+``run_batch`` gets the trajectory it would get alone.  ``set_atoms`` opens a new handle and so restarts the stream from step 0.  The
+centre-of-mass momentum is removed after every noise step (mass-weighted, 3 degrees of freedom), while the reported temperature
+stays ``T = 2 Ekin / (3 n kB)`` as for the other ensembles: it equilibrates at ``temperature * (n - 1) / n``.
+tests/langevin_ref.py restates integrator and noise.
+
 Out of scope, refused with ``ValueError``: the Nose-Hoover thermostat (ASE ``NPT``), and NPT without ``bulk_modulus`` (the
 reference then fits an equation of state).  Deviations from the reference:
   - ``starting_temperature`` draws from a seeded numpy ``Generator`` (``seed``), not ASE's global RNG: same distribution,
@@ -35,8 +45,9 @@ FS = 1e-15 * (1e10 * np.sqrt(_E / _AMU))   # units.fs = 1e-15 * second
 KB = _KB_J / _E                             # units.kB, eV/K
 GPA = 1e9 * ((1 / _E) / 1e30)               # units.GPa = 1e9 * Pascal, eV/A^3
 
-ENSEMBLE_CODES = {"nve": 0, "nvt": 1, "npt_inhomogeneous": 2, "npt_berendsen": 3}
+ENSEMBLE_CODES = {"nve": 0, "nvt": 1, "npt_inhomogeneous": 2, "npt_berendsen": 3, "nvt_langevin": 4}
 STATUS_NAMES = ("RUNNING", "NONFINITE")
+_U64 = (1 << 64) - 1
 
 # ase.data.atomic_masses (IUPAC 2016 standard atomic weights), Z = 0..94
 ATOMIC_MASSES = np.array([
@@ -131,7 +142,11 @@ def _resolve(ensemble: str, thermostat: str, bulk_modulus) -> str:
     if ens == "nvt":
         if th.startswith("berendsen"):
             return "nvt"
+        if th == "langevin":
+            return "nvt_langevin"
         raise ValueError("Thermostat not supported, choose in 'Nose-Hoover', 'Berendsen', 'Berendsen_inhomogeneous'")
+    if th == "langevin":
+        raise ValueError("Thermostat not supported for NPT: 'Langevin' keeps the cell fixed (ensemble='nvt')")
     if bulk_modulus is None:
         raise ValueError("NPT without bulk_modulus is not supported by the device MD (the reference fits an equation of state "
                          "there); pass bulk_modulus in GPa")
@@ -147,7 +162,8 @@ class _DeviceRun:
 
     RING = 32
 
-    def __init__(self, calc: CHGNetCalculator, structures: list, masses: np.ndarray, momenta: np.ndarray, kind: str, cfg: dict) -> None:
+    def __init__(self, calc: CHGNetCalculator, structures: list, masses: np.ndarray, momenta: np.ndarray, kind: str, cfg: dict,
+                 seeds=None) -> None:
         model = calc.model
         self.eng, self.model, self.calc = model.engine, model, calc
         conv = model.graph_converter
@@ -167,8 +183,16 @@ class _DeviceRun:
         dp = ctypes.POINTER(ctypes.c_double)
         host = prep.host()
         self.handle = ctypes.c_void_p()
-        self.eng._check(self.eng.lib.chg_md_create(self.eng.handle, ctypes.byref(host), self.masses.ctypes.data_as(dp), mom.ctypes.data_as(dp),
-                                                   ctypes.byref(params), ctypes.byref(self.handle)))
+        if kind == "nvt_langevin":       # friction and one noise key per replica travel beside the params struct
+            keys = np.array([int(k) & _U64 for k in seeds], np.uint64)
+            if len(keys) != self.B:
+                raise ValueError("one thermostat seed per structure")
+            self.eng._check(self.eng.lib.chg_md_create_langevin(
+                self.eng.handle, ctypes.byref(host), self.masses.ctypes.data_as(dp), mom.ctypes.data_as(dp), ctypes.byref(params),
+                cfg["friction"], keys.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(self.handle)))
+        else:
+            self.eng._check(self.eng.lib.chg_md_create(self.eng.handle, ctypes.byref(host), self.masses.ctypes.data_as(dp),
+                                                       mom.ctypes.data_as(dp), ctypes.byref(params), ctypes.byref(self.handle)))
         self.started = False
         self.step = 0
 
@@ -207,16 +231,26 @@ class _DeviceRun:
 
 
 class MolecularDynamics:
-    """Molecular dynamics on the device (reference MolecularDynamics: same arguments and defaults, plus ``seed``)."""
+    """Molecular dynamics on the device (reference MolecularDynamics: same arguments and defaults, plus ``seed``, and
+    ``thermostat="Langevin"`` with ``friction`` in 1/fs for NVT, see the module docstring)."""
 
     def __init__(self, atoms, *, model=None, ensemble: str = "nvt", thermostat: str = "Berendsen_inhomogeneous", temperature: float = 300,
                  starting_temperature: float | None = None, timestep: float = 2.0, pressure: float = 1.01325e-4, taut: float | None = None,
                  taup: float | None = None, bulk_modulus: float | None = None, trajectory: str | None = None, logfile: str | None = None,
                  loginterval: int = 1, crystal_feas_logfile: str | None = None, append_trajectory: bool = False,  # noqa: ARG002
                  on_isolated_atoms: str = "warn", return_site_energies: bool = False, use_device: str | None = None,
-                 seed: int | None = None) -> None:
+                 seed: int | None = None, friction: float | None = None) -> None:
         self.ensemble, self.thermostat = ensemble, thermostat
         self.kind = _resolve(ensemble, thermostat, bulk_modulus)
+        langevin = self.kind == "nvt_langevin"
+        if friction is not None and not langevin:
+            raise ValueError(f"{friction=} belongs to ensemble='nvt', thermostat='Langevin'")
+        friction = 0.01 if friction is None else float(friction)
+        if langevin and not (np.isfinite(friction) and friction >= 0):
+            raise ValueError(f"{friction=} must be >= 0 and finite (1/fs)")
+        self.friction = friction if langevin else None
+        # the key of the thermostat's noise stream: the given seed, else 64 fresh bits
+        self.thermostat_seed = None if not langevin else (int(np.random.SeedSequence().entropy) if seed is None else int(seed)) & _U64
         if int(loginterval) < 1:
             raise ValueError(f"{loginterval=} must be positive")
         if not timestep > 0:
@@ -232,7 +266,7 @@ class MolecularDynamics:
         compressibility = 0.0 if bulk_modulus is None else 1.0 / (bulk_modulus / 160.2176)
         self.cfg = {"dt": timestep * FS, "temperature": float(temperature), "taut": taut * FS, "taup": taup * FS, "pressure": pressure * GPA,
                     "compressibility": compressibility, "loginterval": int(loginterval), "crystal_fea": crystal_feas_logfile is not None,
-                    "log_stress": False}
+                    "log_stress": False, "friction": friction / FS}
         self.trajectory, self.logfile, self.loginterval, self.timestep = trajectory, logfile, int(loginterval), timestep
         self.crystal_feas_logfile = crystal_feas_logfile
         self.starting_temperature, self.seed = starting_temperature, seed
@@ -330,7 +364,8 @@ class MolecularDynamics:
             raise ValueError(f"{steps=} must be >= 0")
         if self._run is None:
             report_isolated_atoms(self.calculator.model, [self._structure])
-            self._run = _DeviceRun(self.calculator, [self._structure], self._masses, self._momenta, self.kind, self.cfg)
+            self._run = _DeviceRun(self.calculator, [self._structure], self._masses, self._momenta, self.kind, self.cfg,
+                                   seeds=[self.thermostat_seed])
             if self.logfile is not None and self._logger is None:
                 self._logger = MDLogger(self.logfile, len(self._structure))
         run = self._run
@@ -358,7 +393,8 @@ class MolecularDynamics:
     @classmethod
     def run_batch(cls, structures, steps: int, *, seeds=None, model=None, **kwargs) -> list[dict]:
         """Run R independent replicas (possibly of different sizes) as one device handle: each gets the trajectory it would get
-        alone with ``MolecularDynamics(structures[i], seed=seeds[i], **kwargs).run(steps)``.  Returns, per replica, ``{"trajectory",
+        alone with ``MolecularDynamics(structures[i], seed=seeds[i], **kwargs).run(steps)`` (with the Langevin thermostat ``seeds[i]`` is
+        also replica i's noise key; ``seeds=None`` draws one per replica).  Returns, per replica, ``{"trajectory",
         "final_structure", "momenta", "status", "n_steps"}``.  ``trajectory`` / ``logfile`` / ``crystal_feas_logfile`` are not
         written here."""
         structures = list(structures)
@@ -378,7 +414,7 @@ class MolecularDynamics:
         structs = [m._structure for m in md]
         report_isolated_atoms(first.calculator.model, structs)
         run = _DeviceRun(first.calculator, structs, np.concatenate([m._masses for m in md]), np.concatenate([m._momenta for m in md]),
-                         first.kind, first.cfg)
+                         first.kind, first.cfg, seeds=[m.thermostat_seed for m in md])
         try:
             trajs = [m.traj for m in md]
             sink, _ = first._sinks(run, trajs, [m._cfeas for m in md], 0)

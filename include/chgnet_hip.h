@@ -108,7 +108,8 @@ typedef struct chg_out_host {
 
 /* Version of this interface: bumped whenever a struct of this header grows or an entry point changes meaning (chg_model_desc gained
  * n_mlp_hidden / mlp_out_bias at 2; chg_batch_build_predict arrived at 3; the chg_relax_* entry points at 4; the chg_md_* entry points at 5;
- * chg_hessian_vector and chg_hessian_vector_strain were added at 5 without a bump: new entry points only, no struct or signature changed).  A binding compiled against another value must refuse the
+ * chg_hessian_vector and chg_hessian_vector_strain were added at 5 without a bump: new entry points only, no struct or signature changed;
+ * so were chg_md_create_langevin and chg_test_md_step_langevin, whose extra parameters travel as arguments, not in chg_md_params).  A binding compiled against another value must refuse the
  * library: chg_engine_create COPIES *desc, so an older, shorter chg_model_desc would be read past its end. */
 #define CHG_ABI_VERSION 5
 int chg_abi_version(void);
@@ -303,7 +304,8 @@ int chg_test_relax_step(chg_engine* eng, const chg_relax_params* params, int32_t
  * task ef, efs for NPT or logged stress) + one step kernel (csrc/kernels_md.h) + one asynchronous copy of the next coordinates.  NPT
  * takes two evaluations per step, as ASE does (the barostat moves the atoms before the first half kick).  Units are ASE's: eV, A,
  * amu, time in A sqrt(amu / eV).  DESIGN.md "Molecular dynamics" states the semantics; tests/md_ref.py restates them in NumPy. */
-enum { CHG_MD_NVE = 0, CHG_MD_NVT_BERENDSEN = 1, CHG_MD_NPT_BERENDSEN_INHOMOGENEOUS = 2, CHG_MD_NPT_BERENDSEN = 3 };
+enum { CHG_MD_NVE = 0, CHG_MD_NVT_BERENDSEN = 1, CHG_MD_NPT_BERENDSEN_INHOMOGENEOUS = 2, CHG_MD_NPT_BERENDSEN = 3,
+       CHG_MD_NVT_LANGEVIN = 4 /* chg_md_create_langevin only */ };
 enum { CHG_MD_RUNNING = 0, CHG_MD_NONFINITE = 1 };
 typedef struct chg_md_params {
   int32_t ensemble;            /* CHG_MD_*                                                                                 */
@@ -344,6 +346,18 @@ typedef struct chg_md_out_host {
  * cannot be allocated. */
 int chg_md_create(chg_engine* eng, const chg_structs_host* host, const double* masses, const double* momenta, const chg_md_params* params,
                   chg_md** out);
+/* NVT Langevin (not in the reference): BAOAB, one evaluation per step, fixed cell.  Per step with c1 = exp(-friction dt):
+ *   p += dt/2 f;  r += dt/2 p/m;  p <- c1 p + sqrt((1 - c1^2) m kB T) xi;  fixcm: p_i -= m_i sum p / sum m;  r += dt/2 p/m;
+ *   evaluation;  p += dt/2 f.
+ * xi (three standard normals per atom) is a pure function of (seeds[replica], atom index within the replica, steps the replica has
+ * completed): Philox4x32-10 and Box-Muller in the step kernel (csrc/philox.h), no generator state in memory, so a replica's
+ * trajectory does not depend on its slot in the batch, on retries or on how chg_md_run calls split the steps.
+ * params->ensemble must be CHG_MD_NVT_LANGEVIN (chg_md_create refuses it with CHG_EINVAL: it has no friction or seeds to give);
+ * friction >= 0 and finite, in inverse ASE time units (0: velocity Verlet); temperature >= 0; taut, taup, pressure and compressibility
+ * are ignored; seeds [B] are copied.  The handle is an ordinary chg_md for chg_md_run / chg_md_download / chg_md_free.
+ * tests/langevin_ref.py restates integrator and noise in NumPy. */
+int chg_md_create_langevin(chg_engine* eng, const chg_structs_host* host, const double* masses, const double* momenta,
+                           const chg_md_params* params, double friction, const uint64_t* seeds, chg_md** out);
 /* n_steps steps of every replica (the first call evaluates the initial configuration first and writes the frame of step 0).  A batch
  * whose results are non-finite is evaluated again on the wide-range sweep; a replica that is non-finite even there stops as
  * CHG_MD_NONFINITE with its state untouched.  CHG_EINVAL (nothing run) when the frames due do not fit the ring. */
@@ -357,6 +371,11 @@ int chg_md_free(chg_engine* eng, chg_md* md);
 int chg_test_md_step(chg_engine* eng, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
                      double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy, const float* force,
                      const float* stress, double* frac_next, double* lat_next);
+/* The same for CHG_MD_NVT_LANGEVIN: friction and seeds [n_struct] as in chg_md_create_langevin; the noise counter is si[0]. */
+int chg_test_md_step_langevin(chg_engine* eng, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
+                              double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy,
+                              const float* force, const float* stress, double* frac_next, double* lat_next, double friction,
+                              const uint64_t* seeds);
 
 /* ---- exchange steps of the multi-GPU path, straight on RCCL (one communicator per process = per GPU) ----------
  * The reference is single-device; these carry what SURVEY 8e needs and nothing else: the all-gather of per-structure

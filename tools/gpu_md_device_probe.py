@@ -3,6 +3,8 @@ of R = 1, 8, 64 replicas of the 256-atom 2x2x2 Li9Co7O16 cell, NVT Berendsen at 
 (chgnet_amd/md.py) through CHGNetCalculator on the same machine.  One JSON line per leg, appended to --out.
 
   --leg device --replicas R   one chg_md handle over R replicas (wall clock of run_batch: create, steps, download)
+      --thermostat langevin   the same leg with the Langevin thermostat (BAOAB, 0.01 / fs, noise generated in the step kernel)
+      --repeats K             K timed runs in one process, one JSON line each (their spread is the run-to-run noise)
   --leg host                  one replica, BerendsenNVT + CHGNetCalculator.calculate per step
 
 Weights: the trained-like golden set (tests/golden/weights_trained_like.npz).  Run every leg under its own time limit.
@@ -36,6 +38,8 @@ def main() -> None:
     ap.add_argument("--leg", choices=("device", "host"), required=True)
     ap.add_argument("--replicas", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--thermostat", choices=("berendsen", "langevin"), default="berendsen")
+    ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "md_device_probe.jsonl"))
     args = ap.parse_args()
 
@@ -44,20 +48,25 @@ def main() -> None:
     W = dict(np.load(os.path.join(REPO, "tests", "golden", "weights_trained_like.npz")))
     lco = np.load(os.path.join(REPO, "tests", "golden", "case_li9co7o16.npz"))
     calc = CHGNetCalculator(model=CHGNet(state_dict=W))
-    out = {"leg": args.leg, "ensemble": "nvt", "atoms_each": 256, "steps": args.steps, "timestep_fs": 2.0}
+    out = {"leg": args.leg, "ensemble": "nvt", "thermostat": args.thermostat, "atoms_each": 256, "steps": args.steps, "timestep_fs": 2.0}
+    lines = []
     if args.leg == "device":
         from chgnet_amd.dynamics import MolecularDynamics
 
         R = args.replicas
         cells = [_cell(lco, 100 + i) for i in range(R)]
         kw = dict(model=calc, ensemble="nvt", temperature=300.0, starting_temperature=300.0, timestep=2.0, loginterval=args.steps)
+        if args.thermostat == "langevin":
+            kw.update(thermostat="Langevin", friction=0.01)
         MolecularDynamics.run_batch(cells, 5, seeds=list(range(R)), **kw)          # warm-up: engine creation, first builds
-        t0 = time.perf_counter()
-        res = MolecularDynamics.run_batch(cells, args.steps, seeds=list(range(R)), **kw)
-        wall = time.perf_counter() - t0
-        out.update(replicas=R, wall_s=wall, replica_steps_per_s=R * args.steps / wall, steps_per_s=args.steps / wall,
-                   nonfinite=int(sum(r["status"] != "RUNNING" for r in res)),
-                   final_T_mean=float(np.mean([r["trajectory"].temperatures[-1] for r in res])))
+        for rep in range(args.repeats):
+            t0 = time.perf_counter()
+            res = MolecularDynamics.run_batch(cells, args.steps, seeds=list(range(R)), **kw)
+            wall = time.perf_counter() - t0
+            out.update(replicas=R, repeat=rep, wall_s=wall, replica_steps_per_s=R * args.steps / wall, steps_per_s=args.steps / wall,
+                       nonfinite=int(sum(r["status"] != "RUNNING" for r in res)),
+                       final_T_mean=float(np.mean([r["trajectory"].temperatures[-1] for r in res])))
+            lines.append(json.dumps(out))
     else:
         from chgnet_amd.md import BerendsenNVT
 
@@ -65,10 +74,10 @@ def main() -> None:
         md.run(5)
         r = md.run(args.steps)
         out.update(replicas=1, wall_s=r["wall_s"], replica_steps_per_s=r["steps_per_s"], steps_per_s=r["steps_per_s"])
-    line = json.dumps(out)
-    print(line, flush=True)
+        lines.append(json.dumps(out))
+    print("\n".join(lines), flush=True)
     with open(args.out, "a") as fh:
-        fh.write(line + "\n")
+        fh.write("\n".join(lines) + "\n")
 
 
 if __name__ == "__main__":
