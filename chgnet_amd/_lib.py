@@ -26,6 +26,7 @@ EXPORTED_SYMBOLS = (
     "chg_backward_allreduce", "chg_batch_all_gather_energy", "chg_engine_stream", "chg_engine_device",
     "chg_host_alloc", "chg_host_free",
     "chg_relax_create", "chg_relax_run", "chg_relax_download", "chg_relax_free", "chg_test_relax_step",
+    "chg_relax_create_lbfgs", "chg_test_lbfgs_step",
     "chg_md_create", "chg_md_run", "chg_md_download", "chg_md_free", "chg_test_md_step",
     "chg_md_create_langevin", "chg_test_md_step_langevin",
     "chg_hessian_vector", "chg_hessian_vector_strain",
@@ -68,6 +69,11 @@ class RelaxParams(ctypes.Structure):
                 ("fdec", ctypes.c_double), ("astart", ctypes.c_double), ("fa", ctypes.c_double), ("nmin", ctypes.c_int32),
                 ("exp_cell_factor", ctypes.c_double), ("r_atom", ctypes.c_double), ("r_bond", ctypes.c_double),
                 ("numerical_tol", ctypes.c_double), ("stress_weight", ctypes.c_double)]
+
+
+class LbfgsParams(ctypes.Structure):
+    _fields_ = [("maxstep", ctypes.c_double), ("damping", ctypes.c_double), ("alpha", ctypes.c_double), ("memory", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
 
 
 class RelaxOutHost(ctypes.Structure):
@@ -205,6 +211,10 @@ def load() -> ctypes.CDLL:
     lib.chg_relax_free.argtypes = [vp, vp]
     lib.chg_test_relax_step.argtypes = [vp, ctypes.POINTER(RelaxParams), ctypes.c_int32, c_int_p, dp, dp, dp, c_int_p, c_float_p, c_float_p,
                                         c_float_p, c_float_p, dp, dp]
+    lib.chg_relax_create_lbfgs.argtypes = [vp, ctypes.POINTER(StructsHost), ctypes.POINTER(RelaxParams), ctypes.POINTER(LbfgsParams),
+                                           ctypes.POINTER(vp)]
+    lib.chg_test_lbfgs_step.argtypes = [vp, ctypes.POINTER(RelaxParams), ctypes.POINTER(LbfgsParams), ctypes.c_int32, c_int_p, dp, dp, dp, dp, dp,
+                                        dp, dp, c_int_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, dp, dp, c_int_p]
     lib.chg_md_create.argtypes = [vp, ctypes.POINTER(StructsHost), dp, dp, ctypes.POINTER(MdParams), ctypes.POINTER(vp)]
     lib.chg_md_run.argtypes = [vp, vp, ctypes.c_int32]
     lib.chg_md_download.argtypes = [vp, vp, ctypes.POINTER(MdOutHost)]

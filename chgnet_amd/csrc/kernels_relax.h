@@ -83,6 +83,82 @@ __device__ inline void expm_frechet3(const double* m, const double* e, double* o
   for (int i = 0; i < 9; ++i) { out_exp[i] = p[i]; if (out_l) out_l[i] = q[i]; }
 }
 
+// Thread-0 algebra of one evaluated configuration, shared by the step kernels (k_relax_step, k_lbfgs_step).  sd: L0[9] L0^-1[9] c;
+// x: the 3 cell rows X of q; stress: the engine's [9] in GPa.  Out: F = expm(X / c) (identity without the cell), the cell rows
+// G = (1/c) L(A^T, W) of the generalized force (zero without the cell) and the cell L = L0 F^T.  Returns whether the stress is finite.
+__device__ inline int cell_frame(const double* sd, const double* x, const float* stress, double stress_weight, int relax_cell, double* F,
+                                 double* G, double* L) {
+  double L0[9], sig[9];
+  int finite = 1;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) L0[i] = sd[i];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) { const float s = stress[i]; finite &= isfinite(s); sig[i] = (double)s * stress_weight; }
+  if (relax_cell) {
+    const double c = sd[18], ic = 1.0 / c;
+    double A[9], At[9], FinvT[9], W[9], Fi[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) A[i] = x[i] * ic;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) At[3 * i + j] = A[3 * j + i];
+    expm_frechet3(A, nullptr, F, nullptr);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)   // cell = L0 F^T: L[i][j] = sum_k L0[i][k] F[j][k]
+#pragma unroll
+      for (int j = 0; j < 3; ++j) L[3 * i + j] = L0[3 * i] * F[3 * j] + L0[3 * i + 1] * F[3 * j + 1] + L0[3 * i + 2] * F[3 * j + 2];
+    const double vol = fabs(det3(L));
+    inv3(F, Fi);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) FinvT[3 * i + j] = Fi[3 * j + i];
+    mm3(sig, FinvT, W);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) W[i] *= -vol;                     // W = -V sigma F^-T
+    double scratch[9];
+    expm_frechet3(At, W, scratch, G);                             // L(A^T, W)
+#pragma unroll
+    for (int i = 0; i < 9; ++i) G[i] *= ic;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { F[i] = (i % 4 == 0) ? 1.0 : 0.0; G[i] = 0.0; L[i] = L0[i]; }
+  }
+  return finite;
+}
+
+// generalized force of row r of a structure with n atoms (atom rows: f F; cell rows: (1/c) L(A^T, W)); force: the structure's [n, 3]
+__device__ __forceinline__ void gen_force_row(const float* force, const double* F, const double* G, int n, int r, double g[3]) {
+  if (r < n) {
+    const float* f = force + 3 * (size_t)r;
+    const double f0 = f[0], f1 = f[1], f2 = f[2];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) g[j] = f0 * F[j] + f1 * F[3 + j] + f2 * F[6 + j];
+  } else {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) g[j] = G[3 * (r - n) + j];
+  }
+}
+
+// the cell L0 expm(X / c)^T of the moved coordinates (L0 without the cell)
+__device__ inline void next_lattice(const double* sd, const double* x, int relax_cell, double* L) {
+  if (relax_cell) {
+    double A[9], F[9];
+    const double ic = 1.0 / sd[18];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) A[i] = x[i] * ic;
+    expm_frechet3(A, nullptr, F, nullptr);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) L[3 * i + j] = sd[3 * i] * F[3 * j] + sd[3 * i + 1] * F[3 * j + 1] + sd[3 * i + 2] * F[3 * j + 2];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) L[i] = sd[i];
+  }
+}
+
 static __global__ __launch_bounds__(256) void k_relax_step(RelaxStepArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int bs = p.sel ? p.sel[blockIdx.x] : blockIdx.x;
@@ -106,45 +182,11 @@ static __global__ __launch_bounds__(256) void k_relax_step(RelaxStepArgs p) {
   }
   int finite = 1;
   if (tid == 0) {
-    double L0[9], F[9], G[9], L[9];
+    double F[9], G[9], L[9];
 #pragma unroll
-    for (int i = 0; i < 9; ++i) { L0[i] = sd[i]; sLinv[i] = sd[9 + i]; }
+    for (int i = 0; i < 9; ++i) sLinv[i] = sd[9 + i];
     const float e = p.energy[bs];
-    finite = isfinite(e);
-    double sig[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) { const float x = p.stress[9 * (size_t)bs + i]; finite &= isfinite(x); sig[i] = (double)x * p.stress_weight; }
-    if (p.relax_cell) {
-      const double c = sd[18], ic = 1.0 / c;
-      double A[9], At[9], FinvT[9], W[9], Fi[9];
-#pragma unroll
-      for (int i = 0; i < 9; ++i) A[i] = q[3 * n + i] * ic;
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) At[3 * i + j] = A[3 * j + i];
-      expm_frechet3(A, nullptr, F, nullptr);
-#pragma unroll
-      for (int i = 0; i < 3; ++i)   // cell = L0 F^T: L[i][j] = sum_k L0[i][k] F[j][k]
-#pragma unroll
-        for (int j = 0; j < 3; ++j) L[3 * i + j] = L0[3 * i] * F[3 * j] + L0[3 * i + 1] * F[3 * j + 1] + L0[3 * i + 2] * F[3 * j + 2];
-      const double vol = fabs(det3(L));
-      inv3(F, Fi);
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) FinvT[3 * i + j] = Fi[3 * j + i];
-      mm3(sig, FinvT, W);
-#pragma unroll
-      for (int i = 0; i < 9; ++i) W[i] *= -vol;                     // W = -V sigma F^-T
-      double scratch[9];
-      expm_frechet3(At, W, scratch, G);                             // L(A^T, W)
-#pragma unroll
-      for (int i = 0; i < 9; ++i) G[i] *= ic;
-    } else {
-#pragma unroll
-      for (int i = 0; i < 9; ++i) { F[i] = (i % 4 == 0) ? 1.0 : 0.0; G[i] = 0.0; L[i] = L0[i]; }
-    }
+    finite = isfinite(e) & cell_frame(sd, q + 3 * (size_t)n, p.stress + 9 * (size_t)bs, p.stress_weight, p.relax_cell, F, G, L);
 #pragma unroll
     for (int i = 0; i < 9; ++i) { sF[i] = F[i]; sG[i] = G[i]; }
     if (p.e_out) p.e_out[o] = e;
@@ -155,17 +197,7 @@ static __global__ __launch_bounds__(256) void k_relax_step(RelaxStepArgs p) {
   }
   __syncthreads();
 
-  auto gen_force = [&](int r, double g[3]) {   // generalized force of row r (atom rows: f F; cell rows: (1/c) L(A^T, W))
-    if (r < n) {
-      const float* f = p.force + 3 * ((size_t)b0 + r);
-      const double f0 = f[0], f1 = f[1], f2 = f[2];
-#pragma unroll
-      for (int j = 0; j < 3; ++j) g[j] = f0 * sF[j] + f1 * sF[3 + j] + f2 * sF[6 + j];
-    } else {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) g[j] = sG[3 * (r - n) + j];
-    }
-  };
+  auto gen_force = [&](int r, double g[3]) { gen_force_row(p.force + 3 * (size_t)b0, sF, sG, n, r, g); };
 
   // pass 0: finiteness, frame of the evaluated configuration, g.v, |g|^2, |v|^2, max row |g|^2
   double gv = 0.0, gg = 0.0, vv = 0.0, gmax = 0.0;
@@ -272,20 +304,7 @@ static __global__ __launch_bounds__(256) void k_relax_step(RelaxStepArgs p) {
   __syncthreads();
   if (tid == 0) {
     double L[9];
-    if (p.relax_cell) {
-      double A[9], F[9];
-      const double ic = 1.0 / sd[18];
-#pragma unroll
-      for (int i = 0; i < 9; ++i) A[i] = q[3 * n + i] * ic;
-      expm_frechet3(A, nullptr, F, nullptr);
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) L[3 * i + j] = sd[3 * i] * F[3 * j] + sd[3 * i + 1] * F[3 * j + 1] + sd[3 * i + 2] * F[3 * j + 2];
-    } else {
-#pragma unroll
-      for (int i = 0; i < 9; ++i) L[i] = sd[i];
-    }
+    next_lattice(sd, q + 3 * (size_t)n, p.relax_cell, L);
 #pragma unroll
     for (int i = 0; i < 9; ++i) p.lat_next[9 * (size_t)bs + i] = L[i];
   }

@@ -3,13 +3,16 @@
 The reference relaxes one structure at a time through ASE: ``FIRE(FrechetCellFilter(atoms)).run(fmax, steps)`` with
 ``CHGNetCalculator`` evaluating every step.  ASE is absent offline, and one Python round trip per step leaves the batch
 engine idle.  Here the whole optimizer runs behind the C-ABI (``chg_relax_*``, include/chgnet_hip.h): every structure
-is an independent FIRE optimizer whose float64 state stays in HBM, one step kernel (csrc/kernels_relax.h) advances all
-active structures at once, and structures that have stopped drop out of the next graph build.  A batch gives every
-structure the result it would get alone.  The semantics are those of ASE's FIRE and FrechetCellFilter with their
-defaults; tests/relax_ref.py restates them in float64 NumPy / SciPy.
+is an independent optimizer whose float64 state stays in HBM, one step kernel advances all active structures at once,
+and structures that have stopped drop out of the next graph build.  A batch gives every structure the result it would
+get alone.  Two optimizers: ``"FIRE"`` (the default, csrc/kernels_relax.h) and ``"LBFGS"`` (csrc/kernels_lbfgs.h), with
+the semantics of ASE's FIRE and LBFGS (no line search) through FrechetCellFilter, with their defaults; tests/relax_ref.py
+and tests/lbfgs_ref.py restate them in float64 NumPy / SciPy.
 
-Deviation: a structure whose energy, forces or stress are non-finite even on the engine's wide-range sweep stops with
-status ``NONFINITE`` without moving (ASE would carry the NaN on).
+Deviations: a structure whose energy, forces or stress are non-finite even on the engine's wide-range sweep stops with
+status ``NONFINITE`` without moving (ASE would carry the NaN on).  L-BFGS skips the history triple of a step whose
+curvature ``y . s`` is exactly zero or non-finite (ASE would divide by zero); a triple with ``y . s < 0`` is kept, as
+ASE keeps it.
 """
 
 from __future__ import annotations
@@ -30,6 +33,8 @@ OPTIMIZERS = ("FIRE",)
 FILTERS = ("FrechetCellFilter",)
 STATUS_NAMES = ("RUNNING", "CONVERGED", "MAX_STEPS", "NONFINITE")
 FIRE_DEFAULTS = {"dt": 0.1, "maxstep": 0.2, "dtmax": 1.0, "Nmin": 5, "finc": 1.1, "fdec": 0.5, "astart": 0.1, "fa": 0.99}
+LBFGS = "LBFGS"                # the alternative to the default: ASE's LBFGS without line search
+LBFGS_DEFAULTS = {"maxstep": 0.2, "memory": 100, "damping": 1.0, "alpha": 70.0}
 
 
 class TrajectoryObserver:
@@ -65,13 +70,13 @@ class TrajectoryObserver:
 
 
 class StructOptimizer:
-    """Relax crystal structures with FIRE (through the Frechet cell filter) on the device."""
+    """Relax crystal structures with FIRE (the default) or L-BFGS (through the Frechet cell filter) on the device."""
 
     def __init__(self, model=None, optimizer_class="FIRE", use_device: str | None = None, stress_weight: float = GPA_TO_EV_A3,
                  on_isolated_atoms: str = "warn") -> None:
         name = optimizer_class if isinstance(optimizer_class, str) else getattr(optimizer_class, "__name__", None)
-        if name not in OPTIMIZERS:
-            raise ValueError(f"Optimizer instance not found. Select from {list(OPTIMIZERS)}")
+        if name not in OPTIMIZERS and name != LBFGS:
+            raise ValueError(f"Optimizer instance not found. Select from {list(OPTIMIZERS)} (default) or {LBFGS!r}")
         self.optimizer_class = name
         if isinstance(model, CHGNetCalculator):
             self.calculator = model
@@ -88,16 +93,29 @@ class StructOptimizer:
         return self.calculator.model.n_params
 
     # ------------------------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _params(fmax, steps, relax_cell, ase_filter, fire_kwargs: dict) -> dict:
+    def _params(self, fmax, steps, relax_cell, ase_filter, opt_kwargs: dict) -> dict:
         if ase_filter not in FILTERS:
             raise ValueError(f"Invalid {ase_filter=}, must be one of {list(FILTERS)}. ")
-        unknown = set(fire_kwargs) - set(FIRE_DEFAULTS) - {"downhill_check"}
-        if unknown:
-            raise TypeError(f"FIRE got unexpected keyword argument(s) {sorted(unknown)}")
-        if fire_kwargs.get("downhill_check"):
-            raise ValueError("FIRE(downhill_check=True) is not supported")
-        fire = {k: fire_kwargs.get(k, v) for k, v in FIRE_DEFAULTS.items()}
+        if self.optimizer_class == LBFGS:
+            unknown = set(opt_kwargs) - set(LBFGS_DEFAULTS) - {"use_line_search"}
+            if unknown:
+                raise TypeError(f"LBFGS got unexpected keyword argument(s) {sorted(unknown)}")
+            if opt_kwargs.get("use_line_search"):
+                raise ValueError("LBFGS(use_line_search=True) is not supported")
+            lbfgs = {k: opt_kwargs.get(k, v) for k, v in LBFGS_DEFAULTS.items()}
+            if int(lbfgs["memory"]) != lbfgs["memory"] or lbfgs["memory"] < 1:
+                raise ValueError(f"LBFGS memory must be a positive integer, got {lbfgs['memory']!r}")
+            for k in ("maxstep", "damping", "alpha"):
+                if not float(lbfgs[k]) > 0.0:
+                    raise ValueError(f"LBFGS {k} must be positive, got {lbfgs[k]!r}")
+            fire = {**FIRE_DEFAULTS, "lbfgs": lbfgs}      # the binding passes FIRE's defaults; the engine ignores them
+        else:
+            unknown = set(opt_kwargs) - set(FIRE_DEFAULTS) - {"downhill_check"}
+            if unknown:
+                raise TypeError(f"FIRE got unexpected keyword argument(s) {sorted(unknown)}")
+            if opt_kwargs.get("downhill_check"):
+                raise ValueError("FIRE(downhill_check=True) is not supported")
+            fire = {k: opt_kwargs.get(k, v) for k, v in FIRE_DEFAULTS.items()}
         fmax = 0.1 if fmax is None else float(fmax)
         steps = 500 if steps is None else int(steps)
         if fmax < 0 or steps < 0:
@@ -123,7 +141,12 @@ class StructOptimizer:
             r_atom=conv.atom_graph_cutoff, r_bond=conv.bond_graph_cutoff, numerical_tol=1e-8, stress_weight=self.calculator.stress_weight)
         host = prep.host()
         handle = ctypes.c_void_p()
-        eng._check(eng.lib.chg_relax_create(eng.handle, ctypes.byref(host), ctypes.byref(params), ctypes.byref(handle)))
+        if "lbfgs" in p:
+            lb = p["lbfgs"]
+            lbfgs = _lib.LbfgsParams(maxstep=float(lb["maxstep"]), damping=float(lb["damping"]), alpha=float(lb["alpha"]), memory=int(lb["memory"]))
+            eng._check(eng.lib.chg_relax_create_lbfgs(eng.handle, ctypes.byref(host), ctypes.byref(params), ctypes.byref(lbfgs), ctypes.byref(handle)))
+        else:
+            eng._check(eng.lib.chg_relax_create(eng.handle, ctypes.byref(host), ctypes.byref(params), ctypes.byref(handle)))
         B, N = prep.n_struct, int(prep.atom_off[-1])
         scale = n_at.astype(np.float64) if model.is_intensive else np.ones(B)
         trajs = [TrajectoryObserver(prep.z[prep.atom_off[i]:prep.atom_off[i + 1]]) for i in range(B)] if frame_every else None
@@ -149,7 +172,7 @@ class StructOptimizer:
                 sl = slice(prep.atom_off[i], prep.atom_off[i + 1])
                 fmax_now = float(np.sqrt((d["force"][sl].astype(np.float64) ** 2).sum(1).max()))
                 last = d["n_steps"][i] - (1 if d["status"][i] == 0 else 0)
-                print(f"FIRE[{i}]: {last:4d}  E = {d['energy'][i] * scale[i]:.6f} eV  max|f| = {fmax_now:.6f} eV/A  {STATUS_NAMES[d['status'][i]]}")
+                print(f"{self.optimizer_class}[{i}]: {last:4d}  E = {d['energy'][i] * scale[i]:.6f} eV  max|f| = {fmax_now:.6f} eV/A  {STATUS_NAMES[d['status'][i]]}")
 
         n_active = ctypes.c_int32(B)
         try:

@@ -109,7 +109,8 @@ typedef struct chg_out_host {
 /* Version of this interface: bumped whenever a struct of this header grows or an entry point changes meaning (chg_model_desc gained
  * n_mlp_hidden / mlp_out_bias at 2; chg_batch_build_predict arrived at 3; the chg_relax_* entry points at 4; the chg_md_* entry points at 5;
  * chg_hessian_vector and chg_hessian_vector_strain were added at 5 without a bump: new entry points only, no struct or signature changed;
- * so were chg_md_create_langevin and chg_test_md_step_langevin, whose extra parameters travel as arguments, not in chg_md_params).  A binding compiled against another value must refuse the
+ * so were chg_md_create_langevin and chg_test_md_step_langevin, whose extra parameters travel as arguments, not in chg_md_params;
+ * so were chg_relax_create_lbfgs and chg_test_lbfgs_step, whose parameters travel in a struct of their own, chg_lbfgs_params).  A binding compiled against another value must refuse the
  * library: chg_engine_create COPIES *desc, so an older, shorter chg_model_desc would be read past its end. */
 #define CHG_ABI_VERSION 5
 int chg_abi_version(void);
@@ -296,6 +297,38 @@ int chg_relax_free(chg_engine* eng, chg_relax* relax);
 int chg_test_relax_step(chg_engine* eng, const chg_relax_params* params, int32_t n_struct, const int32_t* atom_off, double* q, double* v,
                         double* sd, int32_t* si, const float* energy, const float* force, const float* stress, const float* magmom,
                         double* frac_next, double* lat_next);
+
+/* L-BFGS instead of FIRE (the reference's StructOptimizer(optimizer_class="LBFGS")): ASE's LBFGS with its defaults and no line search,
+ * on the same generalized coordinates q and forces g, with the same stop rules, retry and compaction.  Per structure and evaluation
+ * that neither stops nor is held back (q, g flattened; the ring holds the last m <= M = max(1, min(memory, max_steps)) triples):
+ *   steps taken > 0:  s0 = q - r0, y0 = g0 - g; when y0 . s0 is finite and not 0 the triple (s0, y0, 1 / (y0 . s0)) is appended,
+ *                     the oldest one dropped beyond M (ASE would divide by zero where this one skips the triple)
+ *   t = -g;  newest to oldest: a_i = rho_i (s_i . t), t -= a_i y_i;  z = t / alpha;  oldest to newest: z += s_i (a_i - rho_i (y_i . z))
+ *   p = -z; when the longest ROW of p (cell rows included) is >= maxstep, p is scaled so that it is maxstep (FIRE clamps the norm)
+ *   r0 = q, g0 = g, q += damping p, steps taken += 1
+ * One step kernel (csrc/kernels_lbfgs.h); tests/lbfgs_ref.py restates it in float64 NumPy.  The history takes
+ * 2 M 3 (N + 3 B) 8 bytes of the state and does not move when structures drop out. */
+typedef struct chg_lbfgs_params {
+  double maxstep, damping, alpha;   /* ASE LBFGS: 0.2, 1.0, 70.0 (H0 = 1 / alpha); all > 0                               */
+  int32_t memory;                   /* 100; >= 1                                                                        */
+  int32_t reserved;                 /* 0                                                                                */
+} chg_lbfgs_params;
+/* As chg_relax_create; of *params dt, maxstep, dtmax, finc, fdec, astart, fa and nmin are ignored.  The handle is an ordinary
+ * chg_relax for chg_relax_run / chg_relax_download / chg_relax_free.  CHG_ENOMEM when the state (history included) cannot be allocated. */
+int chg_relax_create_lbfgs(chg_engine* eng, const chg_structs_host* host, const chg_relax_params* params, const chg_lbfgs_params* lbfgs,
+                           chg_relax** out);
+/* Tests only: ONE L-BFGS step kernel on caller-given state and results, in place.  R = N + 3 B rows; the rows of structure o start at
+ * atom_off[o] + 3 o (atom rows, then 3 cell rows) in every row array:
+ *   q, r0, g0 [R, 3];  S, Y [M, R, 3]: the k-th triple appended (k from 0) sits in slot k % M;  rho [B, M] by slot;
+ *   sd [B, 24] as chg_test_relax_step (L0[9], L0^-1[9], exp_cell_factor, rest unused);
+ *   si [B, 4] ints: triples appended so far (the ring holds the last min(that, M)), steps taken, status, spare.
+ * energy [B], force [N,3], stress [B,9] GPa, magmom [N] or null.  final_try 0: a structure with non-finite results is left untouched
+ * and retry[o] is set to 1 (retry [B] is in / out, the caller zeroes it); 1: it stops as CHG_RELAX_NONFINITE.
+ * out: frac_next [N,3], lat_next [B,9] (the moved structures'). */
+int chg_test_lbfgs_step(chg_engine* eng, const chg_relax_params* params, const chg_lbfgs_params* lbfgs, int32_t n_struct,
+                        const int32_t* atom_off, double* q, double* r0, double* g0, double* S, double* Y, double* rho, double* sd, int32_t* si,
+                        const float* energy, const float* force, const float* stress, const float* magmom, int32_t final_try,
+                        double* frac_next, double* lat_next, int32_t* retry);
 
 /* ---- molecular dynamics: NVE, NVT Berendsen, NPT Berendsen, every structure an independent replica ---------------------------
  * Reference: MolecularDynamics (chgnet/model/dynamics.py:433-780) with ASE VelocityVerlet, NVTBerendsen, Inhomogeneous_NPTBerendsen and
