@@ -282,7 +282,7 @@ int chg_debug_fetch_i32(chg_engine* eng, chg_batch* b, const char* name, int32_t
     return CHG_OK;
   }
   if (std::strcmp(name, "route") == 0) {        // host-side state: the route of the last prediction (chg_batch::route)
-    const int64_t n = std::min<int64_t>(5, std::max<int64_t>(capacity, 0));
+    const int64_t n = std::min<int64_t>(6, std::max<int64_t>(capacity, 0));
     std::copy(b->route, b->route + n, dst);
     if (n_written) *n_written = n;
     return CHG_OK;
@@ -363,10 +363,10 @@ int chg_predict(chg_engine* eng, chg_batch* b, uint32_t task_mask) {
     hipGraphDestroy(graph);
     if (ei != hipSuccess) { b->graph_exec = nullptr; eng->err = std::string("hipGraphInstantiate: ") + hipGetErrorString(ei); return CHG_EHIP; }
     b->graph_task = task;
-    std::copy(b->route, b->route + 5, b->graph_route);
+    std::copy(b->route, b->route + 6, b->graph_route);
   }
   HIP_TRY(eng, hipGraphLaunch(b->graph_exec, eng->stream));
-  std::copy(b->graph_route, b->graph_route + 5, b->route);
+  std::copy(b->graph_route, b->graph_route + 6, b->route);
   b->last_task = task;
   b->seed1_adjoints = (task & (CHG_TASK_F | CHG_TASK_S)) != 0;
   b->q_tables = b->seed1_adjoints;

@@ -174,8 +174,10 @@ struct chg_batch {
   bool win_pending = false; // uploaded, prepare_windows not launched yet (ensure_windows: first predict / debug fetch)
   bool zsave_now = false;   // this prediction has a reverse sweep: its forward angle kernels keep z (zsave_l)
   // route of the last prediction (chg_debug_fetch_i32 "route"): tiny launch sequence, chained row GEMMs, zsave rows kept, per-atom
-  // index built, TEAM mode -- 0 / 1 each; graph_route: the route of the captured sweep, restored when it is replayed
-  int32_t route[5] = {}, graph_route[5] = {};
+  // index built, TEAM mode, 32-bit row offsets in the large-batch tile kernels -- 0 / 1 each; graph_route: the route of the captured
+  // sweep, restored when it is replayed
+  int32_t route[6] = {}, graph_route[6] = {};
+  size_t addr_span = 0;     // bytes: the largest span a tile kernel addresses from one base pointer (carve; 0: unknown -> 64-bit offsets)
   int p_table_done = -1;    // forward sweep, small batches: the AtomConv layer whose P table an angle layer's launch has contracted already
   float *zero1, *zero1_end, *zero2, *zero2_end;   // contiguous ranges cleared by one memset each
   float* zero2_keep_end = nullptr;                // group 2 holds [energy, magmom) up to here: results of the prediction a later chg_backward keeps

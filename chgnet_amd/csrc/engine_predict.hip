@@ -206,6 +206,24 @@ int zero(chg_engine* eng, void* p, size_t bytes) {
 
 
 
+// ---- address mode of the tile kernels that have one (mfma_tile.h grow) ------------------------------------------------------
+// The kernels with a mode are the ones a large batch runs; three of them (k_atomconv_fwd, k_atomconv_bwd<false>, k_angle<true, false>)
+// also serve MD-size batches, whose spans are tiny: in practice every batch short of 4 GiB per table -- all but the very largest --
+// runs the 32-bit twins, the whole GPU suite included, and the 64-bit twins are reached by huge batches and by
+// tests/test_gpu_addr_modes.py.
+// 32-bit row offsets when every span a tile kernel addresses from ONE base pointer is below 4 GiB (chg_batch::addr_span, computed
+// from the batch's sizes where its arena is carved), 64-bit offsets otherwise: the headline batch (largest table: one layer's kept
+// z rows, 2.1 GB) takes the former, a 4096-structure batch (4.2 GB of angle rows) the latter.  CHGNET_ADDR_MODE=32 / 64 forces a mode
+// and CHGNET_ADDR32_MAX_BYTES moves the threshold (tests: a small batch through the 64-bit decision); a batch that really spans
+// 4 GiB runs 64-bit whatever they say -- a 32-bit offset would wrap.  Both are read once.
+static bool addr32_mode(const chg_batch* b) {
+  constexpr size_t HARD = (size_t)1 << 32;
+  static const int forced = [] { const char* e = std::getenv("CHGNET_ADDR_MODE"); return e ? std::atoi(e) : 0; }();
+  static const size_t limit = [] { const char* e = std::getenv("CHGNET_ADDR32_MAX_BYTES"); return e ? (size_t)std::strtoull(e, nullptr, 10) : HARD; }();
+  if (b->addr_span == 0 || b->addr_span >= HARD || forced == 64) return false;
+  return forced == 32 || b->addr_span < limit;
+}
+
 // ---- AtomConv ----------------------------------------------------------------------------------------
 // tables of layer l:  P = atom[l] . [Wc;Wn]^T (+b1 on the centre half).  The bond partial Q = h_bond^l . Wb^T is contracted inside
 // k_atomconv_fwd, which leaves it behind as a table when a reverse sweep follows; chg_backward after an energy-only predict builds
@@ -316,7 +334,8 @@ int atomconv_fwd_kernel(chg_engine* eng, chg_batch* b, int l, bool keep_q) {
     a.image = eng->img_ac_fwd[a.q_bias ? 1 : 0][l];
     a.e_nbr = b->p_nbr;
     a.Qout = keep_q ? b->Ql[l] : nullptr;   // the reverse sweep gathers the bond partial as a table
-    hipLaunchKernelGGL((k_atomconv_fwd<FWD_WAVES>), dim3(tile_grid(eng, b->Ed, TILE_ROWS * FWD_WAVES)), dim3(64 * FWD_WAVES), lds, eng->stream, a);
+    if (addr32_mode(b)) hipLaunchKernelGGL((k_atomconv_fwd<FWD_WAVES, true>), dim3(tile_grid(eng, b->Ed, TILE_ROWS * FWD_WAVES)), dim3(64 * FWD_WAVES), lds, eng->stream, a);
+    else hipLaunchKernelGGL((k_atomconv_fwd<FWD_WAVES>), dim3(tile_grid(eng, b->Ed, TILE_ROWS * FWD_WAVES)), dim3(64 * FWD_WAVES), lds, eng->stream, a);
     HIP_TRY(eng, hipGetLastError());
   }
   return CHG_OK;
@@ -346,7 +365,8 @@ int atomconv_bwd_kernel(chg_engine* eng, chg_batch* b, int l) {
     a.Gb = b->Gb;
     a.gb_accumulate = l == b->L - 1 ? 0 : 1;
     LaunchScope ls(eng, "atomconv_bwd");
-    hipLaunchKernelGGL(k_atomconv_bwd<false>, dim3(tile_grid(eng, b->Ed)), dim3(BLOCK), acb_fused_lds(), eng->stream, a);
+    if (addr32_mode(b)) hipLaunchKernelGGL((k_atomconv_bwd<false, true>), dim3(tile_grid(eng, b->Ed)), dim3(BLOCK), acb_fused_lds(), eng->stream, a);
+    else hipLaunchKernelGGL(k_atomconv_bwd<false>, dim3(tile_grid(eng, b->Ed)), dim3(BLOCK), acb_fused_lds(), eng->stream, a);
     HIP_TRY(eng, hipGetLastError());
   }
   return CHG_OK;
@@ -411,11 +431,13 @@ int launch_angle(chg_engine* eng, const char* label, chg_batch* b, const AngleAr
   // k_win_* kernels in prepare_windows (device-built batches of more than 8,191 atoms, or builds that did not expect to need it) can
   // still clear the flag, and then the row-order kernel is what computes the layer.
   const bool index_from_builder = b->canonical && (b->win_index_ready || b->blk_ready);
+  const bool a32 = addr32_mode(b);   // the large-batch kernels: row-order BondConv forward, per-atom AngleUpdate forward, per-atom adjoints
   if (!BWD && !HIDDEN && b->win_built && per_atom_forward()) {
     AngleWArgs w{};
     w.a = a; w.w = b->win;
     w.a.image = eng->img_angle[0][a.slot];
-    hipLaunchKernelGGL(k_angleupd_fwd_a, dim3(b->win_grid), dim3(BLOCK), angle_fa_lds(), eng->stream, w);
+    if (a32) hipLaunchKernelGGL(k_angleupd_fwd_a<true>, dim3(b->win_grid), dim3(BLOCK), angle_fa_lds(), eng->stream, w);
+    else hipLaunchKernelGGL(k_angleupd_fwd_a<>, dim3(b->win_grid), dim3(BLOCK), angle_fa_lds(), eng->stream, w);
     HIP_TRY(eng, hipGetLastError());
     if (index_from_builder) return CHG_OK;
   } else if (BWD && b->blk_cap > 0) {
@@ -447,9 +469,13 @@ int launch_angle(chg_engine* eng, const char* label, chg_batch* b, const AngleAr
     AngleWArgs w{};
     w.a = a; w.w = b->win;
     w.a.image = eng->img_angle[1][a.slot];
-    if (HIDDEN && w.a.zsave) hipLaunchKernelGGL((k_angle_bwd_w<HIDDEN, false, HIDDEN>), dim3(b->win_grid), dim3(BLOCK), angle_w_lds<HIDDEN>(), eng->stream, w);
-    else
-    hipLaunchKernelGGL((k_angle_bwd_w<HIDDEN>), dim3(b->win_grid), dim3(BLOCK), angle_w_lds<HIDDEN>(), eng->stream, w);
+    if (HIDDEN && w.a.zsave) {
+      if (a32) hipLaunchKernelGGL((k_angle_bwd_w<HIDDEN, false, HIDDEN, true>), dim3(b->win_grid), dim3(BLOCK), angle_w_lds<HIDDEN>(), eng->stream, w);
+      else hipLaunchKernelGGL((k_angle_bwd_w<HIDDEN, false, HIDDEN>), dim3(b->win_grid), dim3(BLOCK), angle_w_lds<HIDDEN>(), eng->stream, w);
+    } else {
+      if (a32) hipLaunchKernelGGL((k_angle_bwd_w<HIDDEN, false, false, true>), dim3(b->win_grid), dim3(BLOCK), angle_w_lds<HIDDEN>(), eng->stream, w);
+      else hipLaunchKernelGGL((k_angle_bwd_w<HIDDEN>), dim3(b->win_grid), dim3(BLOCK), angle_w_lds<HIDDEN>(), eng->stream, w);
+    }
     HIP_TRY(eng, hipGetLastError());
     if (index_from_builder) return CHG_OK;
   } else {
@@ -457,7 +483,8 @@ int launch_angle(chg_engine* eng, const char* label, chg_batch* b, const AngleAr
   }
   plain.image = eng->img_angle[BWD ? 1 : 0][a.slot];
   const size_t lds = angle_lds<HIDDEN, NW, BWD>();
-  hipLaunchKernelGGL((k_angle<HIDDEN, BWD, NW>), dim3(tile_grid(eng, b->A, TILE_ROWS * NW)), dim3(64 * NW), lds, eng->stream, plain);
+  if (HIDDEN && !BWD && a32) hipLaunchKernelGGL((k_angle<HIDDEN, BWD, NW, false, HIDDEN && !BWD>), dim3(tile_grid(eng, b->A, TILE_ROWS * NW)), dim3(64 * NW), lds, eng->stream, plain);
+  else hipLaunchKernelGGL((k_angle<HIDDEN, BWD, NW>), dim3(tile_grid(eng, b->A, TILE_ROWS * NW)), dim3(64 * NW), lds, eng->stream, plain);
   HIP_TRY(eng, hipGetLastError());
   return CHG_OK;
 }
@@ -724,6 +751,7 @@ int run_predict(chg_engine* eng, chg_batch* b, uint32_t task) {
   b->route[2] = want_grad && b->zsave_l[0] && (b->win_built || b->win_team > 0);   // (angle_args: AngleArgs::zsave)
   b->route[3] = b->win_built;
   b->route[4] = b->win_team > 0;
+  b->route[5] = addr32_mode(b);   // 32-bit row offsets in the large-batch tile kernels
   if (chained) {
     TRY(forward_tiny(eng, b, want_grad, want_m));
   } else {
@@ -883,6 +911,18 @@ void carve(chg_batch* b, char* base, size_t& total) {
     b->blk_tiles = c.take<int>(b->blk_cap ? 4 : 0);
   }
   if (A == 0) for (int l = 1; l < L; ++l) b->hbc[l] = b->hbc[0];   // no BondConv: bond features never change
+  {   // the largest span (bytes) a tile kernel addresses from one base pointer: decides the batch's address mode (addr32_mode)
+    auto tab = [](size_t rows, size_t ld) { return rows * ld * sizeof(float); };
+    size_t span = std::max({tab(N, 4 * D) /* P, GP */, tab(Eu, 2 * D) /* Q */, tab(Eb, 4 * D) /* R, GR */, tab(A, D) /* angle rows, Gang */,
+                            b->zsave_l[0] ? tab(A + TILE_ROWS, 2 * D) : 0 /* kept z rows */});   // (S, wag, agg, Gb, ...: narrower tables of the same rows)
+    // the AtomConv forward reaches the bond rows hb0 [Eu,64] AND the bond-graph nodes' layer features hbc[l] [Eb,64] from the hb0 base
+    // (bond_row_offset): the span is the distance actually covered
+    for (int l = 0; l < L; ++l) {
+      if (!b->hbc[l]) continue;
+      span = b->hbc[l] < b->hb0 ? ~size_t(0) : std::max(span, (size_t)(b->hbc[l] - b->hb0) * sizeof(float) + tab(Eb, D));
+    }
+    b->addr_span = span;
+  }
   total = (c.pos + 255) & ~size_t(255);
 }
 
@@ -1030,7 +1070,15 @@ int predict_set_lds(chg_engine* eng) {
   if ((s = set_lds(eng, (k_rows_gemm<128, 64, 2>), (rows_gemm_lds<128, 64, 2>())))) return s;
   if ((s = set_lds(eng, k_atomconv_fwd<FWD_WAVES>, (atomconv_lds<FWD_WAVES, false, true>())))) return s;
   if ((s = set_lds(eng, k_atomconv_bwd<false>, acb_fused_lds()))) return s;
-  if ((s = set_lds(eng, k_angleupd_fwd_a, angle_fa_lds()))) return s;
+  if ((s = set_lds(eng, k_angleupd_fwd_a<>, angle_fa_lds()))) return s;
+  // ... and the 32-bit-offset twins of the large-batch kernels (addr32_mode)
+  if ((s = set_lds(eng, (k_atomconv_fwd<FWD_WAVES, true>), (atomconv_lds<FWD_WAVES, false, true>())))) return s;
+  if ((s = set_lds(eng, (k_atomconv_bwd<false, true>), acb_fused_lds()))) return s;
+  if ((s = set_lds(eng, k_angleupd_fwd_a<true>, angle_fa_lds()))) return s;
+  if ((s = set_lds(eng, (k_angle_bwd_w<true, false, false, true>), angle_w_lds<true>()))) return s;
+  if ((s = set_lds(eng, (k_angle_bwd_w<true, false, true, true>), angle_w_lds<true>()))) return s;
+  if ((s = set_lds(eng, (k_angle_bwd_w<false, false, false, true>), angle_w_lds<false>()))) return s;
+  if ((s = set_lds(eng, (k_angle<true, false, WAVES, false, true>), angle_lds<true>()))) return s;
   if ((s = set_lds(eng, k_angle_bwd_blk<true>, angle_blk_lds<true>()))) return s;
   if ((s = set_lds(eng, k_angle_bwd_blk<false>, angle_blk_lds<false>()))) return s;
   if ((s = set_lds(eng, k_angle_bwd_w<true>, angle_w_lds<true>()))) return s;

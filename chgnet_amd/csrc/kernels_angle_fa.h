@@ -30,11 +30,12 @@ constexpr size_t angle_fa_lds() { return sizeof(float) * (size_t)(AngleLds<false
 struct FaRows { f32x4 r[FA_NSL]; f32x4 s; };     // one atom's table rows in flight: lane t holds floats 4 t .. 4 t + 3 of every row
 
 // request the rows of the atom (c, n short bonds, bond list `bkv` in lanes 0 .. n - 1)
+template <bool A32 = false>
 __device__ __forceinline__ void fa_request(FaRows& q, const AngleArgs& p, int c, int n, int bkv, int lane) {
 #pragma unroll
   for (int k = 0; k < FA_NSL; ++k)
-    if (k < n) q.r[k] = *reinterpret_cast<const f32x4*>(p.R + (size_t)(unsigned)__builtin_amdgcn_readlane(bkv, k) * 4 * D + 4 * lane);
-  q.s = lane < 32 ? *reinterpret_cast<const f32x4*>(p.S + (size_t)c * 2 * D + 4 * lane) : zero4();
+    if (k < n) q.r[k] = *grow<f32x4, A32>(p.R, (unsigned)__builtin_amdgcn_readlane(bkv, k), 4 * D, 4 * lane);
+  q.s = lane < 32 ? *grow<f32x4, A32>(p.S, (unsigned)c, 2 * D, 4 * lane) : zero4();
 }
 __device__ __forceinline__ void fa_commit(const FaRows& q, float* tab, int n, int lane) {
 #pragma unroll
@@ -42,6 +43,8 @@ __device__ __forceinline__ void fa_commit(const FaRows& q, float* tab, int n, in
     if (k < n) *reinterpret_cast<f32x4*>(tab + k * FA_RS + 4 * lane) = q.r[k] + q.s;      // q.s is zero in the R_j half
 }
 
+// A32: address mode of the table rows (mfma_tile.h grow), picked per batch by the launcher.
+template <bool A32 = false>
 __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angleupd_fwd_a(AngleWArgs pw) {
   const AngleArgs& p = pw.a;
   const WinIndex& w = pw.w;
@@ -75,8 +78,8 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angleupd_fwd_a(AngleWAr
     const int bkv = w.abbond[ab0 + min(lane, n - 1)];
     const int ra = min(r0 + j, r0 + n * (n - 1) - 1);
     aA = w.q_a[ra]; q1A = w.q_ab1[ra]; q2A = w.q_ab2[ra];
-    fa_request(rows, p, c, min(n, FA_NSL), bkv, lane);
-    read_dl_g<VT>(p.ang, (unsigned)aA, D, g, xn.t);
+    fa_request<A32>(rows, p, c, min(n, FA_NSL), bkv, lane);
+    read_dl_g<VT, A32>(p.ang, (unsigned)aA, D, g, xn.t);
   }
   V64 y_prev;                                    // the previous tile's result: stored one tile late, behind this tile's requests
   CHG_EV(ft) y_prev.t[ft] = zero4();
@@ -114,7 +117,7 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angleupd_fwd_a(AngleWAr
       const bool last = row0 + TILE_ROWS >= r_end;
       // requests for later tiles: angle rows of the next tile (after this atom's last tile: of the next atom's first), indices two ahead
       const int a_ld = last ? (c_next >= 0 ? aA_n : a) : a_n;
-      read_dl_g<VT>(p.ang, (unsigned)a_ld, D, g, xn.t);
+      read_dl_g<VT, A32>(p.ang, (unsigned)a_ld, D, g, xn.t);
       const int rr2 = min(row0 + 2 * TILE_ROWS + j, r_end - 1);
       const int a_n2 = w.q_a[rr2], q1_n2 = w.q_ab1[rr2], q2_n2 = w.q_ab2[rr2];
       // ---- z = W_ang x + (R_i + S)[first bond] + R_j[second bond] ----
@@ -124,7 +127,7 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angleupd_fwd_a(AngleWAr
       gemm_split<VT, 2 * VT, false, true>(z, Wang, 2 * D, x.t, j, g);
       // the previous tile's rows leave now: behind this tile's requests, so that no wait for those covers the stores
       asm volatile("" ::: "memory");
-      if (j < nvalid_prev) write_dl_g<VT>(p.out, (unsigned)a_prev, D, g, y_prev.t);
+      if (j < nvalid_prev) write_dl_g<VT, A32>(p.out, (unsigned)a_prev, D, g, y_prev.t);
       asm volatile("" ::: "memory");
       const bool in_lds = r1 < FA_NSL && r2 >= 0 && r2 < FA_NSL;        // (r1 >= 0 always: the row's own first bond)
       if (__builtin_amdgcn_ballot_w64(!in_lds) == 0) {
@@ -135,16 +138,16 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angleupd_fwd_a(AngleWAr
           z[fo] += *reinterpret_cast<const f32x4*>(t1 + 16 * fo) + *reinterpret_cast<const f32x4*>(t2 + 16 * fo);
       } else {                                                           // a rank past the LDS rows: this tile gathers from the tables
         const int row = min(row0 + j, r_end - 1);
-        const float* g1 = p.R + (size_t)w.q_b1c[row] * 4 * D + 4 * g;
-        const float* g2 = p.R + (size_t)w.q_b2c[row] * 4 * D + 2 * D + 4 * g;
-        const float* gs = p.S + (size_t)c * 2 * D + 4 * g;
+        const float* g1 = grow<float, A32>(p.R, (unsigned)w.q_b1c[row], 4 * D, 4 * g);
+        const float* g2 = grow<float, A32>(p.R, (unsigned)w.q_b2c[row], 4 * D, 2 * D + 4 * g);
+        const float* gs = grow<float, A32>(p.S, (unsigned)c, 2 * D, 4 * g);
 #pragma unroll
         for (int fo = 0; fo < 2 * VT; ++fo)
           z[fo] += (*reinterpret_cast<const f32x4*>(g1 + 16 * fo) + *reinterpret_cast<const f32x4*>(gs + 16 * fo)) +
                    *reinterpret_cast<const f32x4*>(g2 + 16 * fo);
       }
       // the next atom's rows are requested during this atom's first tile (its bond list, asked for at the top of the atom, has landed)
-      if (row0 == r_begin && c_next >= 0) fa_request(rows, p, c_next, min(n1, FA_NSL), bkv_n, lane);
+      if (row0 == r_begin && c_next >= 0) fa_request<A32>(rows, p, c_next, min(n1, FA_NSL), bkv_n, lane);
       V64 zc{{z[0], z[1], z[2], z[3]}}, zg{{z[4], z[5], z[6], z[7]}};
       GatedState st;
       V64 y;
@@ -159,7 +162,7 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angleupd_fwd_a(AngleWAr
     c_nx = c_n2; n_nraw = n_n2raw; ab_nraw = ab_n2raw; r_nraw = r_n2raw; c_n2 = c_n3;
     aA = aA_n; q1A = q1A_n; q2A = q2A_n;
   }
-  if (j < nvalid_prev) write_dl_g<VT>(p.out, (unsigned)a_prev, D, g, y_prev.t);
+  if (j < nvalid_prev) write_dl_g<VT, A32>(p.out, (unsigned)a_prev, D, g, y_prev.t);
 }
 
 }  // namespace chg

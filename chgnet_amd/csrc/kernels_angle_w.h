@@ -245,6 +245,7 @@ constexpr size_t angle_w_lds() {
 
 // sum of three 64-wide table row halves into a 64-wide tile: 16 lanes per row, 4 rows per load instruction
 struct Gather64 { f32x4 a[TILE_ROWS / 4], b[TILE_ROWS / 4], c[TILE_ROWS / 4]; };
+template <bool A32 = false>
 __device__ __forceinline__ void gather64_issue(Gather64& gr, const float* __restrict__ t0, int i0, int ld0, const float* __restrict__ t1, int i1,
                                                int ld1, const float* __restrict__ t2, int i2, int ld2, int lane) {
   const int sub = lane >> 4, t = lane & 15;
@@ -256,9 +257,9 @@ __device__ __forceinline__ void gather64_issue(Gather64& gr, const float* __rest
   }
 #pragma unroll
   for (int it = 0; it < TILE_ROWS / 4; ++it) {
-    gr.a[it] = *grow<f32x4>(t0, (unsigned)r0[it], ld0, 4 * t);
-    gr.b[it] = *grow<f32x4>(t1, (unsigned)r1[it], ld1, 4 * t);
-    gr.c[it] = *grow<f32x4>(t2, (unsigned)r2[it], ld2, 4 * t);
+    gr.a[it] = *grow<f32x4, A32>(t0, (unsigned)r0[it], ld0, 4 * t);
+    gr.b[it] = *grow<f32x4, A32>(t1, (unsigned)r1[it], ld1, 4 * t);
+    gr.c[it] = *grow<f32x4, A32>(t2, (unsigned)r2[it], ld2, 4 * t);
   }
 }
 __device__ __forceinline__ void gather64_commit(const Gather64& gr, float* tile, int lane) {
@@ -281,13 +282,14 @@ __device__ __forceinline__ void to_columns(const V64& x, float* T, float* Trow, 
 }
 // Run sum for a key that is sorted along the rows, carried across tiles (`sum` / `cur` live in the caller); a finished run
 // leaves with one 256-byte atomic.
+template <bool A32 = false>
 __device__ __forceinline__ void run_sum64(const Cols64& c, int nvalid, int key, float& sum, int& cur, float* __restrict__ dst, int ld, int lane) {
 #pragma unroll
   for (int rr = 0; rr < TILE_ROWS; ++rr) {
     if (rr < nvalid) {
       const int k = __builtin_amdgcn_readlane(key, rr);
       if (k != cur) {
-        if (cur >= 0) atomicAdd(grow<float>(dst, (unsigned)cur, ld, lane), sum);
+        if (cur >= 0) atomicAdd(grow<float, A32>(dst, (unsigned)cur, ld, lane), sum);
         sum = 0.f;
         cur = k;
       }
@@ -295,15 +297,17 @@ __device__ __forceinline__ void run_sum64(const Cols64& c, int nvalid, int key, 
     }
   }
 }
+template <bool A32 = false>
 __device__ __forceinline__ void run_flush64(float& sum, int& cur, float* __restrict__ dst, int ld, int lane) {
-  if (cur >= 0) atomicAdd(grow<float>(dst, (unsigned)cur, ld, lane), sum);
+  if (cur >= 0) atomicAdd(grow<float, A32>(dst, (unsigned)cur, ld, lane), sum);
   sum = 0.f;
   cur = -1;
 }
+template <bool A32 = false>
 __device__ __forceinline__ void row_add64(const Cols64& c, int nvalid, float* __restrict__ base, int row, int ld, int lane) {
 #pragma unroll
   for (int rr = 0; rr < TILE_ROWS; ++rr)
-    if (rr < nvalid) atomicAdd(grow<float>(base, (unsigned)__builtin_amdgcn_readlane(row, rr), ld, lane), c.v[rr]);
+    if (rr < nvalid) atomicAdd(grow<float, A32>(base, (unsigned)__builtin_amdgcn_readlane(row, rr), ld, lane), c.v[rr]);
 }
 // Second-bond rows (NB column blocks of 64) into the wave-private LDS rows: plain read-modify-write, two rows per step
 // (neighbouring rows of the centre-major order never share a second bond; rows further apart may, and the LDS executes a
@@ -336,7 +340,8 @@ __device__ __forceinline__ void private_add(const Cols64 (&c)[NB], int nvalid, i
 // Run sums of a wave's non-adjacent tiles simply end at the tile's last row.
 // ZS (BondConv, large batches): the forward kernel kept z (AngleArgs::zsave) -- the tile starts from ONE 512-byte row per angle instead of
 // four gathered rows and the W_ang contraction.
-template <bool HIDDEN, bool TEAM = false, bool ZS = false>
+// A32: address mode of the table rows (mfma_tile.h grow), picked per batch by the launcher.
+template <bool HIDDEN, bool TEAM = false, bool ZS = false, bool A32 = false>
 __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs pw) {
   const AngleArgs& p = pw.a;
   const WinIndex& w = pw.w;
@@ -448,18 +453,18 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
       if (ZS) {
         // (requesting the NEXT tile's rows a tile ahead -- 32 loop-carried registers -- spilled 11-13 and cost 2.06 -> 2.24 ms, like every
         // other attempt to pipeline this kernel)
-        read_dl_g_nt<2 * VT>(p.zsave, (unsigned)a, 2 * D, g, z);
-        if (!HIDDEN) rows64_issue(gy_rows, p.Gang, a, lane_t);
+        read_dl_g_nt<2 * VT, A32>(p.zsave, (unsigned)a, 2 * D, g, z);
+        if (!HIDDEN) rows64_issue<A32>(gy_rows, p.Gang, a, lane_t);
         if (HIDDEN) {
-          read_dl_g<VT>(p.wbgc, (unsigned)b1, D, g, w1.t);
-          read_dl_g<VT>(p.wbgc, (unsigned)b2, D, g, w2.t);
-          read_dl_g<VT>(p.Gagg, (unsigned)b1, D, g, gu.t);
+          read_dl_g<VT, A32>(p.wbgc, (unsigned)b1, D, g, w1.t);
+          read_dl_g<VT, A32>(p.wbgc, (unsigned)b2, D, g, w2.t);
+          read_dl_g<VT, A32>(p.Gagg, (unsigned)b1, D, g, gu.t);
         }
       } else {
       Gather64 gc, gg;
-      gather64_issue(gc, p.R, b1, 4 * D, p.R + 2 * D, b2, 4 * D, p.S, c, 2 * D, lane_t);
-      gather64_issue(gg, p.R + D, b1, 4 * D, p.R + 3 * D, b2, 4 * D, p.S + D, c, 2 * D, lane_t);
-      gather_rows64(T, TS64, p.ang, a, lane_t);
+      gather64_issue<A32>(gc, p.R, b1, 4 * D, p.R + 2 * D, b2, 4 * D, p.S, c, 2 * D, lane_t);
+      gather64_issue<A32>(gg, p.R + D, b1, 4 * D, p.R + 3 * D, b2, 4 * D, p.S + D, c, 2 * D, lane_t);
+      gather_rows64<A32>(T, TS64, p.ang, a, lane_t);
       __builtin_amdgcn_wave_barrier();
       V64 x;
       read_dl<VT>(Trow, g, x.t);
@@ -472,11 +477,11 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
       __builtin_amdgcn_wave_barrier();
       read_dl<VT>(Trow, g, *reinterpret_cast<f32x4(*)[VT]>(&z[VT]));
       __builtin_amdgcn_wave_barrier();
-      if (!HIDDEN) rows64_issue(gy_rows, p.Gang, a, lane_t);
+      if (!HIDDEN) rows64_issue<A32>(gy_rows, p.Gang, a, lane_t);
       if (HIDDEN) {
-        read_dl_g<VT>(p.wbgc, (unsigned)b1, D, g, w1.t);
-        read_dl_g<VT>(p.wbgc, (unsigned)b2, D, g, w2.t);
-        read_dl_g<VT>(p.Gagg, (unsigned)b1, D, g, gu.t);
+        read_dl_g<VT, A32>(p.wbgc, (unsigned)b1, D, g, w1.t);
+        read_dl_g<VT, A32>(p.wbgc, (unsigned)b2, D, g, w2.t);
+        read_dl_g<VT, A32>(p.Gagg, (unsigned)b1, D, g, gu.t);
       }
       if (HIDDEN) gemm_rm<VT, 2 * VT, false, false>(z, reinterpret_cast<const _Float16*>(Wang), 2 * D, D, x.t, j, g, lane_t);
       else gemm_split<VT, 2 * VT, false>(z, reinterpret_cast<const h16x8*>(Wang), 2 * D, x.t, j, g);
@@ -501,8 +506,8 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
           Cols64 c1, c2[1];
           to_columns(g1, T, Trow, g, lane_t, c1);
           to_columns(g2, T, Trow, g, lane_t, c2[0]);
-          run_sum64(c1, nvalid, b1, rg, curg, p.Gwbgc, D, lane_t);
-          row_add64(c2[0], nvalid, p.Gwbgc, b2, D, lane_t);
+          run_sum64<A32>(c1, nvalid, b1, rg, curg, p.Gwbgc, D, lane_t);
+          row_add64<A32>(c2[0], nvalid, p.Gwbgc, b2, D, lane_t);
         }
       } else {
         rows64_commit(gy_rows, T, TS64, lane_t);
@@ -522,13 +527,13 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
 #pragma unroll
           for (int it = 0; it < TILE_ROWS / 4; ++it) gang_old.v[it] = zero4();
         } else {
-          rows64_issue(gang_old, p.Gang, a, lane_t);
+          rows64_issue<A32>(gang_old, p.Gang, a, lane_t);
         }
         if (HIDDEN) gemm_rm<2 * VT, VT, true, true>(ga.t, reinterpret_cast<const _Float16*>(Wang), 2 * D, D, gz, j, g, lane_t);
         else gemm_split<2 * VT, VT, true>(ga.t, reinterpret_cast<const h16x8*>(WangT), D, gz, j, g);
         write_dl<VT>(Trow, g, ga.t);
         __builtin_amdgcn_wave_barrier();
-        scatter_rows64_add<HIDDEN>(T, TS64, p.Gang, a, nvalid, lane_t, gang_old);
+        scatter_rows64_add<HIDDEN, A32>(T, TS64, p.Gang, a, nvalid, lane_t, gang_old);
         __builtin_amdgcn_wave_barrier();
       }
       // ---- scatter: first bond and centre as carried run sums, second bond into the private rows ----
@@ -539,14 +544,15 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
 #pragma unroll
         for (int rr = 0; rr < TILE_ROWS; ++rr)
           if (rr < nvalid) { rs0 += cc[0].v[rr]; rs1 += cc[1].v[rr]; }
-        run_sum64(cc[0], nvalid, b1, ri0, cur0, p.GR, 4 * D, lane_t);
-        run_sum64(cc[1], nvalid, b1, ri1, cur1, p.GR + D, 4 * D, lane_t);
+        run_sum64<A32>(cc[0], nvalid, b1, ri0, cur0, p.GR, 4 * D, lane_t);
+        run_sum64<A32>(cc[1], nvalid, b1, ri1, cur1, p.GR + D, 4 * D, lane_t);
         private_add<2>(cc, nvalid, s2, pacc, T, lane_t);
         if (__builtin_amdgcn_ballot_w64(j < nvalid && lane_t < TILE_ROWS && s2 < 0)) {   // rare: no private row for this second bond
 #pragma unroll
           for (int rr = 0; rr < TILE_ROWS; ++rr)
             if (rr < nvalid && __builtin_amdgcn_readlane(s2, rr) < 0) {
-              float* d = p.GR + (size_t)__builtin_amdgcn_readlane(b2, rr) * 4 * D + 2 * D + lane_t;
+              float* d = A32 ? grow<float, true>(p.GR, (unsigned)__builtin_amdgcn_readlane(b2, rr), 4 * D, 2 * D + lane_t)
+                               : p.GR + (size_t)__builtin_amdgcn_readlane(b2, rr) * 4 * D + 2 * D + lane_t;
               atomicAdd(d, cc[0].v[rr]);
               atomicAdd(d + D, cc[1].v[rr]);
             }
@@ -557,11 +563,11 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
     // ---- the atom is done: runs, centre sum, private second-bond rows ----
     int lane_f = lane;
     if (HIDDEN) asm volatile("" : "+v"(lane_f));   // as lane_t above
-    run_flush64(ri0, cur0, p.GR, 4 * D, lane_f);
-    run_flush64(ri1, cur1, p.GR + D, 4 * D, lane_f);
-    if (HIDDEN) run_flush64(rg, curg, p.Gwbgc, D, lane_f);
-    atomicAdd(grow<float>(p.GS, (unsigned)c, 2 * D, lane_f), rs0);
-    atomicAdd(grow<float>(p.GS, (unsigned)c, 2 * D, D + lane_f), rs1);
+    run_flush64<A32>(ri0, cur0, p.GR, 4 * D, lane_f);
+    run_flush64<A32>(ri1, cur1, p.GR + D, 4 * D, lane_f);
+    if (HIDDEN) run_flush64<A32>(rg, curg, p.Gwbgc, D, lane_f);
+    atomicAdd(grow<float, A32>(p.GS, (unsigned)c, 2 * D, lane_f), rs0);
+    atomicAdd(grow<float, A32>(p.GS, (unsigned)c, 2 * D, D + lane_f), rs1);
     if (!TEAM) {
       const int nrows = min(n, NS);
       const int bond_of = w.abbond[ab0 + min(lane_f, nrows - 1)];
@@ -570,8 +576,8 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
         float* src = pacc + sl * PST;
         const float v0 = src[lane_f], v1 = src[D + lane_f];
         src[lane_f] = 0.f; src[D + lane_f] = 0.f;
-        atomicAdd(grow<float>(p.GR, (unsigned)bond, 4 * D, 2 * D + lane_f), v0);
-        atomicAdd(grow<float>(p.GR, (unsigned)bond, 4 * D, 3 * D + lane_f), v1);
+        atomicAdd(grow<float, A32>(p.GR, (unsigned)bond, 4 * D, 2 * D + lane_f), v0);
+        atomicAdd(grow<float, A32>(p.GR, (unsigned)bond, 4 * D, 3 * D + lane_f), v1);
       }
     }
     }   // active
@@ -590,8 +596,8 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
             v0 += src[lane]; v1 += src[D + lane];
             src[lane] = 0.f; src[D + lane] = 0.f;
           }
-          atomicAdd(grow<float>(p.GR, (unsigned)bond, 4 * D, 2 * D + lane), v0);
-          atomicAdd(grow<float>(p.GR, (unsigned)bond, 4 * D, 3 * D + lane), v1);
+          atomicAdd(grow<float, A32>(p.GR, (unsigned)bond, 4 * D, 2 * D + lane), v0);
+          atomicAdd(grow<float, A32>(p.GR, (unsigned)bond, 4 * D, 3 * D + lane), v1);
         }
       }
       __syncthreads();

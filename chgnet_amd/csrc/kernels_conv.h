@@ -540,13 +540,17 @@ static __global__ __launch_bounds__(BLOCK) void k_atomconv_image_rm(AtomConvArgs
 // consumed at the load (compare + select) it made every tile wait for it and, the memory counter being in order, for the gathers of
 // the next tile issued just before.
 __device__ __forceinline__ int bond_node(const AtomConvArgs& p, int k) { return p.hbc ? p.u_bnode[k] : -1; }
+// (A32: hbc lies above hb0 and its last row within 4 GiB of it -- the launcher's condition -- so the offset is formed in 32 bits)
+template <bool A32 = false>
 __device__ __forceinline__ long bond_row_offset(const AtomConvArgs& p, int k, int bn) {
-  return bn >= 0 ? (p.hbc - p.hb0) + (long)bn * D : (long)k * D;
+  if constexpr (A32) return (long)(bn >= 0 ? (unsigned)(p.hbc - p.hb0) + (unsigned)bn * D : (unsigned)k * D);
+  else return bn >= 0 ? (p.hbc - p.hb0) + (long)bn * D : (long)k * D;
 }
 
 // NW waves per workgroup.  The bond partial Q[k] = hb[k] . W_bond^T is contracted here (one more split contraction per tile)
 // instead of being read from a table: no gemm_Q / gemm_Qnode launches, 256 B instead of 512 B read per bond.
-template <int NW>
+// A32: address mode of the table rows (mfma_tile.h grow), picked per batch by the launcher.
+template <int NW, bool A32 = false>
 __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_atomconv_fwd(AtomConvArgs p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   h16x8* I2c = reinterpret_cast<h16x8*>(smem);
@@ -573,8 +577,8 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_atomconv_fwd(AtomConv
     const int r0 = row_of(0);
     c_nx = p.e_center[r0]; n_nx = p.e_nbr[r0];
     bn_nx = bond_node(p, r0 >> 1);
-    gather_issue_ph(gr, p.P, c_nx, p.P + 2 * D, n_nx, 4 * D, 4 * D, p.hb0, bond_row_offset(p, r0 >> 1, bn_nx), lane);
-    read_dl_g<VT>(p.wag, (unsigned)(r0 >> 1), D, g, wv_nx.t);
+    gather_issue_ph<A32>(gr, p.P, c_nx, p.P + 2 * D, n_nx, 4 * D, 4 * D, p.hb0, bond_row_offset<A32>(p, r0 >> 1, bn_nx), lane);
+    read_dl_g<VT, A32>(p.wag, (unsigned)(r0 >> 1), D, g, wv_nx.t);
     const int r1 = row_of(1);
     c_n2 = p.e_center[r1]; n_n2 = p.e_nbr[r1];
     bn_n2 = bond_node(p, r1 >> 1);
@@ -601,8 +605,8 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_atomconv_fwd(AtomConv
     c_nx = c_n2; n_nx = n_n2; bn_nx = bn_n2;
     if (v + 1 < ts.count) {
       const int r1 = row_of(v + 1);
-      gather_issue_ph(gr, p.P, c_nx, p.P + 2 * D, n_nx, 4 * D, 4 * D, p.hb0, bond_row_offset(p, r1 >> 1, bn_nx), lane);
-      read_dl_g<VT>(p.wag, (unsigned)(r1 >> 1), D, g, wv_nx.t);
+      gather_issue_ph<A32>(gr, p.P, c_nx, p.P + 2 * D, n_nx, 4 * D, 4 * D, p.hb0, bond_row_offset<A32>(p, r1 >> 1, bn_nx), lane);
+      read_dl_g<VT, A32>(p.wag, (unsigned)(r1 >> 1), D, g, wv_nx.t);
       const int r2 = row_of(v + 2);
       c_n2 = p.e_center[r2]; n_n2 = p.e_nbr[r2];
       bn_n2 = bond_node(p, r2 >> 1);
@@ -618,9 +622,7 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_atomconv_fwd(AtomConv
     }
     gemm_split<VT, 2 * VT, false, true>(z, Ib, 2 * D, x.t, j, g);
     if (p.Qout && !(j & 1) && j < nvalid) {   // the adjoint sweep gathers the partial as a table: one row per bond, from the even rows
-      float* q = p.Qout + (size_t)((row0 + j) >> 1) * 2 * D + 4 * g;
-#pragma unroll
-      for (int ft = 0; ft < 2 * VT; ++ft) *reinterpret_cast<f32x4*>(q + 16 * ft) = z[ft];
+      write_dl_g<2 * VT, A32>(p.Qout, (unsigned)((row0 + j) >> 1), 2 * D, g, z);
     }
     {
       f32x4 ps[2 * VT];
@@ -650,12 +652,12 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_atomconv_fwd(AtomConv
         if (2 * b < nvalid) {
           const int c1 = __builtin_amdgcn_readlane(c, 2 * b), c2 = __builtin_amdgcn_readlane(c, 2 * b + 1);
           if (c1 != cur1) {
-            tile_atomic_add(grow<float>(p.agg, (unsigned)cur1, D, lane), acc1);
+            tile_atomic_add(grow<float, A32>(p.agg, (unsigned)cur1, D, lane), acc1);
             acc1 = 0.f;
             cur1 = c1;
           }
           if (c2 != cur2) {
-            tile_atomic_add(grow<float>(p.agg, (unsigned)cur2, D, lane), acc2);
+            tile_atomic_add(grow<float, A32>(p.agg, (unsigned)cur2, D, lane), acc2);
             acc2 = 0.f;
             cur2 = c2;
           }
@@ -663,8 +665,8 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_atomconv_fwd(AtomConv
           acc2 += T[(2 * b + 1) * TS + lane];
         }
       }
-      tile_atomic_add(grow<float>(p.agg, (unsigned)cur1, D, lane), acc1);
-      tile_atomic_add(grow<float>(p.agg, (unsigned)cur2, D, lane), acc2);
+      tile_atomic_add(grow<float, A32>(p.agg, (unsigned)cur1, D, lane), acc1);
+      tile_atomic_add(grow<float, A32>(p.agg, (unsigned)cur2, D, lane), acc2);
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -679,7 +681,7 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_atomconv_fwd(AtomConv
 //
 // Scatter of one AtomConv-adjoint tile (gz rows in LDS, pair order).  Lane owns columns
 // (lane, lane+64) of the 128-wide rows.  dE/dQ[k] is a plain store (the tile owns bond k).
-template <bool STORE_GQ = true>
+template <bool STORE_GQ = true, bool A32 = false>
 __device__ __forceinline__ void acbwd_scatter(const float* T, int c, int nvalid, int k0, const AtomConvArgs& p, int lane) {
   // Both sides leave the tile as run sums: c1 is sorted along the pair order, and within one c1 the
   // bonds are ordered by c2 (then image), so periodic images of one neighbour are adjacent too
@@ -698,13 +700,13 @@ __device__ __forceinline__ void acbwd_scatter(const float* T, int c, int nvalid,
       }
       const int c1 = __builtin_amdgcn_readlane(c, 2 * b), c2 = __builtin_amdgcn_readlane(c, 2 * b + 1);
       if (c1 != cur1) {
-        float* d = p.GP + (size_t)cur1 * 4 * D + lane;
+        float* d = grow<float, A32>(p.GP, (unsigned)cur1, 4 * D, lane);
         tile_atomic_add(d, a1[0]); tile_atomic_add(d + 64, a1[1]); tile_atomic_add(d + 128, a1[2]); tile_atomic_add(d + 192, a1[3]);
         a1[0] = a1[1] = a1[2] = a1[3] = 0.f;
         cur1 = c1;
       }
       if (c2 != cur2) {
-        float* d = p.GP + (size_t)cur2 * 4 * D + lane;
+        float* d = grow<float, A32>(p.GP, (unsigned)cur2, 4 * D, lane);
         tile_atomic_add(d, a2[0]); tile_atomic_add(d + 64, a2[1]); tile_atomic_add(d + 128, a2[2]); tile_atomic_add(d + 192, a2[3]);
         a2[0] = a2[1] = a2[2] = a2[3] = 0.f;
         cur2 = c2;
@@ -713,9 +715,9 @@ __device__ __forceinline__ void acbwd_scatter(const float* T, int c, int nvalid,
       a2[0] += o0; a2[1] += o1; a2[2] += e0; a2[3] += e1;   // atom c2: centre part <- odd row, neighbour part <- even row
     }
   }
-  float* d1 = p.GP + (size_t)cur1 * 4 * D + lane;
+  float* d1 = grow<float, A32>(p.GP, (unsigned)cur1, 4 * D, lane);
   tile_atomic_add(d1, a1[0]); tile_atomic_add(d1 + 64, a1[1]); tile_atomic_add(d1 + 128, a1[2]); tile_atomic_add(d1 + 192, a1[3]);
-  float* d2 = p.GP + (size_t)cur2 * 4 * D + lane;
+  float* d2 = grow<float, A32>(p.GP, (unsigned)cur2, 4 * D, lane);
   tile_atomic_add(d2, a2[0]); tile_atomic_add(d2 + 64, a2[1]); tile_atomic_add(d2 + 128, a2[2]); tile_atomic_add(d2 + 192, a2[3]);
 }
 
@@ -724,7 +726,7 @@ __device__ __forceinline__ void acbwd_scatter(const float* T, int c, int nvalid,
 // read back by a row GEMM (gemm_GQ: 1.4 ms per headline step at the HBM rate).  The 32 KB image of W_bond^T fits because the hidden
 // layer then uses the row-major images (18 KB per matrix for both directions instead of 32 KB; with the split images and 7 waves per workgroup
 // the kernel was 8 % slower: profiles/r04_experiments.md section 12).
-template <bool TRAIN>
+template <bool TRAIN, bool A32 = false>
 __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_atomconv_bwd(AtomConvArgs p) {
   constexpr bool FUSE_GQ = !TRAIN;   // the training sweep keeps the dE/dQ table (its weight gradients contract it)
   constexpr int NW = WAVES;
@@ -750,7 +752,7 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_atomconv_bwd(AtomConvAr
     const int row = max(0, min(ts.at(0) * TILE_ROWS + j, last_row));
     c = p.e_center[row]; n = p.e_nbr[row]; k = row >> 1;   // pair-ordered index arrays
     GatherRegs gr;
-    gather_issue128(gr, p.P, c, p.P + 2 * D, n, p.Q, k, 4 * D, 4 * D, 2 * D, lane);
+    gather_issue128<A32>(gr, p.P, c, p.P + 2 * D, n, p.Q, k, 4 * D, 4 * D, 2 * D, lane);
     if (TRAIN) atomconv_bwd_stage(smem, p, tid, 64 * NW);   // fine-tuning: the weights change every step
     else stage_image<ac_bwd_rm_image_floats() / 4, 64 * NW>(smem, p.image, tid);
     gather_commit128(gr, T, TS, lane);
@@ -772,10 +774,10 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_atomconv_bwd(AtomConvAr
       cn = p.e_center[row]; nn = p.e_nbr[row]; kn = row >> 1;
     }
     V64 wv, gm;
-    read_dl_g<VT>(p.wag, (unsigned)k, D, g, wv.t);
-    read_dl_g<VT>(p.GA, (unsigned)c, D, g, gm.t);
+    read_dl_g<VT, A32>(p.wag, (unsigned)k, D, g, wv.t);
+    read_dl_g<VT, A32>(p.GA, (unsigned)c, D, g, gm.t);
     const int k0 = row0 >> 1, nb = nvalid >> 1;
-    float* gwag_rows = p.Gwag + (size_t)k0 * D + lane;     // this tile owns these rows of Gwag: old values read here,
+    float* gwag_rows = grow<float, A32>(p.Gwag, (unsigned)k0, D, lane);     // this tile owns these rows of Gwag: old values read here,
     float prev[TILE_ROWS / 2];                             // under the forward recomputation
 #pragma unroll
     for (int b = 0; b < TILE_ROWS / 2; ++b) prev[b] = p.first_wag ? 0.f : gwag_rows[(size_t)min(b, nb - 1) * D];
@@ -812,7 +814,7 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_atomconv_bwd(AtomConvAr
     if (FUSE_GQ) {
       // dE/d h_bond[k] (+)= (gz(2b) + gz(2b+1)) . W_bond: contracted per direction (linear), the pair summed by a lane swap; the
       // even lane of a pair owns the bond's row (four 64-byte segments), plain read-modify-write: the tile owns bonds k0 .. k0 + 7
-      float* gb_row = p.Gb + (size_t)(k0 + (j >> 1)) * D + 4 * g;
+      float* gb_row = grow<float, A32>(p.Gb, (unsigned)(k0 + (j >> 1)), D, 4 * g);
       const bool owner = !(j & 1) && j < nvalid;
       V64 old = zero64();
       if (p.gb_accumulate && owner) {
@@ -834,12 +836,12 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_atomconv_bwd(AtomConvAr
     __builtin_amdgcn_wave_barrier();
     if (v + 1 < ts.count) {  // the next tile's gathers fly while this tile's run sums are formed and sent
       GatherRegs gr;
-      gather_issue128(gr, p.P, cn, p.P + 2 * D, nn, p.Q, kn, 4 * D, 4 * D, 2 * D, lane);
-      acbwd_scatter<!FUSE_GQ>(T, c, nvalid, k0, p, lane);
+      gather_issue128<A32>(gr, p.P, cn, p.P + 2 * D, nn, p.Q, kn, 4 * D, 4 * D, 2 * D, lane);
+      acbwd_scatter<!FUSE_GQ, A32>(T, c, nvalid, k0, p, lane);
       __builtin_amdgcn_wave_barrier();
       gather_commit128(gr, T, TS, lane);
     } else {   // the wave's last tile (MD-size batches: its only one) does not wait for rows nobody reads: 5.6k of 47k clocks per wave
-      acbwd_scatter<!FUSE_GQ>(T, c, nvalid, k0, p, lane);
+      acbwd_scatter<!FUSE_GQ, A32>(T, c, nvalid, k0, p, lane);
     }
     c = cn; n = nn; k = kn;
   }
@@ -929,7 +931,7 @@ __global__ __launch_bounds__(BLOCK) void k_angle_image(const float* w_ang, Gated
 
 // HIDDEN = true: BondConv (gated MLP with one hidden layer, weighted, aggregated over the owning bond)
 // HIDDEN = false: AngleUpdate (single gated layer, residual on the angle itself)
-template <bool HIDDEN, bool BWD, int NW = WAVES, bool TRAIN = false>
+template <bool HIDDEN, bool BWD, int NW = WAVES, bool TRAIN = false, bool A32 = false>
 __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_angle(AngleArgs p) {
   static_assert(!TRAIN || BWD, "TRAIN is a variant of the adjoint kernels");
   if (!TRAIN && p.skip_flag && *p.skip_flag == 1) return;   // a per-atom kernel does this launch's work (kernels_angle_w.h / kernels_angle_fa.h)
@@ -962,8 +964,8 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_angle(AngleArgs p) {
     const int a0 = row_of(0);
     ctr_nx = p.a_ctr[a0]; b1_nx = p.a_b1c[a0]; b2_nx = p.a_b2c[a0];
     if (PIPE) {
-      gather_issue128(gr_p, p.R, b1_nx, p.R + 2 * D, b2_nx, p.S, ctr_nx, 4 * D, 4 * D, 2 * D, lane);
-      read_dl_g<VT>(p.ang, (unsigned)a0, D, g, x_p.t);
+      gather_issue128<A32>(gr_p, p.R, b1_nx, p.R + 2 * D, b2_nx, p.S, ctr_nx, 4 * D, 4 * D, 2 * D, lane);
+      read_dl_g<VT, A32>(p.ang, (unsigned)a0, D, g, x_p.t);
       if (1 < ts.count) {
         const int a1 = row_of(1);
         ctr_n2 = p.a_ctr[a1]; b1_n2 = p.a_b1c[a1]; b2_n2 = p.a_b2c[a1];
@@ -1006,12 +1008,12 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_angle(AngleArgs p) {
       read_dl<2 * VT>(Trow, g, z);
       if (v + 1 < ts.count) {
         const int a1 = row_of(v + 1);
-        gather_issue128(gr_p, p.R, b1_n2, p.R + 2 * D, b2_n2, p.S, ctr_n2, 4 * D, 4 * D, 2 * D, lane_t);
+        gather_issue128<A32>(gr_p, p.R, b1_n2, p.R + 2 * D, b2_n2, p.S, ctr_n2, 4 * D, 4 * D, 2 * D, lane_t);
         // lane_t group recomputed in place (volatile: not hoisted): the loop-invariant p.ang + lane_t offset otherwise lives in a register pair
         // over the whole tile -- at 256 registers it is spilled, and its reload waits (vmcnt, in order) behind the gathers just issued
         int lane_here;
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_here));
-        read_dl_g<VT>(p.ang, (unsigned)a1, D, lane_here >> 4, x_p.t);
+        read_dl_g<VT, A32>(p.ang, (unsigned)a1, D, lane_here >> 4, x_p.t);
         ctr_nx = ctr_n2; b1_nx = b1_n2; b2_nx = b2_n2;
         if (v + 2 < ts.count) {   // (row index from the recomputed lane_t as well: the strength-reduced constant 2 stride + j was spilled too)
           const int a2 = max(0, min(ts.at(v + 2) * tstride + (lane_here & 15), p.n_angles - 1));
@@ -1020,16 +1022,16 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_angle(AngleArgs p) {
       }
     } else {
       // the angle rows are consumed (B operand of the first contraction) before the table sum is written
-      gather_rows64(T, TS, p.ang, a, lane_t);
+      gather_rows64<A32>(T, TS, p.ang, a, lane_t);
       __builtin_amdgcn_wave_barrier();
       read_dl<VT>(Trow, g, x.t);
       __builtin_amdgcn_wave_barrier();
-      gather_sum128(T, TS, p.R, b1, p.R + 2 * D, b2, p.S, ctr, 4 * D, 4 * D, 2 * D, lane_t);
+      gather_sum128<A32>(T, TS, p.R, b1, p.R + 2 * D, b2, p.S, ctr, 4 * D, 4 * D, 2 * D, lane_t);
       __builtin_amdgcn_wave_barrier();
       read_dl<2 * VT>(Trow, g, z);
     }
     Rows64 gy_rows;
-    if (BWD && !HIDDEN) rows64_issue(gy_rows, p.Gang, a, lane_t);   // AngleUpdate adjoint: dE/d(new angle), read under the first contraction
+    if (BWD && !HIDDEN) rows64_issue<A32>(gy_rows, p.Gang, a, lane_t);   // AngleUpdate adjoint: dE/d(new angle), read under the first contraction
     if (SPLIT == 2) gemm_rm<VT, 2 * VT, false, false>(z, reinterpret_cast<const _Float16*>(Wang), 2 * D, D, x.t, j, g, lane_t);
     else gemm_split<VT, 2 * VT, false, !BWD>(z, reinterpret_cast<const h16x8*>(Wang), 2 * D, x.t, j, g);
     if (BWD && !HIDDEN) {
@@ -1039,7 +1041,7 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_angle(AngleArgs p) {
     // (unconditional stores -- the rows past the end of the last tile go to 16 spare rows behind the array -- so that the compiler's count
     // of outstanding memory operations stays exact.  The stores cost this kernel 0.26 ms per headline launch (0.90 -> 1.16 ms) whichever
     // way they are issued: conditional or not, non-temporal or not; as whole 512-byte rows through the wave's LDS tile 1.28 ms.)
-    if (!BWD && p.zsave) write_dl_g_nt<2 * VT>(p.zsave, (unsigned)(valid ? a : p.n_angles + j), 2 * D, g, z);
+    if (!BWD && p.zsave) write_dl_g_nt<2 * VT, A32>(p.zsave, (unsigned)(valid ? a : p.n_angles + j), 2 * D, g, z);
     V64 zc{{z[0], z[1], z[2], z[3]}}, zg{{z[4], z[5], z[6], z[7]}};
     GatedState s;
     V64 y;
@@ -1048,8 +1050,8 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_angle(AngleArgs p) {
     __builtin_amdgcn_wave_barrier();
     V64 w1, w2;   // small L2-resident tables: loaded after the MFMA phase to keep its register pressure low
     if (HIDDEN) {
-      read_dl_g<VT>(p.wbgc, (unsigned)b1, D, g, w1.t);
-      read_dl_g<VT>(p.wbgc, (unsigned)b2, D, g, w2.t);
+      read_dl_g<VT, A32>(p.wbgc, (unsigned)b1, D, g, w1.t);
+      read_dl_g<VT, A32>(p.wbgc, (unsigned)b2, D, g, w2.t);
     }
     if (!BWD) {
       CHG_EV(ft) {
@@ -1058,13 +1060,13 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_angle(AngleArgs p) {
       }
       write_dl<VT>(Trow, g, y.t);
       __builtin_amdgcn_wave_barrier();
-      if (HIDDEN) seg_colsum_atomic<D>(T, TS, valid ? b1 : -1, nvalid, p.out, D, lane_t);
-      else scatter_rows64<false>(T, TS, p.out, a, nvalid, lane_t);
+      if (HIDDEN) seg_colsum_atomic<D, A32>(T, TS, valid ? b1 : -1, nvalid, p.out, D, lane_t);
+      else scatter_rows64<false, A32>(T, TS, p.out, a, nvalid, lane_t);
     } else {
       V64 gy, gzc, gzg;
       if (HIDDEN) {
         V64 g1, g2, gu;
-        read_dl_g<VT>(p.Gagg, (unsigned)b1, D, g, gu.t);
+        read_dl_g<VT, A32>(p.Gagg, (unsigned)b1, D, g, gu.t);
         CHG_EV(ft) {
           const f32x4 gyu = gu.t[ft] * y.t[ft];
           g1.t[ft] = gyu * w2.t[ft];      // dE/d wbgc[b1]
@@ -1074,8 +1076,8 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_angle(AngleArgs p) {
         write_dl<VT>(Trow, g, g1.t);
         write_dl<VT>(Trow + D, g, g2.t);
         __builtin_amdgcn_wave_barrier();
-        seg_colsum_atomic<D>(T, TS, valid ? b1 : -1, nvalid, p.Gwbgc, D, lane_t);
-        row_atomic_add<D>(T + D, TS, valid ? b2 : -1, nvalid, p.Gwbgc, D, lane_t);
+        seg_colsum_atomic<D, A32>(T, TS, valid ? b1 : -1, nvalid, p.Gwbgc, D, lane_t);
+        row_atomic_add<D, A32>(T + D, TS, valid ? b2 : -1, nvalid, p.Gwbgc, D, lane_t);
       } else {
         rows64_commit(gy_rows, T, TS, lane_t);             // dE/d(new angle) of this tile, issued above
         __builtin_amdgcn_wave_barrier();
@@ -1096,24 +1098,24 @@ __global__ __launch_bounds__(64 * NW) CHG_TWO_WAVES void k_angle(AngleArgs p) {
 #pragma unroll
           for (int it = 0; it < TILE_ROWS / 4; ++it) gang_old.v[it] = zero4();
         } else {
-          rows64_issue(gang_old, p.Gang, a, lane_t);
+          rows64_issue<A32>(gang_old, p.Gang, a, lane_t);
         }
         gemm_rm<2 * VT, VT, true, true>(ga.t, reinterpret_cast<const _Float16*>(Wang), 2 * D, D, gz, j, g, lane_t);
         write_dl<VT>(Trow, g, ga.t);
         __builtin_amdgcn_wave_barrier();
-        scatter_rows64_add(T, TS, p.Gang, a, nvalid, lane_t, gang_old);
+        scatter_rows64_add<false, A32>(T, TS, p.Gang, a, nvalid, lane_t, gang_old);
       } else {
         gemm_split<2 * VT, VT, true>(ga.t, reinterpret_cast<const h16x8*>(WangT), D, gz, j, g);
         write_dl<VT>(Trow, g, ga.t);
         __builtin_amdgcn_wave_barrier();
-        scatter_rows64<true>(T, TS, p.Gang, a, nvalid, lane_t);
+        scatter_rows64<true, A32>(T, TS, p.Gang, a, nvalid, lane_t);
       }
       __builtin_amdgcn_wave_barrier();
       write_dl<2 * VT>(Trow, g, gz);
       __builtin_amdgcn_wave_barrier();
-      seg_colsum_atomic<2 * D>(T, TS, valid ? b1 : -1, nvalid, p.GR, 4 * D, lane_t);
-      row_atomic_add<2 * D>(T, TS, valid ? b2 : -1, nvalid, p.GR + 2 * D, 4 * D, lane_t);
-      seg_colsum_atomic<2 * D>(T, TS, valid ? ctr : -1, nvalid, p.GS, 2 * D, lane_t);
+      seg_colsum_atomic<2 * D, A32>(T, TS, valid ? b1 : -1, nvalid, p.GR, 4 * D, lane_t);
+      row_atomic_add<2 * D, A32>(T, TS, valid ? b2 : -1, nvalid, p.GR + 2 * D, 4 * D, lane_t);
+      seg_colsum_atomic<2 * D, A32>(T, TS, valid ? ctr : -1, nvalid, p.GS, 2 * D, lane_t);
     }
     __builtin_amdgcn_wave_barrier();
   }

@@ -49,6 +49,11 @@ constexpr bool WIDE_RANGE = false;
 #endif
 constexpr float LO_SCALE = 2048.0f, LO_UNSCALE = 1.0f / LO_SCALE;   // low planes scaled by 2^11 in their own accumulator (see above)
 
+// low half of one value: f16((x - hi) * 2^11) as ONE mixed-precision FMA on the f16 high half, fma(hi, -2^11, x * 2^11) with xs = x * 2^11
+// (v_fma_mix*: reads the f16 operand as it is -- no v_cvt_f32_f16 back to f32).  x - hi and the power-of-two scaling are both exact in
+// f32, so this is the same number as the subtract-then-scale form, bit for bit (tests/test_split_fma_cpu.py).
+__device__ __forceinline__ _Float16 split_lo(_Float16 hi, float xs) { return (_Float16)__builtin_fmaf((float)hi, -LO_SCALE, xs); }
+
 // bytes of one split image of a [F][K] matrix (both planes)
 constexpr size_t split_image_bytes(int F, int K) { return (size_t)F * K * 4; }
 
@@ -71,7 +76,7 @@ __device__ __forceinline__ void stage_split(h16x8* img, const float* __restrict_
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       hi[e] = (_Float16)w[e];
-      lo[e] = (_Float16)((w[e] - (float)hi[e]) * LO_SCALE);
+      lo[e] = split_lo(hi[e], w[e] * LO_SCALE);
     }
     img[c] = hi;
     img[nchunks + c] = lo;
@@ -79,21 +84,43 @@ __device__ __forceinline__ void stage_split(h16x8* img, const float* __restrict_
 }
 
 // ---- operand split of 32 contraction values held by this lane (feature tiles 2 mk, 2 mk + 1) -------
+// 16 vector instructions (+ one s_nop) per eight values: 4 v_cvt_pk_f16_f32 (the high halves, two per register), 4 v_pk_mul_f32 (x * 2^11) and one
+// v_fma_mixlo_f16 / v_fma_mixhi_f16 per value, which reads the f16 high half from its half of the packed register (op_sel) and writes the
+// rounded f16 low half into its half of the result.  (Before: 24 -- every high half converted back with v_cvt_f32_f16, packed subtract
+// and multiply, and a second v_cvt_pk_f16_f32 per pair.)  Written as one asm statement because the compiler does not select this form
+// from split_lo: its vectoriser pairs the FMAs into v_pk_fma_f32, which needs the f32 high halves again (24 instructions, no gain),
+// and where it does select the mixed FMA it converts the high half a second time into a register of its own instead of using op_sel.
+// Two hazards the compiler cannot see inside the string, both settled by the statement itself:
+//  * gfx940+: a VALU result written with a destination half-select must not be read by the very next VALU instruction -- the four
+//    high-half writes come first, the low-half writes after them, so the register a v_fma_mixhi_f16 wrote is next touched four
+//    instructions later;
+//  * a VGPR written by the vector ALU needs two wait states before a matrix instruction reads it, and the low planes ARE the B operand
+//    of the next v_mfma: the statement ends with `s_nop 1` (the compiler, which pads this pair itself everywhere else, sees no
+//    producer here and would leave one state).
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, h16x8& hi, h16x8& lo) {
-  f32x4 ha, hb;      // the high halves back in f32; the residuals on vectors (packed subtract / multiply)
+  const f32x4 as = a * LO_SCALE, bs = b * LO_SCALE;      // packed multiplies (two values per issue slot)
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     hi[e] = (_Float16)a[e];
     hi[4 + e] = (_Float16)b[e];
-    ha[e] = (float)hi[e];
-    hb[e] = (float)hi[4 + e];
   }
-  const f32x4 la = (a - ha) * LO_SCALE, lb = (b - hb) * LO_SCALE;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    lo[e] = (_Float16)la[e];
-    lo[4 + e] = (_Float16)lb[e];
-  }
+  const u32x4 h = __builtin_bit_cast(u32x4, hi);         // (a0 a1) (a2 a3) (b0 b1) (b2 b3)
+  const float ns = -LO_SCALE;
+  unsigned l0, l1, l2, l3;
+  asm("v_fma_mixhi_f16 %0, %4, %8, %10 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+      "v_fma_mixhi_f16 %1, %5, %8, %12 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+      "v_fma_mixhi_f16 %2, %6, %8, %14 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+      "v_fma_mixhi_f16 %3, %7, %8, %16 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+      "v_fma_mixlo_f16 %0, %4, %8, %9 op_sel_hi:[1,0,0]\n\t"
+      "v_fma_mixlo_f16 %1, %5, %8, %11 op_sel_hi:[1,0,0]\n\t"
+      "v_fma_mixlo_f16 %2, %6, %8, %13 op_sel_hi:[1,0,0]\n\t"
+      "v_fma_mixlo_f16 %3, %7, %8, %15 op_sel_hi:[1,0,0]\n\t"
+      "s_nop 1"
+      : "=&v"(l0), "=&v"(l1), "=&v"(l2), "=&v"(l3)
+      : "v"(h[0]), "v"(h[1]), "v"(h[2]), "v"(h[3]), "s"(ns), "v"(as[0]), "v"(as[1]), "v"(as[2]), "v"(as[3]), "v"(bs[0]), "v"(bs[1]),
+        "v"(bs[2]), "v"(bs[3]));
+  lo = __builtin_bit_cast(h16x8, u32x4{l0, l1, l2, l3});
 }
 
 // max over the four lanes that share a tile row (cf. quad_sum)
@@ -278,7 +305,7 @@ __device__ __forceinline__ void stage_rm(_Float16* img, const float* __restrict_
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       hi[e] = (_Float16)w[e];
-      lo[e] = (_Float16)((w[e] - (float)hi[e]) * LO_SCALE);
+      lo[e] = split_lo(hi[e], w[e] * LO_SCALE);
     }
     *reinterpret_cast<h16x4*>(img + f * S + c) = hi;
     *reinterpret_cast<h16x4*>(lo_plane + f * S + c) = lo;

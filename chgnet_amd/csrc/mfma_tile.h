@@ -85,20 +85,25 @@ __device__ __forceinline__ float hsum4(f32x4 v) { return (v[0] + v[1]) + (v[2] +
 #define CHG_EW(ft, r) _Pragma("unroll") for (int ft = 0; ft < VT; ++ft) _Pragma("unroll") for (int r = 0; r < 4; ++r)
 
 // ---- global row addressing ------------------------------------------------------------------------------------------------
-// Row `r` of a row-major float table with `ld` floats per row, at float column `c`, with a 64-bit offset.  A 32-bit byte offset
-// against the uniform table base (`global_load ... v_off, s[base:base+1]`: one 32-bit multiply-add and one VGPR per address instead
-// of three 64-bit vector instructions and a register pair) measured (profiles/r05_experiments.md section 7): 231 -> 99 64-bit
-// address instructions in the BondConv adjoint, -1.5 % of its vector instructions, -1 % of the step -- not worth the 4 GiB-per-table
-// limit it brings (a 4096-structure batch has 4.2 GB of angle rows).
-template <class T>
+// Row `r` of a row-major float table with `ld` floats per row, at float column `c`.  Two address modes, a template parameter (A32) of
+// every helper below and of the tile kernels of a large batch, chosen PER BATCH at launch (engine_predict.hip addr32_mode):
+//   A32 = false  64-bit offset: v_mad_u64_u32 + v_lshl_add_u64 and a register pair per address -- any table size
+//   A32 = true   the byte offset r * ld * 4 + c * 4 in ONE unsigned 32-bit register against the uniform table base
+//                (`global_load ... v_off, s[base:base+1]`: one 32-bit multiply-add).  Valid while every span addressed from one base in
+//                the kernel is below 4 GiB -- the launcher's condition; it wraps beyond.
+// profiles/r05_experiments.md section 7 measured the 32-bit form as a compile-time switch (231 -> 99 64-bit address instructions in the
+// BondConv adjoint, -1 % of the step) and dropped it for the 4 GiB-per-table limit (a 4096-structure batch has 4.2 GB of angle rows);
+// per batch that limit costs nothing: profiles/r07_experiments.md.
+template <class T, bool A32 = false>
 __device__ __forceinline__ const T* grow(const float* __restrict__ base, unsigned r, int ld, int c) {
-  return reinterpret_cast<const T*>(base + (size_t)r * ld + c);
+  if constexpr (A32) return reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + (r * (unsigned)(4 * ld) + (unsigned)(4 * c)));
+  else return reinterpret_cast<const T*>(base + (size_t)r * ld + c);
 }
-template <class T>
+template <class T, bool A32 = false>
 __device__ __forceinline__ T* grow(float* __restrict__ base, unsigned r, int ld, int c) {
-  return reinterpret_cast<T*>(base + (size_t)r * ld + c);
+  if constexpr (A32) return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + (r * (unsigned)(4 * ld) + (unsigned)(4 * c)));
+  else return reinterpret_cast<T*>(base + (size_t)r * ld + c);
 }
-
 // ---- D-layout loads / stores ---------------------------------------------------------------
 // `row` points at feature 0 of the lane's row in a row-major buffer (LDS tile or global table)
 template <int NT>
@@ -112,28 +117,28 @@ __device__ __forceinline__ void write_dl(float* row, int g, const f32x4 (&x)[NT]
   for (int ft = 0; ft < NT; ++ft) *reinterpret_cast<f32x4*>(row + 16 * ft + 4 * g) = x[ft];
 }
 
-// the same for row `r` of a global table (32-bit offsets: grow above)
-template <int NT>
+// the same for row `r` of a global table (address mode: grow above)
+template <int NT, bool A32 = false>
 __device__ __forceinline__ void read_dl_g(const float* __restrict__ base, unsigned r, int ld, int g, f32x4 (&x)[NT]) {
 #pragma unroll
-  for (int ft = 0; ft < NT; ++ft) x[ft] = *grow<f32x4>(base, r, ld, 16 * ft + 4 * g);
+  for (int ft = 0; ft < NT; ++ft) x[ft] = *grow<f32x4, A32>(base, r, ld, 16 * ft + 4 * g);
 }
-template <int NT>
+template <int NT, bool A32 = false>
 __device__ __forceinline__ void write_dl_g(float* __restrict__ base, unsigned r, int ld, int g, const f32x4 (&x)[NT]) {
 #pragma unroll
-  for (int ft = 0; ft < NT; ++ft) *grow<f32x4>(base, r, ld, 16 * ft + 4 * g) = x[ft];
+  for (int ft = 0; ft < NT; ++ft) *grow<f32x4, A32>(base, r, ld, 16 * ft + 4 * g) = x[ft];
 }
 
 // streaming forms (non-temporal: the lines are not kept in L2, which the table gathers of the same kernel live on)
-template <int NT>
+template <int NT, bool A32 = false>
 __device__ __forceinline__ void read_dl_g_nt(const float* __restrict__ base, unsigned r, int ld, int g, f32x4 (&x)[NT]) {
 #pragma unroll
-  for (int ft = 0; ft < NT; ++ft) x[ft] = __builtin_nontemporal_load(grow<f32x4>(base, r, ld, 16 * ft + 4 * g));
+  for (int ft = 0; ft < NT; ++ft) x[ft] = __builtin_nontemporal_load(grow<f32x4, A32>(base, r, ld, 16 * ft + 4 * g));
 }
-template <int NT>
+template <int NT, bool A32 = false>
 __device__ __forceinline__ void write_dl_g_nt(float* __restrict__ base, unsigned r, int ld, int g, const f32x4 (&x)[NT]) {
 #pragma unroll
-  for (int ft = 0; ft < NT; ++ft) __builtin_nontemporal_store(x[ft], grow<f32x4>(base, r, ld, 16 * ft + 4 * g));
+  for (int ft = 0; ft < NT; ++ft) __builtin_nontemporal_store(x[ft], grow<f32x4, A32>(base, r, ld, 16 * ft + 4 * g));
 }
 
 // ---- MFMA GEMMs in swapped form ---------------------------------------------------------------
@@ -345,7 +350,7 @@ __device__ __forceinline__ void tile_atomic_add(float* p, float v) {
 // tile: [16][stride] LDS, W columns; lane `rr` holds the (sorted-run) key of row rr in `key`
 // (key < 0: skip).  Runs of equal keys are summed per column and flushed with one fp32 atomic
 // per (run, column); runs that continue in another tile meet in memory.
-template <int W>
+template <int W, bool A32 = false>
 __device__ __forceinline__ void seg_colsum_atomic(const float* tile, int stride, int key, int nvalid, float* __restrict__ dst,
                                                   int ldd, int lane) {
   constexpr int NC = W / 64;
@@ -359,7 +364,7 @@ __device__ __forceinline__ void seg_colsum_atomic(const float* tile, int stride,
     if (kk != cur) {
       if (cur >= 0) {
 #pragma unroll
-        for (int c = 0; c < NC; ++c) tile_atomic_add(grow<float>(dst, (unsigned)cur, ldd, 64 * c + lane), acc[c]);
+        for (int c = 0; c < NC; ++c) tile_atomic_add(grow<float, A32>(dst, (unsigned)cur, ldd, 64 * c + lane), acc[c]);
       }
 #pragma unroll
       for (int c = 0; c < NC; ++c) acc[c] = 0.f;
@@ -370,12 +375,12 @@ __device__ __forceinline__ void seg_colsum_atomic(const float* tile, int stride,
   }
   if (cur >= 0) {
 #pragma unroll
-    for (int c = 0; c < NC; ++c) tile_atomic_add(grow<float>(dst, (unsigned)cur, ldd, 64 * c + lane), acc[c]);
+    for (int c = 0; c < NC; ++c) tile_atomic_add(grow<float, A32>(dst, (unsigned)cur, ldd, 64 * c + lane), acc[c]);
   }
 }
 
 // every row goes to its own (unsorted) destination row: one 256-B coalesced atomic per 64 columns
-template <int W>
+template <int W, bool A32 = false>
 __device__ __forceinline__ void row_atomic_add(const float* tile, int stride, int key, int nvalid, float* __restrict__ dst,
                                                int ldd, int lane) {
 #pragma unroll
@@ -383,7 +388,7 @@ __device__ __forceinline__ void row_atomic_add(const float* tile, int stride, in
     const int kk = __builtin_amdgcn_readlane(key, rr);   // rows past the end carry key -1
     if (kk >= 0) {
 #pragma unroll
-      for (int c = 0; c < W / 64; ++c) tile_atomic_add(grow<float>(dst, (unsigned)kk, ldd, 64 * c + lane), tile[rr * stride + 64 * c + lane]);
+      for (int c = 0; c < W / 64; ++c) tile_atomic_add(grow<float, A32>(dst, (unsigned)kk, ldd, 64 * c + lane), tile[rr * stride + 64 * c + lane]);
     }
   }
 }
@@ -393,6 +398,7 @@ __device__ __forceinline__ void row_atomic_add(const float* tile, int stride, in
 // every load instruction covers two full rows and all 24 loads of a tile are in flight together.
 // Lane rr (< 16) holds the three row indices of tile row rr; they must be valid (clamped) even for
 // rows past the end of the problem.
+template <bool A32 = false>
 __device__ __forceinline__ void gather_sum128(float* tile, int stride, const float* __restrict__ t0, int i0,
                                               const float* __restrict__ t1, int i1, const float* __restrict__ t2, int i2,
                                               int ld0, int ld1, int ld2, int lane) {
@@ -408,9 +414,9 @@ __device__ __forceinline__ void gather_sum128(float* tile, int stride, const flo
   f32x4 a[TILE_ROWS / 2], b[TILE_ROWS / 2], c[TILE_ROWS / 2];
 #pragma unroll
   for (int it = 0; it < TILE_ROWS / 2; ++it) {
-    a[it] = *grow<f32x4>(t0, (unsigned)r0[it], ld0, 4 * t);
-    b[it] = *grow<f32x4>(t1, (unsigned)r1[it], ld1, 4 * t);
-    c[it] = *grow<f32x4>(t2, (unsigned)r2[it], ld2, 4 * t);
+    a[it] = *grow<f32x4, A32>(t0, (unsigned)r0[it], ld0, 4 * t);
+    b[it] = *grow<f32x4, A32>(t1, (unsigned)r1[it], ld1, 4 * t);
+    c[it] = *grow<f32x4, A32>(t2, (unsigned)r2[it], ld2, 4 * t);
   }
 #pragma unroll
   for (int it = 0; it < TILE_ROWS / 2; ++it) {
@@ -424,6 +430,7 @@ __device__ __forceinline__ void gather_sum128(float* tile, int stride, const flo
 struct GatherRegs { f32x4 a[TILE_ROWS / 2], b[TILE_ROWS / 2], c[TILE_ROWS / 2]; };
 __device__ __forceinline__ void gather_take(GatherRegs& gr);   // (defined below, next to GatherPH's)
 
+template <bool A32 = false>
 __device__ __forceinline__ void gather_issue128(GatherRegs& gr, const float* __restrict__ t0, int i0, const float* __restrict__ t1,
                                                 int i1, const float* __restrict__ t2, int i2, int ld0, int ld1, int ld2, int lane) {
   const int hw = lane >> 5, t = lane & 31;
@@ -435,9 +442,9 @@ __device__ __forceinline__ void gather_issue128(GatherRegs& gr, const float* __r
   }
 #pragma unroll
   for (int it = 0; it < TILE_ROWS / 2; ++it) {
-    gr.a[it] = *grow<f32x4>(t0, (unsigned)r0[it], ld0, 4 * t);
-    gr.b[it] = *grow<f32x4>(t1, (unsigned)r1[it], ld1, 4 * t);
-    gr.c[it] = *grow<f32x4>(t2, (unsigned)r2[it], ld2, 4 * t);
+    gr.a[it] = *grow<f32x4, A32>(t0, (unsigned)r0[it], ld0, 4 * t);
+    gr.b[it] = *grow<f32x4, A32>(t1, (unsigned)r1[it], ld1, 4 * t);
+    gr.c[it] = *grow<f32x4, A32>(t2, (unsigned)r2[it], ld2, 4 * t);
   }
 }
 __device__ __forceinline__ void gather_commit128(const GatherRegs& gr, float* tile, int stride, int lane) {
@@ -464,6 +471,7 @@ __device__ __forceinline__ void gather_take(GatherRegs& gr) {
 #pragma unroll
   for (int it = 0; it < TILE_ROWS / 2; ++it) asm volatile("" : "+v"(gr.a[it]), "+v"(gr.b[it]), "+v"(gr.c[it]));
 }
+template <bool A32 = false>
 __device__ __forceinline__ void gather_issue_ph(GatherPH& gr, const float* __restrict__ t0, int i0, const float* __restrict__ t1, int i1, int ld0,
                                                 int ld1, const float* __restrict__ hbase, long hoff, int lane) {
   const int hw = lane >> 5, t = lane & 31, sub = lane >> 4, t16 = lane & 15;
@@ -474,19 +482,24 @@ __device__ __forceinline__ void gather_issue_ph(GatherPH& gr, const float* __res
     const int rr = 2 * it + hw;
     r0[it] = __shfl(i0, rr); r1[it] = __shfl(i1, rr);
   }
+  // (A32: the launcher has checked that every row the offset can reach lies within 4 GiB above hbase: its low word is all of it)
   const int hlo = (int)(hoff & 0xffffffffL), hhi = (int)(hoff >> 32);
 #pragma unroll
   for (int it = 0; it < TILE_ROWS / 4; ++it) {
     const int rr = 4 * it + sub;
-    ho[it] = ((long)__shfl(hhi, rr) << 32) | (unsigned)__shfl(hlo, rr);
+    if constexpr (A32) ho[it] = (long)(unsigned)__shfl(hlo, rr);
+    else ho[it] = ((long)__shfl(hhi, rr) << 32) | (unsigned)__shfl(hlo, rr);
   }
 #pragma unroll
   for (int it = 0; it < TILE_ROWS / 2; ++it) {
-    gr.a[it] = *grow<f32x4>(t0, (unsigned)r0[it], ld0, 4 * t);
-    gr.b[it] = *grow<f32x4>(t1, (unsigned)r1[it], ld1, 4 * t);
+    gr.a[it] = *grow<f32x4, A32>(t0, (unsigned)r0[it], ld0, 4 * t);
+    gr.b[it] = *grow<f32x4, A32>(t1, (unsigned)r1[it], ld1, 4 * t);
   }
 #pragma unroll
-  for (int it = 0; it < TILE_ROWS / 4; ++it) gr.h[it] = *reinterpret_cast<const f32x4*>(hbase + ho[it] + 4 * t16);
+  for (int it = 0; it < TILE_ROWS / 4; ++it) {
+    if constexpr (A32) gr.h[it] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(hbase) + (4u * (unsigned)ho[it] + 16u * (unsigned)t16));
+    else gr.h[it] = *reinterpret_cast<const f32x4*>(hbase + ho[it] + 4 * t16);
+  }
 }
 __device__ __forceinline__ void gather_commit_p(const GatherPH& gr, float* tile, int stride, int lane) {
   const int hw = lane >> 5, t = lane & 31;
@@ -502,20 +515,21 @@ __device__ __forceinline__ void gather_commit_h(const GatherPH& gr, float* tile,
 // The read half of a row-wise read-modify-write, issued early (its round trip then runs under the
 // contraction that produces the increment); scatter_rows64_add finishes it.
 struct Rows64 { f32x4 v[TILE_ROWS / 4]; };
+template <bool A32 = false>
 __device__ __forceinline__ void rows64_issue(Rows64& rr, const float* __restrict__ src, int idx, int lane) {
   const int sub = lane >> 4, t = lane & 15;
   int r[TILE_ROWS / 4];
 #pragma unroll
   for (int it = 0; it < TILE_ROWS / 4; ++it) r[it] = __shfl(idx, 4 * it + sub);
 #pragma unroll
-  for (int it = 0; it < TILE_ROWS / 4; ++it) rr.v[it] = *grow<f32x4>(src, (unsigned)r[it], D, 4 * t);
+  for (int it = 0; it < TILE_ROWS / 4; ++it) rr.v[it] = *grow<f32x4, A32>(src, (unsigned)r[it], D, 4 * t);
 }
 __device__ __forceinline__ void rows64_commit(const Rows64& rr, float* tile, int stride, int lane) {
   const int sub = lane >> 4, t = lane & 15;
 #pragma unroll
   for (int it = 0; it < TILE_ROWS / 4; ++it) *reinterpret_cast<f32x4*>(tile + (4 * it + sub) * stride + 4 * t) = rr.v[it];
 }
-template <bool OPAQUE = false>
+template <bool OPAQUE = false, bool A32 = false>
 __device__ __forceinline__ void scatter_rows64_add(const float* tile, int stride, float* __restrict__ dst, int idx, int nvalid, int lane,
                                                    const Rows64& old) {
   const int sub = lane >> 4, t = lane & 15;
@@ -538,11 +552,12 @@ __device__ __forceinline__ void scatter_rows64_add(const float* tile, int stride
     // these stores: the wait for a scratch reload is a wait for every store before it -- 3 store round trips per tile
     int lim = nvalid - 4 * it;
     if (OPAQUE) asm volatile("" : "+v"(lim));
-    if (sub < lim) *grow<f32x4>(dst, (unsigned)r[it], D, 4 * t) = v[it];
+    if (sub < lim) *grow<f32x4, A32>(dst, (unsigned)r[it], D, 4 * t) = v[it];
   }
 }
 
 // contiguous or gathered 64-wide rows into an LDS tile (16 lanes per row, 4 rows per step)
+template <bool A32 = false>
 __device__ __forceinline__ void gather_rows64(float* tile, int stride, const float* __restrict__ src, int idx, int lane) {
   const int sub = lane >> 4, t = lane & 15;
   f32x4 v[TILE_ROWS / 4];
@@ -550,13 +565,13 @@ __device__ __forceinline__ void gather_rows64(float* tile, int stride, const flo
 #pragma unroll
   for (int it = 0; it < TILE_ROWS / 4; ++it) r[it] = __shfl(idx, 4 * it + sub);
 #pragma unroll
-  for (int it = 0; it < TILE_ROWS / 4; ++it) v[it] = *grow<f32x4>(src, (unsigned)r[it], D, 4 * t);
+  for (int it = 0; it < TILE_ROWS / 4; ++it) v[it] = *grow<f32x4, A32>(src, (unsigned)r[it], D, 4 * t);
 #pragma unroll
   for (int it = 0; it < TILE_ROWS / 4; ++it) *reinterpret_cast<f32x4*>(tile + (4 * it + sub) * stride + 4 * t) = v[it];
 }
 
 // LDS tile (64 wide) -> global rows (coalesced 256-B rows), plain store or read-modify-write add
-template <bool ACCUM>
+template <bool ACCUM, bool A32 = false>
 __device__ __forceinline__ void scatter_rows64(const float* tile, int stride, float* __restrict__ dst, int idx, int nvalid,
                                                int lane) {
   const int sub = lane >> 4, t = lane & 15;
@@ -566,7 +581,7 @@ __device__ __forceinline__ void scatter_rows64(const float* tile, int stride, fl
   for (int it = 0; it < TILE_ROWS / 4; ++it) r[it] = (unsigned)__shfl(idx, 4 * it + sub);
   if (ACCUM) {   // all loads first: one memory round trip for the tile, not one per step (idx of rows past nvalid is a valid row)
 #pragma unroll
-    for (int it = 0; it < TILE_ROWS / 4; ++it) v[it] = *grow<f32x4>(dst, r[it], D, 4 * t);
+    for (int it = 0; it < TILE_ROWS / 4; ++it) v[it] = *grow<f32x4, A32>(dst, r[it], D, 4 * t);
 #pragma unroll
     for (int it = 0; it < TILE_ROWS / 4; ++it) v[it] += *reinterpret_cast<const f32x4*>(tile + (4 * it + sub) * stride + 4 * t);
   } else {
@@ -575,7 +590,7 @@ __device__ __forceinline__ void scatter_rows64(const float* tile, int stride, fl
   }
 #pragma unroll
   for (int it = 0; it < TILE_ROWS / 4; ++it)
-    if (sub < nvalid - 4 * it) *grow<f32x4>(dst, r[it], D, 4 * t) = v[it];
+    if (sub < nvalid - 4 * it) *grow<f32x4, A32>(dst, r[it], D, 4 * t) = v[it];
 }
 
 }  // namespace chg

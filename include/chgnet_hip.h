@@ -170,7 +170,9 @@ int chg_engine_cell_stats(chg_engine* eng, int64_t* cell_builds, int64_t* all_pa
 /* int32 index array of a batch by pack.py name (e_center, e_nbr, e_d2u, u_u2d, a_ctr, ...) -- tests only; "wide_range": one int,
  * 1 when chg_batch_download has moved the batch to the wide-range sweeps (an activation beyond the f16 operand range); "route": five
  * ints (0 / 1) for the last prediction of the batch -- the launch sequence of MD-size batches, its chained row GEMMs, z rows kept for
- * the angle adjoints (zsave), the per-atom window index, TEAM mode */
+ * the angle adjoints (zsave), the per-atom window index, TEAM mode; a sixth int when the capacity allows: 1 = the large-batch tile
+ * kernels ran with 32-bit row offsets (every table span below 4 GiB; CHGNET_ADDR_MODE=32 / 64 forces a mode, CHGNET_ADDR32_MAX_BYTES
+ * moves the threshold), 0 = 64-bit */
 int chg_debug_fetch_i32(chg_engine* eng, chg_batch* batch, const char* name, int32_t* dst, int64_t capacity, int64_t* n_written);
 /* new positions / cells on an unchanged graph topology (finite differences, strain scans, a relaxation step that keeps its neighbours) */
 int chg_batch_update_geometry(chg_engine* eng, chg_batch* batch, const float* frac, const float* lattice);
