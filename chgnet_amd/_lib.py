@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = (
     "chg_relax_create_lbfgs", "chg_test_lbfgs_step",
     "chg_md_create", "chg_md_run", "chg_md_download", "chg_md_free", "chg_test_md_step",
     "chg_md_create_langevin", "chg_test_md_step_langevin",
+    "chg_md_create_nhc", "chg_md_download_nhc", "chg_test_md_step_nhc",
     "chg_hessian_vector", "chg_hessian_vector_strain",
 )
 
@@ -96,6 +97,8 @@ class MdOutHost(ctypes.Structure):
                 ("frame_positions", _dp), ("frame_momenta", _dp), ("frame_cell", _dp), ("frame_force", c_float_p),
                 ("frame_stress", c_float_p), ("frame_crystal_fea", c_float_p)]
 
+
+MD_NHC_STATE = 20   # include/chgnet_hip.h CHG_MD_NHC_STATE
 
 _POINTER_OF = {"float64": ctypes.POINTER(ctypes.c_double), "float32": c_float_p, "int32": c_int_p}
 
@@ -224,6 +227,9 @@ def load() -> ctypes.CDLL:
     u64p = ctypes.POINTER(ctypes.c_uint64)
     lib.chg_md_create_langevin.argtypes = [*lib.chg_md_create.argtypes[:5], ctypes.c_double, u64p, ctypes.POINTER(vp)]
     lib.chg_test_md_step_langevin.argtypes = [*lib.chg_test_md_step.argtypes, ctypes.c_double, u64p]
+    lib.chg_md_create_nhc.argtypes = [*lib.chg_md_create.argtypes[:5], ctypes.c_int32, ctypes.POINTER(vp)]
+    lib.chg_md_download_nhc.argtypes = [vp, vp, dp, dp, ctypes.c_int32]
+    lib.chg_test_md_step_nhc.argtypes = [*lib.chg_test_md_step.argtypes, ctypes.c_int32, dp]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is ctypes.c_int and name not in ("chg_device_count", "chg_profile_count"):

@@ -1,11 +1,13 @@
 // engine_md.hip -- batched molecular dynamics (chg_md_*): NVE, NVT Berendsen, NPT Berendsen (inhomogeneous and isotropic), NVT
-// Langevin (BAOAB with counter-based noise, chg_md_create_langevin; not in the reference), one independent replica per structure,
-// state in HBM (kernels_md.h).  Reference: MolecularDynamics, chgnet/model/dynamics.py:433-780.
+// Langevin (BAOAB with counter-based noise, chg_md_create_langevin; not in the reference), Nose-Hoover-chain NVT and isotropic NPT
+// (Martyna-Tobias-Klein, chg_md_create_nhc; not in the reference), one independent replica per structure, state in HBM
+// (kernels_md.h).  Reference: MolecularDynamics, chgnet/model/dynamics.py:433-780.
 //
 // One evaluation of chg_md_run is one evaluate_and_step of the shared driver (engine_stepper.h) on ALL replicas, with k_md_step as
 // the step launch (one workgroup per replica: finish the step, frame, start the next one).  Every replica runs the same number of
 // steps, so there is no compaction.  NPT takes two evaluations per step, as ASE does: the barostat's set_cell(scale_atoms=True)
-// moves the atoms and the forces are evaluated again before the first half kick.
+// moves the atoms and the forces are evaluated again before the first half kick.  The Nose-Hoover-chain NPT scales the cell inside
+// the step and takes one evaluation (task efs) like every other ensemble.
 #include "engine_stepper.h"
 
 #include "kernels_md.h"
@@ -19,16 +21,22 @@ struct chg_md : chgh::Stepper {
   double *r, *pm, *f, *m, *sd;
   int *si, *d_aoff;
   unsigned long long* seeds = nullptr;   // [B] noise keys (MD_NVT_LANGEVIN)
+  int chain_length = 0;                  // MD_NVT_NHC / MD_NPT_NHC
+  double* nhc = nullptr;                 // [B, MD_NHC] chain and barostat state
   // frame ring: K slots
   int K = 0, ring_head = 0, ring_count = 0;
   std::vector<int> ring_step;
   double *fr_scal, *fr_pos, *fr_mom, *fr_cell;
   float *fr_force, *fr_stress, *fr_cfea;
+  double* fr_cons = nullptr;             // [K, B] H - Epot (Nose-Hoover chains)
 };
 
 namespace {
 
 constexpr int FEA = chg::D;
+
+bool is_npt(int e) { return e == MD_NPT_BERENDSEN_INHOMOGENEOUS || e == MD_NPT_BERENDSEN; }   // the two-evaluation Berendsen loop
+bool is_nhc(int e) { return e == MD_NVT_NHC || e == MD_NPT_NHC; }
 
 void carve_md(chg_md* d, Carver& c) {
   const size_t B = d->B, N = d->N, K = d->K;
@@ -41,6 +49,8 @@ void carve_md(chg_md* d, Carver& c) {
   d->lat_next = c.take<double>(9 * B);
   d->si = c.take<int>(MD_SI * B);
   d->seeds = c.take<unsigned long long>(d->p.ensemble == MD_NVT_LANGEVIN ? B : 0);
+  d->nhc = c.take<double>(is_nhc(d->p.ensemble) ? MD_NHC * B : 0);
+  d->fr_cons = c.take<double>(is_nhc(d->p.ensemble) ? K * B : 0);
   d->d_aoff = c.take<int>(B + 1);
   d->d_sel = c.take<int>(B);
   d->retry = c.take<int>(B);
@@ -53,10 +63,19 @@ void carve_md(chg_md* d, Carver& c) {
   d->fr_cfea = c.take<float>(d->p.log_crystal_fea ? K * FEA * B : 0);
 }
 
-bool is_npt(int e) { return e == MD_NPT_BERENDSEN_INHOMOGENEOUS || e == MD_NPT_BERENDSEN; }
-
-// langevin: the caller is an entry point that carries friction and seeds (the only ones that may run MD_NVT_LANGEVIN)
-const char* bad_params(const chg_md_params* p, bool langevin = false, double friction = 0.0) {
+// langevin: the caller is an entry point that carries friction and seeds (the only ones that may run MD_NVT_LANGEVIN); chain_length
+// > 0 or < 0: one that carries the chain length (the only ones that may run MD_NVT_NHC / MD_NPT_NHC)
+const char* bad_params(const chg_md_params* p, bool langevin = false, double friction = 0.0, int chain_length = 0) {
+  if (chain_length != 0) {
+    if (!is_nhc(p->ensemble)) return "ensemble must be CHG_MD_NVT_NHC or CHG_MD_NPT_NHC";
+    if (chain_length < 1 || chain_length > MD_NHC_MAX) return "chain_length must be 1..4";
+    if (!(p->temperature > 0.0) || !std::isfinite(p->temperature)) return "temperature must be > 0 (the thermostat masses are kB T tau^2)";
+    if (!(p->taut > 0.0) || !std::isfinite(p->taut)) return "taut must be > 0";
+    if (p->ensemble == MD_NPT_NHC && (!(p->taup > 0.0) || !std::isfinite(p->taup) || !std::isfinite(p->pressure)))
+      return "taup must be > 0 and pressure finite";
+  } else if (is_nhc(p->ensemble)) {
+    return "CHG_MD_NVT_NHC / CHG_MD_NPT_NHC need a chain length: use chg_md_create_nhc";
+  }
   if (langevin) {
     if (p->ensemble != MD_NVT_LANGEVIN) return "ensemble must be CHG_MD_NVT_LANGEVIN";
     if (!(friction >= 0.0) || !std::isfinite(friction)) return "friction must be >= 0 and finite";
@@ -64,7 +83,7 @@ const char* bad_params(const chg_md_params* p, bool langevin = false, double fri
   } else if (p->ensemble == MD_NVT_LANGEVIN) {
     return "CHG_MD_NVT_LANGEVIN needs friction and seeds: use chg_md_create_langevin";
   }
-  if (p->ensemble < MD_NVE || p->ensemble > MD_NVT_LANGEVIN) return "unknown ensemble";
+  if (p->ensemble < MD_NVE || p->ensemble > MD_NPT_NHC) return "unknown ensemble";
   if (!(p->dt > 0.0) || !std::isfinite(p->dt)) return "dt must be > 0";
   if (!langevin && p->ensemble != MD_NVE && (!(p->taut > 0.0) || !(p->temperature >= 0.0))) return "taut must be > 0 and temperature >= 0";
   if (is_npt(p->ensemble) && (!(p->taup > 0.0) || !(p->compressibility > 0.0) || !std::isfinite(p->pressure)))
@@ -89,6 +108,7 @@ chg::MdStepArgs base_args(chg_md* d) {
     a.lg_sig = std::sqrt((1.0 - a.lg_c1 * a.lg_c1) * a.kB * p.temperature);
     a.seeds = d->seeds;
   }
+  if (is_nhc(p.ensemble)) { a.nhc = d->nhc; a.nhc_len = d->chain_length; }
   return a;
 }
 
@@ -118,29 +138,37 @@ void set_frame(chg_md* d, MdStepArgs& a, int step) {
   a.fr_force = d->fr_force + slot * 3 * N;
   a.fr_stress = d->fr_stress + slot * 9 * B;
   a.fr_cfea = d->p.log_crystal_fea ? d->fr_cfea + slot * FEA * B : nullptr;
+  a.fr_cons = is_nhc(d->p.ensemble) ? d->fr_cons + slot * B : nullptr;
   d->ring_step[slot] = step;
   d->ring_count += 1;
 }
 
 bool frame_due(const chg_md* d, int step) { return d->p.loginterval > 0 && step % d->p.loginterval == 0; }
 
-// chg_md_create (seeds null) and chg_md_create_langevin
+// chg_md_create (seeds null, chain_length 0), chg_md_create_langevin and chg_md_create_nhc (chain_length != 0)
 int create(chg_engine* eng, const char* fn, const chg_structs_host* h, const double* masses, const double* momenta, const chg_md_params* params,
-           double friction, const uint64_t* seeds, chg_md** out) {
+           double friction, const uint64_t* seeds, int chain_length, chg_md** out) {
   if (!eng || !h || !masses || !params || !out) return CHG_EINVAL;
   *out = nullptr;
-  if (const char* bad = bad_params(params, seeds != nullptr, friction)) { eng->err = std::string(fn) + ": " + bad; return CHG_EINVAL; }
+  if (const char* bad = bad_params(params, seeds != nullptr, friction, chain_length)) { eng->err = std::string(fn) + ": " + bad; return CHG_EINVAL; }
   TRY(check_structs(eng, fn, h));
   const int B = h->n_struct, N = h->n_atoms;
+  if (chain_length != 0)
+    for (int o = 0; o < B; ++o)
+      if (h->atom_off[o + 1] - h->atom_off[o] < 2) {
+        eng->err = std::string(fn) + ": a structure of one atom has no internal degrees of freedom to thermostat";
+        return CHG_EINVAL;
+      }
   for (int i = 0; i < N; ++i)
     if (!(masses[i] > 0.0)) { eng->err = std::string(fn) + ": masses must be > 0"; return CHG_EINVAL; }
   HIP_TRY(eng, hipSetDevice(eng->device));
   chg_md* d = new chg_md();
   d->p = *params;
   d->friction = friction;
+  d->chain_length = chain_length;
   d->K = params->loginterval > 0 ? params->ring_frames : 0;
   d->ring_step.assign(std::max(d->K, 1), 0);
-  d->task = CHG_TASK_E | CHG_TASK_F | ((is_npt(params->ensemble) || params->log_stress) ? CHG_TASK_S : 0u);
+  d->task = CHG_TASK_E | CHG_TASK_F | ((is_npt(params->ensemble) || params->ensemble == MD_NPT_NHC || params->log_stress) ? CHG_TASK_S : 0u);
   d->r_atom = params->r_atom; d->r_bond = params->r_bond; d->numerical_tol = params->numerical_tol;
   int s = alloc_state(eng, fn, d, h, 0, [&](Carver& c) { carve_md(d, c); });
   if (s != CHG_OK) { chg_md_free(eng, d); return s; }
@@ -154,6 +182,7 @@ int create(chg_engine* eng, const char* fn, const chg_structs_host* h, const dou
   up(d->sd, sd.data(), sizeof(double) * sd.size());
   up(d->si, si.data(), sizeof(int) * si.size());
   if (seeds) up(d->seeds, seeds, sizeof(uint64_t) * B);
+  if (chain_length != 0) up.zero(d->nhc, sizeof(double) * MD_NHC * (size_t)B);
   up(d->d_aoff, h->atom_off, sizeof(int) * (B + 1));
   up(d->frac_next, h->frac, sizeof(double) * 3 * N);
   up(d->lat_next, h->lattice, sizeof(double) * 9 * B);
@@ -171,13 +200,18 @@ extern "C" {
 
 int chg_md_create(chg_engine* eng, const chg_structs_host* h, const double* masses, const double* momenta, const chg_md_params* params,
                   chg_md** out) {
-  return create(eng, "chg_md_create", h, masses, momenta, params, 0.0, nullptr, out);
+  return create(eng, "chg_md_create", h, masses, momenta, params, 0.0, nullptr, 0, out);
 }
 
 int chg_md_create_langevin(chg_engine* eng, const chg_structs_host* h, const double* masses, const double* momenta,
                            const chg_md_params* params, double friction, const uint64_t* seeds, chg_md** out) {
   if (!seeds) return CHG_EINVAL;
-  return create(eng, "chg_md_create_langevin", h, masses, momenta, params, friction, seeds, out);
+  return create(eng, "chg_md_create_langevin", h, masses, momenta, params, friction, seeds, 0, out);
+}
+
+int chg_md_create_nhc(chg_engine* eng, const chg_structs_host* h, const double* masses, const double* momenta, const chg_md_params* params,
+                      int32_t chain_length, chg_md** out) {
+  return create(eng, "chg_md_create_nhc", h, masses, momenta, params, 0.0, nullptr, chain_length != 0 ? chain_length : -1, out);
 }
 
 int chg_md_run(chg_engine* eng, chg_md* d, int32_t n_steps) {
@@ -258,6 +292,21 @@ int chg_md_download(chg_engine* eng, chg_md* d, const chg_md_out_host* o) {
   return CHG_OK;
 }
 
+int chg_md_download_nhc(chg_engine* eng, chg_md* d, double* nhc_state, double* frame_conserved, int32_t frame_capacity) {
+  if (!eng || !d) return CHG_EINVAL;
+  if (!is_nhc(d->p.ensemble)) { eng->err = "chg_md_download_nhc: the handle was not created by chg_md_create_nhc"; return CHG_EINVAL; }
+  HIP_TRY(eng, hipSetDevice(eng->device));
+  const size_t B = d->B;
+  TRY(d2h(eng, nhc_state, d->nhc, MD_NHC * B));
+  const int take = std::min(d->ring_count, std::max(frame_capacity, 0));
+  for (int k = 0; k < take; ++k) {   // oldest first; the ring is left as it is (chg_md_download drains it)
+    const size_t slot = (size_t)((d->ring_head + k) % std::max(d->K, 1));
+    TRY(d2h(eng, frame_conserved ? frame_conserved + k * B : nullptr, d->fr_cons + slot * B, B));
+  }
+  HIP_TRY(eng, hipStreamSynchronize(eng->stream));
+  return CHG_OK;
+}
+
 int chg_md_free(chg_engine* eng, chg_md* d) {
   if (!d) return CHG_OK;
   release(eng, d);
@@ -269,30 +318,34 @@ int chg_md_free(chg_engine* eng, chg_md* d) {
 
 namespace {
 
-// chg_test_md_step (seeds null) and chg_test_md_step_langevin
+// chg_test_md_step (seeds and nhc null), chg_test_md_step_langevin and chg_test_md_step_nhc
 int test_step(chg_engine* eng, const char* fn, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
               double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy, const float* force,
-              const float* stress, double* frac_next, double* lat_next, double friction, const uint64_t* seeds) {
+              const float* stress, double* frac_next, double* lat_next, double friction, const uint64_t* seeds, int chain_length = 0,
+              double* nhc = nullptr) {
   if (!eng || !params || n_struct <= 0 || !atom_off || !r || !momenta || !forces || !masses || !sd || !si || !frac_next || !lat_next)
     return CHG_EINVAL;
   if ((flags & MD_ABSORB) && (!energy || !force)) return CHG_EINVAL;
   if (flags & ~(MD_ABSORB | MD_KICK2 | MD_START)) return CHG_EINVAL;
-  if (const char* bad = bad_params(params, seeds != nullptr, friction)) { eng->err = std::string(fn) + ": " + bad; return CHG_EINVAL; }
+  if (const char* bad = bad_params(params, seeds != nullptr, friction, chain_length)) { eng->err = std::string(fn) + ": " + bad; return CHG_EINVAL; }
+  if (params->ensemble == MD_NPT_NHC && (flags & MD_ABSORB) && !stress) return CHG_EINVAL;
   const size_t B = n_struct, N = atom_off[n_struct];
   if (atom_off[0] != 0) return CHG_EINVAL;
   for (size_t o = 0; o < B; ++o)
-    if (atom_off[o + 1] <= atom_off[o]) return CHG_EINVAL;
+    if (atom_off[o + 1] - atom_off[o] < (nhc ? 2 : 1)) return CHG_EINVAL;
   TestBuf bufs[] = {{r, r, sizeof(double) * 3 * N}, {momenta, momenta, sizeof(double) * 3 * N}, {forces, forces, sizeof(double) * 3 * N},
                     {masses, nullptr, sizeof(double) * N}, {sd, sd, sizeof(double) * MD_SD * B}, {si, si, sizeof(int) * MD_SI * B},
                     {atom_off, nullptr, sizeof(int) * (B + 1)}, {energy, nullptr, sizeof(float) * B}, {force, nullptr, sizeof(float) * 3 * N},
                     {stress, nullptr, sizeof(float) * 9 * B}, {frac_next, frac_next, sizeof(double) * 3 * N},
                     {lat_next, lat_next, sizeof(double) * 9 * B}, {nullptr, nullptr, sizeof(int) * B},
-                    {seeds, nullptr, sizeof(uint64_t) * B}};
+                    {seeds, nullptr, sizeof(uint64_t) * B}, {nhc, nhc, sizeof(double) * MD_NHC * B}};
   return run_test_step(eng, fn, bufs, [&] {
     chg_md tmp;
     tmp.p = *params;
     tmp.friction = friction;
     tmp.seeds = (unsigned long long*)bufs[13].d;
+    tmp.chain_length = chain_length;
+    tmp.nhc = (double*)bufs[14].d;
     MdStepArgs a = base_args(&tmp);
     a.r = (double*)bufs[0].d; a.p = (double*)bufs[1].d; a.f = (double*)bufs[2].d; a.m = (const double*)bufs[3].d;
     a.sd = (double*)bufs[4].d; a.si = (int*)bufs[5].d; a.aoff = (const int*)bufs[6].d;
@@ -323,6 +376,14 @@ int chg_test_md_step_langevin(chg_engine* eng, const chg_md_params* params, int3
   if (!seeds) return CHG_EINVAL;
   return test_step(eng, "chg_test_md_step_langevin", params, n_struct, atom_off, flags, r, momenta, forces, masses, sd, si, energy, force,
                    stress, frac_next, lat_next, friction, seeds);
+}
+
+int chg_test_md_step_nhc(chg_engine* eng, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
+                         double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy,
+                         const float* force, const float* stress, double* frac_next, double* lat_next, int32_t chain_length, double* nhc) {
+  if (!nhc) return CHG_EINVAL;
+  return test_step(eng, "chg_test_md_step_nhc", params, n_struct, atom_off, flags, r, momenta, forces, masses, sd, si, energy, force,
+                   stress, frac_next, lat_next, 0.0, nullptr, chain_length != 0 ? chain_length : -1, nhc);
 }
 
 }  // extern "C"

@@ -17,6 +17,10 @@
 //              MD_NVT_LANGEVIN (no reference counterpart; BAOAB, Leimkuhler & Matthews 2013): half kick, half drift, the
 //              Ornstein-Uhlenbeck step p <- c1 p + sqrt((1 - c1^2) m kB T) xi with counter-based noise (philox.h), mass-weighted
 //              fixcm, half drift.  tests/langevin_ref.py restates it.
+//              MD_NVT_NHC / MD_NPT_NHC (no reference counterpart; Martyna-Tobias-Klein with Nose-Hoover chains on the particles
+//              and on the isotropic barostat, Tuckerman et al., J. Phys. A 39 (2006) 5629): barostat chain, particle chain,
+//              barostat kick, half kick and drift with the strain-rate factors, cell scaled; MD_ABSORB | MD_KICK2 runs the mirror
+//              image after the kick.  One evaluation per step (phase stays 0), no fixcm.  tests/nhc_ref.py restates it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -27,11 +31,16 @@
 namespace chg {
 
 enum : int { MD_RUNNING = 0, MD_NONFINITE = 1 };
-enum : int { MD_NVE = 0, MD_NVT_BERENDSEN = 1, MD_NPT_BERENDSEN_INHOMOGENEOUS = 2, MD_NPT_BERENDSEN = 3, MD_NVT_LANGEVIN = 4 };
+enum : int { MD_NVE = 0, MD_NVT_BERENDSEN = 1, MD_NPT_BERENDSEN_INHOMOGENEOUS = 2, MD_NPT_BERENDSEN = 3, MD_NVT_LANGEVIN = 4,
+             MD_NVT_NHC = 5, MD_NPT_NHC = 6 };
 enum : int { MD_ABSORB = 1, MD_KICK2 = 2, MD_START = 4 };
 constexpr int MD_SD = 40;   // doubles per replica: L[9] L^-1[9] Epot Ekin T stress[9] (eV/A^3, no ideal gas) G[9] (sum p p / m) spare
 constexpr int MD_SI = 4;    // ints per replica: steps completed, status, phase, spare
 constexpr int MD_FRAME_SCAL = 3;   // frame scalars per replica: Epot (engine units), Ekin, T
+// Nose-Hoover chains, doubles per replica: particle chain velocities v[4] and positions eta[4], barostat chain vb[4] and xi[4] (the
+// first chain_length of each are used), strain rate veps, H - Epot of the last absorbed evaluation (eV), 2 spare
+constexpr int MD_NHC = 20;
+constexpr int MD_NHC_MAX = 4;
 
 struct MdStepArgs {
   // state, replica o owns atom rows aoff[o]..aoff[o+1] (the batch has the same numbering: every replica is evaluated every time)
@@ -60,7 +69,66 @@ struct MdStepArgs {
   // MD_NVT_LANGEVIN: c1 = exp(-friction dt), sig = sqrt((1 - c1^2) kB T), one noise key per replica
   double lg_c1, lg_sig;
   const unsigned long long* seeds;   // [B]
+  // MD_NVT_NHC / MD_NPT_NHC (null / 0 otherwise): chain state, chain length 1..MD_NHC_MAX, frame slot of H - Epot
+  double* nhc;            // [B, MD_NHC]
+  double* fr_cons;        // [B] or null
+  int nhc_len;
 };
+
+// masses and constants of the Nose-Hoover chains of one replica of n atoms
+struct NhcConst {
+  double kT, nf, alpha, Q0, Qk, Qb, W;
+  __device__ NhcConst(const MdStepArgs& a, int n) {
+    kT = a.kB * a.temperature;
+    nf = 3.0 * (n - 1);
+    alpha = 1.0 + 3.0 / nf;
+    Qk = kT * a.taut * a.taut;
+    Q0 = nf * Qk;
+    Qb = kT * a.taup * a.taup;
+    W = (nf + 3.0) * Qb;
+  }
+};
+
+// one sweep over the chain velocities, k = M-1 .. 0 (down) or 0 .. M-1: v[k] is scaled by exp(-tau/4 v[k+1]) around its kick tau/2 G(k),
+// G(0) = (K2 - dof kT) / Q0, G(k) = (Q[k-1] v[k-1]^2 - kT) / Qk.  Fully unrolled: v stays in registers.
+template <bool DOWN>
+__device__ inline void nhc_sweep(double (&v)[MD_NHC_MAX], int M, double Q0, double Qk, double K2, double dof, double kT, double tau) {
+#pragma unroll
+  for (int kk = 0; kk < MD_NHC_MAX; ++kk) {
+    constexpr int last = MD_NHC_MAX - 1;
+    const int k = DOWN ? last - kk : kk;
+    if (k < M) {
+      const double below = v[k > 0 ? k - 1 : 0];
+      const double G = k == 0 ? (K2 - dof * kT) / Q0 : ((k == 1 ? Q0 : Qk) * below * below - kT) / Qk;
+      const bool inner = k + 1 < M;
+      const double e = inner ? exp(-0.25 * tau * v[k < last ? k + 1 : last]) : 1.0;
+      v[k] = (v[k] * e + 0.5 * tau * G) * e;
+    }
+  }
+}
+
+// half a step (tau) of one chain in registers: returns the factor s for what it thermostats (K2 = twice its kinetic energy)
+__device__ inline double nhc_chain(double (&v)[MD_NHC_MAX], double (&eta)[MD_NHC_MAX], int M, double Q0, double Qk, double K2, double dof,
+                                   double kT, double tau) {
+  nhc_sweep<true>(v, M, Q0, Qk, K2, dof, kT, tau);
+  const double s = exp(-tau * v[0]);
+#pragma unroll
+  for (int k = 0; k < MD_NHC_MAX; ++k)
+    if (k < M) eta[k] += tau * v[k];
+  nhc_sweep<false>(v, M, Q0, Qk, K2 * s * s, dof, kT, tau);
+  return s;
+}
+
+// H - Epot of the extended system: kinetic energy, chain energies and, for NPT, Pext V and the barostat's
+__device__ inline double nhc_extended_energy(const NhcConst& c, const double* x, int M, double K2, bool npt, double pext, double vol) {
+  double h = 0.5 * K2;
+  for (int k = 0; k < M; ++k) h += 0.5 * (k == 0 ? c.Q0 : c.Qk) * x[k] * x[k] + (k == 0 ? c.nf : 1.0) * c.kT * x[4 + k];
+  if (npt) {
+    h += pext * vol + 0.5 * c.W * x[16] * x[16];
+    for (int k = 0; k < M; ++k) h += 0.5 * c.Qb * x[8 + k] * x[8 + k] + c.kT * x[12 + k];
+  }
+  return h;
+}
 
 static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -73,11 +141,13 @@ static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
   double* sd = a.sd + (size_t)MD_SD * o;
   int* si = a.si + (size_t)MD_SI * o;
   const bool npt = a.ensemble == MD_NPT_BERENDSEN_INHOMOGENEOUS || a.ensemble == MD_NPT_BERENDSEN;
+  const bool nhc = a.ensemble == MD_NVT_NHC || a.ensemble == MD_NPT_NHC, nhc_npt = a.ensemble == MD_NPT_NHC;
+  double* xs = nhc ? a.nhc + (size_t)MD_NHC * o : nullptr;
   const double hdt = 0.5 * a.dt;
 
   __shared__ double red[4][9];
   __shared__ int rfin[4];
-  __shared__ double sLinv[9], sM[9], s_lam, s_mean[3];
+  __shared__ double sLinv[9], sM[9], s_lam, s_mean[3], s_e[2];
   __shared__ int s_status, s_phase, s_go, s_steps;
 
   if (tid == 0) { s_status = si[1]; s_phase = si[2]; }
@@ -120,6 +190,99 @@ static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
         s_lam = 1.0;
       }
       advance = true;
+    } else if (nhc) {
+      // second half of the step: kick with the strain-rate factor and sum p p / m in one pass, thread 0 runs the barostat kick and the
+      // two chains (their factor s scales p, Ekin and G without another reduction), one scaling pass writes the frame's momenta
+      const bool kick = a.flags & MD_KICK2;
+      const bool frame = a.fr_scal != nullptr;
+      const NhcConst c(a, n);
+      const double e1 = kick ? exp(-0.5 * c.alpha * xs[16] * hdt) : 1.0;
+      double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+      for (int i = tid; i < n; i += 256) {
+        const float* fi = a.force + 3 * ((size_t)a0 + i);
+        double pi[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          const double fj = fi[j];
+          f[3 * i + j] = fj;
+          pi[j] = kick ? (p[3 * i + j] * e1 + hdt * fj) * e1 : p[3 * i + j];
+          p[3 * i + j] = pi[j];
+        }
+        const double im = 1.0 / m[i];
+        acc[1] += pi[0] * pi[0] * im; acc[2] += pi[1] * pi[1] * im; acc[3] += pi[2] * pi[2] * im;
+        acc[4] += pi[1] * pi[2] * im; acc[5] += pi[0] * pi[2] * im; acc[6] += pi[0] * pi[1] * im;
+        if (frame) {
+          const size_t ro = 3 * ((size_t)a0 + i);
+#pragma unroll
+          for (int j = 0; j < 3; ++j) { a.fr_pos[ro + j] = r[3 * i + j]; a.fr_force[ro + j] = fi[j]; }
+        }
+      }
+#pragma unroll
+      for (int k = 1; k < 7; ++k) acc[k] = wave_sum_f64(acc[k]);
+      if (lane == 0)
+        for (int k = 1; k < 7; ++k) red[wv][k] = acc[k];
+      __syncthreads();
+      if (tid == 0) {
+        double G[7];
+        for (int k = 1; k < 7; ++k) G[k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
+        double K2 = G[1] + G[2] + G[3], s = 1.0;
+        const double vol = fabs(det3(sd));
+        sd[18] = a.energy[o];
+        if (a.stress)
+          for (int i = 0; i < 9; ++i) sd[21 + i] = (double)a.stress[9 * (size_t)o + i] * a.stress_weight;
+        if (kick) {
+          const int M = a.nhc_len;
+          double v[MD_NHC_MAX], eta[MD_NHC_MAX];
+          double veps = xs[16];
+          if (nhc_npt) veps += hdt * (c.alpha * K2 - vol * (sd[21] + sd[25] + sd[29]) - 3.0 * a.pressure * vol) / c.W;
+#pragma unroll
+          for (int k = 0; k < MD_NHC_MAX; ++k) { v[k] = xs[k]; eta[k] = xs[4 + k]; }
+          s = nhc_chain(v, eta, M, c.Q0, c.Qk, K2, c.nf, c.kT, hdt);
+          K2 *= s * s;
+#pragma unroll
+          for (int k = 0; k < MD_NHC_MAX; ++k) { xs[k] = v[k]; xs[4 + k] = eta[k]; }
+          if (nhc_npt) {
+#pragma unroll
+            for (int k = 0; k < MD_NHC_MAX; ++k) { v[k] = xs[8 + k]; eta[k] = xs[12 + k]; }
+            veps *= nhc_chain(v, eta, M, c.Qb, c.Qb, c.W * veps * veps, 1.0, c.kT, hdt);
+#pragma unroll
+            for (int k = 0; k < MD_NHC_MAX; ++k) { xs[8 + k] = v[k]; xs[12 + k] = eta[k]; }
+            xs[16] = veps;
+          }
+          si[0] += 1;
+        }
+        const double ekin = 0.5 * K2;
+        const double T = 2.0 * ekin / (3.0 * n * a.kB);
+        const double cons = nhc_extended_energy(c, xs, a.nhc_len, K2, nhc_npt, a.pressure, vol);
+        xs[17] = cons;
+        sd[19] = ekin;
+        sd[20] = T;
+        const double s2 = s * s;
+        const double Gm[9] = {G[1], G[6], G[5], G[6], G[2], G[4], G[5], G[4], G[3]};
+        for (int i = 0; i < 9; ++i) sd[30 + i] = Gm[i] * s2;
+        s_lam = s;
+        if (frame) {
+          a.fr_scal[MD_FRAME_SCAL * (size_t)o] = a.energy[o];
+          a.fr_scal[MD_FRAME_SCAL * (size_t)o + 1] = ekin;
+          a.fr_scal[MD_FRAME_SCAL * (size_t)o + 2] = T;
+          if (a.fr_cons) a.fr_cons[o] = cons;
+          for (int i = 0; i < 9; ++i) a.fr_cell[9 * (size_t)o + i] = sd[i];
+          for (int i = 0; i < 9; ++i) a.fr_stress[9 * (size_t)o + i] = a.stress ? a.stress[9 * (size_t)o + i] : 0.0f;
+          if (a.cfea && a.fr_cfea)
+            for (int i = 0; i < a.fea_dim; ++i) a.fr_cfea[(size_t)a.fea_dim * o + i] = a.cfea[(size_t)a.fea_dim * o + i];
+        }
+      }
+      __syncthreads();
+      if (kick || frame) {
+        const double s = s_lam;
+        for (int i = tid; i < n; i += 256)
+#pragma unroll
+          for (int j = 0; j < 3; ++j) {
+            const double pj = p[3 * i + j] * s;
+            p[3 * i + j] = pj;
+            if (frame) a.fr_mom[3 * ((size_t)a0 + i) + j] = pj;
+          }
+      }
     } else {
       const bool kick = a.flags & MD_KICK2;
       const bool frame = a.fr_scal != nullptr;
@@ -221,6 +384,61 @@ static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
         const double pj = a.fixcm ? p[3 * i + j] - mi * s_mean[j] : p[3 * i + j];
         p[3 * i + j] = pj;
         r[3 * i + j] += hdt * pj / mi;
+      }
+      const double y0 = r[3 * i], y1 = r[3 * i + 1], y2 = r[3 * i + 2];
+      double* fr = a.frac_next + 3 * ((size_t)a0 + i);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) fr[j] = y0 * sLinv[j] + y1 * sLinv[3 + j] + y2 * sLinv[6 + j];
+    }
+    return;
+  }
+
+  if ((a.flags & MD_START) && nhc) {
+    // up to the evaluation: barostat chain, particle chain, barostat kick (cached stress, sum p p / m scaled by s^2), then one pass
+    // p <- (p s e1 + dt/2 f) e1, r <- (r e2 + dt p / m) e2 with e1 = exp(-alpha veps dt/4), e2 = exp(veps dt/2); the cell scales by e2^2
+    __syncthreads();   // sd, the chain state and p written above
+    if (tid == 0) {
+      const NhcConst c(a, n);
+      const int M = a.nhc_len;
+      double v[MD_NHC_MAX], eta[MD_NHC_MAX];
+      double veps = xs[16], K2 = sd[30] + sd[34] + sd[38];
+      if (nhc_npt) {
+#pragma unroll
+        for (int k = 0; k < MD_NHC_MAX; ++k) { v[k] = xs[8 + k]; eta[k] = xs[12 + k]; }
+        veps *= nhc_chain(v, eta, M, c.Qb, c.Qb, c.W * veps * veps, 1.0, c.kT, hdt);
+#pragma unroll
+        for (int k = 0; k < MD_NHC_MAX; ++k) { xs[8 + k] = v[k]; xs[12 + k] = eta[k]; }
+      }
+#pragma unroll
+      for (int k = 0; k < MD_NHC_MAX; ++k) { v[k] = xs[k]; eta[k] = xs[4 + k]; }
+      const double s = nhc_chain(v, eta, M, c.Q0, c.Qk, K2, c.nf, c.kT, hdt);
+      K2 *= s * s;
+#pragma unroll
+      for (int k = 0; k < MD_NHC_MAX; ++k) { xs[k] = v[k]; xs[4 + k] = eta[k]; }
+      double L[9];
+      for (int i = 0; i < 9; ++i) L[i] = sd[i];
+      if (nhc_npt) {
+        const double vol = fabs(det3(L));
+        veps += hdt * (c.alpha * K2 - vol * (sd[21] + sd[25] + sd[29]) - 3.0 * a.pressure * vol) / c.W;
+        xs[16] = veps;
+        const double eh = exp(veps * a.dt);
+        for (int i = 0; i < 9; ++i) { L[i] *= eh; sd[i] = L[i]; }
+        inv3(L, sd + 9);
+      }
+      s_lam = s;
+      s_e[0] = exp(-0.5 * c.alpha * veps * hdt);
+      s_e[1] = exp(0.5 * veps * a.dt);
+      for (int i = 0; i < 9; ++i) { sLinv[i] = sd[9 + i]; a.lat_next[9 * (size_t)o + i] = L[i]; }
+    }
+    __syncthreads();
+    const double e1 = s_e[0], e2 = s_e[1], se1 = s_lam * e1;
+    for (int i = tid; i < n; i += 256) {
+      const double idm = a.dt / m[i];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const double pj = (p[3 * i + j] * se1 + hdt * f[3 * i + j]) * e1;
+        p[3 * i + j] = pj;
+        r[3 * i + j] = (r[3 * i + j] * e2 + idm * pj) * e2;
       }
       const double y0 = r[3 * i], y1 = r[3 * i + 1], y2 = r[3 * i + 2];
       double* fr = a.frac_next + 3 * ((size_t)a0 + i);

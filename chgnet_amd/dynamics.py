@@ -17,8 +17,21 @@ centre-of-mass momentum is removed after every noise step (mass-weighted, 3 degr
 stays ``T = 2 Ekin / (3 n kB)`` as for the other ensembles: it equilibrates at ``temperature * (n - 1) / n``.
 tests/langevin_ref.py restates integrator and noise.
 
-Out of scope, refused with ``ValueError``: the Nose-Hoover thermostat (ASE ``NPT``), and NPT without ``bulk_modulus`` (the
-reference then fits an equation of state).  Deviations from the reference:
+Also beyond the reference: ``thermostat="Nose-Hoover-Chain"`` is the deterministic canonical thermostat (``ensemble="nvt"``) and the
+barostat that samples the isothermal-isobaric ensemble (``ensemble="npt"``; every Berendsen barostat only relaxes the mean pressure).
+The integrator is Martyna-Tobias-Klein with Nose-Hoover chains of ``chain_length`` (1-4, default 3) thermostats on the particles
+and, for NPT, on the barostat, in the reversible second-order factorisation of Tuckerman et al., J. Phys. A 39 (2006) 5629: one
+evaluation per step, isotropic cell scaling that keeps any cell shape, ``taut`` / ``taup`` (fs) as the thermostat and barostat
+periods, scalar ``pressure`` (GPa); ``bulk_modulus`` is not needed.  ``MDTrajectory.conserved`` holds the conserved extended energy
+(eV) of every frame and ``thermostat_state`` the chain and barostat variables, which stay in the device handle, so ``run(10);
+run(10)`` equals ``run(20)``; ``set_atoms`` opens a new handle with zeroed chains.  The centre-of-mass momentum is removed once,
+mass-weighted, when the atoms are set, and never per step (the equations conserve it; N_f = 3 (n - 1)), while the reported
+temperature stays ``T = 2 Ekin / (3 n kB)``: it equilibrates at ``temperature * (n - 1) / n``.  ``temperature <= 0`` and a
+one-atom structure are refused.  tests/nhc_ref.py restates the integrator.  This is not ASE's ``NPT`` class, which the reference
+calls "Nose-Hoover" (Melchionna leap-frog: upper-triangular cells only, conserved quantity of first order in the time step).
+
+Out of scope, refused with ``ValueError``: ``thermostat="Nose-Hoover"`` (ASE ``NPT``; use ``"Nose-Hoover-Chain"``), and NPT with a
+Berendsen barostat without ``bulk_modulus`` (the reference then fits an equation of state).  Deviations from the reference:
   - ``starting_temperature`` draws from a seeded numpy ``Generator`` (``seed``), not ASE's global RNG: same distribution,
     different draws;
   - a replica whose energy or forces are non-finite even on the engine's wide-range sweep stops with status ``NONFINITE`` and
@@ -45,7 +58,8 @@ FS = 1e-15 * (1e10 * np.sqrt(_E / _AMU))   # units.fs = 1e-15 * second
 KB = _KB_J / _E                             # units.kB, eV/K
 GPA = 1e9 * ((1 / _E) / 1e30)               # units.GPa = 1e9 * Pascal, eV/A^3
 
-ENSEMBLE_CODES = {"nve": 0, "nvt": 1, "npt_inhomogeneous": 2, "npt_berendsen": 3, "nvt_langevin": 4}
+ENSEMBLE_CODES = {"nve": 0, "nvt": 1, "npt_inhomogeneous": 2, "npt_berendsen": 3, "nvt_langevin": 4, "nvt_nhc": 5, "npt_nhc": 6}
+NHC_KINDS = ("nvt_nhc", "npt_nhc")
 STATUS_NAMES = ("RUNNING", "NONFINITE")
 _U64 = (1 << 64) - 1
 
@@ -94,15 +108,19 @@ class MDTrajectory:
         self.momenta: list[np.ndarray] = []
         self.temperatures: list[float] = []
         self.crystal_feas: list[np.ndarray] = []
+        self.conserved: list[float] = []          # thermostat="Nose-Hoover-Chain": the conserved extended energy (eV) of every frame
 
     def __len__(self) -> int:
         return len(self.energies)
 
     def save(self, filename: str) -> None:
-        """Pickle with TrajectoryObserver's keys (reference dynamics.py:389-405) plus momenta and temperature."""
+        """Pickle with TrajectoryObserver's keys (reference dynamics.py:389-405) plus momenta and temperature (and ``conserved``
+        when the ensemble has one)."""
         out_pkl = {"energy": self.energies, "forces": self.forces, "stresses": self.stresses, "magmoms": self.magmoms,
                    "atom_positions": self.atom_positions, "cell": self.cells, "atomic_number": self.atomic_numbers,
                    "momenta": self.momenta, "temperature": self.temperatures}
+        if self.conserved:
+            out_pkl["conserved"] = self.conserved
         with open(filename, "wb") as file:
             pickle.dump(out_pkl, file)
 
@@ -137,8 +155,11 @@ def _resolve(ensemble: str, thermostat: str, bulk_modulus) -> str:
     if ens not in ("nvt", "npt"):
         raise ValueError(f"Ensemble {ensemble!r} not supported, choose in 'nve', 'nvt', 'npt'")
     if th == "nose-hoover":
-        raise ValueError("thermostat='Nose-Hoover' (ASE NPT, upper-triangular cells) is not supported by the device MD; "
-                         "use 'Berendsen_inhomogeneous', 'Berendsen' (NVT) or 'npt_berendsen' (NPT)")
+        raise ValueError("thermostat='Nose-Hoover' (ASE NPT, upper-triangular cells) is not supported by the device MD; use "
+                         "'Nose-Hoover-Chain' (another integrator: Martyna-Tobias-Klein chains, second order, any cell shape), "
+                         "'Berendsen_inhomogeneous', 'Berendsen' (NVT) or 'npt_berendsen' (NPT)")
+    if th == "nose-hoover-chain":
+        return ens + "_nhc"
     if ens == "nvt":
         if th.startswith("berendsen"):
             return "nvt"
@@ -175,7 +196,8 @@ class _DeviceRun:
         self.stress = kind.startswith("npt") or bool(cfg["log_stress"])
         self.masses = np.ascontiguousarray(masses, np.float64)
         mom = np.ascontiguousarray(momenta, np.float64)
-        params = _lib.MdParams(ensemble=ENSEMBLE_CODES[kind], fixcm=1, dt=cfg["dt"], temperature=cfg["temperature"], taut=cfg["taut"],
+        self.nhc = kind in NHC_KINDS
+        params = _lib.MdParams(ensemble=ENSEMBLE_CODES[kind], fixcm=0 if self.nhc else 1, dt=cfg["dt"], temperature=cfg["temperature"], taut=cfg["taut"],
                                taup=cfg["taup"], pressure=cfg["pressure"], compressibility=cfg["compressibility"], kB=KB,
                                stress_weight=calc.stress_weight, loginterval=self.loginterval, ring_frames=self.RING,
                                log_stress=int(self.stress), log_crystal_fea=int(self.cfea), r_atom=conv.atom_graph_cutoff,
@@ -190,9 +212,14 @@ class _DeviceRun:
             self.eng._check(self.eng.lib.chg_md_create_langevin(
                 self.eng.handle, ctypes.byref(host), self.masses.ctypes.data_as(dp), mom.ctypes.data_as(dp), ctypes.byref(params),
                 cfg["friction"], keys.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(self.handle)))
+        elif self.nhc:                   # the chain length travels beside the params struct; the centre of mass is never touched
+            self.eng._check(self.eng.lib.chg_md_create_nhc(
+                self.eng.handle, ctypes.byref(host), self.masses.ctypes.data_as(dp), mom.ctypes.data_as(dp), ctypes.byref(params),
+                int(cfg["chain_length"]), ctypes.byref(self.handle)))
         else:
             self.eng._check(self.eng.lib.chg_md_create(self.eng.handle, ctypes.byref(host), self.masses.ctypes.data_as(dp),
                                                        mom.ctypes.data_as(dp), ctypes.byref(params), ctypes.byref(self.handle)))
+        self.chain_length = int(cfg["chain_length"]) if self.nhc else 0
         self.started = False
         self.step = 0
 
@@ -210,8 +237,22 @@ class _DeviceRun:
              "frame_crystal_fea": np.empty((K, B, 64), np.float32)}
         o = _lib.fill_out(_lib.MdOutHost(), d)
         o.frame_capacity = K
+        extra = {}
+        if self.nhc:                     # before chg_md_download drains the ring
+            extra = {"nhc_state": np.empty((B, _lib.MD_NHC_STATE)), "frame_conserved": np.empty((K, B))}
+            dp = ctypes.POINTER(ctypes.c_double)
+            self.eng._check(self.eng.lib.chg_md_download_nhc(self.eng.handle, self.handle, extra["nhc_state"].ctypes.data_as(dp),
+                                                             extra["frame_conserved"].ctypes.data_as(dp), K))
         self.eng._check(self.eng.lib.chg_md_download(self.eng.handle, self.handle, ctypes.byref(o)))
+        d.update(extra)
         return d
+
+    def thermostat_state(self, d: dict, i: int) -> dict | None:
+        """Chain and barostat variables of replica ``i`` from a download (ASE units): ``None`` for the other ensembles."""
+        if not self.nhc:
+            return None
+        x, M = d["nhc_state"][i], self.chain_length
+        return {"v": x[0:M].copy(), "eta": x[4:4 + M].copy(), "vb": x[8:8 + M].copy(), "xi": x[12:12 + M].copy(), "veps": float(x[16])}
 
     def run(self, steps: int, sink) -> dict:
         """``steps`` more steps in chunks whose frames fit the ring; every drained frame goes to ``sink(d, k)``.  Returns the final state."""
@@ -232,17 +273,31 @@ class _DeviceRun:
 
 class MolecularDynamics:
     """Molecular dynamics on the device (reference MolecularDynamics: same arguments and defaults, plus ``seed``, and
-    ``thermostat="Langevin"`` with ``friction`` in 1/fs for NVT, see the module docstring)."""
+    ``thermostat="Langevin"`` with ``friction`` in 1/fs for NVT and ``thermostat="Nose-Hoover-Chain"`` with ``chain_length`` for NVT and
+    NPT, see the module docstring)."""
 
     def __init__(self, atoms, *, model=None, ensemble: str = "nvt", thermostat: str = "Berendsen_inhomogeneous", temperature: float = 300,
                  starting_temperature: float | None = None, timestep: float = 2.0, pressure: float = 1.01325e-4, taut: float | None = None,
                  taup: float | None = None, bulk_modulus: float | None = None, trajectory: str | None = None, logfile: str | None = None,
                  loginterval: int = 1, crystal_feas_logfile: str | None = None, append_trajectory: bool = False,  # noqa: ARG002
                  on_isolated_atoms: str = "warn", return_site_energies: bool = False, use_device: str | None = None,
-                 seed: int | None = None, friction: float | None = None) -> None:
+                 seed: int | None = None, friction: float | None = None, chain_length: int | None = None) -> None:
         self.ensemble, self.thermostat = ensemble, thermostat
         self.kind = _resolve(ensemble, thermostat, bulk_modulus)
         langevin = self.kind == "nvt_langevin"
+        nhc = self.kind in NHC_KINDS
+        if chain_length is not None and not nhc:
+            raise ValueError(f"{chain_length=} belongs to thermostat='Nose-Hoover-Chain' (ensemble 'nvt' or 'npt')")
+        if nhc:
+            chain_length = 3 if chain_length is None else chain_length
+            if isinstance(chain_length, bool) or chain_length != int(chain_length) or not 1 <= int(chain_length) <= 4:
+                raise ValueError(f"{chain_length=} must be an integer from 1 to 4")
+            if np.ndim(pressure) != 0:
+                raise ValueError("pressure must be a scalar (GPa) with thermostat='Nose-Hoover-Chain': the cell scales isotropically")
+            if not (np.isfinite(temperature) and temperature > 0):
+                raise ValueError(f"{temperature=} must be > 0 with thermostat='Nose-Hoover-Chain' (the thermostat masses are kB T taut^2)")
+        self.chain_length = int(chain_length) if nhc else None
+        self.thermostat_state: dict | None = None
         if friction is not None and not langevin:
             raise ValueError(f"{friction=} belongs to ensemble='nvt', thermostat='Langevin'")
         friction = 0.01 if friction is None else float(friction)
@@ -266,7 +321,7 @@ class MolecularDynamics:
         compressibility = 0.0 if bulk_modulus is None else 1.0 / (bulk_modulus / 160.2176)
         self.cfg = {"dt": timestep * FS, "temperature": float(temperature), "taut": taut * FS, "taup": taup * FS, "pressure": pressure * GPA,
                     "compressibility": compressibility, "loginterval": int(loginterval), "crystal_fea": crystal_feas_logfile is not None,
-                    "log_stress": False, "friction": friction / FS}
+                    "log_stress": False, "friction": friction / FS, "chain_length": self.chain_length}
         self.trajectory, self.logfile, self.loginterval, self.timestep = trajectory, logfile, int(loginterval), timestep
         self.crystal_feas_logfile = crystal_feas_logfile
         self.starting_temperature, self.seed = starting_temperature, seed
@@ -298,6 +353,12 @@ class MolecularDynamics:
         self.close()
         rng = np.random.default_rng(self.seed)
         self._structure, self._masses, self._momenta = self._initial(atoms, self.starting_temperature, rng)
+        if self.kind in NHC_KINDS:
+            if len(self._masses) < 2:
+                raise ValueError("thermostat='Nose-Hoover-Chain' needs more than one atom: a single atom has no internal degree of freedom")
+            # once, mass-weighted; the integrator conserves the total momentum and never removes it
+            self._momenta = self._momenta - self._masses[:, None] * (self._momenta.sum(axis=0) / self._masses.sum())
+            self.thermostat_state = None
         self._step_offset = getattr(self, "nsteps", 0)
         self.nsteps = self._step_offset
         self.traj = MDTrajectory(self._structure.atomic_numbers)
@@ -347,6 +408,8 @@ class MolecularDynamics:
                 tr.atom_positions.append(d["frame_positions"][k, sl].copy())
                 tr.momenta.append(d["frame_momenta"][k, sl].copy())
                 tr.cells.append(d["frame_cell"][k, i].copy())
+                if run.nhc:
+                    tr.conserved.append(float(d["frame_conserved"][k, i]) + e)
                 if run.cfea:
                     cfeas[i].append(d["frame_crystal_fea"][k, i].copy())
                 if i == 0:
@@ -388,6 +451,7 @@ class MolecularDynamics:
         lat = d["cell"][0]
         self._structure = Structure(Lattice(lat), self._structure.atomic_numbers, d["positions"] @ np.linalg.inv(lat))
         self._momenta = d["momenta"].copy()
+        self.thermostat_state = self._run.thermostat_state(d, 0)
 
     # ------------------------------------------------------------------------------------------------------------------------
     @classmethod
@@ -395,7 +459,8 @@ class MolecularDynamics:
         """Run R independent replicas (possibly of different sizes) as one device handle: each gets the trajectory it would get
         alone with ``MolecularDynamics(structures[i], seed=seeds[i], **kwargs).run(steps)`` (with the Langevin thermostat ``seeds[i]`` is
         also replica i's noise key; ``seeds=None`` draws one per replica).  Returns, per replica, ``{"trajectory",
-        "final_structure", "momenta", "status", "n_steps"}``.  ``trajectory`` / ``logfile`` / ``crystal_feas_logfile`` are not
+        "final_structure", "momenta", "status", "n_steps", "thermostat_state"}`` (the last one ``None`` unless the thermostat is
+        "Nose-Hoover-Chain").  ``trajectory`` / ``logfile`` / ``crystal_feas_logfile`` are not
         written here."""
         structures = list(structures)
         if not structures:
@@ -427,5 +492,6 @@ class MolecularDynamics:
             lat = d["cell"][i]
             fin = Structure(Lattice(lat), structs[i].atomic_numbers, d["positions"][sl] @ np.linalg.inv(lat))
             out.append({"trajectory": tr, "final_structure": fin, "momenta": d["momenta"][sl].copy(),
-                        "status": STATUS_NAMES[d["status"][i]], "n_steps": int(d["n_steps"][i])})
+                        "status": STATUS_NAMES[d["status"][i]], "n_steps": int(d["n_steps"][i]),
+                        "thermostat_state": run.thermostat_state(d, i)})
         return out

@@ -110,7 +110,9 @@ typedef struct chg_out_host {
  * n_mlp_hidden / mlp_out_bias at 2; chg_batch_build_predict arrived at 3; the chg_relax_* entry points at 4; the chg_md_* entry points at 5;
  * chg_hessian_vector and chg_hessian_vector_strain were added at 5 without a bump: new entry points only, no struct or signature changed;
  * so were chg_md_create_langevin and chg_test_md_step_langevin, whose extra parameters travel as arguments, not in chg_md_params;
- * so were chg_relax_create_lbfgs and chg_test_lbfgs_step, whose parameters travel in a struct of their own, chg_lbfgs_params).  A binding compiled against another value must refuse the
+ * so were chg_relax_create_lbfgs and chg_test_lbfgs_step, whose parameters travel in a struct of their own, chg_lbfgs_params;
+ * so were chg_md_create_nhc, chg_md_download_nhc and chg_test_md_step_nhc: the chain length travels as an argument, the chain state and
+ * the conserved energy in arrays of their own).  A binding compiled against another value must refuse the
  * library: chg_engine_create COPIES *desc, so an older, shorter chg_model_desc would be read past its end. */
 #define CHG_ABI_VERSION 5
 int chg_abi_version(void);
@@ -340,7 +342,7 @@ int chg_test_lbfgs_step(chg_engine* eng, const chg_relax_params* params, const c
  * takes two evaluations per step, as ASE does (the barostat moves the atoms before the first half kick).  Units are ASE's: eV, A,
  * amu, time in A sqrt(amu / eV).  DESIGN.md "Molecular dynamics" states the semantics; tests/md_ref.py restates them in NumPy. */
 enum { CHG_MD_NVE = 0, CHG_MD_NVT_BERENDSEN = 1, CHG_MD_NPT_BERENDSEN_INHOMOGENEOUS = 2, CHG_MD_NPT_BERENDSEN = 3,
-       CHG_MD_NVT_LANGEVIN = 4 /* chg_md_create_langevin only */ };
+       CHG_MD_NVT_LANGEVIN = 4 /* chg_md_create_langevin only */, CHG_MD_NVT_NHC = 5, CHG_MD_NPT_NHC = 6 /* chg_md_create_nhc only */ };
 enum { CHG_MD_RUNNING = 0, CHG_MD_NONFINITE = 1 };
 typedef struct chg_md_params {
   int32_t ensemble;            /* CHG_MD_*                                                                                 */
@@ -393,6 +395,25 @@ int chg_md_create(chg_engine* eng, const chg_structs_host* host, const double* m
  * tests/langevin_ref.py restates integrator and noise in NumPy. */
 int chg_md_create_langevin(chg_engine* eng, const chg_structs_host* host, const double* masses, const double* momenta,
                            const chg_md_params* params, double friction, const uint64_t* seeds, chg_md** out);
+/* Nose-Hoover-chain NVT (CHG_MD_NVT_NHC) and isotropic NPT (CHG_MD_NPT_NHC), not in the reference: the Martyna-Tobias-Klein equations
+ * with a chain of chain_length (1..4) thermostats on the particles and another on the barostat, integrated reversibly to second order
+ * (Tuckerman et al., J. Phys. A 39 (2006) 5629), one evaluation per step (task efs for NPT), any cell shape: the cell only scales.
+ * With kT = kB temperature, N_f = 3 (n - 1): Q_1 = N_f kT taut^2, Q_k = kT taut^2, Q'_k = kT taup^2, W = (N_f + 3) kT taup^2.
+ * tests/nhc_ref.py restates the step in NumPy; DESIGN.md "Nose-Hoover chains" gives the equations.  temperature > 0, taut > 0 (NPT: taup > 0,
+ * pressure finite, eV/A^3); compressibility and fixcm are ignored: the centre-of-mass momentum is never touched, the caller removes it
+ * from the initial momenta.  Every structure needs at least two atoms.  chg_md_create refuses the two codes with CHG_EINVAL.  The
+ * handle is an ordinary chg_md for chg_md_run / chg_md_download / chg_md_free.
+ * State per replica, CHG_MD_NHC_STATE doubles, all zero at creation: chain velocities v[4] and positions eta[4] of the particles, vb[4]
+ * and xi[4] of the barostat (the first chain_length of each are used), the strain rate veps, H - Epot of the last evaluation (eV), 2 spare.
+ * H = Epot + sum p^2/2m + sum Q_k v_k^2 / 2 + N_f kT eta_1 + kT sum_{k>1} eta_k (+ Pext V + W veps^2 / 2 + sum Q'_k vb_k^2 / 2 + kT sum xi_k)
+ * is conserved. */
+#define CHG_MD_NHC_STATE 20
+int chg_md_create_nhc(chg_engine* eng, const chg_structs_host* host, const double* masses, const double* momenta, const chg_md_params* params,
+                      int32_t chain_length, chg_md** out);
+/* The chain state nhc_state [B, CHG_MD_NHC_STATE] and H - Epot (eV) of up to frame_capacity of the oldest frames in the ring,
+ * frame_conserved [K, B], in the order chg_md_download returns them.  The ring is NOT drained: call this before chg_md_download.  Null
+ * pointers are skipped.  CHG_EINVAL for a handle of another ensemble. */
+int chg_md_download_nhc(chg_engine* eng, chg_md* md, double* nhc_state, double* frame_conserved, int32_t frame_capacity);
 /* n_steps steps of every replica (the first call evaluates the initial configuration first and writes the frame of step 0).  A batch
  * whose results are non-finite is evaluated again on the wide-range sweep; a replica that is non-finite even there stops as
  * CHG_MD_NONFINITE with its state untouched.  CHG_EINVAL (nothing run) when the frames due do not fit the ring. */
@@ -411,6 +432,11 @@ int chg_test_md_step_langevin(chg_engine* eng, const chg_md_params* params, int3
                               double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy,
                               const float* force, const float* stress, double* frac_next, double* lat_next, double friction,
                               const uint64_t* seeds);
+/* The same for CHG_MD_NVT_NHC / CHG_MD_NPT_NHC: nhc [n_struct, CHG_MD_NHC_STATE] in place.  MD_START reads the cached forces, the stress
+ * sd[21..29] and the trace of sd[30..38]; stress is required with flag 1 for CHG_MD_NPT_NHC. */
+int chg_test_md_step_nhc(chg_engine* eng, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
+                         double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy,
+                         const float* force, const float* stress, double* frac_next, double* lat_next, int32_t chain_length, double* nhc);
 
 /* ---- exchange steps of the multi-GPU path, straight on RCCL (one communicator per process = per GPU) ----------
  * The reference is single-device; these carry what SURVEY 8e needs and nothing else: the all-gather of per-structure

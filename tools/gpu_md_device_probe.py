@@ -4,6 +4,8 @@ of R = 1, 8, 64 replicas of the 256-atom 2x2x2 Li9Co7O16 cell, NVT Berendsen at 
 
   --leg device --replicas R   one chg_md handle over R replicas (wall clock of run_batch: create, steps, download)
       --thermostat langevin   the same leg with the Langevin thermostat (BAOAB, 0.01 / fs, noise generated in the step kernel)
+      --thermostat nhc        the same leg with Nose-Hoover chains (3 thermostats); with --ensemble npt the isotropic barostat too
+                              (task efs: the stress is evaluated every step, so compare it with Berendsen NVT only as an upper bound)
       --repeats K             K timed runs in one process, one JSON line each (their spread is the run-to-run noise)
   --leg host                  one replica, BerendsenNVT + CHGNetCalculator.calculate per step
 
@@ -38,17 +40,20 @@ def main() -> None:
     ap.add_argument("--leg", choices=("device", "host"), required=True)
     ap.add_argument("--replicas", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--thermostat", choices=("berendsen", "langevin"), default="berendsen")
+    ap.add_argument("--thermostat", choices=("berendsen", "langevin", "nhc"), default="berendsen")
+    ap.add_argument("--ensemble", choices=("nvt", "npt"), default="nvt", help="npt: --thermostat nhc only")
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "md_device_probe.jsonl"))
     args = ap.parse_args()
+    if args.ensemble == "npt" and args.thermostat != "nhc":
+        ap.error("--ensemble npt is probed with --thermostat nhc only")
 
     from chgnet_amd import CHGNet, CHGNetCalculator
 
     W = dict(np.load(os.path.join(REPO, "tests", "golden", "weights_trained_like.npz")))
     lco = np.load(os.path.join(REPO, "tests", "golden", "case_li9co7o16.npz"))
     calc = CHGNetCalculator(model=CHGNet(state_dict=W))
-    out = {"leg": args.leg, "ensemble": "nvt", "thermostat": args.thermostat, "atoms_each": 256, "steps": args.steps, "timestep_fs": 2.0}
+    out = {"leg": args.leg, "ensemble": args.ensemble, "thermostat": args.thermostat, "atoms_each": 256, "steps": args.steps, "timestep_fs": 2.0}
     lines = []
     if args.leg == "device":
         from chgnet_amd.dynamics import MolecularDynamics
@@ -58,6 +63,8 @@ def main() -> None:
         kw = dict(model=calc, ensemble="nvt", temperature=300.0, starting_temperature=300.0, timestep=2.0, loginterval=args.steps)
         if args.thermostat == "langevin":
             kw.update(thermostat="Langevin", friction=0.01)
+        if args.thermostat == "nhc":
+            kw.update(ensemble=args.ensemble, thermostat="Nose-Hoover-Chain", chain_length=3)
         MolecularDynamics.run_batch(cells, 5, seeds=list(range(R)), **kw)          # warm-up: engine creation, first builds
         for rep in range(args.repeats):
             t0 = time.perf_counter()
