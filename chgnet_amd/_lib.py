@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = (
     "chg_md_create_langevin", "chg_test_md_step_langevin",
     "chg_md_create_nhc", "chg_md_download_nhc", "chg_test_md_step_nhc",
     "chg_hessian_vector", "chg_hessian_vector_strain",
+    "chg_relax_set_fixed", "chg_md_set_fixed", "chg_test_relax_step_fixed", "chg_test_lbfgs_step_fixed", "chg_test_md_step_fixed",
 )
 
 
@@ -230,6 +231,12 @@ def load() -> ctypes.CDLL:
     lib.chg_md_create_nhc.argtypes = [*lib.chg_md_create.argtypes[:5], ctypes.c_int32, ctypes.POINTER(vp)]
     lib.chg_md_download_nhc.argtypes = [vp, vp, dp, dp, ctypes.c_int32]
     lib.chg_test_md_step_nhc.argtypes = [*lib.chg_test_md_step.argtypes, ctypes.c_int32, dp]
+    # constraints: the mask [N,3] uint8 travels as an argument of entry points of its own
+    lib.chg_relax_set_fixed.argtypes = [vp, vp, u8p]
+    lib.chg_md_set_fixed.argtypes = [vp, vp, u8p]
+    lib.chg_test_relax_step_fixed.argtypes = [*lib.chg_test_relax_step.argtypes, u8p]
+    lib.chg_test_lbfgs_step_fixed.argtypes = [*lib.chg_test_lbfgs_step.argtypes, u8p]
+    lib.chg_test_md_step_fixed.argtypes = [*lib.chg_test_md_step.argtypes, ctypes.c_double, u64p, ctypes.c_int32, dp, u8p]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is ctypes.c_int and name not in ("chg_device_count", "chg_profile_count"):

@@ -9,6 +9,8 @@ in-repo MD smoke driver and the tests still work.
 
 from __future__ import annotations
 
+import warnings
+
 import numpy as np
 
 from chgnet_amd.graph.structure import Lattice, Structure
@@ -47,11 +49,96 @@ except ImportError:
 
 def atoms_to_structure(atoms) -> Structure:
     """ASE ``Atoms`` (or anything with get_cell / get_scaled_positions / get_atomic_numbers) or one
-    of our / pymatgen's structures -> ``Structure`` (replaces AseAtomsAdaptor, dynamics.py:156)."""
+    of our / pymatgen's structures -> ``Structure`` (replaces AseAtomsAdaptor, dynamics.py:156).  The ``constraints`` of an
+    ASE-like object become the ``selective_dynamics`` site property ([n, 3], True = free: pymatgen's convention), as
+    AseAtomsAdaptor does: ``FixAtoms`` (``index``) and ``FixCartesian`` (``index``, ``mask`` with True = held, ASE >= 3.23),
+    matched by class name; any other constraint is reported with a ``UserWarning`` and left out."""
     if hasattr(atoms, "frac_coords") and hasattr(atoms, "lattice"):
         return atoms
     cell = np.asarray(atoms.get_cell()[:] if hasattr(atoms.get_cell(), "__getitem__") else atoms.get_cell())
-    return Structure(Lattice(cell), np.asarray(atoms.get_atomic_numbers()), np.asarray(atoms.get_scaled_positions(wrap=False)))
+    structure = Structure(Lattice(cell), np.asarray(atoms.get_atomic_numbers()), np.asarray(atoms.get_scaled_positions(wrap=False)))
+    constraints = getattr(atoms, "constraints", None)
+    if constraints is None:
+        return structure
+    if not isinstance(constraints, (list, tuple)):
+        constraints = [constraints]
+    n = len(structure)
+    held, seen = np.zeros((n, 3), bool), False
+    for c in constraints:
+        name = type(c).__name__
+        if name not in ("FixAtoms", "FixCartesian"):
+            warnings.warn(f"constraint {name} is not supported by the device drivers and is ignored (FixAtoms and FixCartesian are honoured)",
+                          UserWarning, stacklevel=2)
+            continue
+        index = np.atleast_1d(np.asarray(c.index))
+        if index.dtype == bool:
+            index = np.flatnonzero(index)
+        if index.size and (index.min() < -n or index.max() >= n):
+            raise ValueError(f"constraint {name} names atom {int(index.max() if index.max() >= n else index.min())} of a structure with {n} atoms")
+        held[index] |= True if name == "FixAtoms" else np.asarray(c.mask, bool).reshape(-1, 3)
+        seen = True
+    if seen:
+        structure.add_site_property("selective_dynamics", (~held).tolist())
+    return structure
+
+
+def normalize_fixed(entry, n: int) -> np.ndarray | None:
+    """One ``fixed_atoms`` entry -> mask [n, 3] uint8 with 1 = held (``None`` stays ``None``): a sequence of atom indices, a bool [n]
+    array (True = the whole atom is held) or a bool [n, 3] array (True = the component is held).  ``ValueError`` for anything else."""
+    if entry is None:
+        return None
+    a = np.asarray(entry)
+    mask = np.zeros((n, 3), np.uint8)
+    if a.dtype == bool:
+        if a.shape == (n,):
+            mask[a] = 1
+        elif a.shape == (n, 3):
+            mask[a] = 1
+        else:
+            raise ValueError(f"a bool fixed_atoms mask must have shape ({n},) or ({n}, 3), got {a.shape}")
+        return mask
+    if a.size == 0:
+        return mask
+    if a.ndim != 1 or a.dtype.kind not in "iu":
+        raise ValueError("fixed_atoms must be a sequence of atom indices, a bool [n] array or a bool [n, 3] array")
+    if a.min() < -n or a.max() >= n:
+        raise ValueError(f"fixed_atoms index {int(a.max() if a.max() >= n else a.min())} is out of range for {n} atoms")
+    mask[a] = 1
+    return mask
+
+
+def structure_fixed(structure, fixed_atoms=None) -> np.ndarray | None:
+    """The mask [n, 3] uint8 (1 = held) of one structure: ``fixed_atoms`` when given, else its ``selective_dynamics`` site property
+    ([n, 3], True = free); ``None`` when there is neither."""
+    n = len(structure)
+    if fixed_atoms is not None:
+        return normalize_fixed(fixed_atoms, n)
+    sd = (getattr(structure, "site_properties", None) or {}).get("selective_dynamics")
+    if sd is None:
+        return None
+    sd = np.asarray(sd)
+    if sd.shape != (n, 3):
+        raise ValueError(f"selective_dynamics must have shape ({n}, 3), got {sd.shape}")
+    return (~sd.astype(bool)).astype(np.uint8)
+
+
+def check_fixed(mask: np.ndarray | None, *, moving_cell: bool, needs_dof: bool, what: str = "the structure") -> None:
+    """The refusals of ``chg_relax_set_fixed`` / ``chg_md_set_fixed``, raised as ``ValueError`` before anything reaches the device."""
+    if mask is None:
+        return
+    held = mask.astype(bool).sum(axis=1)
+    if moving_cell and np.any((held != 0) & (held != 3)):
+        raise ValueError(f"{what} holds only some cartesian components of atom {int(np.flatnonzero((held != 0) & (held != 3))[0])}: that has "
+                         "no meaning while the cell moves (hold the whole atom, or keep the cell fixed)")
+    if needs_dof and held.sum() == 3 * len(mask):
+        raise ValueError(f"{what} has no free component left for the thermostat")
+
+
+def join_fixed(masks: list, n_atoms) -> np.ndarray | None:
+    """Per-structure masks (``None``: nothing held) -> one [N, 3] uint8 array for the handle, or ``None`` when nothing is held at all."""
+    if all(m is None or not m.any() for m in masks):
+        return None
+    return np.ascontiguousarray(np.concatenate([np.zeros((int(n), 3), np.uint8) if m is None else m for m, n in zip(masks, n_atoms)]))
 
 
 def voigt(s: np.ndarray) -> np.ndarray:

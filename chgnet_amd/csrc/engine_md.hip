@@ -16,6 +16,7 @@ struct chg_md : chgh::Stepper {
   chg_md_params p{};
   double friction = 0.0;     // MD_NVT_LANGEVIN, inverse ASE time units
   bool started = false;      // the initial configuration has been evaluated (frame of step 0 written)
+  std::vector<double> p0;    // the momenta as created: chg_md_set_fixed derives the masked ones from them on every call
   int step = 0;              // steps completed (all replicas; a NONFINITE replica stops counting)
   // device: state + per-evaluation buffers
   double *r, *pm, *f, *m, *sd;
@@ -61,7 +62,11 @@ void carve_md(chg_md* d, Carver& c) {
   d->fr_force = c.take<float>(K * 3 * N);
   d->fr_stress = c.take<float>(K * 9 * B);
   d->fr_cfea = c.take<float>(d->p.log_crystal_fea ? K * FEA * B : 0);
+  d->d_fixed = c.take<unsigned char>(3 * N);
+  d->d_nfree = c.take<int>(B);
 }
+
+bool moving_cell(int e) { return is_npt(e) || e == MD_NPT_NHC; }
 
 // langevin: the caller is an entry point that carries friction and seeds (the only ones that may run MD_NVT_LANGEVIN); chain_length
 // > 0 or < 0: one that carries the chain length (the only ones that may run MD_NVT_NHC / MD_NPT_NHC)
@@ -109,12 +114,14 @@ chg::MdStepArgs base_args(chg_md* d) {
     a.seeds = d->seeds;
   }
   if (is_nhc(p.ensemble)) { a.nhc = d->nhc; a.nhc_len = d->chain_length; }
+  if (d->has_fixed) { a.fixed = d->d_fixed; a.nfree = d->d_nfree; }
   return a;
 }
 
 void launch_step(chg_engine* eng, const MdStepArgs& a, int grid) {
   LaunchScope ls(eng, "md_step");
-  hipLaunchKernelGGL(k_md_step, dim3((unsigned)grid), dim3(256), 0, eng->stream, a);
+  if (a.fixed) hipLaunchKernelGGL(k_md_step<true>, dim3((unsigned)grid), dim3(256), 0, eng->stream, a);
+  else hipLaunchKernelGGL(k_md_step<false>, dim3((unsigned)grid), dim3(256), 0, eng->stream, a);
 }
 
 // evaluate all replicas, then one step launch with `a` (flags and frame slot set by the caller)
@@ -186,8 +193,9 @@ int create(chg_engine* eng, const char* fn, const chg_structs_host* h, const dou
   up(d->d_aoff, h->atom_off, sizeof(int) * (B + 1));
   up(d->frac_next, h->frac, sizeof(double) * 3 * N);
   up(d->lat_next, h->lattice, sizeof(double) * 9 * B);
-  if (momenta) up(d->pm, momenta, sizeof(double) * 3 * N);
-  else up.zero(d->pm, sizeof(double) * 3 * (size_t)N);
+  d->p0.assign(3 * (size_t)N, 0.0);
+  if (momenta) std::memcpy(d->p0.data(), momenta, sizeof(double) * 3 * (size_t)N);
+  up(d->pm, d->p0.data(), sizeof(double) * 3 * N);
   up.zero(d->f, sizeof(double) * 3 * (size_t)N);
   if ((s = up.finish()) != CHG_OK) { chg_md_free(eng, d); return s; }
   *out = d;
@@ -212,6 +220,23 @@ int chg_md_create_langevin(chg_engine* eng, const chg_structs_host* h, const dou
 int chg_md_create_nhc(chg_engine* eng, const chg_structs_host* h, const double* masses, const double* momenta, const chg_md_params* params,
                       int32_t chain_length, chg_md** out) {
   return create(eng, "chg_md_create_nhc", h, masses, momenta, params, 0.0, nullptr, chain_length != 0 ? chain_length : -1, out);
+}
+
+int chg_md_set_fixed(chg_engine* eng, chg_md* d, const uint8_t* fixed) {
+  if (!eng || !d) return CHG_EINVAL;
+  const char* fn = "chg_md_set_fixed";
+  if (d->started) { eng->err = std::string(fn) + ": the run has already started"; return CHG_EINVAL; }
+  const size_t B = d->B, N = d->N;
+  std::vector<int> nfree(B);
+  if (fixed) TRY(check_fixed(eng, fn, d->B, d->h_aoff, fixed, moving_cell(d->p.ensemble), d->p.ensemble != MD_NVE, nfree.data()));
+  HIP_TRY(eng, hipSetDevice(eng->device));
+  {   // the momenta as created, with the held ones at 0: a later call with another mask, or with null, starts from the created ones again
+    std::vector<double> pm(d->p0);
+    for (size_t k = 0; fixed && k < 3 * N; ++k)
+      if (fixed[k]) pm[k] = 0.0;
+    HIP_TRY(eng, hipMemcpy(d->pm, pm.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
+  }
+  return upload_fixed(eng, fn, d, fixed, nfree.data());
 }
 
 int chg_md_run(chg_engine* eng, chg_md* d, int32_t n_steps) {
@@ -322,7 +347,7 @@ namespace {
 int test_step(chg_engine* eng, const char* fn, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
               double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy, const float* force,
               const float* stress, double* frac_next, double* lat_next, double friction, const uint64_t* seeds, int chain_length = 0,
-              double* nhc = nullptr) {
+              double* nhc = nullptr, const uint8_t* fixed = nullptr) {
   if (!eng || !params || n_struct <= 0 || !atom_off || !r || !momenta || !forces || !masses || !sd || !si || !frac_next || !lat_next)
     return CHG_EINVAL;
   if ((flags & MD_ABSORB) && (!energy || !force)) return CHG_EINVAL;
@@ -333,12 +358,15 @@ int test_step(chg_engine* eng, const char* fn, const chg_md_params* params, int3
   if (atom_off[0] != 0) return CHG_EINVAL;
   for (size_t o = 0; o < B; ++o)
     if (atom_off[o + 1] - atom_off[o] < (nhc ? 2 : 1)) return CHG_EINVAL;
+  std::vector<int> nfree(B);
+  if (fixed) TRY(check_fixed(eng, fn, (int)B, atom_off, fixed, moving_cell(params->ensemble), params->ensemble != MD_NVE, nfree.data()));
   TestBuf bufs[] = {{r, r, sizeof(double) * 3 * N}, {momenta, momenta, sizeof(double) * 3 * N}, {forces, forces, sizeof(double) * 3 * N},
                     {masses, nullptr, sizeof(double) * N}, {sd, sd, sizeof(double) * MD_SD * B}, {si, si, sizeof(int) * MD_SI * B},
                     {atom_off, nullptr, sizeof(int) * (B + 1)}, {energy, nullptr, sizeof(float) * B}, {force, nullptr, sizeof(float) * 3 * N},
                     {stress, nullptr, sizeof(float) * 9 * B}, {frac_next, frac_next, sizeof(double) * 3 * N},
                     {lat_next, lat_next, sizeof(double) * 9 * B}, {nullptr, nullptr, sizeof(int) * B},
-                    {seeds, nullptr, sizeof(uint64_t) * B}, {nhc, nhc, sizeof(double) * MD_NHC * B}};
+                    {seeds, nullptr, sizeof(uint64_t) * B}, {nhc, nhc, sizeof(double) * MD_NHC * B}, {fixed, nullptr, 3 * N},
+                    {fixed ? nfree.data() : nullptr, nullptr, sizeof(int) * B}};
   return run_test_step(eng, fn, bufs, [&] {
     chg_md tmp;
     tmp.p = *params;
@@ -354,6 +382,7 @@ int test_step(chg_engine* eng, const char* fn, const chg_md_params* params, int3
     a.frac_next = (double*)bufs[10].d; a.lat_next = (double*)bufs[11].d; a.retry = (int*)bufs[12].d;
     a.flags = flags;
     a.final_try = 1;
+    if (fixed) { a.fixed = (const unsigned char*)bufs[15].d; a.nfree = (const int*)bufs[16].d; }
     launch_step(eng, a, (int)B);
   });
 }
@@ -384,6 +413,26 @@ int chg_test_md_step_nhc(chg_engine* eng, const chg_md_params* params, int32_t n
   if (!nhc) return CHG_EINVAL;
   return test_step(eng, "chg_test_md_step_nhc", params, n_struct, atom_off, flags, r, momenta, forces, masses, sd, si, energy, force,
                    stress, frac_next, lat_next, 0.0, nullptr, chain_length != 0 ? chain_length : -1, nhc);
+}
+
+int chg_test_md_step_fixed(chg_engine* eng, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
+                           double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy,
+                           const float* force, const float* stress, double* frac_next, double* lat_next, double friction,
+                           const uint64_t* seeds, int32_t chain_length, double* nhc, const uint8_t* fixed) {
+  if (!params) return CHG_EINVAL;
+  const char* fn = "chg_test_md_step_fixed";
+  if (params->ensemble == MD_NVT_LANGEVIN) {
+    if (!seeds) return CHG_EINVAL;
+    return test_step(eng, fn, params, n_struct, atom_off, flags, r, momenta, forces, masses, sd, si, energy, force, stress, frac_next, lat_next,
+                     friction, seeds, 0, nullptr, fixed);
+  }
+  if (is_nhc(params->ensemble)) {
+    if (!nhc) return CHG_EINVAL;
+    return test_step(eng, fn, params, n_struct, atom_off, flags, r, momenta, forces, masses, sd, si, energy, force, stress, frac_next, lat_next,
+                     0.0, nullptr, chain_length != 0 ? chain_length : -1, nhc, fixed);
+  }
+  return test_step(eng, fn, params, n_struct, atom_off, flags, r, momenta, forces, masses, sd, si, energy, force, stress, frac_next, lat_next,
+                   0.0, nullptr, 0, nullptr, fixed);
 }
 
 }  // extern "C"

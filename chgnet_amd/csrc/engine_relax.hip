@@ -23,6 +23,8 @@ struct chg_relax : chgh::Stepper {
   // pinned host (Stepper::h_extra): batch -> original index and the step's statuses, in batch order
   int *h_orig, *h_status;
   int n_active = 0;
+  bool ran = false;                            // chg_relax_run has been called: the mask can no longer change
+  double* frac0 = nullptr;                     // the fractional coordinates as given (fully held atoms keep them)
 };
 
 namespace {
@@ -58,6 +60,9 @@ void carve_relax(chg_relax* r, Carver& c) {
   r->f_out = c.take<float>(3 * N);
   r->s_out = c.take<float>(9 * B);
   r->m_out = c.take<float>(N);
+  r->d_fixed = c.take<unsigned char>(3 * N);
+  r->d_nfree = c.take<int>(B);
+  r->frac0 = c.take<double>(3 * N);
 }
 
 // lbfgs null: the FIRE numbers of *p are checked; otherwise they are ignored and *lbfgs is checked
@@ -98,9 +103,11 @@ void init_state(const chg_structs_host* h, const chg_relax_params* p, int o, dou
   si[0] = si[1] = si[2] = si[3] = 0;
 }
 
-void launch_step(chg_engine* eng, const RelaxStepArgs& a, int grid) {
+// mk.fixed null: the unconstrained kernel
+void launch_step(chg_engine* eng, const RelaxStepArgs& a, const RelaxMask& mk, int grid) {
   LaunchScope ls(eng, "relax_step");
-  hipLaunchKernelGGL(k_relax_step, dim3((unsigned)grid), dim3(256), 0, eng->stream, a);
+  if (mk.fixed) hipLaunchKernelGGL(k_relax_step<true>, dim3((unsigned)grid), dim3(256), 0, eng->stream, a, mk);
+  else hipLaunchKernelGGL(k_relax_step<false>, dim3((unsigned)grid), dim3(256), 0, eng->stream, a, mk);
 }
 
 LbfgsStepArgs lbfgs_args(const chg_relax_params& p, const chg_lbfgs_params& lp, int M, size_t rows) {
@@ -114,9 +121,10 @@ LbfgsStepArgs lbfgs_args(const chg_relax_params& p, const chg_lbfgs_params& lp, 
 
 int ring_slots(const chg_relax_params& p, const chg_lbfgs_params& lp) { return std::max(1, std::min(lp.memory, p.max_steps)); }
 
-void launch_lbfgs(chg_engine* eng, const LbfgsStepArgs& a, int grid) {
+void launch_lbfgs(chg_engine* eng, const LbfgsStepArgs& a, const RelaxMask& mk, int grid) {
   LaunchScope ls(eng, "lbfgs_step");
-  hipLaunchKernelGGL(k_lbfgs_step, dim3((unsigned)grid), dim3(256), 0, eng->stream, a);
+  if (mk.fixed) hipLaunchKernelGGL(k_lbfgs_step<true>, dim3((unsigned)grid), dim3(256), 0, eng->stream, a, mk);
+  else hipLaunchKernelGGL(k_lbfgs_step<false>, dim3((unsigned)grid), dim3(256), 0, eng->stream, a, mk);
 }
 
 // chg_relax_create and chg_relax_create_lbfgs (lbfgs non-null)
@@ -187,6 +195,9 @@ int chg_relax_run(chg_engine* eng, chg_relax* r, int32_t n_steps, int32_t* n_act
   a.e_out = r->e_out; a.f_out = r->f_out; a.s_out = r->s_out; a.m_out = r->m_out; a.frac_eval = r->frac_eval; a.lat_eval = r->lat_eval;
   a.frac_next = r->frac_next; a.lat_next = r->lat_next; a.status_next = r->status_next; a.retry = r->retry;
   a.orig = r->d_orig;
+  RelaxMask mk{};
+  if (r->has_fixed) { mk.fixed = r->d_fixed; mk.frac0 = r->frac0; }
+  r->ran = true;
   LbfgsStepArgs l{};
   if (r->lbfgs) {
     l = lbfgs_args(r->p, r->lp, r->M, (size_t)r->N + 3 * (size_t)r->B);
@@ -200,9 +211,9 @@ int chg_relax_run(chg_engine* eng, chg_relax* r, int32_t n_steps, int32_t* n_act
       const double maxstep = l.c.maxstep;
       l.c = a;
       l.c.maxstep = maxstep;
-      launch_lbfgs(eng, l, grid);
+      launch_lbfgs(eng, l, mk, grid);
     } else {
-      launch_step(eng, a, grid);
+      launch_step(eng, a, mk, grid);
     }
   };
   for (int it = 0; it < n_steps && r->n_active > 0; ++it) {
@@ -235,6 +246,20 @@ int chg_relax_run(chg_engine* eng, chg_relax* r, int32_t n_steps, int32_t* n_act
   return CHG_OK;
 }
 
+int chg_relax_set_fixed(chg_engine* eng, chg_relax* r, const uint8_t* fixed) {
+  if (!eng || !r) return CHG_EINVAL;
+  const char* fn = "chg_relax_set_fixed";
+  if (r->ran) { eng->err = std::string(fn) + ": the relaxation has already run"; return CHG_EINVAL; }
+  std::vector<int> nfree((size_t)r->B);
+  if (fixed) TRY(check_fixed(eng, fn, r->B, r->h_aoff, fixed, r->p.relax_cell != 0, false, nfree.data()));
+  HIP_TRY(eng, hipSetDevice(eng->device));
+  if (fixed && hipMemcpyAsync(r->frac0, r->h_frac, sizeof(double) * 3 * (size_t)r->N, hipMemcpyHostToDevice, eng->stream) != hipSuccess) {
+    eng->err = std::string(fn) + ": mask upload failed";
+    return CHG_EHIP;
+  }
+  return upload_fixed(eng, fn, r, fixed, nfree.data());
+}
+
 int chg_relax_download(chg_engine* eng, chg_relax* r, const chg_relax_out_host* o) {
   if (!eng || !r || !o) return CHG_EINVAL;
   HIP_TRY(eng, hipSetDevice(eng->device));
@@ -265,51 +290,72 @@ int chg_relax_free(chg_engine* eng, chg_relax* r) {
   return CHG_OK;
 }
 
-int chg_test_relax_step(chg_engine* eng, const chg_relax_params* params, int32_t n_struct, const int32_t* atom_off, double* q, double* v,
-                        double* sd, int32_t* si, const float* energy, const float* force, const float* stress, const float* magmom,
-                        double* frac_next, double* lat_next) {
+// chg_test_relax_step (fixed null) and chg_test_relax_step_fixed
+static int test_relax_step(chg_engine* eng, const char* fn, const chg_relax_params* params, int32_t n_struct, const int32_t* atom_off, double* q,
+                           double* v, double* sd, int32_t* si, const float* energy, const float* force, const float* stress,
+                           const float* magmom, double* frac_next, double* lat_next, const uint8_t* fixed) {
   if (!eng || !params || n_struct <= 0 || !atom_off || !q || !v || !sd || !si || !energy || !force || !stress || !frac_next || !lat_next)
     return CHG_EINVAL;
   const size_t B = n_struct, N = atom_off[n_struct], rows = N + 3 * B;
   if (atom_off[0] != 0) return CHG_EINVAL;
   for (size_t o = 0; o < B; ++o)
     if (atom_off[o + 1] <= atom_off[o]) return CHG_EINVAL;
+  std::vector<int> nfree(B);
+  if (fixed) TRY(check_fixed(eng, fn, (int)B, atom_off, fixed, params->relax_cell != 0, false, nfree.data()));
   TestBuf bufs[] = {{q, q, sizeof(double) * 3 * rows}, {v, v, sizeof(double) * 3 * rows}, {sd, sd, sizeof(double) * RELAX_SD * B},
                     {si, si, sizeof(int) * RELAX_SI * B}, {atom_off, nullptr, sizeof(int) * (B + 1)}, {energy, nullptr, sizeof(float) * B},
                     {force, nullptr, sizeof(float) * 3 * N}, {stress, nullptr, sizeof(float) * 9 * B}, {magmom, nullptr, sizeof(float) * N},
                     {frac_next, frac_next, sizeof(double) * 3 * N}, {lat_next, lat_next, sizeof(double) * 9 * B},
-                    {nullptr, nullptr, sizeof(int) * B}, {nullptr, nullptr, sizeof(int) * B}};
-  return run_test_step(eng, "chg_test_relax_step", bufs, [&] {
+                    {nullptr, nullptr, sizeof(int) * B}, {nullptr, nullptr, sizeof(int) * B}, {fixed, nullptr, 3 * N}};
+  return run_test_step(eng, fn, bufs, [&] {
     RelaxStepArgs a = step_args(*params, params->relax_cell);
     a.q = (double*)bufs[0].d; a.v = (double*)bufs[1].d; a.sd = (double*)bufs[2].d; a.si = (int*)bufs[3].d; a.aoff = (const int*)bufs[4].d;
     a.energy = (const float*)bufs[5].d; a.force = (const float*)bufs[6].d; a.stress = (const float*)bufs[7].d;
     a.magmom = magmom ? (const float*)bufs[8].d : nullptr; a.b_atom_off = (const int*)bufs[4].d;
     a.frac_next = (double*)bufs[9].d; a.lat_next = (double*)bufs[10].d; a.status_next = (int*)bufs[11].d; a.retry = (int*)bufs[12].d;
     a.final_try = 1;
-    launch_step(eng, a, (int)B);
+    RelaxMask mk{};
+    if (fixed) mk.fixed = (const unsigned char*)bufs[13].d;
+    launch_step(eng, a, mk, (int)B);
   });
 }
 
-int chg_test_lbfgs_step(chg_engine* eng, const chg_relax_params* params, const chg_lbfgs_params* lbfgs, int32_t n_struct,
-                        const int32_t* atom_off, double* q, double* r0, double* g0, double* S, double* Y, double* rho, double* sd, int32_t* si,
-                        const float* energy, const float* force, const float* stress, const float* magmom, int32_t final_try,
-                        double* frac_next, double* lat_next, int32_t* retry) {
+int chg_test_relax_step(chg_engine* eng, const chg_relax_params* params, int32_t n_struct, const int32_t* atom_off, double* q, double* v,
+                        double* sd, int32_t* si, const float* energy, const float* force, const float* stress, const float* magmom,
+                        double* frac_next, double* lat_next) {
+  return test_relax_step(eng, "chg_test_relax_step", params, n_struct, atom_off, q, v, sd, si, energy, force, stress, magmom, frac_next,
+                         lat_next, nullptr);
+}
+
+int chg_test_relax_step_fixed(chg_engine* eng, const chg_relax_params* params, int32_t n_struct, const int32_t* atom_off, double* q, double* v,
+                              double* sd, int32_t* si, const float* energy, const float* force, const float* stress, const float* magmom,
+                              double* frac_next, double* lat_next, const uint8_t* fixed) {
+  return test_relax_step(eng, "chg_test_relax_step_fixed", params, n_struct, atom_off, q, v, sd, si, energy, force, stress, magmom, frac_next,
+                         lat_next, fixed);
+}
+
+// chg_test_lbfgs_step (fixed null) and chg_test_lbfgs_step_fixed
+static int test_lbfgs_step(chg_engine* eng, const char* fn, const chg_relax_params* params, const chg_lbfgs_params* lbfgs, int32_t n_struct,
+                           const int32_t* atom_off, double* q, double* r0, double* g0, double* S, double* Y, double* rho, double* sd,
+                           int32_t* si, const float* energy, const float* force, const float* stress, const float* magmom, int32_t final_try,
+                           double* frac_next, double* lat_next, int32_t* retry, const uint8_t* fixed) {
   if (!eng || !params || !lbfgs || n_struct <= 0 || !atom_off || !q || !r0 || !g0 || !S || !Y || !rho || !sd || !si || !energy || !force ||
       !stress || !frac_next || !lat_next || !retry)
     return CHG_EINVAL;
-  const char* fn = "chg_test_lbfgs_step";
   TRY(check_params(eng, fn, params, lbfgs));
   const size_t B = n_struct, N = atom_off[n_struct], rows = N + 3 * B, M = ring_slots(*params, *lbfgs);
   if (atom_off[0] != 0) return CHG_EINVAL;
   for (size_t o = 0; o < B; ++o)
     if (atom_off[o + 1] <= atom_off[o]) return CHG_EINVAL;
+  std::vector<int> nfree(B);
+  if (fixed) TRY(check_fixed(eng, fn, (int)B, atom_off, fixed, params->relax_cell != 0, false, nfree.data()));
   TestBuf bufs[] = {{q, q, sizeof(double) * 3 * rows}, {r0, r0, sizeof(double) * 3 * rows}, {g0, g0, sizeof(double) * 3 * rows},
                     {S, S, sizeof(double) * M * 3 * rows}, {Y, Y, sizeof(double) * M * 3 * rows}, {rho, rho, sizeof(double) * M * B},
                     {sd, sd, sizeof(double) * RELAX_SD * B}, {si, si, sizeof(int) * RELAX_SI * B}, {atom_off, nullptr, sizeof(int) * (B + 1)},
                     {energy, nullptr, sizeof(float) * B}, {force, nullptr, sizeof(float) * 3 * N}, {stress, nullptr, sizeof(float) * 9 * B},
                     {magmom, nullptr, sizeof(float) * N}, {frac_next, frac_next, sizeof(double) * 3 * N},
                     {lat_next, lat_next, sizeof(double) * 9 * B}, {retry, retry, sizeof(int) * B}, {nullptr, nullptr, sizeof(int) * B},
-                    {nullptr, nullptr, sizeof(double) * M * B}, {nullptr, nullptr, sizeof(double) * 3 * rows}};
+                    {nullptr, nullptr, sizeof(double) * M * B}, {nullptr, nullptr, sizeof(double) * 3 * rows}, {fixed, nullptr, 3 * N}};
   return run_test_step(eng, fn, bufs, [&] {
     LbfgsStepArgs a = lbfgs_args(*params, *lbfgs, (int)M, rows);
     a.c.q = (double*)bufs[0].d; a.r0 = (double*)bufs[1].d; a.g0 = (double*)bufs[2].d; a.S = (double*)bufs[3].d; a.Y = (double*)bufs[4].d;
@@ -319,8 +365,26 @@ int chg_test_lbfgs_step(chg_engine* eng, const chg_relax_params* params, const c
     a.c.frac_next = (double*)bufs[13].d; a.c.lat_next = (double*)bufs[14].d; a.c.retry = (int*)bufs[15].d; a.c.status_next = (int*)bufs[16].d;
     a.abuf = (double*)bufs[17].d; a.w = (double*)bufs[18].d;
     a.c.final_try = final_try ? 1 : 0;
-    launch_lbfgs(eng, a, (int)B);
+    RelaxMask mk{};
+    if (fixed) mk.fixed = (const unsigned char*)bufs[19].d;
+    launch_lbfgs(eng, a, mk, (int)B);
   });
+}
+
+int chg_test_lbfgs_step(chg_engine* eng, const chg_relax_params* params, const chg_lbfgs_params* lbfgs, int32_t n_struct,
+                        const int32_t* atom_off, double* q, double* r0, double* g0, double* S, double* Y, double* rho, double* sd, int32_t* si,
+                        const float* energy, const float* force, const float* stress, const float* magmom, int32_t final_try,
+                        double* frac_next, double* lat_next, int32_t* retry) {
+  return test_lbfgs_step(eng, "chg_test_lbfgs_step", params, lbfgs, n_struct, atom_off, q, r0, g0, S, Y, rho, sd, si, energy, force, stress,
+                         magmom, final_try, frac_next, lat_next, retry, nullptr);
+}
+
+int chg_test_lbfgs_step_fixed(chg_engine* eng, const chg_relax_params* params, const chg_lbfgs_params* lbfgs, int32_t n_struct,
+                              const int32_t* atom_off, double* q, double* r0, double* g0, double* S, double* Y, double* rho, double* sd,
+                              int32_t* si, const float* energy, const float* force, const float* stress, const float* magmom,
+                              int32_t final_try, double* frac_next, double* lat_next, int32_t* retry, const uint8_t* fixed) {
+  return test_lbfgs_step(eng, "chg_test_lbfgs_step_fixed", params, lbfgs, n_struct, atom_off, q, r0, g0, S, Y, rho, sd, si, energy, force,
+                         stress, magmom, final_try, frac_next, lat_next, retry, fixed);
 }
 
 }  // extern "C"

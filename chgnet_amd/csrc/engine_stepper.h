@@ -26,6 +26,11 @@ struct Stepper {
   char* d_mem = nullptr;
   double *frac_next = nullptr, *lat_next = nullptr;
   int *d_sel = nullptr, *retry = nullptr;
+  // constraint (chg_relax_set_fixed / chg_md_set_fixed, DESIGN.md "Constraints"): the mask [N, 3] in original numbering and the free
+  // components of every structure; the step kernels see them only while has_fixed
+  unsigned char* d_fixed = nullptr;
+  int* d_nfree = nullptr;
+  bool has_fixed = false;
   // pinned staging: the configuration the next build evaluates (first n structures of h_aoff), retry flags, held-back structures,
   // and the integrator's own per-structure ints
   char* h_mem = nullptr;
@@ -42,6 +47,44 @@ inline int check_structs(chg_engine* eng, const char* fn, const chg_structs_host
     for (int o = 0; o < B && !bad; ++o)
       if (h->atom_off[o + 1] <= h->atom_off[o]) bad = "every structure needs at least one atom";
   if (bad) { eng->err = std::string(fn) + ": " + bad; return CHG_EINVAL; }
+  return CHG_OK;
+}
+
+// A mask [N, 3] (1 = component held) against the rules both integrators share: a partially held atom needs a cell that stays put, and
+// a thermostat needs something to act on.  nfree [B]: free components per structure.
+inline int check_fixed(chg_engine* eng, const char* fn, int B, const int* aoff, const uint8_t* fixed, bool moving_cell, bool needs_dof,
+                       int* nfree) {
+  for (int o = 0; o < B; ++o) {
+    int held = 0;
+    for (int i = aoff[o]; i < aoff[o + 1]; ++i) {
+      const int h = (fixed[3 * (size_t)i] ? 1 : 0) + (fixed[3 * (size_t)i + 1] ? 1 : 0) + (fixed[3 * (size_t)i + 2] ? 1 : 0);
+      if (moving_cell && h != 0 && h != 3) {
+        eng->err = std::string(fn) + ": structure " + std::to_string(o) + " holds only some components of atom " + std::to_string(i - aoff[o]) +
+                   ", which has no meaning while the cell moves";
+        return CHG_EINVAL;
+      }
+      held += h;
+    }
+    nfree[o] = 3 * (aoff[o + 1] - aoff[o]) - held;
+    if (needs_dof && nfree[o] == 0) {
+      eng->err = std::string(fn) + ": structure " + std::to_string(o) + " has no free component left for the thermostat";
+      return CHG_EINVAL;
+    }
+  }
+  return CHG_OK;
+}
+
+// chg_*_set_fixed after the checks: the mask and the counts into the arena (null: the handle is unconstrained again)
+inline int upload_fixed(chg_engine* eng, const char* fn, Stepper* s, const uint8_t* fixed, const int* nfree) {
+  s->has_fixed = false;
+  if (!fixed) return CHG_OK;
+  if (hipMemcpyAsync(s->d_fixed, fixed, 3 * (size_t)s->N, hipMemcpyHostToDevice, eng->stream) != hipSuccess ||
+      hipMemcpyAsync(s->d_nfree, nfree, sizeof(int) * (size_t)s->B, hipMemcpyHostToDevice, eng->stream) != hipSuccess ||
+      hipStreamSynchronize(eng->stream) != hipSuccess) {
+    eng->err = std::string(fn) + ": mask upload failed";
+    return CHG_EHIP;
+  }
+  s->has_fixed = true;
   return CHG_OK;
 }
 

@@ -44,7 +44,9 @@ __device__ __forceinline__ double block_sum_f64(double x, double (*red)[4], int&
   return s;
 }
 
-static __global__ __launch_bounds__(256) void k_lbfgs_step(LbfgsStepArgs a) {
+// MASK: mk.fixed is set; <false> is the unconstrained kernel, instruction for instruction
+template <bool MASK>
+static __global__ __launch_bounds__(256) void k_lbfgs_step(LbfgsStepArgs a, RelaxMask mk) {
   const RelaxStepArgs& p = a.c;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int bs = p.sel ? p.sel[blockIdx.x] : blockIdx.x;
@@ -61,6 +63,7 @@ static __global__ __launch_bounds__(256) void k_lbfgs_step(LbfgsStepArgs a) {
   int* si = p.si + (size_t)RELAX_SI * o;
   const int nrows = n + (p.relax_cell ? 3 : 0);
   const float* force = p.force + 3 * (size_t)b0;
+  const unsigned char* fixed = MASK ? mk.fixed + 3 * (size_t)a0 : nullptr;
   auto hist = [&](double* base, int slot) { return base + 3 * ((size_t)slot * a.R + row0); };
 
   __shared__ double sF[9], sG[9], sLinv[9];
@@ -95,18 +98,23 @@ static __global__ __launch_bounds__(256) void k_lbfgs_step(LbfgsStepArgs a) {
   double gmax = 0.0, ys = 0.0;
   for (int r = tid; r < nrows; r += 256) {
     double g[3];
-    gen_force_row(force, sF, sG, n, r, g);
+    gen_force_row(force, sF, sG, n, r, g, held_bits<MASK>(fixed, n, r));
     if (r < n) {
       const float* f = force + 3 * (size_t)r;
       const float m = p.magmom ? p.magmom[b0 + r] : 0.0f;
       finite &= isfinite(f[0]) && isfinite(f[1]) && isfinite(f[2]) && isfinite(m);
       const size_t ro = (size_t)a0 + r;
-      if (p.f_out) { p.f_out[3 * ro] = f[0]; p.f_out[3 * ro + 1] = f[1]; p.f_out[3 * ro + 2] = f[2]; }
+      if (p.f_out) {   // the reported forces are the masked ones; the finiteness test above saw the raw ones
+        const unsigned held = held_bits<MASK>(fixed, n, r);
+        p.f_out[3 * ro] = (held & 1u) ? 0.0f : f[0]; p.f_out[3 * ro + 1] = (held & 2u) ? 0.0f : f[1]; p.f_out[3 * ro + 2] = (held & 4u) ? 0.0f : f[2];
+      }
       if (p.m_out && p.magmom) p.m_out[ro] = m;
       if (p.frac_eval) {
         const double u0 = q[3 * r], u1 = q[3 * r + 1], u2 = q[3 * r + 2];
 #pragma unroll
         for (int j = 0; j < 3; ++j) p.frac_eval[3 * ro + j] = u0 * sLinv[j] + u1 * sLinv[3 + j] + u2 * sLinv[6 + j];
+        if (MASK && mk.frac0 && held_bits<MASK>(fixed, n, r) == 7u)   // a fully held atom keeps the fractional coordinates it was given, bit for bit
+          for (int j = 0; j < 3; ++j) p.frac_eval[3 * ro + j] = mk.frac0[3 * ro + j];
       }
     }
     finite &= isfinite(g[0]) && isfinite(g[1]) && isfinite(g[2]);
@@ -164,7 +172,7 @@ static __global__ __launch_bounds__(256) void k_lbfgs_step(LbfgsStepArgs a) {
     double part = 0.0;
     for (int r = tid; r < nrows; r += 256) {
       double g[3];
-      gen_force_row(force, sF, sG, n, r, g);
+      gen_force_row(force, sF, sG, n, r, g, held_bits<MASK>(fixed, n, r));
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
         const int k = 3 * r + j;
@@ -246,6 +254,8 @@ static __global__ __launch_bounds__(256) void k_lbfgs_step(LbfgsStepArgs a) {
       double* fr = p.frac_next + 3 * ((size_t)b0 + r);
 #pragma unroll
       for (int j = 0; j < 3; ++j) fr[j] = u0 * sLinv[j] + u1 * sLinv[3 + j] + u2 * sLinv[6 + j];
+      if (MASK && mk.frac0 && held_bits<MASK>(fixed, n, r) == 7u)
+        for (int j = 0; j < 3; ++j) fr[j] = mk.frac0[3 * ((size_t)a0 + r) + j];
     }
   }
   __syncthreads();

@@ -73,14 +73,30 @@ struct MdStepArgs {
   double* nhc;            // [B, MD_NHC]
   double* fr_cons;        // [B] or null
   int nhc_len;
+  // constraint (DESIGN.md "Constraints"; null: none, the <false> instantiation): [N, 3] 1 = component held, and the number of free
+  // components of every replica (3 n: nothing held, the replica keeps the unconstrained degrees of freedom)
+  const unsigned char* fixed;
+  const int* nfree;       // [B]
 };
 
-// masses and constants of the Nose-Hoover chains of one replica of n atoms
+// bit j set: component j of atom i is held (fixed: the replica's [n, 3] mask)
+template <bool MASK>
+__device__ __forceinline__ unsigned md_held_bits(const unsigned char* fixed, int i) {
+  if (!MASK) return 0u;
+  const unsigned char* h = fixed + 3 * (size_t)i;
+  return (h[0] ? 1u : 0u) | (h[1] ? 2u : 0u) | (h[2] ? 4u : 0u);
+}
+// x, or 0 for a held component j
+template <bool MASK>
+__device__ __forceinline__ double md_free(unsigned held, int j, double x) { return (MASK && ((held >> j) & 1u)) ? 0.0 : x; }
+
+// masses and constants of the Nose-Hoover chains of one replica with nf_ degrees of freedom (3 (n - 1), or the free components of a
+// replica that holds some)
 struct NhcConst {
   double kT, nf, alpha, Q0, Qk, Qb, W;
-  __device__ NhcConst(const MdStepArgs& a, int n) {
+  __device__ NhcConst(const MdStepArgs& a, double nf_) {
     kT = a.kB * a.temperature;
-    nf = 3.0 * (n - 1);
+    nf = nf_;
     alpha = 1.0 + 3.0 / nf;
     Qk = kT * a.taut * a.taut;
     Q0 = nf * Qk;
@@ -130,6 +146,9 @@ __device__ inline double nhc_extended_energy(const NhcConst& c, const double* x,
   return h;
 }
 
+// MASK: a.fixed and a.nfree are set; <false> is the unconstrained kernel, instruction for instruction.  Under MASK the absorbed forces
+// and every write of p are masked (selects, no divergent branch), so held components neither drift nor enter a sum.
+template <bool MASK>
 static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int o = a.sel ? a.sel[blockIdx.x] : blockIdx.x;
@@ -144,6 +163,11 @@ static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
   const bool nhc = a.ensemble == MD_NVT_NHC || a.ensemble == MD_NPT_NHC, nhc_npt = a.ensemble == MD_NPT_NHC;
   double* xs = nhc ? a.nhc + (size_t)MD_NHC * o : nullptr;
   const double hdt = 0.5 * a.dt;
+  const unsigned char* fixed = MASK ? a.fixed + 3 * (size_t)a0 : nullptr;
+  // degrees of freedom of the temperature and N_f of the chains (a held atom breaks momentum conservation): the free components of a
+  // replica that holds any, else 3 n and 3 (n - 1); evaluated where they are used, as the unconstrained kernel always did
+  auto dof = [&]() -> double { return (MASK && a.nfree[o] < 3 * n) ? (double)a.nfree[o] : 3.0 * n; };
+  auto nhc_nf = [&]() -> double { return (MASK && a.nfree[o] < 3 * n) ? (double)a.nfree[o] : 3.0 * (n - 1); };
 
   __shared__ double red[4][9];
   __shared__ int rfin[4];
@@ -180,7 +204,8 @@ static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
     if (s_phase == 1) {                 // NPT: forces of the scaled configuration
       for (int i = tid; i < n; i += 256) {
         const float* fi = a.force + 3 * ((size_t)a0 + i);
-        f[3 * i] = fi[0]; f[3 * i + 1] = fi[1]; f[3 * i + 2] = fi[2];
+        const unsigned held = md_held_bits<MASK>(fixed, i);
+        f[3 * i] = md_free<MASK>(held, 0, fi[0]); f[3 * i + 1] = md_free<MASK>(held, 1, fi[1]); f[3 * i + 2] = md_free<MASK>(held, 2, fi[2]);
       }
       if (tid == 0) {
         sd[18] = a.energy[o];
@@ -195,17 +220,19 @@ static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
       // two chains (their factor s scales p, Ekin and G without another reduction), one scaling pass writes the frame's momenta
       const bool kick = a.flags & MD_KICK2;
       const bool frame = a.fr_scal != nullptr;
-      const NhcConst c(a, n);
+      const NhcConst c(a, nhc_nf());
       const double e1 = kick ? exp(-0.5 * c.alpha * xs[16] * hdt) : 1.0;
       double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
       for (int i = tid; i < n; i += 256) {
         const float* fi = a.force + 3 * ((size_t)a0 + i);
+        const unsigned held = md_held_bits<MASK>(fixed, i);
+        auto fm = [&](int j) -> float { return (MASK && ((held >> j) & 1u)) ? 0.0f : fi[j]; };   // cached, kicked with and reported
         double pi[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-          const double fj = fi[j];
+          const double fj = fm(j);
           f[3 * i + j] = fj;
-          pi[j] = kick ? (p[3 * i + j] * e1 + hdt * fj) * e1 : p[3 * i + j];
+          pi[j] = md_free<MASK>(held, j, kick ? (p[3 * i + j] * e1 + hdt * fj) * e1 : p[3 * i + j]);
           p[3 * i + j] = pi[j];
         }
         const double im = 1.0 / m[i];
@@ -214,7 +241,7 @@ static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
         if (frame) {
           const size_t ro = 3 * ((size_t)a0 + i);
 #pragma unroll
-          for (int j = 0; j < 3; ++j) { a.fr_pos[ro + j] = r[3 * i + j]; a.fr_force[ro + j] = fi[j]; }
+          for (int j = 0; j < 3; ++j) { a.fr_pos[ro + j] = r[3 * i + j]; a.fr_force[ro + j] = fm(j); }
         }
       }
 #pragma unroll
@@ -252,7 +279,7 @@ static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
           si[0] += 1;
         }
         const double ekin = 0.5 * K2;
-        const double T = 2.0 * ekin / (3.0 * n * a.kB);
+        const double T = (!MASK || dof() > 0.0) ? 2.0 * ekin / (dof() * a.kB) : 0.0;   // everything held (NVE only): T = 0
         const double cons = nhc_extended_energy(c, xs, a.nhc_len, K2, nhc_npt, a.pressure, vol);
         xs[17] = cons;
         sd[19] = ekin;
@@ -275,13 +302,15 @@ static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
       __syncthreads();
       if (kick || frame) {
         const double s = s_lam;
-        for (int i = tid; i < n; i += 256)
+        for (int i = tid; i < n; i += 256) {
+          const unsigned held = md_held_bits<MASK>(fixed, i);
 #pragma unroll
           for (int j = 0; j < 3; ++j) {
-            const double pj = p[3 * i + j] * s;
+            const double pj = md_free<MASK>(held, j, p[3 * i + j] * s);
             p[3 * i + j] = pj;
             if (frame) a.fr_mom[3 * ((size_t)a0 + i) + j] = pj;
           }
+        }
       }
     } else {
       const bool kick = a.flags & MD_KICK2;
@@ -289,12 +318,14 @@ static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
       double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // sum p.p / m, then G xx yy zz yz xz xy
       for (int i = tid; i < n; i += 256) {
         const float* fi = a.force + 3 * ((size_t)a0 + i);
+        const unsigned held = md_held_bits<MASK>(fixed, i);
+        auto fm = [&](int j) -> float { return (MASK && ((held >> j) & 1u)) ? 0.0f : fi[j]; };   // cached, kicked with and reported
         double pi[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-          const double fj = fi[j];
+          const double fj = fm(j);
           f[3 * i + j] = fj;
-          pi[j] = kick ? p[3 * i + j] + hdt * fj : p[3 * i + j];
+          pi[j] = md_free<MASK>(held, j, kick ? p[3 * i + j] + hdt * fj : p[3 * i + j]);
           p[3 * i + j] = pi[j];
         }
         const double im = 1.0 / m[i];
@@ -303,7 +334,7 @@ static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
         if (frame) {
           const size_t ro = 3 * ((size_t)a0 + i);
 #pragma unroll
-          for (int j = 0; j < 3; ++j) { a.fr_pos[ro + j] = r[3 * i + j]; a.fr_mom[ro + j] = pi[j]; a.fr_force[ro + j] = fi[j]; }
+          for (int j = 0; j < 3; ++j) { a.fr_pos[ro + j] = r[3 * i + j]; a.fr_mom[ro + j] = pi[j]; a.fr_force[ro + j] = fm(j); }
         }
       }
 #pragma unroll
@@ -315,7 +346,7 @@ static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
         double G[7];
         for (int k = 1; k < 7; ++k) G[k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
         const double ekin = 0.5 * (G[1] + G[2] + G[3]);
-        const double T = 2.0 * ekin / (3.0 * n * a.kB);
+        const double T = (!MASK || dof() > 0.0) ? 2.0 * ekin / (dof() * a.kB) : 0.0;   // everything held (NVE only): T = 0
         sd[18] = a.energy[o];
         sd[19] = ekin;
         sd[20] = T;
@@ -355,11 +386,12 @@ static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
       double xi[3] = {0.0, 0.0, 0.0};
       if (noisy) philox_normal3(seed, (unsigned)i, step, xi);
       const double sg = a.lg_sig * sqrt(mi);
+      const unsigned held = md_held_bits<MASK>(fixed, i);   // the noise of a held component is drawn and dropped
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
-        double pj = p[3 * i + j] + hdt * f[3 * i + j];
+        double pj = md_free<MASK>(held, j, p[3 * i + j] + hdt * f[3 * i + j]);
         r[3 * i + j] += hdt * pj / mi;
-        pj = a.lg_c1 * pj + sg * xi[j];
+        pj = md_free<MASK>(held, j, a.lg_c1 * pj + sg * xi[j]);
         p[3 * i + j] = pj;
         ps[j] += pj;
       }
@@ -379,9 +411,10 @@ static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
     }
     for (int i = tid; i < n; i += 256) {
       const double mi = m[i];
+      const unsigned held = md_held_bits<MASK>(fixed, i);
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
-        const double pj = a.fixcm ? p[3 * i + j] - mi * s_mean[j] : p[3 * i + j];
+        const double pj = md_free<MASK>(held, j, a.fixcm ? p[3 * i + j] - mi * s_mean[j] : p[3 * i + j]);
         p[3 * i + j] = pj;
         r[3 * i + j] += hdt * pj / mi;
       }
@@ -398,7 +431,7 @@ static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
     // p <- (p s e1 + dt/2 f) e1, r <- (r e2 + dt p / m) e2 with e1 = exp(-alpha veps dt/4), e2 = exp(veps dt/2); the cell scales by e2^2
     __syncthreads();   // sd, the chain state and p written above
     if (tid == 0) {
-      const NhcConst c(a, n);
+      const NhcConst c(a, nhc_nf());
       const int M = a.nhc_len;
       double v[MD_NHC_MAX], eta[MD_NHC_MAX];
       double veps = xs[16], K2 = sd[30] + sd[34] + sd[38];
@@ -434,9 +467,10 @@ static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
     const double e1 = s_e[0], e2 = s_e[1], se1 = s_lam * e1;
     for (int i = tid; i < n; i += 256) {
       const double idm = a.dt / m[i];
+      const unsigned held = md_held_bits<MASK>(fixed, i);
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
-        const double pj = (p[3 * i + j] * se1 + hdt * f[3 * i + j]) * e1;
+        const double pj = md_free<MASK>(held, j, (p[3 * i + j] * se1 + hdt * f[3 * i + j]) * e1);
         p[3 * i + j] = pj;
         r[3 * i + j] = (r[3 * i + j] * e2 + idm * pj) * e2;
       }
@@ -487,8 +521,9 @@ static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
     __syncthreads();
     const double lam = s_lam;
     for (int i = tid; i < n; i += 256) {
+      const unsigned held = md_held_bits<MASK>(fixed, i);
 #pragma unroll
-      for (int j = 0; j < 3; ++j) p[3 * i + j] *= lam;
+      for (int j = 0; j < 3; ++j) p[3 * i + j] = md_free<MASK>(held, j, p[3 * i + j] * lam);
       if (npt) {
         const double x0 = r[3 * i], x1 = r[3 * i + 1], x2 = r[3 * i + 2];
         double* fr = a.frac_next + 3 * ((size_t)a0 + i);
@@ -507,13 +542,15 @@ static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
   // first half kick with the cached forces, fixcm (mean momentum, not mass-weighted), drift r += dt p / m
   __syncthreads();
   double ps[3] = {0.0, 0.0, 0.0};
-  for (int i = tid; i < n; i += 256)
+  for (int i = tid; i < n; i += 256) {
+    const unsigned held = md_held_bits<MASK>(fixed, i);
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-      const double pj = p[3 * i + j] + hdt * f[3 * i + j];
+      const double pj = md_free<MASK>(held, j, p[3 * i + j] + hdt * f[3 * i + j]);
       p[3 * i + j] = pj;
       ps[j] += pj;
     }
+  }
   if (a.fixcm) {
 #pragma unroll
     for (int j = 0; j < 3; ++j) ps[j] = wave_sum_f64(ps[j]);
@@ -530,9 +567,10 @@ static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
   __syncthreads();
   for (int i = tid; i < n; i += 256) {
     const double mi = m[i];
+    const unsigned held = md_held_bits<MASK>(fixed, i);
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-      const double pj = a.fixcm ? p[3 * i + j] - s_mean[j] : p[3 * i + j];
+      const double pj = md_free<MASK>(held, j, a.fixcm ? p[3 * i + j] - s_mean[j] : p[3 * i + j]);
       p[3 * i + j] = pj;
       r[3 * i + j] += a.dt * pj / mi;
     }

@@ -48,6 +48,12 @@ struct RelaxStepArgs {
   int max_steps, nmin, relax_cell, final_try;
 };
 
+// constraint (DESIGN.md "Constraints"), a kernel argument of its own so that the layout of RelaxStepArgs stays what it was
+struct RelaxMask {
+  const unsigned char* fixed;   // [N, 3] original numbering, 1 = component held; null: none (the <false> instantiations)
+  const double* frac0;          // [N, 3] original numbering: the fractional coordinates as given, which a fully held atom keeps (or null)
+};
+
 // expm(M) and, when e != null, the Frechet derivative L(M, E) = top-right block of expm([[M, E], [0, M]]).  The 6x6 block matrix is
 // kept as its two distinct 3x3 blocks ([[P, Q], [0, P]] is closed under products), scaled by 2^-s until ||M||_1 <= 1/4, summed as a
 // degree-14 Taylor polynomial (Horner) and squared back s times ([[P, Q], [0, P]]^2 = [[P^2, PQ + QP], [0, P^2]]).  The truncation
@@ -128,11 +134,21 @@ __device__ inline int cell_frame(const double* sd, const double* x, const float*
   return finite;
 }
 
-// generalized force of row r of a structure with n atoms (atom rows: f F; cell rows: (1/c) L(A^T, W)); force: the structure's [n, 3]
-__device__ __forceinline__ void gen_force_row(const float* force, const double* F, const double* G, int n, int r, double g[3]) {
+// bit j set: component j of atom row r is held (fixed: the structure's [n, 3] mask); cell rows are never held
+template <bool MASK>
+__device__ __forceinline__ unsigned held_bits(const unsigned char* fixed, int n, int r) {
+  if (!MASK || r >= n) return 0u;
+  const unsigned char* h = fixed + 3 * (size_t)r;
+  return (h[0] ? 1u : 0u) | (h[1] ? 2u : 0u) | (h[2] ? 4u : 0u);
+}
+
+// generalized force of row r of a structure with n atoms (atom rows: f F; cell rows: (1/c) L(A^T, W)); force: the structure's [n, 3];
+// the engine's force on a held component (bit of `held`) counts as 0
+__device__ __forceinline__ void gen_force_row(const float* force, const double* F, const double* G, int n, int r, double g[3],
+                                              unsigned held = 0u) {
   if (r < n) {
     const float* f = force + 3 * (size_t)r;
-    const double f0 = f[0], f1 = f[1], f2 = f[2];
+    const double f0 = (held & 1u) ? 0.0 : (double)f[0], f1 = (held & 2u) ? 0.0 : (double)f[1], f2 = (held & 4u) ? 0.0 : (double)f[2];
 #pragma unroll
     for (int j = 0; j < 3; ++j) g[j] = f0 * F[j] + f1 * F[3 + j] + f2 * F[6 + j];
   } else {
@@ -159,7 +175,9 @@ __device__ inline void next_lattice(const double* sd, const double* x, int relax
   }
 }
 
-static __global__ __launch_bounds__(256) void k_relax_step(RelaxStepArgs p) {
+// MASK: mk.fixed is set; <false> is the unconstrained kernel, instruction for instruction
+template <bool MASK>
+static __global__ __launch_bounds__(256) void k_relax_step(RelaxStepArgs p, RelaxMask mk) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int bs = p.sel ? p.sel[blockIdx.x] : blockIdx.x;
   const int o = p.orig ? p.orig[bs] : bs;
@@ -169,6 +187,7 @@ static __global__ __launch_bounds__(256) void k_relax_step(RelaxStepArgs p) {
   double* sd = p.sd + (size_t)RELAX_SD * o;
   int* si = p.si + (size_t)RELAX_SI * o;
   const int nrows = n + (p.relax_cell ? 3 : 0);
+  const unsigned char* fixed = MASK ? mk.fixed + 3 * (size_t)a0 : nullptr;
 
   __shared__ double sF[9], sG[9], sLinv[9];
   __shared__ double red[4][4];
@@ -197,7 +216,7 @@ static __global__ __launch_bounds__(256) void k_relax_step(RelaxStepArgs p) {
   }
   __syncthreads();
 
-  auto gen_force = [&](int r, double g[3]) { gen_force_row(p.force + 3 * (size_t)b0, sF, sG, n, r, g); };
+  auto gen_force = [&](int r, double g[3]) { gen_force_row(p.force + 3 * (size_t)b0, sF, sG, n, r, g, held_bits<MASK>(fixed, n, r)); };
 
   // pass 0: finiteness, frame of the evaluated configuration, g.v, |g|^2, |v|^2, max row |g|^2
   double gv = 0.0, gg = 0.0, vv = 0.0, gmax = 0.0;
@@ -209,12 +228,17 @@ static __global__ __launch_bounds__(256) void k_relax_step(RelaxStepArgs p) {
       const float m = p.magmom ? p.magmom[b0 + r] : 0.0f;
       finite &= isfinite(f[0]) && isfinite(f[1]) && isfinite(f[2]) && isfinite(m);
       const size_t ro = (size_t)a0 + r;
-      if (p.f_out) { p.f_out[3 * ro] = f[0]; p.f_out[3 * ro + 1] = f[1]; p.f_out[3 * ro + 2] = f[2]; }
+      if (p.f_out) {   // the reported forces are the masked ones; the finiteness test above saw the raw ones
+        const unsigned held = held_bits<MASK>(fixed, n, r);
+        p.f_out[3 * ro] = (held & 1u) ? 0.0f : f[0]; p.f_out[3 * ro + 1] = (held & 2u) ? 0.0f : f[1]; p.f_out[3 * ro + 2] = (held & 4u) ? 0.0f : f[2];
+      }
       if (p.m_out && p.magmom) p.m_out[ro] = m;
       if (p.frac_eval) {
         const double u0 = q[3 * r], u1 = q[3 * r + 1], u2 = q[3 * r + 2];
 #pragma unroll
         for (int j = 0; j < 3; ++j) p.frac_eval[3 * ro + j] = u0 * sLinv[j] + u1 * sLinv[3 + j] + u2 * sLinv[6 + j];
+        if (MASK && mk.frac0 && held_bits<MASK>(fixed, n, r) == 7u)   // a fully held atom keeps the fractional coordinates it was given, bit for bit
+          for (int j = 0; j < 3; ++j) p.frac_eval[3 * ro + j] = mk.frac0[3 * ro + j];
       }
     }
     finite &= isfinite(g[0]) && isfinite(g[1]) && isfinite(g[2]);
@@ -299,6 +323,8 @@ static __global__ __launch_bounds__(256) void k_relax_step(RelaxStepArgs p) {
       double* fr = p.frac_next + 3 * ((size_t)b0 + r);
 #pragma unroll
       for (int j = 0; j < 3; ++j) fr[j] = u0 * sLinv[j] + u1 * sLinv[3 + j] + u2 * sLinv[6 + j];
+      if (MASK && mk.frac0 && held_bits<MASK>(fixed, n, r) == 7u)
+        for (int j = 0; j < 3; ++j) fr[j] = mk.frac0[3 * ((size_t)a0 + r) + j];
     }
   }
   __syncthreads();

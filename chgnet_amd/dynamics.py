@@ -30,6 +30,15 @@ temperature stays ``T = 2 Ekin / (3 n kB)``: it equilibrates at ``temperature * 
 one-atom structure are refused.  tests/nhc_ref.py restates the integrator.  This is not ASE's ``NPT`` class, which the reference
 calls "Nose-Hoover" (Melchionna leap-frog: upper-triangular cells only, conserved quantity of first order in the time step).
 
+Constraints (DESIGN.md "Constraints"): ``fixed_atoms`` -- atom indices, a bool [n] array or a bool [n, 3] array with True = held --
+or, without the keyword, the ``selective_dynamics`` site property (True = free) and the ``FixAtoms`` / ``FixCartesian`` constraints of
+an ASE ``Atoms``.  Held components get no force and no momentum (the initial momenta are masked after they are drawn, as ASE's
+``set_momenta`` does), so they never drift; under a moving cell held atoms scale with it, and a mask that holds only some components
+of an atom is refused there.  A replica that holds at least one component has ``dof`` = its free components: the reported
+temperature is ``2 Ekin / (dof kB)`` (ASE >= 3.23), the Berendsen thermostat uses it, the Nose-Hoover chains take ``N_f = dof`` and
+the one-time centre-of-mass removal is skipped (a pinned atom breaks momentum conservation).  A replica with nothing free is refused
+except in NVE.
+
 Out of scope, refused with ``ValueError``: ``thermostat="Nose-Hoover"`` (ASE ``NPT``; use ``"Nose-Hoover-Chain"``), and NPT with a
 Berendsen barostat without ``bulk_modulus`` (the reference then fits an equation of state).  Deviations from the reference:
   - ``starting_temperature`` draws from a seeded numpy ``Generator`` (``seed``), not ASE's global RNG: same distribution,
@@ -49,7 +58,8 @@ import sys
 import numpy as np
 
 from chgnet_amd import _lib
-from chgnet_amd.calculator import CHGNetCalculator, atoms_to_structure, report_isolated_atoms, voigt
+from chgnet_amd.calculator import (CHGNetCalculator, atoms_to_structure, check_fixed, join_fixed, report_isolated_atoms, structure_fixed,
+                                   voigt)
 from chgnet_amd.graph.structure import Lattice, Structure
 
 # ase.units (CODATA 2014)
@@ -184,7 +194,7 @@ class _DeviceRun:
     RING = 32
 
     def __init__(self, calc: CHGNetCalculator, structures: list, masses: np.ndarray, momenta: np.ndarray, kind: str, cfg: dict,
-                 seeds=None) -> None:
+                 seeds=None, fixed: list | None = None) -> None:
         model = calc.model
         self.eng, self.model, self.calc = model.engine, model, calc
         conv = model.graph_converter
@@ -219,6 +229,12 @@ class _DeviceRun:
         else:
             self.eng._check(self.eng.lib.chg_md_create(self.eng.handle, ctypes.byref(host), self.masses.ctypes.data_as(dp),
                                                        mom.ctypes.data_as(dp), ctypes.byref(params), ctypes.byref(self.handle)))
+        mask = join_fixed(fixed, self.n_at) if fixed is not None else None
+        if mask is not None:             # one mask [n, 3] uint8 or None per replica; the held momenta are zeroed there too
+            rc = self.eng.lib.chg_md_set_fixed(self.eng.handle, self.handle, mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+            if rc != 0:
+                self.free()
+                self.eng._check(rc)
         self.chain_length = int(cfg["chain_length"]) if self.nhc else 0
         self.started = False
         self.step = 0
@@ -281,8 +297,9 @@ class MolecularDynamics:
                  taup: float | None = None, bulk_modulus: float | None = None, trajectory: str | None = None, logfile: str | None = None,
                  loginterval: int = 1, crystal_feas_logfile: str | None = None, append_trajectory: bool = False,  # noqa: ARG002
                  on_isolated_atoms: str = "warn", return_site_energies: bool = False, use_device: str | None = None,
-                 seed: int | None = None, friction: float | None = None, chain_length: int | None = None) -> None:
+                 seed: int | None = None, friction: float | None = None, chain_length: int | None = None, fixed_atoms=None) -> None:
         self.ensemble, self.thermostat = ensemble, thermostat
+        self.fixed_atoms = fixed_atoms
         self.kind = _resolve(ensemble, thermostat, bulk_modulus)
         langevin = self.kind == "nvt_langevin"
         nhc = self.kind in NHC_KINDS
@@ -353,16 +370,35 @@ class MolecularDynamics:
         self.close()
         rng = np.random.default_rng(self.seed)
         self._structure, self._masses, self._momenta = self._initial(atoms, self.starting_temperature, rng)
+        self._fixed = structure_fixed(self._structure, self.fixed_atoms)
+        check_fixed(self._fixed, moving_cell=self.kind.startswith("npt"), needs_dof=self.kind != "nve")
+        constrained = self._fixed is not None and bool(self._fixed.any())
+        if constrained:                  # ASE: set_momenta zeroes the held components after they are drawn
+            self._momenta = np.where(self._fixed.astype(bool), 0.0, self._momenta)
+            self._structure = self._with_fixed(self._structure)
         if self.kind in NHC_KINDS:
             if len(self._masses) < 2:
                 raise ValueError("thermostat='Nose-Hoover-Chain' needs more than one atom: a single atom has no internal degree of freedom")
-            # once, mass-weighted; the integrator conserves the total momentum and never removes it
-            self._momenta = self._momenta - self._masses[:, None] * (self._momenta.sum(axis=0) / self._masses.sum())
+            # once, mass-weighted; the integrator conserves the total momentum and never removes it (unless an atom is pinned: then
+            # the momentum is not conserved, N_f counts the free components and nothing is removed)
+            if not constrained:
+                self._momenta = self._momenta - self._masses[:, None] * (self._momenta.sum(axis=0) / self._masses.sum())
             self.thermostat_state = None
         self._step_offset = getattr(self, "nsteps", 0)
         self.nsteps = self._step_offset
         self.traj = MDTrajectory(self._structure.atomic_numbers)
         self._cfeas: list[np.ndarray] = []
+
+    def _with_fixed(self, structure: Structure) -> Structure:
+        """A copy of ``structure`` that carries the mask as ``selective_dynamics`` (True = free) beside the site properties it had; the
+        caller's object is not touched."""
+        out = Structure(Lattice(structure.lattice.matrix.copy()), np.asarray(structure.atomic_numbers).copy(), np.array(structure.frac_coords))
+        for name, values in (getattr(structure, "site_properties", None) or {}).items():
+            if name != "selective_dynamics":
+                out.add_site_property(name, list(values))
+        if self._fixed is not None and self._fixed.any():
+            out.add_site_property("selective_dynamics", (self._fixed == 0).tolist())
+        return out
 
     @property
     def atoms(self) -> Structure:
@@ -428,7 +464,7 @@ class MolecularDynamics:
         if self._run is None:
             report_isolated_atoms(self.calculator.model, [self._structure])
             self._run = _DeviceRun(self.calculator, [self._structure], self._masses, self._momenta, self.kind, self.cfg,
-                                   seeds=[self.thermostat_seed])
+                                   seeds=[self.thermostat_seed], fixed=[self._fixed])
             if self.logfile is not None and self._logger is None:
                 self._logger = MDLogger(self.logfile, len(self._structure))
         run = self._run
@@ -449,22 +485,26 @@ class MolecularDynamics:
 
     def _update_state(self, d: dict) -> None:
         lat = d["cell"][0]
-        self._structure = Structure(Lattice(lat), self._structure.atomic_numbers, d["positions"] @ np.linalg.inv(lat))
+        self._structure = self._with_fixed(Structure(Lattice(lat), self._structure.atomic_numbers, d["positions"] @ np.linalg.inv(lat)))
         self._momenta = d["momenta"].copy()
         self.thermostat_state = self._run.thermostat_state(d, 0)
 
     # ------------------------------------------------------------------------------------------------------------------------
     @classmethod
-    def run_batch(cls, structures, steps: int, *, seeds=None, model=None, **kwargs) -> list[dict]:
+    def run_batch(cls, structures, steps: int, *, seeds=None, model=None, fixed_atoms=None, **kwargs) -> list[dict]:
         """Run R independent replicas (possibly of different sizes) as one device handle: each gets the trajectory it would get
         alone with ``MolecularDynamics(structures[i], seed=seeds[i], **kwargs).run(steps)`` (with the Langevin thermostat ``seeds[i]`` is
         also replica i's noise key; ``seeds=None`` draws one per replica).  Returns, per replica, ``{"trajectory",
         "final_structure", "momenta", "status", "n_steps", "thermostat_state"}`` (the last one ``None`` unless the thermostat is
         "Nose-Hoover-Chain").  ``trajectory`` / ``logfile`` / ``crystal_feas_logfile`` are not
-        written here."""
+        written here.  ``fixed_atoms``: one entry per structure (``None``: that structure's own ``selective_dynamics``, or nothing
+        held)."""
         structures = list(structures)
         if not structures:
             return []
+        fixed_atoms = [None] * len(structures) if fixed_atoms is None else list(fixed_atoms)
+        if len(fixed_atoms) != len(structures):
+            raise ValueError(f"fixed_atoms has {len(fixed_atoms)} entries for {len(structures)} structures")
         seeds = [None] * len(structures) if seeds is None else list(seeds)
         if len(seeds) != len(structures):
             raise ValueError("one seed per structure")
@@ -472,14 +512,14 @@ class MolecularDynamics:
             if kwargs.get(k) is not None:
                 raise ValueError(f"run_batch does not write {k}: save each returned trajectory instead")
         md, calc = [], model
-        for s, sd in zip(structures, seeds):      # one calculator for all replicas
-            md.append(cls(s, model=calc, seed=sd, **kwargs))
+        for s, sd, fx in zip(structures, seeds, fixed_atoms):      # one calculator for all replicas
+            md.append(cls(s, model=calc, seed=sd, fixed_atoms=fx, **kwargs))
             calc = md[-1].calculator
         first = md[0]
         structs = [m._structure for m in md]
         report_isolated_atoms(first.calculator.model, structs)
         run = _DeviceRun(first.calculator, structs, np.concatenate([m._masses for m in md]), np.concatenate([m._momenta for m in md]),
-                         first.kind, first.cfg, seeds=[m.thermostat_seed for m in md])
+                         first.kind, first.cfg, seeds=[m.thermostat_seed for m in md], fixed=[m._fixed for m in md])
         try:
             trajs = [m.traj for m in md]
             sink, _ = first._sinks(run, trajs, [m._cfeas for m in md], 0)
@@ -490,7 +530,7 @@ class MolecularDynamics:
         for i, tr in enumerate(trajs):
             sl = slice(run.prep.atom_off[i], run.prep.atom_off[i + 1])
             lat = d["cell"][i]
-            fin = Structure(Lattice(lat), structs[i].atomic_numbers, d["positions"][sl] @ np.linalg.inv(lat))
+            fin = md[i]._with_fixed(Structure(Lattice(lat), structs[i].atomic_numbers, d["positions"][sl] @ np.linalg.inv(lat)))
             out.append({"trajectory": tr, "final_structure": fin, "momenta": d["momenta"][sl].copy(),
                         "status": STATUS_NAMES[d["status"][i]], "n_steps": int(d["n_steps"][i]),
                         "thermostat_state": run.thermostat_state(d, i)})

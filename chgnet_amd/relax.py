@@ -13,6 +13,12 @@ Deviations: a structure whose energy, forces or stress are non-finite even on th
 status ``NONFINITE`` without moving (ASE would carry the NaN on).  L-BFGS skips the history triple of a step whose
 curvature ``y . s`` is exactly zero or non-finite (ASE would divide by zero); a triple with ``y . s < 0`` is kept, as
 ASE keeps it.
+
+Constraints (DESIGN.md "Constraints"): ``fixed_atoms`` -- atom indices, a bool [n] array or a bool [n, 3] array with True = held --
+or, without the keyword, the ``selective_dynamics`` site property (True = free) and the ``FixAtoms`` / ``FixCartesian`` constraints of
+an ASE ``Atoms``.  The force on a held component counts as zero everywhere, the reported forces included (ASE's ``get_forces``
+returns the masked forces too); with ``relax_cell`` a held atom keeps its fractional coordinates and follows the cell, and a mask
+that holds only some components of an atom is refused.
 """
 
 from __future__ import annotations
@@ -26,7 +32,8 @@ import sys
 import numpy as np
 
 from chgnet_amd import _lib
-from chgnet_amd.calculator import GPA_TO_EV_A3, CHGNetCalculator, atoms_to_structure, report_isolated_atoms, voigt
+from chgnet_amd.calculator import (GPA_TO_EV_A3, CHGNetCalculator, atoms_to_structure, check_fixed, join_fixed, report_isolated_atoms,
+                                   structure_fixed, voigt)
 from chgnet_amd.graph.structure import Lattice, Structure
 
 OPTIMIZERS = ("FIRE",)
@@ -129,8 +136,21 @@ class StructOptimizer:
                 raise ValueError("every structure needs at least one site")
         return structs
 
-    def _run(self, structures: list, p: dict, frame_every: int | None, verbose: bool):
-        """Relax ``structures`` together: one ``chg_relax`` handle, frames every ``frame_every`` evaluations (None: none)."""
+    @staticmethod
+    def _fixed(structs: list, fixed_atoms, relax_cell: bool) -> list:
+        """One mask [n, 3] uint8 (1 = held) or None per structure, checked against the rules of ``chg_relax_set_fixed``."""
+        if fixed_atoms is None:
+            fixed_atoms = [None] * len(structs)
+        elif len(fixed_atoms) != len(structs):
+            raise ValueError(f"fixed_atoms has {len(fixed_atoms)} entries for {len(structs)} structures")
+        masks = [structure_fixed(s, f) for s, f in zip(structs, fixed_atoms)]
+        for i, m in enumerate(masks):
+            check_fixed(m, moving_cell=relax_cell, needs_dof=False, what=f"structure {i}")
+        return masks
+
+    def _run(self, structures: list, p: dict, frame_every: int | None, verbose: bool, fixed: list | None = None):
+        """Relax ``structures`` together: one ``chg_relax`` handle, frames every ``frame_every`` evaluations (None: none).  ``fixed``:
+        one mask [n, 3] uint8 or None per structure."""
         model = self.calculator.model
         eng, conv = model.engine, model.graph_converter
         prep = eng.prepare_structures(structures)
@@ -148,6 +168,12 @@ class StructOptimizer:
         else:
             eng._check(eng.lib.chg_relax_create(eng.handle, ctypes.byref(host), ctypes.byref(params), ctypes.byref(handle)))
         B, N = prep.n_struct, int(prep.atom_off[-1])
+        mask = join_fixed(fixed, n_at) if fixed is not None else None
+        if mask is not None:
+            rc = eng.lib.chg_relax_set_fixed(eng.handle, handle, mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+            if rc != 0:
+                eng.lib.chg_relax_free(eng.handle, handle)
+                eng._check(rc)
         scale = n_at.astype(np.float64) if model.is_intensive else np.ones(B)
         trajs = [TrajectoryObserver(prep.z[prep.atom_off[i]:prep.atom_off[i + 1]]) for i in range(B)] if frame_every else None
 
@@ -198,9 +224,11 @@ class StructOptimizer:
             eng.lib.chg_relax_free(eng.handle, handle)
         return prep, d, scale, trajs
 
-    def _result(self, prep, d, scale, i: int, assign_magmoms: bool) -> dict:
+    def _result(self, prep, d, scale, i: int, assign_magmoms: bool, fixed=None) -> dict:
         sl = slice(prep.atom_off[i], prep.atom_off[i + 1])
         struct = Structure(Lattice(d["lattice"][i]), prep.z[sl].copy(), d["frac"][sl].copy())
+        if fixed is not None:
+            struct.add_site_property("selective_dynamics", (fixed == 0).tolist())
         if assign_magmoms:
             struct.add_site_property("magmom", [float(m) for m in d["magmom"][sl]])
         return {"final_structure": struct, "energy": float(d["energy"][i] * scale[i]), "forces": d["force"][sl].astype(np.float64),
@@ -210,9 +238,11 @@ class StructOptimizer:
     # ------------------------------------------------------------------------------------------------------------------------
     def relax(self, atoms, *, fmax: float | None = 0.1, steps: int | None = 500, relax_cell: bool | None = True,
               ase_filter: str | None = "FrechetCellFilter", save_path: str | None = None, loginterval: int | None = 1,
-              crystal_feas_save_path: str | None = None, verbose: bool = True, assign_magmoms: bool = True, **kwargs) -> dict:
+              crystal_feas_save_path: str | None = None, verbose: bool = True, assign_magmoms: bool = True, fixed_atoms=None,
+              **kwargs) -> dict:
         """Relax one Structure / Atoms until the largest generalized force is below ``fmax`` (reference dynamics.py:246-346).
-        Returns ``{"final_structure", "trajectory"}``."""
+        ``fixed_atoms``: the atoms or components to hold (module docstring); ``final_structure`` carries them as
+        ``selective_dynamics``.  Returns ``{"final_structure", "trajectory"}``."""
         if crystal_feas_save_path is not None:
             raise ValueError("crystal_feas_save_path is not supported by the device relaxation")
         p = self._params(fmax, steps, relax_cell, ase_filter, kwargs)
@@ -220,22 +250,24 @@ class StructOptimizer:
         if loginterval < 1:
             raise ValueError(f"{loginterval=} must be positive")
         structs = self._structures([atoms])
+        fixed = self._fixed(structs, None if fixed_atoms is None else [fixed_atoms], p["relax_cell"])
         report_isolated_atoms(self.calculator.model, structs)
         stream = sys.stdout if verbose else io.StringIO()
         with contextlib.redirect_stdout(stream):
-            prep, d, scale, trajs = self._run(structs, p, loginterval, verbose)
+            prep, d, scale, trajs = self._run(structs, p, loginterval, verbose, fixed)
         if save_path is not None:
             trajs[0].save(save_path)
-        res = self._result(prep, d, scale, 0, assign_magmoms)
+        res = self._result(prep, d, scale, 0, assign_magmoms, fixed[0])
         return {"final_structure": res["final_structure"], "trajectory": trajs[0]}
 
     def relax_batch(self, structures, *, fmax: float | None = 0.1, steps: int | None = 500, relax_cell: bool | None = True,
                     ase_filter: str | None = "FrechetCellFilter", loginterval: int | None = 1, verbose: bool = False,
-                    assign_magmoms: bool = True, trajectory: bool = False, **kwargs) -> list[dict]:
+                    assign_magmoms: bool = True, trajectory: bool = False, fixed_atoms=None, **kwargs) -> list[dict]:
         """Relax many structures at once, each an independent optimizer (same result as ``relax`` on it alone).  Returns one
         dict per structure: ``final_structure``, ``energy`` (eV), ``forces``, ``stress`` (Voigt, eV/A^3), ``magmoms``, ``n_steps``,
         ``converged``, ``status`` (and ``trajectory`` when asked).  Chunked by atoms like ``predict_structure``; a chunk whose
-        batch does not fit in device memory is split in two and relaxed again."""
+        batch does not fit in device memory is split in two and relaxed again.  ``fixed_atoms``: one entry per structure (``None``:
+        that structure's own ``selective_dynamics``, or nothing held)."""
         from chgnet_amd.model import _plan_chunks, _run_splitting  # noqa: PLC0415
 
         p = self._params(fmax, steps, relax_cell, ase_filter, kwargs)
@@ -246,14 +278,16 @@ class StructOptimizer:
         if not structs:
             return []
         model = self.calculator.model
+        fixed = self._fixed(structs, None if fixed_atoms is None else list(fixed_atoms), p["relax_cell"])
+        items = list(zip(structs, fixed))           # a chunk that is split keeps every structure with its mask
 
         def run(chunk):
             stream = sys.stdout if verbose else io.StringIO()
             with contextlib.redirect_stdout(stream):
-                prep, d, scale, trajs = self._run(chunk, p, loginterval if trajectory else None, verbose)
+                prep, d, scale, trajs = self._run([s for s, _ in chunk], p, loginterval if trajectory else None, verbose, [m for _, m in chunk])
             out = []
             for i in range(len(chunk)):
-                r = self._result(prep, d, scale, i, assign_magmoms)
+                r = self._result(prep, d, scale, i, assign_magmoms, chunk[i][1])
                 if trajectory:
                     r["trajectory"] = trajs[i]
                 out.append(r)
@@ -262,5 +296,5 @@ class StructOptimizer:
         results = []
         for a, b in _plan_chunks([len(s) for s in structs], 1, model.min_atoms_per_batch):
             report_isolated_atoms(model, structs[a:b])
-            results.extend(_run_splitting(run, structs[a:b]))
+            results.extend(_run_splitting(run, items[a:b]))
         return results

@@ -112,7 +112,8 @@ typedef struct chg_out_host {
  * so were chg_md_create_langevin and chg_test_md_step_langevin, whose extra parameters travel as arguments, not in chg_md_params;
  * so were chg_relax_create_lbfgs and chg_test_lbfgs_step, whose parameters travel in a struct of their own, chg_lbfgs_params;
  * so were chg_md_create_nhc, chg_md_download_nhc and chg_test_md_step_nhc: the chain length travels as an argument, the chain state and
- * the conserved energy in arrays of their own).  A binding compiled against another value must refuse the
+ * the conserved energy in arrays of their own; so were chg_relax_set_fixed, chg_md_set_fixed and the chg_test_*_step_fixed siblings: the
+ * mask travels as an argument to entry points of its own).  A binding compiled against another value must refuse the
  * library: chg_engine_create COPIES *desc, so an older, shorter chg_model_desc would be read past its end. */
 #define CHG_ABI_VERSION 5
 int chg_abi_version(void);
@@ -437,6 +438,42 @@ int chg_test_md_step_langevin(chg_engine* eng, const chg_md_params* params, int3
 int chg_test_md_step_nhc(chg_engine* eng, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
                          double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy,
                          const float* force, const float* stress, double* frac_next, double* lat_next, int32_t chain_length, double* nhc);
+
+/* ---- constraints: fixed atoms and fixed cartesian components in relaxation and molecular dynamics --------------------------------
+ * fixed [N,3] uint8, 1 = the component is held (ASE FixAtoms: all three of an atom; FixCartesian: some).  A constrained step is the
+ * unconstrained step with the constraint projected after every update, as ASE does (DESIGN.md "Constraints";
+ * tests/constraint_ref.py restates it in NumPy):
+ *   relaxation  the engine's force on a held component counts as 0 (generalized force, dot products, maxstep clamp, convergence test and
+ *               the reported forces; the finiteness test sees the raw forces).  With relax_cell a held atom keeps its fractional
+ *               coordinates and follows the cell; the stress is not masked.
+ *   MD          the absorbed forces and every write of the momenta are masked, so are the sums they feed.  A replica that holds at least
+ *               one component has dof = its free components: T = 2 Ekin / (dof kB), and N_f = dof in the Nose-Hoover chains (alpha, Q_1,
+ *               W, the N_f kT eta_1 term of H).  A replica that holds nothing keeps 3 n and 3 (n - 1).  Langevin noise stays a function
+ *               of (seed, atom, step): what is drawn for a held component is dropped.  Under a moving cell held atoms scale with it.
+ * Both calls are valid between create and the first run; null clears the mask (an all-zero mask computes bit for bit what no mask
+ * computes).  chg_md_set_fixed also sets the momenta: those given to the create call, with the held ones at 0 -- every call derives
+ * them from the created ones again, so another mask, or null, gives back what an earlier mask had zeroed.
+ * A fully held atom of a relaxation is evaluated at, and reported with, exactly the fractional coordinates the create call was given:
+ * the handle keeps a copy of them (u L0^-1 would round them in the last bit).  The chg_test_*_step_fixed entry points have no such
+ * copy and report u L0^-1 for every atom.  CHG_EINVAL with a message: after the first run; an atom with only some
+ * components held while the cell moves (relax_cell, CHG_MD_NPT_BERENDSEN*, CHG_MD_NPT_NHC); a replica with no free component in any
+ * ensemble but CHG_MD_NVE. */
+int chg_relax_set_fixed(chg_engine* eng, chg_relax* relax, const uint8_t* fixed /* [N,3] */);
+int chg_md_set_fixed(chg_engine* eng, chg_md* md, const uint8_t* fixed /* [N,3] */);
+/* Tests only: chg_test_relax_step, chg_test_lbfgs_step and the three chg_test_md_step* with a mask (null: exactly the entry point they
+ * extend; the refusals above apply).  chg_test_md_step_fixed takes the arguments of all three: friction and seeds for
+ * CHG_MD_NVT_LANGEVIN, chain_length and nhc for the two chain ensembles, null / 0 otherwise. */
+int chg_test_relax_step_fixed(chg_engine* eng, const chg_relax_params* params, int32_t n_struct, const int32_t* atom_off, double* q, double* v,
+                              double* sd, int32_t* si, const float* energy, const float* force, const float* stress, const float* magmom,
+                              double* frac_next, double* lat_next, const uint8_t* fixed);
+int chg_test_lbfgs_step_fixed(chg_engine* eng, const chg_relax_params* params, const chg_lbfgs_params* lbfgs, int32_t n_struct,
+                              const int32_t* atom_off, double* q, double* r0, double* g0, double* S, double* Y, double* rho, double* sd,
+                              int32_t* si, const float* energy, const float* force, const float* stress, const float* magmom,
+                              int32_t final_try, double* frac_next, double* lat_next, int32_t* retry, const uint8_t* fixed);
+int chg_test_md_step_fixed(chg_engine* eng, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
+                           double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy,
+                           const float* force, const float* stress, double* frac_next, double* lat_next, double friction,
+                           const uint64_t* seeds, int32_t chain_length, double* nhc, const uint8_t* fixed);
 
 /* ---- exchange steps of the multi-GPU path, straight on RCCL (one communicator per process = per GPU) ----------
  * The reference is single-device; these carry what SURVEY 8e needs and nothing else: the all-gather of per-structure

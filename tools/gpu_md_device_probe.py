@@ -7,6 +7,7 @@ of R = 1, 8, 64 replicas of the 256-atom 2x2x2 Li9Co7O16 cell, NVT Berendsen at 
       --thermostat nhc        the same leg with Nose-Hoover chains (3 thermostats); with --ensemble npt the isotropic barostat too
                               (task efs: the stress is evaluated every step, so compare it with Berendsen NVT only as an upper bound)
       --repeats K             K timed runs in one process, one JSON line each (their spread is the run-to-run noise)
+      --fixed-fraction F      hold every atom whose index is below F n in every replica (fixed_atoms; 0: no mask at all)
   --leg host                  one replica, BerendsenNVT + CHGNetCalculator.calculate per step
 
 Weights: the trained-like golden set (tests/golden/weights_trained_like.npz).  Run every leg under its own time limit.
@@ -43,6 +44,7 @@ def main() -> None:
     ap.add_argument("--thermostat", choices=("berendsen", "langevin", "nhc"), default="berendsen")
     ap.add_argument("--ensemble", choices=("nvt", "npt"), default="nvt", help="npt: --thermostat nhc only")
     ap.add_argument("--repeats", type=int, default=1)
+    ap.add_argument("--fixed-fraction", type=float, default=0.0)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "md_device_probe.jsonl"))
     args = ap.parse_args()
     if args.ensemble == "npt" and args.thermostat != "nhc":
@@ -65,6 +67,9 @@ def main() -> None:
             kw.update(thermostat="Langevin", friction=0.01)
         if args.thermostat == "nhc":
             kw.update(ensemble=args.ensemble, thermostat="Nose-Hoover-Chain", chain_length=3)
+        if args.fixed_fraction > 0:
+            kw.update(fixed_atoms=[list(range(int(args.fixed_fraction * len(c)))) for c in cells])
+            out.update(fixed_fraction=args.fixed_fraction)
         MolecularDynamics.run_batch(cells, 5, seeds=list(range(R)), **kw)          # warm-up: engine creation, first builds
         for rep in range(args.repeats):
             t0 = time.perf_counter()

@@ -6,6 +6,7 @@
                 structure at a time (the first --host-structures of the 1024 cells, then the 256-atom cell)
 
   --optimizer FIRE (default) or LBFGS: the optimizer_class of StructOptimizer, with its defaults.
+  --fixed-fraction F: hold every atom whose index is below F n in every structure of the batch leg (fixed_atoms; 0: no mask at all).
 
 Weights: the trained-like golden set (tests/golden/weights_trained_like.npz).  Run every leg under its own time limit.
 """
@@ -43,6 +44,7 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--host-structures", type=int, default=8)
     ap.add_argument("--optimizer", choices=("FIRE", "LBFGS"), default="FIRE")
+    ap.add_argument("--fixed-fraction", type=float, default=0.0)
     args = ap.parse_args()
 
     from chgnet_amd import CHGNet
@@ -59,6 +61,9 @@ def main() -> None:
     opt.relax_batch(cells[:4], fmax=args.fmax, steps=3)          # warm-up: engine creation, first builds
     out = {"leg": args.leg, "optimizer": args.optimizer, "fmax": args.fmax, "max_steps": args.steps}
     if args.leg == "batch":
+        if args.fixed_fraction > 0:
+            kw.update(fixed_atoms=[list(range(int(args.fixed_fraction * len(c)))) for c in cells])
+            out.update(fixed_fraction=args.fixed_fraction)
         t0 = time.perf_counter()
         res = opt.relax_batch(cells, **kw)
         wall = time.perf_counter() - t0
