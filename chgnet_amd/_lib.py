@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = (
     "chg_md_create", "chg_md_run", "chg_md_download", "chg_md_free", "chg_test_md_step",
     "chg_md_create_langevin", "chg_test_md_step_langevin",
     "chg_md_create_nhc", "chg_md_download_nhc", "chg_test_md_step_nhc",
+    "chg_md_create_nhc_flex", "chg_md_download_vg", "chg_test_md_step_nhc_flex",
     "chg_hessian_vector", "chg_hessian_vector_strain",
     "chg_relax_set_fixed", "chg_md_set_fixed", "chg_test_relax_step_fixed", "chg_test_lbfgs_step_fixed", "chg_test_md_step_fixed",
 )
@@ -100,6 +101,8 @@ class MdOutHost(ctypes.Structure):
 
 
 MD_NHC_STATE = 20   # include/chgnet_hip.h CHG_MD_NHC_STATE
+MD_VG = 9           # include/chgnet_hip.h CHG_MD_VG
+MD_CELL_MODES = {"flexible": 1, "axes": 2}   # CHG_MD_CELL_*
 
 _POINTER_OF = {"float64": ctypes.POINTER(ctypes.c_double), "float32": c_float_p, "int32": c_int_p}
 
@@ -231,6 +234,9 @@ def load() -> ctypes.CDLL:
     lib.chg_md_create_nhc.argtypes = [*lib.chg_md_create.argtypes[:5], ctypes.c_int32, ctypes.POINTER(vp)]
     lib.chg_md_download_nhc.argtypes = [vp, vp, dp, dp, ctypes.c_int32]
     lib.chg_test_md_step_nhc.argtypes = [*lib.chg_test_md_step.argtypes, ctypes.c_int32, dp]
+    lib.chg_md_create_nhc_flex.argtypes = [*lib.chg_md_create.argtypes[:5], ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(vp)]
+    lib.chg_md_download_vg.argtypes = [vp, vp, dp]
+    lib.chg_test_md_step_nhc_flex.argtypes = [*lib.chg_test_md_step_nhc.argtypes, dp, u8p]
     # constraints: the mask [N,3] uint8 travels as an argument of entry points of its own
     lib.chg_relax_set_fixed.argtypes = [vp, vp, u8p]
     lib.chg_md_set_fixed.argtypes = [vp, vp, u8p]

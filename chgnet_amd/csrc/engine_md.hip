@@ -1,6 +1,7 @@
 // engine_md.hip -- batched molecular dynamics (chg_md_*): NVE, NVT Berendsen, NPT Berendsen (inhomogeneous and isotropic), NVT
 // Langevin (BAOAB with counter-based noise, chg_md_create_langevin; not in the reference), Nose-Hoover-chain NVT and isotropic NPT
-// (Martyna-Tobias-Klein, chg_md_create_nhc; not in the reference), one independent replica per structure, state in HBM
+// (Martyna-Tobias-Klein, chg_md_create_nhc; not in the reference) and its flexible-cell forms (chg_md_create_nhc_flex: a symmetric
+// strain-rate matrix, all six components or the three diagonal ones), one independent replica per structure, state in HBM
 // (kernels_md.h).  Reference: MolecularDynamics, chgnet/model/dynamics.py:433-780.
 //
 // One evaluation of chg_md_run is one evaluate_and_step of the shared driver (engine_stepper.h) on ALL replicas, with k_md_step as
@@ -24,6 +25,7 @@ struct chg_md : chgh::Stepper {
   unsigned long long* seeds = nullptr;   // [B] noise keys (MD_NVT_LANGEVIN)
   int chain_length = 0;                  // MD_NVT_NHC / MD_NPT_NHC
   double* nhc = nullptr;                 // [B, MD_NHC] chain and barostat state
+  double* vg = nullptr;                  // [B, MD_VG] strain-rate matrix (MD_NPT_NHC_FLEX / MD_NPT_NHC_AXES)
   // frame ring: K slots
   int K = 0, ring_head = 0, ring_count = 0;
   std::vector<int> ring_step;
@@ -37,7 +39,8 @@ namespace {
 constexpr int FEA = chg::D;
 
 bool is_npt(int e) { return e == MD_NPT_BERENDSEN_INHOMOGENEOUS || e == MD_NPT_BERENDSEN; }   // the two-evaluation Berendsen loop
-bool is_nhc(int e) { return e == MD_NVT_NHC || e == MD_NPT_NHC; }
+bool is_flex(int e) { return e == MD_NPT_NHC_FLEX || e == MD_NPT_NHC_AXES; }   // chg_md_create_nhc_flex only
+bool is_nhc(int e) { return e == MD_NVT_NHC || e == MD_NPT_NHC || is_flex(e); }
 
 void carve_md(chg_md* d, Carver& c) {
   const size_t B = d->B, N = d->N, K = d->K;
@@ -52,6 +55,7 @@ void carve_md(chg_md* d, Carver& c) {
   d->seeds = c.take<unsigned long long>(d->p.ensemble == MD_NVT_LANGEVIN ? B : 0);
   d->nhc = c.take<double>(is_nhc(d->p.ensemble) ? MD_NHC * B : 0);
   d->fr_cons = c.take<double>(is_nhc(d->p.ensemble) ? K * B : 0);
+  d->vg = c.take<double>(is_flex(d->p.ensemble) ? MD_VG * B : 0);
   d->d_aoff = c.take<int>(B + 1);
   d->d_sel = c.take<int>(B);
   d->retry = c.take<int>(B);
@@ -66,17 +70,22 @@ void carve_md(chg_md* d, Carver& c) {
   d->d_nfree = c.take<int>(B);
 }
 
-bool moving_cell(int e) { return is_npt(e) || e == MD_NPT_NHC; }
+bool nhc_npt(int e) { return e == MD_NPT_NHC || is_flex(e); }
+bool moving_cell(int e) { return is_npt(e) || nhc_npt(e); }
 
 // langevin: the caller is an entry point that carries friction and seeds (the only ones that may run MD_NVT_LANGEVIN); chain_length
-// > 0 or < 0: one that carries the chain length (the only ones that may run MD_NVT_NHC / MD_NPT_NHC)
-const char* bad_params(const chg_md_params* p, bool langevin = false, double friction = 0.0, int chain_length = 0) {
+// > 0 or < 0: one that carries the chain length (the only ones that may run MD_NVT_NHC / MD_NPT_NHC); flex: the one that carries the
+// cell mode and the strain-rate matrix (the only one that may run MD_NPT_NHC_FLEX / MD_NPT_NHC_AXES, and nothing else)
+const char* bad_params(const chg_md_params* p, bool langevin = false, double friction = 0.0, int chain_length = 0, bool flex = false) {
+  if (flex != is_flex(p->ensemble))
+    return flex ? "ensemble must be CHG_MD_NPT_NHC_FLEX or CHG_MD_NPT_NHC_AXES"
+                : "CHG_MD_NPT_NHC_FLEX / CHG_MD_NPT_NHC_AXES need a strain-rate matrix: use chg_md_create_nhc_flex";
   if (chain_length != 0) {
     if (!is_nhc(p->ensemble)) return "ensemble must be CHG_MD_NVT_NHC or CHG_MD_NPT_NHC";
     if (chain_length < 1 || chain_length > MD_NHC_MAX) return "chain_length must be 1..4";
     if (!(p->temperature > 0.0) || !std::isfinite(p->temperature)) return "temperature must be > 0 (the thermostat masses are kB T tau^2)";
     if (!(p->taut > 0.0) || !std::isfinite(p->taut)) return "taut must be > 0";
-    if (p->ensemble == MD_NPT_NHC && (!(p->taup > 0.0) || !std::isfinite(p->taup) || !std::isfinite(p->pressure)))
+    if (nhc_npt(p->ensemble) && (!(p->taup > 0.0) || !std::isfinite(p->taup) || !std::isfinite(p->pressure)))
       return "taup must be > 0 and pressure finite";
   } else if (is_nhc(p->ensemble)) {
     return "CHG_MD_NVT_NHC / CHG_MD_NPT_NHC need a chain length: use chg_md_create_nhc";
@@ -88,7 +97,7 @@ const char* bad_params(const chg_md_params* p, bool langevin = false, double fri
   } else if (p->ensemble == MD_NVT_LANGEVIN) {
     return "CHG_MD_NVT_LANGEVIN needs friction and seeds: use chg_md_create_langevin";
   }
-  if (p->ensemble < MD_NVE || p->ensemble > MD_NPT_NHC) return "unknown ensemble";
+  if (p->ensemble < MD_NVE || p->ensemble > MD_NPT_NHC_AXES) return "unknown ensemble";
   if (!(p->dt > 0.0) || !std::isfinite(p->dt)) return "dt must be > 0";
   if (!langevin && p->ensemble != MD_NVE && (!(p->taut > 0.0) || !(p->temperature >= 0.0))) return "taut must be > 0 and temperature >= 0";
   if (is_npt(p->ensemble) && (!(p->taup > 0.0) || !(p->compressibility > 0.0) || !std::isfinite(p->pressure)))
@@ -118,8 +127,15 @@ chg::MdStepArgs base_args(chg_md* d) {
   return a;
 }
 
-void launch_step(chg_engine* eng, const MdStepArgs& a, int grid) {
+// vg: the strain-rate matrices of the flexible-cell ensembles, which have a kernel of their own
+void launch_step(chg_engine* eng, const MdStepArgs& a, int grid, double* vg) {
   LaunchScope ls(eng, "md_step");
+  if (is_flex(a.ensemble)) {
+    const MdFlexArgs x{vg};
+    if (a.fixed) hipLaunchKernelGGL(k_md_step_flex<true>, dim3((unsigned)grid), dim3(256), 0, eng->stream, a, x);
+    else hipLaunchKernelGGL(k_md_step_flex<false>, dim3((unsigned)grid), dim3(256), 0, eng->stream, a, x);
+    return;
+  }
   if (a.fixed) hipLaunchKernelGGL(k_md_step<true>, dim3((unsigned)grid), dim3(256), 0, eng->stream, a);
   else hipLaunchKernelGGL(k_md_step<false>, dim3((unsigned)grid), dim3(256), 0, eng->stream, a);
 }
@@ -131,7 +147,7 @@ int evaluate_and_step(chg_engine* eng, chg_md* d, MdStepArgs a) {
     a.cfea = a.fr_cfea ? b->crystal_fea : nullptr;
     a.sel = sel;
     a.final_try = final_try;
-    launch_step(eng, a, grid);
+    launch_step(eng, a, grid, d->vg);
   });
 }
 
@@ -152,12 +168,13 @@ void set_frame(chg_md* d, MdStepArgs& a, int step) {
 
 bool frame_due(const chg_md* d, int step) { return d->p.loginterval > 0 && step % d->p.loginterval == 0; }
 
-// chg_md_create (seeds null, chain_length 0), chg_md_create_langevin and chg_md_create_nhc (chain_length != 0)
+// chg_md_create (seeds null, chain_length 0), chg_md_create_langevin, chg_md_create_nhc (chain_length != 0) and chg_md_create_nhc_flex
+// (flex: params->ensemble is one of the two flexible-cell codes)
 int create(chg_engine* eng, const char* fn, const chg_structs_host* h, const double* masses, const double* momenta, const chg_md_params* params,
-           double friction, const uint64_t* seeds, int chain_length, chg_md** out) {
+           double friction, const uint64_t* seeds, int chain_length, chg_md** out, bool flex = false) {
   if (!eng || !h || !masses || !params || !out) return CHG_EINVAL;
   *out = nullptr;
-  if (const char* bad = bad_params(params, seeds != nullptr, friction, chain_length)) { eng->err = std::string(fn) + ": " + bad; return CHG_EINVAL; }
+  if (const char* bad = bad_params(params, seeds != nullptr, friction, chain_length, flex)) { eng->err = std::string(fn) + ": " + bad; return CHG_EINVAL; }
   TRY(check_structs(eng, fn, h));
   const int B = h->n_struct, N = h->n_atoms;
   if (chain_length != 0)
@@ -175,7 +192,7 @@ int create(chg_engine* eng, const char* fn, const chg_structs_host* h, const dou
   d->chain_length = chain_length;
   d->K = params->loginterval > 0 ? params->ring_frames : 0;
   d->ring_step.assign(std::max(d->K, 1), 0);
-  d->task = CHG_TASK_E | CHG_TASK_F | ((is_npt(params->ensemble) || params->ensemble == MD_NPT_NHC || params->log_stress) ? CHG_TASK_S : 0u);
+  d->task = CHG_TASK_E | CHG_TASK_F | ((is_npt(params->ensemble) || nhc_npt(params->ensemble) || params->log_stress) ? CHG_TASK_S : 0u);
   d->r_atom = params->r_atom; d->r_bond = params->r_bond; d->numerical_tol = params->numerical_tol;
   int s = alloc_state(eng, fn, d, h, 0, [&](Carver& c) { carve_md(d, c); });
   if (s != CHG_OK) { chg_md_free(eng, d); return s; }
@@ -190,6 +207,7 @@ int create(chg_engine* eng, const char* fn, const chg_structs_host* h, const dou
   up(d->si, si.data(), sizeof(int) * si.size());
   if (seeds) up(d->seeds, seeds, sizeof(uint64_t) * B);
   if (chain_length != 0) up.zero(d->nhc, sizeof(double) * MD_NHC * (size_t)B);
+  if (flex) up.zero(d->vg, sizeof(double) * MD_VG * (size_t)B);
   up(d->d_aoff, h->atom_off, sizeof(int) * (B + 1));
   up(d->frac_next, h->frac, sizeof(double) * 3 * N);
   up(d->lat_next, h->lattice, sizeof(double) * 9 * B);
@@ -220,6 +238,18 @@ int chg_md_create_langevin(chg_engine* eng, const chg_structs_host* h, const dou
 int chg_md_create_nhc(chg_engine* eng, const chg_structs_host* h, const double* masses, const double* momenta, const chg_md_params* params,
                       int32_t chain_length, chg_md** out) {
   return create(eng, "chg_md_create_nhc", h, masses, momenta, params, 0.0, nullptr, chain_length != 0 ? chain_length : -1, out);
+}
+
+int chg_md_create_nhc_flex(chg_engine* eng, const chg_structs_host* h, const double* masses, const double* momenta, const chg_md_params* params,
+                           int32_t chain_length, int32_t cell_mode, chg_md** out) {
+  if (!eng || !params) return CHG_EINVAL;
+  if (cell_mode != CHG_MD_CELL_FLEXIBLE && cell_mode != CHG_MD_CELL_AXES) {
+    eng->err = "chg_md_create_nhc_flex: cell_mode must be CHG_MD_CELL_FLEXIBLE or CHG_MD_CELL_AXES";
+    return CHG_EINVAL;
+  }
+  chg_md_params p = *params;   // the cell mode chooses the ensemble code: params->ensemble is ignored
+  p.ensemble = cell_mode == CHG_MD_CELL_FLEXIBLE ? MD_NPT_NHC_FLEX : MD_NPT_NHC_AXES;
+  return create(eng, "chg_md_create_nhc_flex", h, masses, momenta, &p, 0.0, nullptr, chain_length != 0 ? chain_length : -1, out, true);
 }
 
 int chg_md_set_fixed(chg_engine* eng, chg_md* d, const uint8_t* fixed) {
@@ -260,7 +290,7 @@ int chg_md_run(chg_engine* eng, chg_md* d, int32_t n_steps) {
   } else if (n_steps > 0) {   // a later call: start the step from the cached forces (ASE: get_forces() is cached)
     MdStepArgs a = base_args(d);
     a.flags = MD_START;
-    launch_step(eng, a, d->B);
+    launch_step(eng, a, d->B, d->vg);
     if (hipGetLastError() != hipSuccess) { eng->err = "chg_md_run: step kernel launch failed"; return CHG_EHIP; }
     TRY(copy_back(eng, "chg_md_run", d, d->B, nullptr, nullptr));
   }
@@ -332,6 +362,15 @@ int chg_md_download_nhc(chg_engine* eng, chg_md* d, double* nhc_state, double* f
   return CHG_OK;
 }
 
+int chg_md_download_vg(chg_engine* eng, chg_md* d, double* vg) {
+  if (!eng || !d || !vg) return CHG_EINVAL;
+  if (!is_flex(d->p.ensemble)) { eng->err = "chg_md_download_vg: the handle was not created by chg_md_create_nhc_flex"; return CHG_EINVAL; }
+  HIP_TRY(eng, hipSetDevice(eng->device));
+  TRY(d2h(eng, vg, d->vg, MD_VG * (size_t)d->B));
+  HIP_TRY(eng, hipStreamSynchronize(eng->stream));
+  return CHG_OK;
+}
+
 int chg_md_free(chg_engine* eng, chg_md* d) {
   if (!d) return CHG_OK;
   release(eng, d);
@@ -343,17 +382,17 @@ int chg_md_free(chg_engine* eng, chg_md* d) {
 
 namespace {
 
-// chg_test_md_step (seeds and nhc null), chg_test_md_step_langevin and chg_test_md_step_nhc
+// chg_test_md_step (seeds and nhc null), chg_test_md_step_langevin, chg_test_md_step_nhc and chg_test_md_step_nhc_flex (vg set)
 int test_step(chg_engine* eng, const char* fn, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
               double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy, const float* force,
               const float* stress, double* frac_next, double* lat_next, double friction, const uint64_t* seeds, int chain_length = 0,
-              double* nhc = nullptr, const uint8_t* fixed = nullptr) {
+              double* nhc = nullptr, const uint8_t* fixed = nullptr, double* vg = nullptr) {
   if (!eng || !params || n_struct <= 0 || !atom_off || !r || !momenta || !forces || !masses || !sd || !si || !frac_next || !lat_next)
     return CHG_EINVAL;
   if ((flags & MD_ABSORB) && (!energy || !force)) return CHG_EINVAL;
   if (flags & ~(MD_ABSORB | MD_KICK2 | MD_START)) return CHG_EINVAL;
-  if (const char* bad = bad_params(params, seeds != nullptr, friction, chain_length)) { eng->err = std::string(fn) + ": " + bad; return CHG_EINVAL; }
-  if (params->ensemble == MD_NPT_NHC && (flags & MD_ABSORB) && !stress) return CHG_EINVAL;
+  if (const char* bad = bad_params(params, seeds != nullptr, friction, chain_length, vg != nullptr)) { eng->err = std::string(fn) + ": " + bad; return CHG_EINVAL; }
+  if (nhc_npt(params->ensemble) && (flags & MD_ABSORB) && !stress) return CHG_EINVAL;
   const size_t B = n_struct, N = atom_off[n_struct];
   if (atom_off[0] != 0) return CHG_EINVAL;
   for (size_t o = 0; o < B; ++o)
@@ -366,7 +405,7 @@ int test_step(chg_engine* eng, const char* fn, const chg_md_params* params, int3
                     {stress, nullptr, sizeof(float) * 9 * B}, {frac_next, frac_next, sizeof(double) * 3 * N},
                     {lat_next, lat_next, sizeof(double) * 9 * B}, {nullptr, nullptr, sizeof(int) * B},
                     {seeds, nullptr, sizeof(uint64_t) * B}, {nhc, nhc, sizeof(double) * MD_NHC * B}, {fixed, nullptr, 3 * N},
-                    {fixed ? nfree.data() : nullptr, nullptr, sizeof(int) * B}};
+                    {fixed ? nfree.data() : nullptr, nullptr, sizeof(int) * B}, {vg, vg, sizeof(double) * MD_VG * B}};
   return run_test_step(eng, fn, bufs, [&] {
     chg_md tmp;
     tmp.p = *params;
@@ -383,7 +422,7 @@ int test_step(chg_engine* eng, const char* fn, const chg_md_params* params, int3
     a.flags = flags;
     a.final_try = 1;
     if (fixed) { a.fixed = (const unsigned char*)bufs[15].d; a.nfree = (const int*)bufs[16].d; }
-    launch_step(eng, a, (int)B);
+    launch_step(eng, a, (int)B, (double*)bufs[17].d);
   });
 }
 
@@ -413,6 +452,15 @@ int chg_test_md_step_nhc(chg_engine* eng, const chg_md_params* params, int32_t n
   if (!nhc) return CHG_EINVAL;
   return test_step(eng, "chg_test_md_step_nhc", params, n_struct, atom_off, flags, r, momenta, forces, masses, sd, si, energy, force,
                    stress, frac_next, lat_next, 0.0, nullptr, chain_length != 0 ? chain_length : -1, nhc);
+}
+
+int chg_test_md_step_nhc_flex(chg_engine* eng, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
+                              double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy,
+                              const float* force, const float* stress, double* frac_next, double* lat_next, int32_t chain_length, double* nhc,
+                              double* vg, const uint8_t* fixed) {
+  if (!nhc || !vg) return CHG_EINVAL;
+  return test_step(eng, "chg_test_md_step_nhc_flex", params, n_struct, atom_off, flags, r, momenta, forces, masses, sd, si, energy, force,
+                   stress, frac_next, lat_next, 0.0, nullptr, chain_length != 0 ? chain_length : -1, nhc, fixed, vg);
 }
 
 int chg_test_md_step_fixed(chg_engine* eng, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,

@@ -21,6 +21,9 @@
 //              and on the isotropic barostat, Tuckerman et al., J. Phys. A 39 (2006) 5629): barostat chain, particle chain,
 //              barostat kick, half kick and drift with the strain-rate factors, cell scaled; MD_ABSORB | MD_KICK2 runs the mirror
 //              image after the kick.  One evaluation per step (phase stays 0), no fixcm.  tests/nhc_ref.py restates it.
+//              MD_NPT_NHC_FLEX / MD_NPT_NHC_AXES (k_md_step_flex, a kernel of its own so that k_md_step keeps its instruction stream):
+//              the same factorisation with a symmetric strain-rate matrix Vg in place of veps -- all six components free, or the three
+//              diagonal ones -- and 3x3 matrix exponentials in place of the scalar factors.  tests/nhc_flex_ref.py restates it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -32,7 +35,7 @@ namespace chg {
 
 enum : int { MD_RUNNING = 0, MD_NONFINITE = 1 };
 enum : int { MD_NVE = 0, MD_NVT_BERENDSEN = 1, MD_NPT_BERENDSEN_INHOMOGENEOUS = 2, MD_NPT_BERENDSEN = 3, MD_NVT_LANGEVIN = 4,
-             MD_NVT_NHC = 5, MD_NPT_NHC = 6 };
+             MD_NVT_NHC = 5, MD_NPT_NHC = 6, MD_NPT_NHC_FLEX = 7, MD_NPT_NHC_AXES = 8 };   // 7, 8: k_md_step_flex only
 enum : int { MD_ABSORB = 1, MD_KICK2 = 2, MD_START = 4 };
 constexpr int MD_SD = 40;   // doubles per replica: L[9] L^-1[9] Epot Ekin T stress[9] (eV/A^3, no ideal gas) G[9] (sum p p / m) spare
 constexpr int MD_SI = 4;    // ints per replica: steps completed, status, phase, spare
@@ -41,6 +44,9 @@ constexpr int MD_FRAME_SCAL = 3;   // frame scalars per replica: Epot (engine un
 // first chain_length of each are used), strain rate veps, H - Epot of the last absorbed evaluation (eV), 2 spare
 constexpr int MD_NHC = 20;
 constexpr int MD_NHC_MAX = 4;
+// flexible-cell chains (MD_NPT_NHC_FLEX / MD_NPT_NHC_AXES), doubles per replica: the symmetric strain-rate matrix Vg, row-major; it takes
+// the place of veps, which stays 0 in the chain state
+constexpr int MD_VG = 9;
 
 struct MdStepArgs {
   // state, replica o owns atom rows aoff[o]..aoff[o+1] (the batch has the same numbering: every replica is evaluated every time)
@@ -578,6 +584,338 @@ static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
     double* fr = a.frac_next + 3 * ((size_t)a0 + i);
 #pragma unroll
     for (int j = 0; j < 3; ++j) fr[j] = y0 * sLinv[j] + y1 * sLinv[3 + j] + y2 * sLinv[6 + j];
+  }
+}
+
+// ---- flexible-cell Nose-Hoover-chain NPT ------------------------------------------------------------------------------------------------
+// Symmetric 3x3 matrices travel as six numbers in the order of the kinetic sums: xx yy zz yz xz xy.
+
+// the upper triangle of a b for two commuting symmetric matrices (a polynomial of a matrix and that matrix): the product is symmetric,
+// and forming one triangle only keeps it so to the bit
+__device__ __forceinline__ void sym_mul(const double (&a)[6], const double (&b)[6], double (&c)[6]) {
+  c[0] = a[0] * b[0] + a[5] * b[5] + a[4] * b[4];
+  c[1] = a[5] * b[5] + a[1] * b[1] + a[3] * b[3];
+  c[2] = a[4] * b[4] + a[3] * b[3] + a[2] * b[2];
+  c[3] = a[5] * b[4] + a[1] * b[3] + a[3] * b[2];
+  c[4] = a[0] * b[4] + a[5] * b[3] + a[4] * b[2];
+  c[5] = a[0] * b[5] + a[5] * b[1] + a[4] * b[3];
+}
+
+// exp(a): a is halved until its row-sum norm is <= 1/4 (exact), the Taylor polynomial of degree 14 (remainder 0.25^15 / 15! < 1e-21) is
+// evaluated by Horner's rule and squared back.  Exactly I at a = 0, exactly diagonal for a multiple of I, no eigenvectors anywhere; exp(-a)
+// runs the same operations on the negated entries and is the inverse of exp(a) to rounding.  The loops stay rolled: thread 0 only.
+__device__ inline void sym_expm(const double (&a)[6], double (&e)[6]) {
+  const double nrm = fmax(fabs(a[0]) + fabs(a[5]) + fabs(a[4]), fmax(fabs(a[5]) + fabs(a[1]) + fabs(a[3]), fabs(a[4]) + fabs(a[3]) + fabs(a[2])));
+  double sc = 1.0;
+  int sq = 0;
+  while (nrm * sc > 0.25 && sq < 64) { sc *= 0.5; ++sq; }
+  double x[6], y[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { x[k] = a[k] * sc; e[k] = k < 3 ? 1.0 : 0.0; }
+#pragma unroll 1
+  for (int k = 14; k >= 1; --k) {
+    sym_mul(x, e, y);
+    const double ik = 1.0 / (double)k;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) e[j] = (j < 3 ? 1.0 : 0.0) + y[j] * ik;
+  }
+#pragma unroll 1
+  for (int s = 0; s < sq; ++s) {
+    sym_mul(e, e, y);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) e[j] = y[j];
+  }
+}
+
+// masses of the flexible barostat on top of NhcConst: W_g = W / 3 per strain-rate component, d_b free components (6, or 3 for the
+// axes), barostat chain masses Q'_1 = d_b kT taup^2, Q'_k = kT taup^2 (= NhcConst::Qb)
+struct FlexConst {
+  double Wg, db, Qb0;
+  bool axes;
+  __device__ FlexConst(const NhcConst& c, int ensemble) {
+    axes = ensemble == MD_NPT_NHC_AXES;
+    db = axes ? 3.0 : 6.0;
+    Wg = c.W / 3.0;
+    Qb0 = db * c.Qb;
+  }
+};
+
+// W_g sum_ab Vg_ab^2: twice the kinetic energy of the cell
+__device__ __forceinline__ double flex_k2(const FlexConst& fc, const double (&vg)[6]) {
+  return fc.Wg * (vg[0] * vg[0] + vg[1] * vg[1] + vg[2] * vg[2] + 2.0 * (vg[3] * vg[3] + vg[4] * vg[4] + vg[5] * vg[5]));
+}
+
+// Vg_ab += tau G_ab / W_g on the free components, G = sum p p / m + (K2 / N_f - Pext V) I - V (sigma + sigma^T) / 2 with the stress sg[9]
+__device__ __forceinline__ void flex_barostat_kick(const NhcConst& c, const FlexConst& fc, double (&vg)[6], const double (&pp)[6], double K2, double vol,
+                                                   const double* sg, double pext, double tau) {
+  const double iso = K2 / c.nf - pext * vol;
+  vg[0] += tau * (pp[0] + iso - vol * sg[0]) / fc.Wg;
+  vg[1] += tau * (pp[1] + iso - vol * sg[4]) / fc.Wg;
+  vg[2] += tau * (pp[2] + iso - vol * sg[8]) / fc.Wg;
+  if (!fc.axes) {
+    vg[3] += tau * (pp[3] - vol * (0.5 * (sg[5] + sg[7]))) / fc.Wg;
+    vg[4] += tau * (pp[4] - vol * (0.5 * (sg[2] + sg[6]))) / fc.Wg;
+    vg[5] += tau * (pp[5] - vol * (0.5 * (sg[1] + sg[3]))) / fc.Wg;
+  }
+}
+
+// half a step of the barostat chain: Vg *= s
+__device__ inline void flex_barostat_chain(const NhcConst& c, const FlexConst& fc, double* xs, int M, double (&vg)[6], double tau) {
+  double v[MD_NHC_MAX], eta[MD_NHC_MAX];
+#pragma unroll
+  for (int k = 0; k < MD_NHC_MAX; ++k) { v[k] = xs[8 + k]; eta[k] = xs[12 + k]; }
+  const double s = nhc_chain(v, eta, M, fc.Qb0, c.Qb, flex_k2(fc, vg), fc.db, c.kT, tau);
+#pragma unroll
+  for (int k = 0; k < MD_NHC_MAX; ++k) { xs[8 + k] = v[k]; xs[12 + k] = eta[k]; }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) vg[k] *= s;
+}
+
+// half a step of the particle chain: returns s, K2 *= s^2
+__device__ inline double flex_particle_chain(const NhcConst& c, double* xs, int M, double& K2, double tau) {
+  double v[MD_NHC_MAX], eta[MD_NHC_MAX];
+#pragma unroll
+  for (int k = 0; k < MD_NHC_MAX; ++k) { v[k] = xs[k]; eta[k] = xs[4 + k]; }
+  const double s = nhc_chain(v, eta, M, c.Q0, c.Qk, K2, c.nf, c.kT, tau);
+#pragma unroll
+  for (int k = 0; k < MD_NHC_MAX; ++k) { xs[k] = v[k]; xs[4 + k] = eta[k]; }
+  K2 *= s * s;
+  return s;
+}
+
+__device__ __forceinline__ void flex_load_vg(const double* g, double (&vg)[6]) {
+  vg[0] = g[0]; vg[1] = g[4]; vg[2] = g[8]; vg[3] = g[5]; vg[4] = g[2]; vg[5] = g[1];
+}
+__device__ __forceinline__ void flex_store_vg(double* g, const double (&vg)[6]) {
+  g[0] = vg[0]; g[4] = vg[1]; g[8] = vg[2]; g[5] = g[7] = vg[3]; g[2] = g[6] = vg[4]; g[1] = g[3] = vg[5];
+}
+
+// exp(-(Vg + tr Vg / N_f I) tau / 2): the factor on either side of the half kick
+__device__ inline void flex_kick_factor(const NhcConst& c, const double (&vg)[6], double tau, double (&e)[6]) {
+  const double tr = (vg[0] + vg[1] + vg[2]) / c.nf;
+  double arg[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) arg[k] = -(vg[k] + (k < 3 ? tr : 0.0)) * (0.5 * tau);
+  sym_expm(arg, e);
+}
+
+// row vector times symmetric matrix
+__device__ __forceinline__ void row_sym(const double (&v)[3], const double* e, double (&w)[3]) {
+  w[0] = v[0] * e[0] + v[1] * e[5] + v[2] * e[4];
+  w[1] = v[0] * e[5] + v[1] * e[1] + v[2] * e[3];
+  w[2] = v[0] * e[4] + v[1] * e[3] + v[2] * e[2];
+}
+
+struct MdFlexArgs {
+  double* vg;   // [B, MD_VG]
+};
+
+// MD_NPT_NHC_FLEX / MD_NPT_NHC_AXES on the launch structure of k_md_step (one workgroup per replica, the chains and the matrix
+// exponentials in thread 0, the factors handed to the row passes through LDS); phase stays 0, no fixcm.  MASK as in k_md_step.
+template <bool MASK>
+static __global__ __launch_bounds__(256) void k_md_step_flex(MdStepArgs a, MdFlexArgs x) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int o = a.sel ? a.sel[blockIdx.x] : blockIdx.x;
+  const int a0 = a.aoff[o], n = a.aoff[o + 1] - a0;
+  double* r = a.r + 3 * (size_t)a0;
+  double* p = a.p + 3 * (size_t)a0;
+  double* f = a.f + 3 * (size_t)a0;
+  const double* m = a.m + a0;
+  double* sd = a.sd + (size_t)MD_SD * o;
+  int* si = a.si + (size_t)MD_SI * o;
+  double* xs = a.nhc + (size_t)MD_NHC * o;
+  double* gv = x.vg + (size_t)MD_VG * o;
+  const double hdt = 0.5 * a.dt;
+  const unsigned char* fixed = MASK ? a.fixed + 3 * (size_t)a0 : nullptr;
+  auto dof = [&]() -> double { return (MASK && a.nfree[o] < 3 * n) ? (double)a.nfree[o] : 3.0 * n; };
+  auto nhc_nf = [&]() -> double { return (MASK && a.nfree[o] < 3 * n) ? (double)a.nfree[o] : 3.0 * (n - 1); };
+
+  __shared__ double red[4][7];
+  __shared__ int rfin[4];
+  __shared__ double sLinv[9], sE1[6], sE2[6], s_lam;
+  __shared__ int s_status, s_go;
+
+  if (tid == 0) s_status = si[1];
+  __syncthreads();
+  if (s_status != MD_RUNNING) return;
+
+  if (a.flags & MD_ABSORB) {
+    const bool kick = a.flags & MD_KICK2;
+    const bool frame = a.fr_scal != nullptr;
+    int fin = 1;
+    for (int i = tid; i < n; i += 256) {
+      const float* fi = a.force + 3 * ((size_t)a0 + i);
+      fin &= isfinite(fi[0]) && isfinite(fi[1]) && isfinite(fi[2]);
+    }
+    fin = __all(fin);
+    if (lane == 0) rfin[wv] = fin;
+    __syncthreads();
+    if (tid == 0) {
+      int ok = rfin[0] & rfin[1] & rfin[2] & rfin[3] & (int)isfinite(a.energy[o]);
+      if (a.stress)
+        for (int i = 0; i < 9; ++i) ok &= (int)isfinite(a.stress[9 * (size_t)o + i]);
+      if (!ok) {
+        if (a.final_try) si[1] = MD_NONFINITE;
+        else a.retry[o] = 1;
+      }
+      s_go = ok;
+      if (ok && kick) {
+        const NhcConst c(a, nhc_nf());
+        double vg[6], e[6];
+        flex_load_vg(gv, vg);
+        flex_kick_factor(c, vg, hdt, e);
+        for (int k = 0; k < 6; ++k) sE1[k] = e[k];
+      }
+    }
+    __syncthreads();
+    if (!s_go) return;
+
+    // second half of the step: p <- (p E1 + dt/2 f) E1 and sum p p / m in one pass, thread 0 runs the barostat kick and the two chains,
+    // one scaling pass writes the frame's momenta
+    double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = tid; i < n; i += 256) {
+      const float* fi = a.force + 3 * ((size_t)a0 + i);
+      const unsigned held = md_held_bits<MASK>(fixed, i);
+      auto fm = [&](int j) -> float { return (MASK && ((held >> j) & 1u)) ? 0.0f : fi[j]; };
+      double pi[3] = {p[3 * i], p[3 * i + 1], p[3 * i + 2]};
+      const double fj[3] = {fm(0), fm(1), fm(2)};
+      if (kick) {
+        double q[3];
+        row_sym(pi, sE1, q);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) q[j] += hdt * fj[j];
+        row_sym(q, sE1, pi);
+      }
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        f[3 * i + j] = fj[j];
+        pi[j] = md_free<MASK>(held, j, pi[j]);
+        p[3 * i + j] = pi[j];
+      }
+      const double im = 1.0 / m[i];
+      acc[1] += pi[0] * pi[0] * im; acc[2] += pi[1] * pi[1] * im; acc[3] += pi[2] * pi[2] * im;
+      acc[4] += pi[1] * pi[2] * im; acc[5] += pi[0] * pi[2] * im; acc[6] += pi[0] * pi[1] * im;
+      if (frame) {
+        const size_t ro = 3 * ((size_t)a0 + i);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { a.fr_pos[ro + j] = r[3 * i + j]; a.fr_force[ro + j] = fm(j); }
+      }
+    }
+#pragma unroll
+    for (int k = 1; k < 7; ++k) acc[k] = wave_sum_f64(acc[k]);
+    if (lane == 0)
+      for (int k = 1; k < 7; ++k) red[wv][k] = acc[k];
+    __syncthreads();
+    if (tid == 0) {
+      const NhcConst c(a, nhc_nf());
+      const FlexConst fc(c, a.ensemble);
+      double pp[6], vg[6];
+      for (int k = 0; k < 6; ++k) pp[k] = red[0][k + 1] + red[1][k + 1] + red[2][k + 1] + red[3][k + 1];
+      double K2 = pp[0] + pp[1] + pp[2], s = 1.0;
+      const double vol = fabs(det3(sd));
+      sd[18] = a.energy[o];
+      if (a.stress)
+        for (int i = 0; i < 9; ++i) sd[21 + i] = (double)a.stress[9 * (size_t)o + i] * a.stress_weight;
+      flex_load_vg(gv, vg);
+      if (kick) {
+        flex_barostat_kick(c, fc, vg, pp, K2, vol, sd + 21, a.pressure, hdt);
+        s = flex_particle_chain(c, xs, a.nhc_len, K2, hdt);
+        flex_barostat_chain(c, fc, xs, a.nhc_len, vg, hdt);
+        flex_store_vg(gv, vg);
+        si[0] += 1;
+      }
+      const double ekin = 0.5 * K2;
+      const double T = (!MASK || dof() > 0.0) ? 2.0 * ekin / (dof() * a.kB) : 0.0;
+      double cons = 0.5 * K2 + a.pressure * vol + 0.5 * flex_k2(fc, vg);
+      for (int k = 0; k < a.nhc_len; ++k)
+        cons += 0.5 * (k == 0 ? c.Q0 : c.Qk) * xs[k] * xs[k] + (k == 0 ? c.nf : 1.0) * c.kT * xs[4 + k] +
+                0.5 * (k == 0 ? fc.Qb0 : c.Qb) * xs[8 + k] * xs[8 + k] + (k == 0 ? fc.db : 1.0) * c.kT * xs[12 + k];
+      xs[17] = cons;
+      sd[19] = ekin;
+      sd[20] = T;
+      const double s2 = s * s;
+      const double Gm[9] = {pp[0], pp[5], pp[4], pp[5], pp[1], pp[3], pp[4], pp[3], pp[2]};
+      for (int i = 0; i < 9; ++i) sd[30 + i] = Gm[i] * s2;
+      s_lam = s;
+      if (frame) {
+        a.fr_scal[MD_FRAME_SCAL * (size_t)o] = a.energy[o];
+        a.fr_scal[MD_FRAME_SCAL * (size_t)o + 1] = ekin;
+        a.fr_scal[MD_FRAME_SCAL * (size_t)o + 2] = T;
+        if (a.fr_cons) a.fr_cons[o] = cons;
+        for (int i = 0; i < 9; ++i) a.fr_cell[9 * (size_t)o + i] = sd[i];
+        for (int i = 0; i < 9; ++i) a.fr_stress[9 * (size_t)o + i] = a.stress ? a.stress[9 * (size_t)o + i] : 0.0f;
+        if (a.cfea && a.fr_cfea)
+          for (int i = 0; i < a.fea_dim; ++i) a.fr_cfea[(size_t)a.fea_dim * o + i] = a.cfea[(size_t)a.fea_dim * o + i];
+      }
+    }
+    __syncthreads();
+    if (kick || frame) {
+      const double s = s_lam;
+      for (int i = tid; i < n; i += 256) {
+        const unsigned held = md_held_bits<MASK>(fixed, i);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          const double pj = md_free<MASK>(held, j, p[3 * i + j] * s);
+          p[3 * i + j] = pj;
+          if (frame) a.fr_mom[3 * ((size_t)a0 + i) + j] = pj;
+        }
+      }
+    }
+  }
+
+  if (!(a.flags & MD_START)) return;
+  // up to the evaluation: barostat chain, particle chain, barostat kick (cached stress, sum p p / m scaled by s^2), then one pass
+  // p <- (p s E1 + dt/2 f) E1, r <- (r E2 + dt p / m) E2 with E2 = exp(Vg dt/2); the cell is multiplied by E2 E2 = exp(Vg dt)
+  __syncthreads();   // sd, the chain state and p written above
+  if (tid == 0) {
+    const NhcConst c(a, nhc_nf());
+    const FlexConst fc(c, a.ensemble);
+    double vg[6], e[6], e3[6], arg[6];
+    flex_load_vg(gv, vg);
+    flex_barostat_chain(c, fc, xs, a.nhc_len, vg, hdt);
+    double K2 = sd[30] + sd[34] + sd[38];
+    const double s = flex_particle_chain(c, xs, a.nhc_len, K2, hdt), s2 = s * s;
+    const double pp[6] = {sd[30] * s2, sd[34] * s2, sd[38] * s2, sd[35] * s2, sd[32] * s2, sd[31] * s2};
+    double L[9], Ln[9];
+    for (int i = 0; i < 9; ++i) L[i] = sd[i];
+    flex_barostat_kick(c, fc, vg, pp, K2, fabs(det3(L)), sd + 21, a.pressure, hdt);
+    flex_store_vg(gv, vg);
+    flex_kick_factor(c, vg, hdt, e);
+    for (int k = 0; k < 6; ++k) sE1[k] = e[k];
+    for (int k = 0; k < 6; ++k) arg[k] = vg[k] * hdt;
+    sym_expm(arg, e);
+    for (int k = 0; k < 6; ++k) sE2[k] = e[k];
+    sym_mul(e, e, e3);
+    const double E3[9] = {e3[0], e3[5], e3[4], e3[5], e3[1], e3[3], e3[4], e3[3], e3[2]};
+    mm3(L, E3, Ln);
+    for (int i = 0; i < 9; ++i) sd[i] = Ln[i];
+    inv3(Ln, sd + 9);
+    s_lam = s;
+    for (int i = 0; i < 9; ++i) { sLinv[i] = sd[9 + i]; a.lat_next[9 * (size_t)o + i] = Ln[i]; }
+  }
+  __syncthreads();
+  const double s = s_lam;
+  for (int i = tid; i < n; i += 256) {
+    const double idm = a.dt / m[i];
+    const unsigned held = md_held_bits<MASK>(fixed, i);
+    double pi[3] = {p[3 * i] * s, p[3 * i + 1] * s, p[3 * i + 2] * s}, q[3], ri[3] = {r[3 * i], r[3 * i + 1], r[3 * i + 2]}, y[3];
+    row_sym(pi, sE1, q);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) q[j] += hdt * f[3 * i + j];
+    row_sym(q, sE1, pi);
+    row_sym(ri, sE2, y);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      pi[j] = md_free<MASK>(held, j, pi[j]);
+      p[3 * i + j] = pi[j];
+      y[j] += idm * pi[j];
+    }
+    row_sym(y, sE2, ri);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) r[3 * i + j] = ri[j];
+    double* fr = a.frac_next + 3 * ((size_t)a0 + i);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) fr[j] = ri[0] * sLinv[j] + ri[1] * sLinv[3 + j] + ri[2] * sLinv[6 + j];
   }
 }
 

@@ -30,6 +30,17 @@ temperature stays ``T = 2 Ekin / (3 n kB)``: it equilibrates at ``temperature * 
 one-atom structure are refused.  tests/nhc_ref.py restates the integrator.  This is not ASE's ``NPT`` class, which the reference
 calls "Nose-Hoover" (Melchionna leap-frog: upper-triangular cells only, conserved quantity of first order in the time step).
 
+``cell_dof`` (``ensemble="npt", thermostat="Nose-Hoover-Chain"`` only) chooses what of the cell the barostat moves.  ``"isotropic"``
+(default) is the scaling above.  ``"flexible"`` is the fully flexible form of the same equations: a symmetric strain-rate matrix
+``Vg`` takes the place of ``veps``, all six components move, so lengths and angles follow the stress (layered/spinel transformations,
+anisotropic expansion).  ``"axes"`` frees only the three cartesian diagonal components: independent axis lengths, angles kept for an
+orthogonal cell -- the sampling counterpart of ``"Berendsen_inhomogeneous"``.  With d_b = 6 or 3 free components, W_g = W / 3 and
+barostat chain masses d_b kT taup^2, kT taup^2, ...: ``Vg_ab += dt/2 (sum p_a p_b / m + (sum p^2/m / N_f - P V) delta_ab - V sym(sigma)_ab) / W_g``,
+``p <- (p E + dt/2 F) E`` with ``E = exp(-(Vg + tr Vg / N_f) dt/4)``, ``r <- (r E + dt p/m) E`` with ``E = exp(Vg dt/2)``, ``h <- h exp(Vg dt)``
+(3x3 matrix exponentials; rows of h are the lattice vectors).  ``pressure`` stays a scalar: an anisotropic target stress needs a
+reference cell.  ``thermostat_state["vg"]`` is the [3, 3] strain-rate matrix (``veps`` stays 0); it continues over split runs like the
+chains.  Held atoms follow the cell map ``r <- r exp(Vg dt)``.  tests/nhc_flex_ref.py restates the integrator.
+
 Constraints (DESIGN.md "Constraints"): ``fixed_atoms`` -- atom indices, a bool [n] array or a bool [n, 3] array with True = held --
 or, without the keyword, the ``selective_dynamics`` site property (True = free) and the ``FixAtoms`` / ``FixCartesian`` constraints of
 an ASE ``Atoms``.  Held components get no force and no momentum (the initial momenta are masked after they are drawn, as ASE's
@@ -70,6 +81,7 @@ GPA = 1e9 * ((1 / _E) / 1e30)               # units.GPa = 1e9 * Pascal, eV/A^3
 
 ENSEMBLE_CODES = {"nve": 0, "nvt": 1, "npt_inhomogeneous": 2, "npt_berendsen": 3, "nvt_langevin": 4, "nvt_nhc": 5, "npt_nhc": 6}
 NHC_KINDS = ("nvt_nhc", "npt_nhc")
+CELL_DOFS = ("isotropic", "flexible", "axes")    # thermostat="Nose-Hoover-Chain", ensemble="npt"; the last two: chg_md_create_nhc_flex
 STATUS_NAMES = ("RUNNING", "NONFINITE")
 _U64 = (1 << 64) - 1
 
@@ -207,6 +219,7 @@ class _DeviceRun:
         self.masses = np.ascontiguousarray(masses, np.float64)
         mom = np.ascontiguousarray(momenta, np.float64)
         self.nhc = kind in NHC_KINDS
+        self.cell_dof = cfg.get("cell_dof", "isotropic")
         params = _lib.MdParams(ensemble=ENSEMBLE_CODES[kind], fixcm=0 if self.nhc else 1, dt=cfg["dt"], temperature=cfg["temperature"], taut=cfg["taut"],
                                taup=cfg["taup"], pressure=cfg["pressure"], compressibility=cfg["compressibility"], kB=KB,
                                stress_weight=calc.stress_weight, loginterval=self.loginterval, ring_frames=self.RING,
@@ -222,6 +235,10 @@ class _DeviceRun:
             self.eng._check(self.eng.lib.chg_md_create_langevin(
                 self.eng.handle, ctypes.byref(host), self.masses.ctypes.data_as(dp), mom.ctypes.data_as(dp), ctypes.byref(params),
                 cfg["friction"], keys.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(self.handle)))
+        elif self.cell_dof != "isotropic":   # chain length and cell mode travel beside the params struct
+            self.eng._check(self.eng.lib.chg_md_create_nhc_flex(
+                self.eng.handle, ctypes.byref(host), self.masses.ctypes.data_as(dp), mom.ctypes.data_as(dp), ctypes.byref(params),
+                int(cfg["chain_length"]), _lib.MD_CELL_MODES[self.cell_dof], ctypes.byref(self.handle)))
         elif self.nhc:                   # the chain length travels beside the params struct; the centre of mass is never touched
             self.eng._check(self.eng.lib.chg_md_create_nhc(
                 self.eng.handle, ctypes.byref(host), self.masses.ctypes.data_as(dp), mom.ctypes.data_as(dp), ctypes.byref(params),
@@ -259,6 +276,9 @@ class _DeviceRun:
             dp = ctypes.POINTER(ctypes.c_double)
             self.eng._check(self.eng.lib.chg_md_download_nhc(self.eng.handle, self.handle, extra["nhc_state"].ctypes.data_as(dp),
                                                              extra["frame_conserved"].ctypes.data_as(dp), K))
+            if self.cell_dof != "isotropic":
+                extra["vg"] = np.empty((B, 3, 3))
+                self.eng._check(self.eng.lib.chg_md_download_vg(self.eng.handle, self.handle, extra["vg"].ctypes.data_as(dp)))
         self.eng._check(self.eng.lib.chg_md_download(self.eng.handle, self.handle, ctypes.byref(o)))
         d.update(extra)
         return d
@@ -268,7 +288,10 @@ class _DeviceRun:
         if not self.nhc:
             return None
         x, M = d["nhc_state"][i], self.chain_length
-        return {"v": x[0:M].copy(), "eta": x[4:4 + M].copy(), "vb": x[8:8 + M].copy(), "xi": x[12:12 + M].copy(), "veps": float(x[16])}
+        st = {"v": x[0:M].copy(), "eta": x[4:4 + M].copy(), "vb": x[8:8 + M].copy(), "xi": x[12:12 + M].copy(), "veps": float(x[16])}
+        if self.cell_dof != "isotropic":
+            st["vg"] = d["vg"][i].copy()
+        return st
 
     def run(self, steps: int, sink) -> dict:
         """``steps`` more steps in chunks whose frames fit the ring; every drained frame goes to ``sink(d, k)``.  Returns the final state."""
@@ -290,14 +313,15 @@ class _DeviceRun:
 class MolecularDynamics:
     """Molecular dynamics on the device (reference MolecularDynamics: same arguments and defaults, plus ``seed``, and
     ``thermostat="Langevin"`` with ``friction`` in 1/fs for NVT and ``thermostat="Nose-Hoover-Chain"`` with ``chain_length`` for NVT and
-    NPT, see the module docstring)."""
+    NPT and ``cell_dof`` ("isotropic", "flexible", "axes") for NPT, see the module docstring)."""
 
     def __init__(self, atoms, *, model=None, ensemble: str = "nvt", thermostat: str = "Berendsen_inhomogeneous", temperature: float = 300,
                  starting_temperature: float | None = None, timestep: float = 2.0, pressure: float = 1.01325e-4, taut: float | None = None,
                  taup: float | None = None, bulk_modulus: float | None = None, trajectory: str | None = None, logfile: str | None = None,
                  loginterval: int = 1, crystal_feas_logfile: str | None = None, append_trajectory: bool = False,  # noqa: ARG002
                  on_isolated_atoms: str = "warn", return_site_energies: bool = False, use_device: str | None = None,
-                 seed: int | None = None, friction: float | None = None, chain_length: int | None = None, fixed_atoms=None) -> None:
+                 seed: int | None = None, friction: float | None = None, chain_length: int | None = None, fixed_atoms=None,
+                 cell_dof: str = "isotropic") -> None:
         self.ensemble, self.thermostat = ensemble, thermostat
         self.fixed_atoms = fixed_atoms
         self.kind = _resolve(ensemble, thermostat, bulk_modulus)
@@ -310,10 +334,15 @@ class MolecularDynamics:
             if isinstance(chain_length, bool) or chain_length != int(chain_length) or not 1 <= int(chain_length) <= 4:
                 raise ValueError(f"{chain_length=} must be an integer from 1 to 4")
             if np.ndim(pressure) != 0:
-                raise ValueError("pressure must be a scalar (GPa) with thermostat='Nose-Hoover-Chain': the cell scales isotropically")
+                raise ValueError("pressure must be a scalar (GPa) with thermostat='Nose-Hoover-Chain': a tensor target needs a reference cell")
             if not (np.isfinite(temperature) and temperature > 0):
                 raise ValueError(f"{temperature=} must be > 0 with thermostat='Nose-Hoover-Chain' (the thermostat masses are kB T taut^2)")
         self.chain_length = int(chain_length) if nhc else None
+        if cell_dof not in CELL_DOFS:
+            raise ValueError(f"{cell_dof=} must be one of {CELL_DOFS}")
+        if cell_dof != "isotropic" and self.kind != "npt_nhc":
+            raise ValueError(f"{cell_dof=} belongs to ensemble='npt', thermostat='Nose-Hoover-Chain'")
+        self.cell_dof = cell_dof
         self.thermostat_state: dict | None = None
         if friction is not None and not langevin:
             raise ValueError(f"{friction=} belongs to ensemble='nvt', thermostat='Langevin'")
@@ -339,6 +368,8 @@ class MolecularDynamics:
         self.cfg = {"dt": timestep * FS, "temperature": float(temperature), "taut": taut * FS, "taup": taup * FS, "pressure": pressure * GPA,
                     "compressibility": compressibility, "loginterval": int(loginterval), "crystal_fea": crystal_feas_logfile is not None,
                     "log_stress": False, "friction": friction / FS, "chain_length": self.chain_length}
+        if cell_dof != "isotropic":      # the isotropic configuration is what it was before the keyword existed
+            self.cfg["cell_dof"] = cell_dof
         self.trajectory, self.logfile, self.loginterval, self.timestep = trajectory, logfile, int(loginterval), timestep
         self.crystal_feas_logfile = crystal_feas_logfile
         self.starting_temperature, self.seed = starting_temperature, seed

@@ -113,7 +113,8 @@ typedef struct chg_out_host {
  * so were chg_relax_create_lbfgs and chg_test_lbfgs_step, whose parameters travel in a struct of their own, chg_lbfgs_params;
  * so were chg_md_create_nhc, chg_md_download_nhc and chg_test_md_step_nhc: the chain length travels as an argument, the chain state and
  * the conserved energy in arrays of their own; so were chg_relax_set_fixed, chg_md_set_fixed and the chg_test_*_step_fixed siblings: the
- * mask travels as an argument to entry points of its own).  A binding compiled against another value must refuse the
+ * mask travels as an argument to entry points of its own; so were chg_md_create_nhc_flex, chg_md_download_vg and
+ * chg_test_md_step_nhc_flex: the cell mode travels as an argument, the strain-rate matrix in an array of its own).  A binding compiled against another value must refuse the
  * library: chg_engine_create COPIES *desc, so an older, shorter chg_model_desc would be read past its end. */
 #define CHG_ABI_VERSION 5
 int chg_abi_version(void);
@@ -343,7 +344,8 @@ int chg_test_lbfgs_step(chg_engine* eng, const chg_relax_params* params, const c
  * takes two evaluations per step, as ASE does (the barostat moves the atoms before the first half kick).  Units are ASE's: eV, A,
  * amu, time in A sqrt(amu / eV).  DESIGN.md "Molecular dynamics" states the semantics; tests/md_ref.py restates them in NumPy. */
 enum { CHG_MD_NVE = 0, CHG_MD_NVT_BERENDSEN = 1, CHG_MD_NPT_BERENDSEN_INHOMOGENEOUS = 2, CHG_MD_NPT_BERENDSEN = 3,
-       CHG_MD_NVT_LANGEVIN = 4 /* chg_md_create_langevin only */, CHG_MD_NVT_NHC = 5, CHG_MD_NPT_NHC = 6 /* chg_md_create_nhc only */ };
+       CHG_MD_NVT_LANGEVIN = 4 /* chg_md_create_langevin only */, CHG_MD_NVT_NHC = 5, CHG_MD_NPT_NHC = 6 /* chg_md_create_nhc only */,
+       CHG_MD_NPT_NHC_FLEX = 7, CHG_MD_NPT_NHC_AXES = 8 /* chg_md_create_nhc_flex only */ };
 enum { CHG_MD_RUNNING = 0, CHG_MD_NONFINITE = 1 };
 typedef struct chg_md_params {
   int32_t ensemble;            /* CHG_MD_*                                                                                 */
@@ -415,6 +417,24 @@ int chg_md_create_nhc(chg_engine* eng, const chg_structs_host* host, const doubl
  * frame_conserved [K, B], in the order chg_md_download returns them.  The ring is NOT drained: call this before chg_md_download.  Null
  * pointers are skipped.  CHG_EINVAL for a handle of another ensemble. */
 int chg_md_download_nhc(chg_engine* eng, chg_md* md, double* nhc_state, double* frame_conserved, int32_t frame_capacity);
+/* Flexible-cell Nose-Hoover-chain NPT, not in the reference: the same equations and factorisation with a symmetric strain-rate matrix Vg
+ * (1/time) in place of the scalar veps.  cell_mode CHG_MD_CELL_FLEXIBLE frees all six components of Vg (lengths and angles move;
+ * ensemble code CHG_MD_NPT_NHC_FLEX), CHG_MD_CELL_AXES the three cartesian diagonal ones (the off-diagonal ones stay exactly 0: an
+ * orthogonal cell keeps its angles; CHG_MD_NPT_NHC_AXES); the isotropic cell is chg_md_create_nhc.  params->ensemble is ignored: the cell
+ * mode chooses the code.  With d_b = 6 or 3 free components: W_g = W / 3 per component, barostat chain masses Q'_1 = d_b kT taup^2,
+ * Q'_k = kT taup^2; the barostat chain thermostats W_g sum_ab Vg_ab^2 with d_b degrees of freedom; the barostat kick is
+ * Vg_ab += dt/2 (sum p_a p_b / m + (sum p^2/m / N_f - Pext V) delta_ab - V (sigma + sigma^T)_ab / 2) / W_g; particles and cell move with
+ * exponentials of symmetric 3x3 matrices (DESIGN.md "Nose-Hoover chains"; tests/nhc_flex_ref.py restates the step in NumPy).  pressure is
+ * a scalar.  Everything chg_md_create_nhc requires for CHG_MD_NPT_NHC is required here, task efs every step; chg_md_create and
+ * chg_md_create_nhc refuse the two codes with CHG_EINVAL.  The chain state is that of chg_md_download_nhc with veps = 0 and
+ * H - Epot = ... + Pext V + W_g sum_ab Vg_ab^2 / 2 + sum Q'_k vb_k^2 / 2 + d_b kT xi_1 + kT sum_{k>1} xi_k; the strain-rate matrix,
+ * CHG_MD_VG doubles per replica (row-major 3x3, symmetric, zero at creation), is read with chg_md_download_vg [B, CHG_MD_VG]
+ * (CHG_EINVAL for a handle of another ensemble). */
+enum { CHG_MD_CELL_FLEXIBLE = 1, CHG_MD_CELL_AXES = 2 };
+#define CHG_MD_VG 9
+int chg_md_create_nhc_flex(chg_engine* eng, const chg_structs_host* host, const double* masses, const double* momenta,
+                           const chg_md_params* params, int32_t chain_length, int32_t cell_mode, chg_md** out);
+int chg_md_download_vg(chg_engine* eng, chg_md* md, double* vg);
 /* n_steps steps of every replica (the first call evaluates the initial configuration first and writes the frame of step 0).  A batch
  * whose results are non-finite is evaluated again on the wide-range sweep; a replica that is non-finite even there stops as
  * CHG_MD_NONFINITE with its state untouched.  CHG_EINVAL (nothing run) when the frames due do not fit the ring. */
@@ -438,6 +458,12 @@ int chg_test_md_step_langevin(chg_engine* eng, const chg_md_params* params, int3
 int chg_test_md_step_nhc(chg_engine* eng, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
                          double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy,
                          const float* force, const float* stress, double* frac_next, double* lat_next, int32_t chain_length, double* nhc);
+/* The same for CHG_MD_NPT_NHC_FLEX / CHG_MD_NPT_NHC_AXES (params->ensemble names the code): vg [n_struct, CHG_MD_VG] in place, and a mask
+ * fixed [N,3] or null as in chg_test_md_step_fixed (which refuses the two codes).  MD_START reads all of sd[30..38]. */
+int chg_test_md_step_nhc_flex(chg_engine* eng, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
+                              double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy,
+                              const float* force, const float* stress, double* frac_next, double* lat_next, int32_t chain_length, double* nhc,
+                              double* vg, const uint8_t* fixed);
 
 /* ---- constraints: fixed atoms and fixed cartesian components in relaxation and molecular dynamics --------------------------------
  * fixed [N,3] uint8, 1 = the component is held (ASE FixAtoms: all three of an atom; FixCartesian: some).  A constrained step is the
@@ -456,7 +482,7 @@ int chg_test_md_step_nhc(chg_engine* eng, const chg_md_params* params, int32_t n
  * A fully held atom of a relaxation is evaluated at, and reported with, exactly the fractional coordinates the create call was given:
  * the handle keeps a copy of them (u L0^-1 would round them in the last bit).  The chg_test_*_step_fixed entry points have no such
  * copy and report u L0^-1 for every atom.  CHG_EINVAL with a message: after the first run; an atom with only some
- * components held while the cell moves (relax_cell, CHG_MD_NPT_BERENDSEN*, CHG_MD_NPT_NHC); a replica with no free component in any
+ * components held while the cell moves (relax_cell, CHG_MD_NPT_BERENDSEN*, CHG_MD_NPT_NHC*); a replica with no free component in any
  * ensemble but CHG_MD_NVE. */
 int chg_relax_set_fixed(chg_engine* eng, chg_relax* relax, const uint8_t* fixed /* [N,3] */);
 int chg_md_set_fixed(chg_engine* eng, chg_md* md, const uint8_t* fixed /* [N,3] */);

@@ -6,6 +6,8 @@ of R = 1, 8, 64 replicas of the 256-atom 2x2x2 Li9Co7O16 cell, NVT Berendsen at 
       --thermostat langevin   the same leg with the Langevin thermostat (BAOAB, 0.01 / fs, noise generated in the step kernel)
       --thermostat nhc        the same leg with Nose-Hoover chains (3 thermostats); with --ensemble npt the isotropic barostat too
                               (task efs: the stress is evaluated every step, so compare it with Berendsen NVT only as an upper bound)
+      --cell-dof flexible|axes  with --thermostat nhc --ensemble npt: the flexible-cell barostat (symmetric strain-rate matrix, all six
+                              components or the three diagonal ones) instead of the isotropic one; compare it with --cell-dof isotropic
       --repeats K             K timed runs in one process, one JSON line each (their spread is the run-to-run noise)
       --fixed-fraction F      hold every atom whose index is below F n in every replica (fixed_atoms; 0: no mask at all)
   --leg host                  one replica, BerendsenNVT + CHGNetCalculator.calculate per step
@@ -43,12 +45,15 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--thermostat", choices=("berendsen", "langevin", "nhc"), default="berendsen")
     ap.add_argument("--ensemble", choices=("nvt", "npt"), default="nvt", help="npt: --thermostat nhc only")
+    ap.add_argument("--cell-dof", choices=("isotropic", "flexible", "axes"), default="isotropic", help="--thermostat nhc --ensemble npt only")
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--fixed-fraction", type=float, default=0.0)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "md_device_probe.jsonl"))
     args = ap.parse_args()
     if args.ensemble == "npt" and args.thermostat != "nhc":
         ap.error("--ensemble npt is probed with --thermostat nhc only")
+    if args.cell_dof != "isotropic" and args.ensemble != "npt":
+        ap.error("--cell-dof belongs to --thermostat nhc --ensemble npt")
 
     from chgnet_amd import CHGNet, CHGNetCalculator
 
@@ -67,6 +72,9 @@ def main() -> None:
             kw.update(thermostat="Langevin", friction=0.01)
         if args.thermostat == "nhc":
             kw.update(ensemble=args.ensemble, thermostat="Nose-Hoover-Chain", chain_length=3)
+        if args.ensemble == "npt":
+            kw.update(cell_dof=args.cell_dof)
+            out.update(cell_dof=args.cell_dof)
         if args.fixed_fraction > 0:
             kw.update(fixed_atoms=[list(range(int(args.fixed_fraction * len(c)))) for c in cells])
             out.update(fixed_fraction=args.fixed_fraction)
