@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = (
     "chg_md_create_nhc_flex", "chg_md_download_vg", "chg_test_md_step_nhc_flex",
     "chg_hessian_vector", "chg_hessian_vector_strain",
     "chg_relax_set_fixed", "chg_md_set_fixed", "chg_test_relax_step_fixed", "chg_test_lbfgs_step_fixed", "chg_test_md_step_fixed",
+    "chg_md_set_observers", "chg_md_download_observables", "chg_test_md_observe",
 )
 
 
@@ -100,11 +101,23 @@ class MdOutHost(ctypes.Structure):
                 ("frame_stress", c_float_p), ("frame_crystal_fea", c_float_p)]
 
 
+class MdObserveParams(ctypes.Structure):
+    _fields_ = [("sample_interval", ctypes.c_int32), ("n_lags", ctypes.c_int32), ("subtract_com", ctypes.c_int32),
+                ("n_species", ctypes.c_int32), ("rdf_bins", ctypes.c_int32), ("reserved", ctypes.c_int32), ("rdf_rmax", ctypes.c_double)]
+
+
+class MdObservablesHost(ctypes.Structure):
+    _dp, _ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
+    _fields_ = [("msd", _dp), ("vacf", _dp), ("cnt", _ip), ("rdf", ctypes.POINTER(ctypes.c_uint64)), ("rdf_samples", _ip), ("vol_sum", _dp)]
+
+
+MD_OBS_MAX_LAGS, MD_OBS_MAX_SPECIES, MD_OBS_RDF_CELLS = 4096, 8, 16384   # csrc/kernels_md_obs.h
 MD_NHC_STATE = 20   # include/chgnet_hip.h CHG_MD_NHC_STATE
 MD_VG = 9           # include/chgnet_hip.h CHG_MD_VG
 MD_CELL_MODES = {"flexible": 1, "axes": 2}   # CHG_MD_CELL_*
 
-_POINTER_OF = {"float64": ctypes.POINTER(ctypes.c_double), "float32": c_float_p, "int32": c_int_p}
+_POINTER_OF = {"float64": ctypes.POINTER(ctypes.c_double), "float32": c_float_p, "int32": c_int_p,
+               "int64": ctypes.POINTER(ctypes.c_int64), "uint64": ctypes.POINTER(ctypes.c_uint64)}
 
 
 def fill_out(out: ctypes.Structure, arrays: dict) -> ctypes.Structure:
@@ -243,6 +256,11 @@ def load() -> ctypes.CDLL:
     lib.chg_test_relax_step_fixed.argtypes = [*lib.chg_test_relax_step.argtypes, u8p]
     lib.chg_test_lbfgs_step_fixed.argtypes = [*lib.chg_test_lbfgs_step.argtypes, u8p]
     lib.chg_test_md_step_fixed.argtypes = [*lib.chg_test_md_step.argtypes, ctypes.c_double, u64p, ctypes.c_int32, dp, u8p]
+    # MD observables: parameters and species in, accumulators out
+    lib.chg_md_set_observers.argtypes = [vp, vp, ctypes.POINTER(MdObserveParams), c_int_p]
+    lib.chg_md_download_observables.argtypes = [vp, vp, ctypes.POINTER(MdObservablesHost)]
+    lib.chg_test_md_observe.argtypes = [vp, ctypes.POINTER(MdObserveParams), ctypes.c_int32, c_int_p, c_int_p, dp, ctypes.c_int32, dp, dp, dp,
+                                        c_int_p, ctypes.POINTER(MdObservablesHost)]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is ctypes.c_int and name not in ("chg_device_count", "chg_profile_count"):

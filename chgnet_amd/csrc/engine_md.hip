@@ -12,6 +12,23 @@
 #include "engine_stepper.h"
 
 #include "kernels_md.h"
+#include "kernels_md_obs.h"
+
+// chg_md_set_observers / chg_test_md_observe: parameters, one device allocation of its own (ring, accumulators, and for a run the
+// private frame slot), and the number of samples taken
+struct MdObservers {
+  chg_md_observe_params p{};
+  int B = 0, N = 0, n_max = 0;   // n_max: atoms of the largest replica (grid of k_md_obs_rdf)
+  long long k = 0;               // samples taken
+  char* mem = nullptr;
+  int* species = nullptr;
+  double *ring_pos = nullptr, *ring_vel = nullptr, *ring_com = nullptr, *msd = nullptr, *vacf = nullptr, *vol_sum = nullptr;
+  long long *cnt = nullptr, *rdf_samples = nullptr;
+  unsigned long long* hist = nullptr;
+  // private frame slot: what the step kernels write of a completed step that is sampled but not logged
+  double *fr_scal = nullptr, *fr_pos = nullptr, *fr_mom = nullptr, *fr_cell = nullptr;
+  float *fr_force = nullptr, *fr_stress = nullptr;
+};
 
 struct chg_md : chgh::Stepper {
   chg_md_params p{};
@@ -32,6 +49,7 @@ struct chg_md : chgh::Stepper {
   double *fr_scal, *fr_pos, *fr_mom, *fr_cell;
   float *fr_force, *fr_stress, *fr_cfea;
   double* fr_cons = nullptr;             // [K, B] H - Epot (Nose-Hoover chains)
+  MdObservers* obs = nullptr;            // chg_md_set_observers
 };
 
 namespace {
@@ -220,6 +238,149 @@ int create(chg_engine* eng, const char* fn, const chg_structs_host* h, const dou
   return CHG_OK;
 }
 
+
+// ---- observers (kernels_md_obs.h)
+
+const char* bad_observe(const chg_md_observe_params* p) {
+  if (p->sample_interval < 1) return "sample_interval must be >= 1";
+  if (p->n_lags < 0 || p->n_lags > MD_OBS_MAX_LAGS) return "n_lags must be 0..4096";
+  if (p->n_species < 1 || p->n_species > MD_OBS_SPECIES) return "n_species must be 1..8";
+  if (p->rdf_bins < 0) return "rdf_bins must be >= 0";
+  if (p->rdf_bins > 0 && (!(p->rdf_rmax > 0.0) || !std::isfinite(p->rdf_rmax))) return "rdf_rmax must be > 0 and finite";
+  if ((int64_t)p->n_species * p->n_species * p->rdf_bins > MD_OBS_RDF_CELLS)
+    return "n_species * n_species * rdf_bins must be <= 16384 (the histogram lives in 64 KB of LDS)";
+  if (p->n_lags == 0 && p->rdf_bins == 0) return "nothing to observe: n_lags and rdf_bins are both 0";
+  return nullptr;
+}
+
+void carve_obs(MdObservers* x, Carver& c, bool frame_slot) {
+  const size_t B = x->B, N = x->N, L = x->p.n_lags, S = x->p.n_species, bins = x->p.rdf_bins;
+  x->species = c.take<int>(N);
+  x->ring_pos = c.take<double>(L * 3 * N);
+  x->ring_vel = c.take<double>(L * 3 * N);
+  x->ring_com = c.take<double>(L * 3 * B);
+  x->msd = c.take<double>(B * L * S);
+  x->vacf = c.take<double>(B * L * S);
+  x->cnt = c.take<long long>(B * L);
+  x->hist = c.take<unsigned long long>(B * S * S * bins);
+  x->rdf_samples = c.take<long long>(B);
+  x->vol_sum = c.take<double>(B);
+  if (!frame_slot) return;
+  x->fr_scal = c.take<double>(MD_FRAME_SCAL * B);
+  x->fr_pos = c.take<double>(3 * N);
+  x->fr_mom = c.take<double>(3 * N);
+  x->fr_cell = c.take<double>(9 * B);
+  x->fr_force = c.take<float>(3 * N);
+  x->fr_stress = c.take<float>(9 * B);
+}
+
+void free_observers(MdObservers* x) {
+  if (!x) return;
+  if (x->mem) hipFree(x->mem);
+  delete x;
+}
+
+// parameters and species checked, buffers allocated, accumulators zeroed, species uploaded (synchronised)
+int create_observers(chg_engine* eng, const char* fn, const chg_md_observe_params* p, int B, const int* aoff, const int32_t* species,
+                     bool frame_slot, MdObservers** out) {
+  if (const char* bad = bad_observe(p)) { eng->err = std::string(fn) + ": " + bad; return CHG_EINVAL; }
+  const int N = aoff[B];
+  for (int i = 0; i < N; ++i)
+    if (species[i] < 0 || species[i] >= p->n_species) {
+      eng->err = std::string(fn) + ": species index " + std::to_string(species[i]) + " of atom " + std::to_string(i) + " is outside 0.." +
+                 std::to_string(p->n_species - 1);
+      return CHG_EINVAL;
+    }
+  MdObservers* x = new MdObservers();
+  x->p = *p;
+  x->B = B; x->N = N;
+  for (int o = 0; o < B; ++o) x->n_max = std::max(x->n_max, aoff[o + 1] - aoff[o]);
+  Carver sizer{nullptr};
+  carve_obs(x, sizer, frame_slot);
+  if (hipMalloc(&x->mem, sizer.pos) != hipSuccess) {
+    (void)hipGetLastError();
+    x->mem = nullptr;
+    free_observers(x);
+    eng->err = std::string(fn) + ": observer state of " + std::to_string(sizer.pos) + " bytes (ring of " + std::to_string(p->n_lags) +
+               " snapshots) cannot be allocated";
+    return CHG_ENOMEM;
+  }
+  Carver carver{x->mem};
+  carve_obs(x, carver, frame_slot);
+  StateUpload up{eng, fn};
+  up(x->species, species, sizeof(int) * (size_t)N);
+  up.zero(x->msd, (size_t)((char*)(x->vol_sum + B) - (char*)x->msd));   // every accumulator: msd .. vol_sum are carved in a row
+  int s = up.finish();
+  if (s == CHG_OK && p->rdf_bins > 0 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(k_md_obs_rdf), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)(sizeof(unsigned) * p->n_species * p->n_species * p->rdf_bins)) != hipSuccess) {
+    eng->err = std::string(fn) + ": the histogram does not fit the LDS";
+    s = CHG_EHIP;
+  }
+  if (s != CHG_OK) { free_observers(x); return s; }
+  *out = x;
+  return CHG_OK;
+}
+
+// one sample: the snapshot of a completed step through the ring and the accumulators (enqueued on the engine's stream)
+int observe(chg_engine* eng, const char* fn, MdObservers* x, const double* pos, const double* mom, const double* cell, const double* mass,
+            const int* status, int status_stride, const int* d_aoff) {
+  LaunchScope ls(eng, "md_observe");
+  const chg_md_observe_params& p = x->p;
+  MdObsArgs a{};
+  a.pos = pos; a.mom = mom; a.cell = cell; a.mass = mass; a.species = x->species; a.status = status; a.status_stride = status_stride;
+  a.aoff = d_aoff; a.N = x->N; a.B = x->B; a.S = p.n_species;
+  a.ring_pos = x->ring_pos; a.ring_vel = x->ring_vel; a.ring_com = x->ring_com; a.L = p.n_lags; a.k = x->k;
+  a.subtract_com = p.subtract_com; a.msd = x->msd; a.vacf = x->vacf; a.cnt = x->cnt;
+  a.hist = x->hist; a.rdf_samples = x->rdf_samples; a.vol_sum = x->vol_sum; a.bins = p.rdf_bins; a.rmax = p.rdf_rmax;
+  if (p.n_lags > 0) {
+    a.slot = (int)(x->k % p.n_lags);
+    const unsigned lags = (unsigned)std::min<long long>(x->k, p.n_lags - 1) + 1;
+    hipLaunchKernelGGL(k_md_obs_push, dim3((unsigned)x->B), dim3(256), 0, eng->stream, a);
+    hipLaunchKernelGGL(k_md_obs_corr, dim3(lags, (unsigned)x->B), dim3(256), 0, eng->stream, a);
+  }
+  if (p.rdf_bins > 0) {
+    const unsigned chunks = (unsigned)((x->n_max + MD_OBS_RDF_ROWS - 1) / MD_OBS_RDF_ROWS);
+    const size_t lds = sizeof(unsigned) * p.n_species * p.n_species * p.rdf_bins;
+    hipLaunchKernelGGL(k_md_obs_rdf, dim3(chunks, (unsigned)x->B), dim3(256), lds, eng->stream, a);
+  }
+  x->k += 1;
+  if (hipGetLastError() != hipSuccess) { eng->err = std::string(fn) + ": observer kernel launch failed"; return CHG_EHIP; }
+  return CHG_OK;
+}
+
+int download_observables(chg_engine* eng, MdObservers* x, const chg_md_observables_host* o) {
+  const size_t B = x->B, L = x->p.n_lags, S = x->p.n_species, bins = x->p.rdf_bins;
+  TRY(d2h(eng, o->msd, x->msd, B * L * S));
+  TRY(d2h(eng, o->vacf, x->vacf, B * L * S));
+  TRY(d2h(eng, (long long*)o->cnt, x->cnt, B * L));
+  TRY(d2h(eng, (unsigned long long*)o->rdf, x->hist, B * S * S * bins));
+  TRY(d2h(eng, (long long*)o->rdf_samples, x->rdf_samples, B));
+  TRY(d2h(eng, o->vol_sum, x->vol_sum, B));
+  HIP_TRY(eng, hipStreamSynchronize(eng->stream));
+  return CHG_OK;
+}
+
+bool sample_due(const chg_md* d, int step) { return d->obs && step % d->obs->p.sample_interval == 0; }
+
+// the observers' private frame slot for a step that is sampled but not logged: not part of the ring, not counted in ring_count
+void set_private_frame(chg_md* d, MdStepArgs& a) {
+  const MdObservers* x = d->obs;
+  a.fr_scal = x->fr_scal; a.fr_pos = x->fr_pos; a.fr_mom = x->fr_mom; a.fr_cell = x->fr_cell;
+  a.fr_force = x->fr_force; a.fr_stress = x->fr_stress;
+  a.fr_cfea = nullptr; a.fr_cons = nullptr;
+}
+
+// one evaluation that completes step `step`: its frame goes to the ring when one is due, to the private slot when only a sample is,
+// and the observers read it once the step launch -- a wide-range retry included -- has returned
+int evaluate_step_observe(chg_engine* eng, chg_md* d, MdStepArgs& a, int step) {
+  const bool sample = sample_due(d, step);
+  if (frame_due(d, step)) set_frame(d, a, step);
+  else if (sample) set_private_frame(d, a);
+  TRY(evaluate_and_step(eng, d, a));
+  if (sample) TRY(observe(eng, "chg_md_run", d->obs, a.fr_pos, a.fr_mom, a.fr_cell, d->m, d->si + 1, MD_SI, d->d_aoff));
+  return CHG_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -269,6 +430,25 @@ int chg_md_set_fixed(chg_engine* eng, chg_md* d, const uint8_t* fixed) {
   return upload_fixed(eng, fn, d, fixed, nfree.data());
 }
 
+int chg_md_set_observers(chg_engine* eng, chg_md* d, const chg_md_observe_params* params, const int32_t* species) {
+  if (!eng || !d || !params || !species) return CHG_EINVAL;
+  const char* fn = "chg_md_set_observers";
+  if (d->started) { eng->err = std::string(fn) + ": the run has already started"; return CHG_EINVAL; }
+  HIP_TRY(eng, hipSetDevice(eng->device));
+  MdObservers* x = nullptr;
+  TRY(create_observers(eng, fn, params, d->B, d->h_aoff, species, true, &x));
+  free_observers(d->obs);
+  d->obs = x;
+  return CHG_OK;
+}
+
+int chg_md_download_observables(chg_engine* eng, chg_md* d, const chg_md_observables_host* o) {
+  if (!eng || !d || !o) return CHG_EINVAL;
+  if (!d->obs) { eng->err = "chg_md_download_observables: the handle has no observers (chg_md_set_observers)"; return CHG_EINVAL; }
+  HIP_TRY(eng, hipSetDevice(eng->device));
+  return download_observables(eng, d->obs, o);
+}
+
 int chg_md_run(chg_engine* eng, chg_md* d, int32_t n_steps) {
   if (!eng || !d || n_steps < 0) return CHG_EINVAL;
   // the frames this call writes must fit the ring: refuse before anything runs
@@ -284,8 +464,7 @@ int chg_md_run(chg_engine* eng, chg_md* d, int32_t n_steps) {
   if (!d->started) {   // evaluate the initial configuration: cached forces, Ekin / T, frame of step 0, and the first step's start
     MdStepArgs a = base_args(d);
     a.flags = MD_ABSORB | (n_steps > 0 ? MD_START : 0);
-    if (frame_due(d, 0)) set_frame(d, a, 0);
-    TRY(evaluate_and_step(eng, d, a));
+    TRY(evaluate_step_observe(eng, d, a, 0));
     d->started = true;
   } else if (n_steps > 0) {   // a later call: start the step from the cached forces (ASE: get_forces() is cached)
     MdStepArgs a = base_args(d);
@@ -303,8 +482,7 @@ int chg_md_run(chg_engine* eng, chg_md* d, int32_t n_steps) {
     const int next = d->step + 1;
     MdStepArgs a = base_args(d);
     a.flags = MD_ABSORB | MD_KICK2 | (k + 1 < n_steps ? MD_START : 0);
-    if (frame_due(d, next)) set_frame(d, a, next);
-    TRY(evaluate_and_step(eng, d, a));
+    TRY(evaluate_step_observe(eng, d, a, next));
     d->step = next;
   }
   if (eng->profiling) return collect_profile(eng);
@@ -374,6 +552,7 @@ int chg_md_download_vg(chg_engine* eng, chg_md* d, double* vg) {
 int chg_md_free(chg_engine* eng, chg_md* d) {
   if (!d) return CHG_OK;
   release(eng, d);
+  free_observers(d->obs);
   delete d;
   return CHG_OK;
 }
@@ -484,3 +663,34 @@ int chg_test_md_step_fixed(chg_engine* eng, const chg_md_params* params, int32_t
 }
 
 }  // extern "C"
+
+extern "C" int chg_test_md_observe(chg_engine* eng, const chg_md_observe_params* params, int32_t n_struct, const int32_t* atom_off,
+                                   const int32_t* species, const double* masses, int32_t n_samples, const double* positions,
+                                   const double* momenta, const double* cell, const int32_t* status,
+                                   const chg_md_observables_host* out) {
+  using namespace chgh;
+  if (!eng || !params || n_struct <= 0 || !atom_off || !species || !masses || n_samples < 1 || !positions || !momenta || !cell || !status || !out)
+    return CHG_EINVAL;
+  const char* fn = "chg_test_md_observe";
+  const size_t B = n_struct, T = n_samples;
+  if (atom_off[0] != 0) return CHG_EINVAL;
+  for (size_t o = 0; o < B; ++o)
+    if (atom_off[o + 1] <= atom_off[o]) return CHG_EINVAL;
+  const size_t N = atom_off[n_struct];
+  HIP_TRY(eng, hipSetDevice(eng->device));
+  MdObservers* x = nullptr;
+  TRY(create_observers(eng, fn, params, n_struct, atom_off, species, false, &x));
+  TestBuf bufs[] = {{positions, nullptr, sizeof(double) * T * 3 * N}, {momenta, nullptr, sizeof(double) * T * 3 * N},
+                    {cell, nullptr, sizeof(double) * T * 9 * B}, {status, nullptr, sizeof(int) * T * B}, {masses, nullptr, sizeof(double) * N},
+                    {atom_off, nullptr, sizeof(int) * (B + 1)}};
+  int rc = CHG_OK;
+  int s = run_test_step(eng, fn, bufs, [&] {
+    for (size_t t = 0; t < T && rc == CHG_OK; ++t)
+      rc = observe(eng, fn, x, (const double*)bufs[0].d + t * 3 * N, (const double*)bufs[1].d + t * 3 * N, (const double*)bufs[2].d + t * 9 * B,
+                   (const double*)bufs[4].d, (const int*)bufs[3].d + t * B, 1, (const int*)bufs[5].d);
+  });
+  if (s == CHG_OK) s = rc;
+  if (s == CHG_OK) s = download_observables(eng, x, out);
+  free_observers(x);
+  return s;
+}

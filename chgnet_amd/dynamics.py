@@ -50,6 +50,11 @@ temperature is ``2 Ekin / (dof kB)`` (ASE >= 3.23), the Berendsen thermostat use
 the one-time centre-of-mass removal is skipped (a pinned atom breaks momentum conservation).  A replica with nothing free is refused
 except in NVE.
 
+Observables (DESIGN.md "MD observables"): ``observers=MDObservers(...)`` (chgnet_amd/observables.py) accumulates the mean-squared
+displacement and velocity autocorrelation per species and the pair histogram of the radial distribution function on the device
+while the run goes on, whatever ``loginterval`` is; ``md.observables`` (``"observables"`` in the results of ``run_batch``) downloads
+the sums as an ``MDObservables``.  ``set_atoms`` opens a new handle and so starts them from zero.  Without observers nothing changes.
+
 Out of scope, refused with ``ValueError``: ``thermostat="Nose-Hoover"`` (ASE ``NPT``; use ``"Nose-Hoover-Chain"``), and NPT with a
 Berendsen barostat without ``bulk_modulus`` (the reference then fits an equation of state).  Deviations from the reference:
   - ``starting_temperature`` draws from a seeded numpy ``Generator`` (``seed``), not ASE's global RNG: same distribution,
@@ -72,6 +77,8 @@ from chgnet_amd import _lib
 from chgnet_amd.calculator import (CHGNetCalculator, atoms_to_structure, check_fixed, join_fixed, report_isolated_atoms, structure_fixed,
                                    voigt)
 from chgnet_amd.graph.structure import Lattice, Structure
+from chgnet_amd.observables import MDObservables, MDObservers
+from chgnet_amd.observables import download as download_observables
 
 # ase.units (CODATA 2014)
 _E, _AMU, _KB_J = 1.6021766208e-19, 1.660539040e-27, 1.38064852e-23
@@ -206,7 +213,7 @@ class _DeviceRun:
     RING = 32
 
     def __init__(self, calc: CHGNetCalculator, structures: list, masses: np.ndarray, momenta: np.ndarray, kind: str, cfg: dict,
-                 seeds=None, fixed: list | None = None) -> None:
+                 seeds=None, fixed: list | None = None, observers: MDObservers | None = None) -> None:
         model = calc.model
         self.eng, self.model, self.calc = model.engine, model, calc
         conv = model.graph_converter
@@ -252,6 +259,20 @@ class _DeviceRun:
             if rc != 0:
                 self.free()
                 self.eng._check(rc)
+        self.observers = observers
+        if observers is not None:        # species: the sorted unique atomic numbers of the batch
+            try:
+                self.species, self.species_index = observers.species_map(prep.z)
+            except ValueError:
+                self.free()
+                raise
+            op = observers.params(len(self.species))
+            rc = self.eng.lib.chg_md_set_observers(self.eng.handle, self.handle, ctypes.byref(op),
+                                                   self.species_index.ctypes.data_as(_lib.c_int_p))
+            if rc != 0:
+                self.free()
+                self.eng._check(rc)
+            self.sample_dt_fs = observers.sample_interval * cfg["dt"] / FS
         self.chain_length = int(cfg["chain_length"]) if self.nhc else 0
         self.started = False
         self.step = 0
@@ -282,6 +303,14 @@ class _DeviceRun:
         self.eng._check(self.eng.lib.chg_md_download(self.eng.handle, self.handle, ctypes.byref(o)))
         d.update(extra)
         return d
+
+    def observables(self) -> list[MDObservables]:
+        """The observers' sums as they stand, one ``MDObservables`` per replica (nothing is reset on the device)."""
+        ob = self.observers
+        d = download_observables(self.eng, self.handle, self.B, ob.msd_lags, len(self.species), ob.rdf_bins)
+        off = self.prep.atom_off
+        return [MDObservables.from_download(d, i, self.species, self.species_index[off[i]:off[i + 1]], self.sample_dt_fs, ob.rdf_rmax)
+                for i in range(self.B)]
 
     def thermostat_state(self, d: dict, i: int) -> dict | None:
         """Chain and barostat variables of replica ``i`` from a download (ASE units): ``None`` for the other ensembles."""
@@ -321,8 +350,11 @@ class MolecularDynamics:
                  loginterval: int = 1, crystal_feas_logfile: str | None = None, append_trajectory: bool = False,  # noqa: ARG002
                  on_isolated_atoms: str = "warn", return_site_energies: bool = False, use_device: str | None = None,
                  seed: int | None = None, friction: float | None = None, chain_length: int | None = None, fixed_atoms=None,
-                 cell_dof: str = "isotropic") -> None:
+                 cell_dof: str = "isotropic", observers: MDObservers | None = None) -> None:
         self.ensemble, self.thermostat = ensemble, thermostat
+        if observers is not None and not isinstance(observers, MDObservers):
+            raise ValueError(f"{observers=} must be an MDObservers")
+        self.observers = observers
         self.fixed_atoms = fixed_atoms
         self.kind = _resolve(ensemble, thermostat, bulk_modulus)
         langevin = self.kind == "nvt_langevin"
@@ -440,6 +472,18 @@ class MolecularDynamics:
     def momenta(self) -> np.ndarray:
         return self._momenta
 
+    def _observer_kw(self) -> dict:
+        return {} if self.observers is None else {"observers": self.observers}   # without observers the handle is made as it always was
+
+    @property
+    def observables(self) -> MDObservables:
+        """What the observers have accumulated since the atoms were set (downloaded on access)."""
+        if self.observers is None:
+            raise ValueError("the run has no observers: pass observers=MDObservers(...)")
+        if self._run is None:
+            raise ValueError("nothing has run yet")
+        return self._run.observables()[0]
+
     def close(self) -> None:
         if getattr(self, "_run", None) is not None:
             self._run.free()
@@ -495,7 +539,7 @@ class MolecularDynamics:
         if self._run is None:
             report_isolated_atoms(self.calculator.model, [self._structure])
             self._run = _DeviceRun(self.calculator, [self._structure], self._masses, self._momenta, self.kind, self.cfg,
-                                   seeds=[self.thermostat_seed], fixed=[self._fixed])
+                                   seeds=[self.thermostat_seed], fixed=[self._fixed], **self._observer_kw())
             if self.logfile is not None and self._logger is None:
                 self._logger = MDLogger(self.logfile, len(self._structure))
         run = self._run
@@ -527,7 +571,7 @@ class MolecularDynamics:
         alone with ``MolecularDynamics(structures[i], seed=seeds[i], **kwargs).run(steps)`` (with the Langevin thermostat ``seeds[i]`` is
         also replica i's noise key; ``seeds=None`` draws one per replica).  Returns, per replica, ``{"trajectory",
         "final_structure", "momenta", "status", "n_steps", "thermostat_state"}`` (the last one ``None`` unless the thermostat is
-        "Nose-Hoover-Chain").  ``trajectory`` / ``logfile`` / ``crystal_feas_logfile`` are not
+        "Nose-Hoover-Chain"), plus ``"observables"`` when ``observers`` are given (one species map for the whole batch).  ``trajectory`` / ``logfile`` / ``crystal_feas_logfile`` are not
         written here.  ``fixed_atoms``: one entry per structure (``None``: that structure's own ``selective_dynamics``, or nothing
         held)."""
         structures = list(structures)
@@ -550,11 +594,12 @@ class MolecularDynamics:
         structs = [m._structure for m in md]
         report_isolated_atoms(first.calculator.model, structs)
         run = _DeviceRun(first.calculator, structs, np.concatenate([m._masses for m in md]), np.concatenate([m._momenta for m in md]),
-                         first.kind, first.cfg, seeds=[m.thermostat_seed for m in md], fixed=[m._fixed for m in md])
+                         first.kind, first.cfg, seeds=[m.thermostat_seed for m in md], fixed=[m._fixed for m in md], **first._observer_kw())
         try:
             trajs = [m.traj for m in md]
             sink, _ = first._sinks(run, trajs, [m._cfeas for m in md], 0)
             d = run.run(int(steps), sink)
+            observed = run.observables() if run.observers is not None else None
         finally:
             run.free()
         out = []
@@ -565,4 +610,6 @@ class MolecularDynamics:
             out.append({"trajectory": tr, "final_structure": fin, "momenta": d["momenta"][sl].copy(),
                         "status": STATUS_NAMES[d["status"][i]], "n_steps": int(d["n_steps"][i]),
                         "thermostat_state": run.thermostat_state(d, i)})
+            if observed is not None:
+                out[-1]["observables"] = observed[i]
         return out

@@ -114,7 +114,9 @@ typedef struct chg_out_host {
  * so were chg_md_create_nhc, chg_md_download_nhc and chg_test_md_step_nhc: the chain length travels as an argument, the chain state and
  * the conserved energy in arrays of their own; so were chg_relax_set_fixed, chg_md_set_fixed and the chg_test_*_step_fixed siblings: the
  * mask travels as an argument to entry points of its own; so were chg_md_create_nhc_flex, chg_md_download_vg and
- * chg_test_md_step_nhc_flex: the cell mode travels as an argument, the strain-rate matrix in an array of its own).  A binding compiled against another value must refuse the
+ * chg_test_md_step_nhc_flex: the cell mode travels as an argument, the strain-rate matrix in an array of its own;
+ * so were chg_md_set_observers, chg_md_download_observables and chg_test_md_observe: their parameters and results travel in two structs
+ * of their own, chg_md_observe_params and chg_md_observables_host, and no older struct or signature changed).  A binding compiled against another value must refuse the
  * library: chg_engine_create COPIES *desc, so an older, shorter chg_model_desc would be read past its end. */
 #define CHG_ABI_VERSION 5
 int chg_abi_version(void);
@@ -500,6 +502,48 @@ int chg_test_md_step_fixed(chg_engine* eng, const chg_md_params* params, int32_t
                            double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy,
                            const float* force, const float* stress, double* frac_next, double* lat_next, double friction,
                            const uint64_t* seeds, int32_t chain_length, double* nhc, const uint8_t* fixed);
+
+/* ---- MD observables accumulated on the device (DESIGN.md "MD observables"; tests/md_observe_ref.py restates them in NumPy) --------
+ * Every sample_interval-th COMPLETED step (step 0 included, counted across chg_md_run calls) is sampled; sample number k = 0, 1, ...
+ * of the handle.  species [N] maps every atom to 0 .. n_species - 1.  With n_lags = L > 0 a ring holds the last L sampled snapshots
+ * (positions, velocities p / m, centre of mass), and for every lag l in 0 .. min(k, L - 1), every replica o still CHG_MD_RUNNING and
+ * every species s
+ *   msd [o,l,s] += sum_{i in o, species s} |(r_i(k) - R_o(k)) - (r_i(k-l) - R_o(k-l))|^2      (A^2, unwrapped positions)
+ *   vacf[o,l,s] += sum_{i in o, species s} v_i(k) . v_i(k-l)                                   (ASE velocity units squared)
+ *   cnt [o,l]   += 1
+ * with R_o the mass-weighted centre of mass of the replica when subtract_com is set and 0 otherwise.  With rdf_bins > 0, for every
+ * ordered pair (i, j) of a running replica and every lattice shift n (i == j with n == 0 excluded) with d = |r_j - r_i + n L| <
+ * rdf_rmax, rdf[o, s_i, s_j, floor(d / rdf_rmax * rdf_bins)] += 1; rdf_samples[o] += 1 and vol_sum[o] += |det L| per sample.  The
+ * sums do not depend on scheduling: no floating-point atomics, integer counts.  A replica that stopped is skipped for good.
+ * chg_md_set_observers is valid between create and the first run (a second call replaces the first); CHG_EINVAL with a message for
+ * a bad parameter (n_species * n_species * rdf_bins > 16384 included), a species index out of range and a call after the first run;
+ * CHG_ENOMEM when the ring (L * (48 N + 24 B) bytes) does not fit.  chg_md_free releases what it allocated.  Without observers a run
+ * launches exactly what it launched before they existed. */
+typedef struct chg_md_observe_params {
+  int32_t sample_interval;  /* sample every this many completed steps, step 0 included; >= 1 */
+  int32_t n_lags;           /* L, 0: no MSD / VACF; <= 4096 */
+  int32_t subtract_com;
+  int32_t n_species;        /* S, 1..8 */
+  int32_t rdf_bins;         /* 0: no RDF */
+  int32_t reserved;
+  double rdf_rmax;          /* A, > 0 when rdf_bins > 0 */
+} chg_md_observe_params;
+int chg_md_set_observers(chg_engine* eng, chg_md* md, const chg_md_observe_params* params, const int32_t* species /* [N] */);
+typedef struct chg_md_observables_host {
+  double* msd;              /* [B,L,S] */
+  double* vacf;             /* [B,L,S] */
+  int64_t* cnt;             /* [B,L]   */
+  uint64_t* rdf;            /* [B,S,S,bins] */
+  int64_t* rdf_samples;     /* [B] */
+  double* vol_sum;          /* [B] A^3 */
+} chg_md_observables_host;
+/* The accumulators as they stand (nothing is reset); null pointers are skipped.  CHG_EINVAL for a handle without observers. */
+int chg_md_download_observables(chg_engine* eng, chg_md* md, const chg_md_observables_host* out);
+/* Tests only: n_samples caller-given snapshots -- positions [T,N,3], momenta [T,N,3], cell [T,B,9], status [T,B] -- through exactly
+ * the kernels and the ring logic of a run, then the accumulators into out. */
+int chg_test_md_observe(chg_engine* eng, const chg_md_observe_params* params, int32_t n_struct, const int32_t* atom_off,
+                        const int32_t* species, const double* masses, int32_t n_samples, const double* positions, const double* momenta,
+                        const double* cell, const int32_t* status, const chg_md_observables_host* out);
 
 /* ---- exchange steps of the multi-GPU path, straight on RCCL (one communicator per process = per GPU) ----------
  * The reference is single-device; these carry what SURVEY 8e needs and nothing else: the all-gather of per-structure

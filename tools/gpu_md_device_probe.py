@@ -10,6 +10,9 @@ of R = 1, 8, 64 replicas of the 256-atom 2x2x2 Li9Co7O16 cell, NVT Berendsen at 
                               components or the three diagonal ones) instead of the isotropic one; compare it with --cell-dof isotropic
       --repeats K             K timed runs in one process, one JSON line each (their spread is the run-to-run noise)
       --fixed-fraction F      hold every atom whose index is below F n in every replica (fixed_atoms; 0: no mask at all)
+      --observe               accumulate observables on the device while the run goes on (MDObservers: every step, 256 MSD / VACF
+                              lags, RDF with 200 bins up to 6 A); lines go to profiles/md_observe_probe.jsonl unless --out is given.
+                              Compare it with the same leg without the flag: their ratio is the cost of observing
   --leg host                  one replica, BerendsenNVT + CHGNetCalculator.calculate per step
 
 Weights: the trained-like golden set (tests/golden/weights_trained_like.npz).  Run every leg under its own time limit.
@@ -48,8 +51,13 @@ def main() -> None:
     ap.add_argument("--cell-dof", choices=("isotropic", "flexible", "axes"), default="isotropic", help="--thermostat nhc --ensemble npt only")
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--fixed-fraction", type=float, default=0.0)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "md_device_probe.jsonl"))
+    ap.add_argument("--observe", action="store_true")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(REPO, "profiles", "md_observe_probe.jsonl" if args.observe else "md_device_probe.jsonl")
+    if args.observe and args.leg != "device":
+        ap.error("--observe belongs to --leg device")
     if args.ensemble == "npt" and args.thermostat != "nhc":
         ap.error("--ensemble npt is probed with --thermostat nhc only")
     if args.cell_dof != "isotropic" and args.ensemble != "npt":
@@ -78,6 +86,11 @@ def main() -> None:
         if args.fixed_fraction > 0:
             kw.update(fixed_atoms=[list(range(int(args.fixed_fraction * len(c)))) for c in cells])
             out.update(fixed_fraction=args.fixed_fraction)
+        if args.observe:
+            from chgnet_amd.observables import MDObservers
+
+            kw.update(observers=MDObservers(sample_interval=1, msd_lags=256, rdf_rmax=6.0, rdf_bins=200))
+            out.update(observe={"sample_interval": 1, "msd_lags": 256, "rdf_bins": 200, "rdf_rmax": 6.0})
         MolecularDynamics.run_batch(cells, 5, seeds=list(range(R)), **kw)          # warm-up: engine creation, first builds
         for rep in range(args.repeats):
             t0 = time.perf_counter()
@@ -86,6 +99,11 @@ def main() -> None:
             out.update(replicas=R, repeat=rep, wall_s=wall, replica_steps_per_s=R * args.steps / wall, steps_per_s=args.steps / wall,
                        nonfinite=int(sum(r["status"] != "RUNNING" for r in res)),
                        final_T_mean=float(np.mean([r["trajectory"].temperatures[-1] for r in res])))
+            if args.observe:                     # what a user reads off: Li MSD at the longest lag every replica has reached
+                ob = res[0]["observables"]
+                reached = int(np.flatnonzero(ob.cnt > 0)[-1])
+                out.update(li_msd_A2=float(ob.msd(3)[reached]), li_msd_lag_fs=float(ob.lag_times_fs[reached]),
+                           rdf_samples=int(ob.rdf_samples), o_around_co=ob.coordination_number(27, 8, 2.4))
             lines.append(json.dumps(out))
     else:
         from chgnet_amd.md import BerendsenNVT
