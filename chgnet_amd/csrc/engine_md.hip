@@ -4,8 +4,9 @@
 // strain-rate matrix, all six components or the three diagonal ones), one independent replica per structure, state in HBM
 // (kernels_md.h).  Reference: MolecularDynamics, chgnet/model/dynamics.py:433-780.
 //
-// One evaluation of chg_md_run is one evaluate_and_step of the shared driver (engine_stepper.h) on ALL replicas, with k_md_step as
-// the step launch (one workgroup per replica: finish the step, frame, start the next one).  Every replica runs the same number of
+// One evaluation of chg_md_run is one evaluate_and_step of the shared driver (engine_stepper.h) on ALL replicas, with the ensemble's
+// step kernel (kernels_md.h: k_md_step, k_md_step_nhc or k_md_step_flex) as the step launch (one workgroup per replica: finish the
+// step, frame, start the next one).  Every replica runs the same number of
 // steps, so there is no compaction.  NPT takes two evaluations per step, as ASE does: the barostat's set_cell(scale_atoms=True)
 // moves the atoms and the forces are evaluated again before the first half kick.  The Nose-Hoover-chain NPT scales the cell inside
 // the step and takes one evaluation (task efs) like every other ensemble.
@@ -25,14 +26,23 @@ struct MdObservers {
   double *ring_pos = nullptr, *ring_vel = nullptr, *ring_com = nullptr, *msd = nullptr, *vacf = nullptr, *vol_sum = nullptr;
   long long *cnt = nullptr, *rdf_samples = nullptr;
   unsigned long long* hist = nullptr;
-  // private frame slot: what the step kernels write of a completed step that is sampled but not logged
-  double *fr_scal = nullptr, *fr_pos = nullptr, *fr_mom = nullptr, *fr_cell = nullptr;
-  float *fr_force = nullptr, *fr_stress = nullptr;
+  chg::MdFrame fr{};             // private frame slot: what the step kernels write of a completed step that is sampled but not logged
+};
+
+// the chg_md_create* / chg_test_md_step* entry point that was called: it decides which ensembles may run (bad_params)
+enum class MdEntry { Plain, Langevin, Nhc, NhcFlex };
+
+// what an entry point was given besides the structures
+struct MdSpec {
+  chg_md_params p{};
+  MdEntry entry = MdEntry::Plain;
+  double friction = 0.0;            // Langevin: inverse ASE time units
+  const uint64_t* seeds = nullptr;  // Langevin: [B] noise keys on the host, read while the entry point runs
+  int chain_length = 0;             // Nhc, NhcFlex
 };
 
 struct chg_md : chgh::Stepper {
-  chg_md_params p{};
-  double friction = 0.0;     // MD_NVT_LANGEVIN, inverse ASE time units
+  MdSpec spec;
   bool started = false;      // the initial configuration has been evaluated (frame of step 0 written)
   std::vector<double> p0;    // the momenta as created: chg_md_set_fixed derives the masked ones from them on every call
   int step = 0;              // steps completed (all replicas; a NONFINITE replica stops counting)
@@ -40,15 +50,12 @@ struct chg_md : chgh::Stepper {
   double *r, *pm, *f, *m, *sd;
   int *si, *d_aoff;
   unsigned long long* seeds = nullptr;   // [B] noise keys (MD_NVT_LANGEVIN)
-  int chain_length = 0;                  // MD_NVT_NHC / MD_NPT_NHC
   double* nhc = nullptr;                 // [B, MD_NHC] chain and barostat state
   double* vg = nullptr;                  // [B, MD_VG] strain-rate matrix (MD_NPT_NHC_FLEX / MD_NPT_NHC_AXES)
   // frame ring: K slots
   int K = 0, ring_head = 0, ring_count = 0;
   std::vector<int> ring_step;
-  double *fr_scal, *fr_pos, *fr_mom, *fr_cell;
-  float *fr_force, *fr_stress, *fr_cfea;
-  double* fr_cons = nullptr;             // [K, B] H - Epot (Nose-Hoover chains)
+  std::vector<chg::MdFrame> ring;        // cfea only when logged, cons only for Nose-Hoover chains
   MdObservers* obs = nullptr;            // chg_md_set_observers
 };
 
@@ -60,8 +67,23 @@ bool is_npt(int e) { return e == MD_NPT_BERENDSEN_INHOMOGENEOUS || e == MD_NPT_B
 bool is_flex(int e) { return e == MD_NPT_NHC_FLEX || e == MD_NPT_NHC_AXES; }   // chg_md_create_nhc_flex only
 bool is_nhc(int e) { return e == MD_NVT_NHC || e == MD_NPT_NHC || is_flex(e); }
 
+// one frame slot
+MdFrame carve_frame(Carver& c, size_t B, size_t N, bool cfea, bool cons) {
+  MdFrame f{};
+  f.scal = c.take<double>(MD_FRAME_SCAL * B);
+  f.pos = c.take<double>(3 * N);
+  f.mom = c.take<double>(3 * N);
+  f.cell = c.take<double>(9 * B);
+  f.force = c.take<float>(3 * N);
+  f.stress = c.take<float>(9 * B);
+  if (cfea) f.cfea = c.take<float>(FEA * B);
+  if (cons) f.cons = c.take<double>(B);
+  return f;
+}
+
 void carve_md(chg_md* d, Carver& c) {
-  const size_t B = d->B, N = d->N, K = d->K;
+  const size_t B = d->B, N = d->N;
+  const int ensemble = d->spec.p.ensemble;
   d->r = c.take<double>(3 * N);
   d->pm = c.take<double>(3 * N);
   d->f = c.take<double>(3 * N);
@@ -70,20 +92,14 @@ void carve_md(chg_md* d, Carver& c) {
   d->frac_next = c.take<double>(3 * N);
   d->lat_next = c.take<double>(9 * B);
   d->si = c.take<int>(MD_SI * B);
-  d->seeds = c.take<unsigned long long>(d->p.ensemble == MD_NVT_LANGEVIN ? B : 0);
-  d->nhc = c.take<double>(is_nhc(d->p.ensemble) ? MD_NHC * B : 0);
-  d->fr_cons = c.take<double>(is_nhc(d->p.ensemble) ? K * B : 0);
-  d->vg = c.take<double>(is_flex(d->p.ensemble) ? MD_VG * B : 0);
+  d->seeds = c.take<unsigned long long>(ensemble == MD_NVT_LANGEVIN ? B : 0);
+  d->nhc = c.take<double>(is_nhc(ensemble) ? MD_NHC * B : 0);
+  d->vg = c.take<double>(is_flex(ensemble) ? MD_VG * B : 0);
   d->d_aoff = c.take<int>(B + 1);
   d->d_sel = c.take<int>(B);
   d->retry = c.take<int>(B);
-  d->fr_scal = c.take<double>(K * MD_FRAME_SCAL * B);
-  d->fr_pos = c.take<double>(K * 3 * N);
-  d->fr_mom = c.take<double>(K * 3 * N);
-  d->fr_cell = c.take<double>(K * 9 * B);
-  d->fr_force = c.take<float>(K * 3 * N);
-  d->fr_stress = c.take<float>(K * 9 * B);
-  d->fr_cfea = c.take<float>(d->p.log_crystal_fea ? K * FEA * B : 0);
+  d->ring.resize(d->K);
+  for (MdFrame& f : d->ring) f = carve_frame(c, B, N, d->spec.p.log_crystal_fea, is_nhc(ensemble));
   d->d_fixed = c.take<unsigned char>(3 * N);
   d->d_nfree = c.take<int>(B);
 }
@@ -91,33 +107,38 @@ void carve_md(chg_md* d, Carver& c) {
 bool nhc_npt(int e) { return e == MD_NPT_NHC || is_flex(e); }
 bool moving_cell(int e) { return is_npt(e) || nhc_npt(e); }
 
-// langevin: the caller is an entry point that carries friction and seeds (the only ones that may run MD_NVT_LANGEVIN); chain_length
-// > 0 or < 0: one that carries the chain length (the only ones that may run MD_NVT_NHC / MD_NPT_NHC); flex: the one that carries the
-// cell mode and the strain-rate matrix (the only one that may run MD_NPT_NHC_FLEX / MD_NPT_NHC_AXES, and nothing else)
-const char* bad_params(const chg_md_params* p, bool langevin = false, double friction = 0.0, int chain_length = 0, bool flex = false) {
-  if (flex != is_flex(p->ensemble))
-    return flex ? "ensemble must be CHG_MD_NPT_NHC_FLEX or CHG_MD_NPT_NHC_AXES"
-                : "CHG_MD_NPT_NHC_FLEX / CHG_MD_NPT_NHC_AXES need a strain-rate matrix: use chg_md_create_nhc_flex";
-  if (chain_length != 0) {
-    if (!is_nhc(p->ensemble)) return "ensemble must be CHG_MD_NVT_NHC or CHG_MD_NPT_NHC";
-    if (chain_length < 1 || chain_length > MD_NHC_MAX) return "chain_length must be 1..4";
+bool is_langevin(int e) { return e == MD_NVT_LANGEVIN; }
+bool is_nhc_iso(int e) { return e == MD_NVT_NHC || e == MD_NPT_NHC; }
+
+// The entry points that carry more than chg_md_params, the ensembles only they may run, and what is said when the two do not match:
+// to such an entry point about another ensemble, and to another entry point about such an ensemble.  The plain entry point runs the rest.
+const struct { MdEntry entry; bool (*runs)(int ensemble); const char *other_ensemble, *other_entry; } ENTRY_RULES[] = {
+    {MdEntry::NhcFlex, is_flex, "ensemble must be CHG_MD_NPT_NHC_FLEX or CHG_MD_NPT_NHC_AXES",
+     "CHG_MD_NPT_NHC_FLEX / CHG_MD_NPT_NHC_AXES need a strain-rate matrix: use chg_md_create_nhc_flex"},
+    {MdEntry::Nhc, is_nhc_iso, "ensemble must be CHG_MD_NVT_NHC or CHG_MD_NPT_NHC",
+     "CHG_MD_NVT_NHC / CHG_MD_NPT_NHC need a chain length: use chg_md_create_nhc"},
+    {MdEntry::Langevin, is_langevin, "ensemble must be CHG_MD_NVT_LANGEVIN",
+     "CHG_MD_NVT_LANGEVIN needs friction and seeds: use chg_md_create_langevin"},
+};
+
+const char* bad_params(const MdSpec& s) {
+  const chg_md_params* p = &s.p;
+  for (const auto& rule : ENTRY_RULES)
+    if ((s.entry == rule.entry) != rule.runs(p->ensemble)) return s.entry == rule.entry ? rule.other_ensemble : rule.other_entry;
+  if (is_nhc(p->ensemble)) {
+    if (s.chain_length < 1 || s.chain_length > MD_NHC_MAX) return "chain_length must be 1..4";
     if (!(p->temperature > 0.0) || !std::isfinite(p->temperature)) return "temperature must be > 0 (the thermostat masses are kB T tau^2)";
     if (!(p->taut > 0.0) || !std::isfinite(p->taut)) return "taut must be > 0";
     if (nhc_npt(p->ensemble) && (!(p->taup > 0.0) || !std::isfinite(p->taup) || !std::isfinite(p->pressure)))
       return "taup must be > 0 and pressure finite";
-  } else if (is_nhc(p->ensemble)) {
-    return "CHG_MD_NVT_NHC / CHG_MD_NPT_NHC need a chain length: use chg_md_create_nhc";
   }
-  if (langevin) {
-    if (p->ensemble != MD_NVT_LANGEVIN) return "ensemble must be CHG_MD_NVT_LANGEVIN";
-    if (!(friction >= 0.0) || !std::isfinite(friction)) return "friction must be >= 0 and finite";
+  if (is_langevin(p->ensemble)) {
+    if (!(s.friction >= 0.0) || !std::isfinite(s.friction)) return "friction must be >= 0 and finite";
     if (!(p->temperature >= 0.0) || !std::isfinite(p->temperature)) return "temperature must be >= 0";
-  } else if (p->ensemble == MD_NVT_LANGEVIN) {
-    return "CHG_MD_NVT_LANGEVIN needs friction and seeds: use chg_md_create_langevin";
   }
   if (p->ensemble < MD_NVE || p->ensemble > MD_NPT_NHC_AXES) return "unknown ensemble";
   if (!(p->dt > 0.0) || !std::isfinite(p->dt)) return "dt must be > 0";
-  if (!langevin && p->ensemble != MD_NVE && (!(p->taut > 0.0) || !(p->temperature >= 0.0))) return "taut must be > 0 and temperature >= 0";
+  if (!is_langevin(p->ensemble) && p->ensemble != MD_NVE && (!(p->taut > 0.0) || !(p->temperature >= 0.0))) return "taut must be > 0 and temperature >= 0";
   if (is_npt(p->ensemble) && (!(p->taup > 0.0) || !(p->compressibility > 0.0) || !std::isfinite(p->pressure)))
     return "taup and compressibility must be > 0 and pressure finite";
   if (p->loginterval < 0 || p->ring_frames < 0) return "loginterval and ring_frames must be >= 0";
@@ -126,76 +147,72 @@ const char* bad_params(const chg_md_params* p, bool langevin = false, double fri
   return nullptr;
 }
 
-chg::MdStepArgs base_args(chg_md* d) {
+// what the parameters decide; the device pointers are the caller's
+MdStepArgs base_args(const MdSpec& s) {
   MdStepArgs a{};
-  a.r = d->r; a.p = d->pm; a.f = d->f; a.m = d->m; a.sd = d->sd; a.si = d->si; a.aoff = d->d_aoff;
-  a.frac_next = d->frac_next; a.lat_next = d->lat_next; a.retry = d->retry;
-  const chg_md_params& p = d->p;
+  const chg_md_params& p = s.p;
   a.dt = p.dt; a.temperature = p.temperature; a.taut = p.taut; a.taup = p.taup; a.pressure = p.pressure;
   a.compressibility = p.compressibility; a.kB = p.kB > 0.0 ? p.kB : 8.6173303e-5;
   a.stress_weight = p.stress_weight > 0.0 ? p.stress_weight : 1.0 / 160.21766208;
   a.ensemble = p.ensemble; a.fixcm = p.ensemble != MD_NVE && p.fixcm; a.fea_dim = FEA;
-  if (p.ensemble == MD_NVT_LANGEVIN) {
-    a.lg_c1 = std::exp(-d->friction * p.dt);
+  if (is_langevin(p.ensemble)) {
+    a.lg_c1 = std::exp(-s.friction * p.dt);
     a.lg_sig = std::sqrt((1.0 - a.lg_c1 * a.lg_c1) * a.kB * p.temperature);
-    a.seeds = d->seeds;
   }
-  if (is_nhc(p.ensemble)) { a.nhc = d->nhc; a.nhc_len = d->chain_length; }
+  if (is_nhc(p.ensemble)) a.nhc_len = s.chain_length;
+  return a;
+}
+
+MdStepArgs handle_args(chg_md* d, int flags) {
+  MdStepArgs a = base_args(d->spec);
+  a.flags = flags;
+  a.r = d->r; a.p = d->pm; a.f = d->f; a.m = d->m; a.sd = d->sd; a.si = d->si; a.aoff = d->d_aoff;
+  a.frac_next = d->frac_next; a.lat_next = d->lat_next; a.retry = d->retry;
+  a.seeds = d->seeds; a.nhc = d->nhc; a.vg = d->vg;   // placeholders of one element where the ensemble has none
   if (d->has_fixed) { a.fixed = d->d_fixed; a.nfree = d->d_nfree; }
   return a;
 }
 
-// vg: the strain-rate matrices of the flexible-cell ensembles, which have a kernel of their own
-void launch_step(chg_engine* eng, const MdStepArgs& a, int grid, double* vg) {
+// the one place that maps the ensemble code to its kernel
+void launch_step(chg_engine* eng, const MdStepArgs& a, int grid) {
   LaunchScope ls(eng, "md_step");
-  if (is_flex(a.ensemble)) {
-    const MdFlexArgs x{vg};
-    if (a.fixed) hipLaunchKernelGGL(k_md_step_flex<true>, dim3((unsigned)grid), dim3(256), 0, eng->stream, a, x);
-    else hipLaunchKernelGGL(k_md_step_flex<false>, dim3((unsigned)grid), dim3(256), 0, eng->stream, a, x);
-    return;
-  }
-  if (a.fixed) hipLaunchKernelGGL(k_md_step<true>, dim3((unsigned)grid), dim3(256), 0, eng->stream, a);
-  else hipLaunchKernelGGL(k_md_step<false>, dim3((unsigned)grid), dim3(256), 0, eng->stream, a);
+  void (*kernel)(MdStepArgs) = is_flex(a.ensemble) ? (a.fixed ? k_md_step_flex<true> : k_md_step_flex<false>)
+                               : is_nhc(a.ensemble) ? (a.fixed ? k_md_step_nhc<true> : k_md_step_nhc<false>)
+                                                    : (a.fixed ? k_md_step<true> : k_md_step<false>);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), 0, eng->stream, a);
 }
 
 // evaluate all replicas, then one step launch with `a` (flags and frame slot set by the caller)
 int evaluate_and_step(chg_engine* eng, chg_md* d, MdStepArgs a) {
   return chgh::evaluate_and_step(eng, "chg_md_run", d, d->B, nullptr, nullptr, [&](const chg_batch* b, const int* sel, int final_try, int grid) {
     a.energy = b->energy; a.force = b->force; a.stress = (d->task & CHG_TASK_S) ? b->virial : nullptr;
-    a.cfea = a.fr_cfea ? b->crystal_fea : nullptr;
+    a.cfea = a.fr.cfea ? b->crystal_fea : nullptr;
     a.sel = sel;
     a.final_try = final_try;
-    launch_step(eng, a, grid, d->vg);
+    launch_step(eng, a, grid);
   });
 }
 
 // frame slot for step `step` (the caller checked that the ring has room)
 void set_frame(chg_md* d, MdStepArgs& a, int step) {
-  const size_t slot = (size_t)((d->ring_head + d->ring_count) % d->K), B = d->B, N = d->N;
-  a.fr_scal = d->fr_scal + slot * MD_FRAME_SCAL * B;
-  a.fr_pos = d->fr_pos + slot * 3 * N;
-  a.fr_mom = d->fr_mom + slot * 3 * N;
-  a.fr_cell = d->fr_cell + slot * 9 * B;
-  a.fr_force = d->fr_force + slot * 3 * N;
-  a.fr_stress = d->fr_stress + slot * 9 * B;
-  a.fr_cfea = d->p.log_crystal_fea ? d->fr_cfea + slot * FEA * B : nullptr;
-  a.fr_cons = is_nhc(d->p.ensemble) ? d->fr_cons + slot * B : nullptr;
+  const size_t slot = (size_t)((d->ring_head + d->ring_count) % d->K);
+  a.fr = d->ring[slot];
   d->ring_step[slot] = step;
   d->ring_count += 1;
 }
 
-bool frame_due(const chg_md* d, int step) { return d->p.loginterval > 0 && step % d->p.loginterval == 0; }
+bool frame_due(const chg_md* d, int step) { return d->spec.p.loginterval > 0 && step % d->spec.p.loginterval == 0; }
 
-// chg_md_create (seeds null, chain_length 0), chg_md_create_langevin, chg_md_create_nhc (chain_length != 0) and chg_md_create_nhc_flex
-// (flex: params->ensemble is one of the two flexible-cell codes)
-int create(chg_engine* eng, const char* fn, const chg_structs_host* h, const double* masses, const double* momenta, const chg_md_params* params,
-           double friction, const uint64_t* seeds, int chain_length, chg_md** out, bool flex = false) {
-  if (!eng || !h || !masses || !params || !out) return CHG_EINVAL;
+// every chg_md_create*: spec.p.ensemble, spec.entry and what that entry point carries are set by the caller
+int create(chg_engine* eng, const char* fn, const chg_structs_host* h, const double* masses, const double* momenta, const MdSpec& spec,
+           chg_md** out) {
+  if (!eng || !h || !masses || !out) return CHG_EINVAL;
   *out = nullptr;
-  if (const char* bad = bad_params(params, seeds != nullptr, friction, chain_length, flex)) { eng->err = std::string(fn) + ": " + bad; return CHG_EINVAL; }
+  const chg_md_params* params = &spec.p;
+  if (const char* bad = bad_params(spec)) { eng->err = std::string(fn) + ": " + bad; return CHG_EINVAL; }
   TRY(check_structs(eng, fn, h));
   const int B = h->n_struct, N = h->n_atoms;
-  if (chain_length != 0)
+  if (is_nhc(params->ensemble))
     for (int o = 0; o < B; ++o)
       if (h->atom_off[o + 1] - h->atom_off[o] < 2) {
         eng->err = std::string(fn) + ": a structure of one atom has no internal degrees of freedom to thermostat";
@@ -205,9 +222,8 @@ int create(chg_engine* eng, const char* fn, const chg_structs_host* h, const dou
     if (!(masses[i] > 0.0)) { eng->err = std::string(fn) + ": masses must be > 0"; return CHG_EINVAL; }
   HIP_TRY(eng, hipSetDevice(eng->device));
   chg_md* d = new chg_md();
-  d->p = *params;
-  d->friction = friction;
-  d->chain_length = chain_length;
+  d->spec = spec;
+  d->spec.seeds = nullptr;   // the caller's array: uploaded below, not kept
   d->K = params->loginterval > 0 ? params->ring_frames : 0;
   d->ring_step.assign(std::max(d->K, 1), 0);
   d->task = CHG_TASK_E | CHG_TASK_F | ((is_npt(params->ensemble) || nhc_npt(params->ensemble) || params->log_stress) ? CHG_TASK_S : 0u);
@@ -223,9 +239,9 @@ int create(chg_engine* eng, const char* fn, const chg_structs_host* h, const dou
   up(d->m, masses, sizeof(double) * N);
   up(d->sd, sd.data(), sizeof(double) * sd.size());
   up(d->si, si.data(), sizeof(int) * si.size());
-  if (seeds) up(d->seeds, seeds, sizeof(uint64_t) * B);
-  if (chain_length != 0) up.zero(d->nhc, sizeof(double) * MD_NHC * (size_t)B);
-  if (flex) up.zero(d->vg, sizeof(double) * MD_VG * (size_t)B);
+  if (spec.seeds) up(d->seeds, spec.seeds, sizeof(uint64_t) * B);
+  if (is_nhc(params->ensemble)) up.zero(d->nhc, sizeof(double) * MD_NHC * (size_t)B);
+  if (is_flex(params->ensemble)) up.zero(d->vg, sizeof(double) * MD_VG * (size_t)B);
   up(d->d_aoff, h->atom_off, sizeof(int) * (B + 1));
   up(d->frac_next, h->frac, sizeof(double) * 3 * N);
   up(d->lat_next, h->lattice, sizeof(double) * 9 * B);
@@ -237,7 +253,6 @@ int create(chg_engine* eng, const char* fn, const chg_structs_host* h, const dou
   *out = d;
   return CHG_OK;
 }
-
 
 // ---- observers (kernels_md_obs.h)
 
@@ -265,13 +280,7 @@ void carve_obs(MdObservers* x, Carver& c, bool frame_slot) {
   x->hist = c.take<unsigned long long>(B * S * S * bins);
   x->rdf_samples = c.take<long long>(B);
   x->vol_sum = c.take<double>(B);
-  if (!frame_slot) return;
-  x->fr_scal = c.take<double>(MD_FRAME_SCAL * B);
-  x->fr_pos = c.take<double>(3 * N);
-  x->fr_mom = c.take<double>(3 * N);
-  x->fr_cell = c.take<double>(9 * B);
-  x->fr_force = c.take<float>(3 * N);
-  x->fr_stress = c.take<float>(9 * B);
+  if (frame_slot) x->fr = carve_frame(c, B, N, false, false);
 }
 
 void free_observers(MdObservers* x) {
@@ -363,22 +372,14 @@ int download_observables(chg_engine* eng, MdObservers* x, const chg_md_observabl
 
 bool sample_due(const chg_md* d, int step) { return d->obs && step % d->obs->p.sample_interval == 0; }
 
-// the observers' private frame slot for a step that is sampled but not logged: not part of the ring, not counted in ring_count
-void set_private_frame(chg_md* d, MdStepArgs& a) {
-  const MdObservers* x = d->obs;
-  a.fr_scal = x->fr_scal; a.fr_pos = x->fr_pos; a.fr_mom = x->fr_mom; a.fr_cell = x->fr_cell;
-  a.fr_force = x->fr_force; a.fr_stress = x->fr_stress;
-  a.fr_cfea = nullptr; a.fr_cons = nullptr;
-}
-
-// one evaluation that completes step `step`: its frame goes to the ring when one is due, to the private slot when only a sample is,
-// and the observers read it once the step launch -- a wide-range retry included -- has returned
+// one evaluation that completes step `step`: its frame goes to the ring when one is due, to the observers' private slot (not part
+// of the ring, not counted in ring_count) when only a sample is, and the observers read it once the step launch -- a wide-range retry included -- has returned
 int evaluate_step_observe(chg_engine* eng, chg_md* d, MdStepArgs& a, int step) {
   const bool sample = sample_due(d, step);
   if (frame_due(d, step)) set_frame(d, a, step);
-  else if (sample) set_private_frame(d, a);
+  else if (sample) a.fr = d->obs->fr;
   TRY(evaluate_and_step(eng, d, a));
-  if (sample) TRY(observe(eng, "chg_md_run", d->obs, a.fr_pos, a.fr_mom, a.fr_cell, d->m, d->si + 1, MD_SI, d->d_aoff));
+  if (sample) TRY(observe(eng, "chg_md_run", d->obs, a.fr.pos, a.fr.mom, a.fr.cell, d->m, d->si + 1, MD_SI, d->d_aoff));
   return CHG_OK;
 }
 }  // namespace
@@ -387,18 +388,20 @@ extern "C" {
 
 int chg_md_create(chg_engine* eng, const chg_structs_host* h, const double* masses, const double* momenta, const chg_md_params* params,
                   chg_md** out) {
-  return create(eng, "chg_md_create", h, masses, momenta, params, 0.0, nullptr, 0, out);
+  if (!params) return CHG_EINVAL;
+  return create(eng, "chg_md_create", h, masses, momenta, MdSpec{*params}, out);
 }
 
 int chg_md_create_langevin(chg_engine* eng, const chg_structs_host* h, const double* masses, const double* momenta,
                            const chg_md_params* params, double friction, const uint64_t* seeds, chg_md** out) {
-  if (!seeds) return CHG_EINVAL;
-  return create(eng, "chg_md_create_langevin", h, masses, momenta, params, friction, seeds, 0, out);
+  if (!params || !seeds) return CHG_EINVAL;
+  return create(eng, "chg_md_create_langevin", h, masses, momenta, MdSpec{*params, MdEntry::Langevin, friction, seeds}, out);
 }
 
 int chg_md_create_nhc(chg_engine* eng, const chg_structs_host* h, const double* masses, const double* momenta, const chg_md_params* params,
                       int32_t chain_length, chg_md** out) {
-  return create(eng, "chg_md_create_nhc", h, masses, momenta, params, 0.0, nullptr, chain_length != 0 ? chain_length : -1, out);
+  if (!params) return CHG_EINVAL;
+  return create(eng, "chg_md_create_nhc", h, masses, momenta, MdSpec{*params, MdEntry::Nhc, 0.0, nullptr, chain_length}, out);
 }
 
 int chg_md_create_nhc_flex(chg_engine* eng, const chg_structs_host* h, const double* masses, const double* momenta, const chg_md_params* params,
@@ -408,9 +411,9 @@ int chg_md_create_nhc_flex(chg_engine* eng, const chg_structs_host* h, const dou
     eng->err = "chg_md_create_nhc_flex: cell_mode must be CHG_MD_CELL_FLEXIBLE or CHG_MD_CELL_AXES";
     return CHG_EINVAL;
   }
-  chg_md_params p = *params;   // the cell mode chooses the ensemble code: params->ensemble is ignored
-  p.ensemble = cell_mode == CHG_MD_CELL_FLEXIBLE ? MD_NPT_NHC_FLEX : MD_NPT_NHC_AXES;
-  return create(eng, "chg_md_create_nhc_flex", h, masses, momenta, &p, 0.0, nullptr, chain_length != 0 ? chain_length : -1, out, true);
+  MdSpec spec{*params, MdEntry::NhcFlex, 0.0, nullptr, chain_length};
+  spec.p.ensemble = cell_mode == CHG_MD_CELL_FLEXIBLE ? MD_NPT_NHC_FLEX : MD_NPT_NHC_AXES;   // params->ensemble is ignored
+  return create(eng, "chg_md_create_nhc_flex", h, masses, momenta, spec, out);
 }
 
 int chg_md_set_fixed(chg_engine* eng, chg_md* d, const uint8_t* fixed) {
@@ -419,7 +422,7 @@ int chg_md_set_fixed(chg_engine* eng, chg_md* d, const uint8_t* fixed) {
   if (d->started) { eng->err = std::string(fn) + ": the run has already started"; return CHG_EINVAL; }
   const size_t B = d->B, N = d->N;
   std::vector<int> nfree(B);
-  if (fixed) TRY(check_fixed(eng, fn, d->B, d->h_aoff, fixed, moving_cell(d->p.ensemble), d->p.ensemble != MD_NVE, nfree.data()));
+  if (fixed) TRY(check_fixed(eng, fn, d->B, d->h_aoff, fixed, moving_cell(d->spec.p.ensemble), d->spec.p.ensemble != MD_NVE, nfree.data()));
   HIP_TRY(eng, hipSetDevice(eng->device));
   {   // the momenta as created, with the held ones at 0: a later call with another mask, or with null, starts from the created ones again
     std::vector<double> pm(d->p0);
@@ -460,28 +463,23 @@ int chg_md_run(chg_engine* eng, chg_md* d, int32_t n_steps) {
     return CHG_EINVAL;
   }
   HIP_TRY(eng, hipSetDevice(eng->device));
-  const bool npt = is_npt(d->p.ensemble);
+  const bool npt = is_npt(d->spec.p.ensemble);
   if (!d->started) {   // evaluate the initial configuration: cached forces, Ekin / T, frame of step 0, and the first step's start
-    MdStepArgs a = base_args(d);
-    a.flags = MD_ABSORB | (n_steps > 0 ? MD_START : 0);
+    MdStepArgs a = handle_args(d, MD_ABSORB | (n_steps > 0 ? MD_START : 0));
     TRY(evaluate_step_observe(eng, d, a, 0));
     d->started = true;
   } else if (n_steps > 0) {   // a later call: start the step from the cached forces (ASE: get_forces() is cached)
-    MdStepArgs a = base_args(d);
-    a.flags = MD_START;
-    launch_step(eng, a, d->B, d->vg);
+    MdStepArgs a = handle_args(d, MD_START);
+    launch_step(eng, a, d->B);
     if (hipGetLastError() != hipSuccess) { eng->err = "chg_md_run: step kernel launch failed"; return CHG_EHIP; }
     TRY(copy_back(eng, "chg_md_run", d, d->B, nullptr, nullptr));
   }
   for (int k = 0; k < n_steps; ++k) {
     if (npt) {   // the barostat's scaled configuration: forces, first half kick, fixcm, drift
-      MdStepArgs a = base_args(d);
-      a.flags = MD_ABSORB;
-      TRY(evaluate_and_step(eng, d, a));
+      TRY(evaluate_and_step(eng, d, handle_args(d, MD_ABSORB)));
     }
     const int next = d->step + 1;
-    MdStepArgs a = base_args(d);
-    a.flags = MD_ABSORB | MD_KICK2 | (k + 1 < n_steps ? MD_START : 0);
+    MdStepArgs a = handle_args(d, MD_ABSORB | MD_KICK2 | (k + 1 < n_steps ? MD_START : 0));
     TRY(evaluate_step_observe(eng, d, a, next));
     d->step = next;
   }
@@ -503,15 +501,15 @@ int chg_md_download(chg_engine* eng, chg_md* d, const chg_md_out_host* o) {
   const int take = std::min(d->ring_count, std::max(o->frame_capacity, 0));
   for (int k = 0; k < take; ++k) {
     const size_t slot = (size_t)((d->ring_head + k) % std::max(d->K, 1));
+    const MdFrame& fr = d->ring[slot];
     if (o->frame_step) o->frame_step[k] = d->ring_step[slot];
-    TRY(d2h(eng, o->frame_scalars ? o->frame_scalars + k * MD_FRAME_SCAL * B : nullptr, d->fr_scal + slot * MD_FRAME_SCAL * B, MD_FRAME_SCAL * B));
-    TRY(d2h(eng, o->frame_positions ? o->frame_positions + k * 3 * N : nullptr, d->fr_pos + slot * 3 * N, 3 * N));
-    TRY(d2h(eng, o->frame_momenta ? o->frame_momenta + k * 3 * N : nullptr, d->fr_mom + slot * 3 * N, 3 * N));
-    TRY(d2h(eng, o->frame_cell ? o->frame_cell + k * 9 * B : nullptr, d->fr_cell + slot * 9 * B, 9 * B));
-    TRY(d2h(eng, o->frame_force ? o->frame_force + k * 3 * N : nullptr, d->fr_force + slot * 3 * N, 3 * N));
-    TRY(d2h(eng, o->frame_stress ? o->frame_stress + k * 9 * B : nullptr, d->fr_stress + slot * 9 * B, 9 * B));
-    if (d->p.log_crystal_fea)
-      TRY(d2h(eng, o->frame_crystal_fea ? o->frame_crystal_fea + k * (size_t)FEA * B : nullptr, d->fr_cfea + slot * FEA * B, FEA * B));
+    TRY(d2h(eng, o->frame_scalars ? o->frame_scalars + k * MD_FRAME_SCAL * B : nullptr, fr.scal, MD_FRAME_SCAL * B));
+    TRY(d2h(eng, o->frame_positions ? o->frame_positions + k * 3 * N : nullptr, fr.pos, 3 * N));
+    TRY(d2h(eng, o->frame_momenta ? o->frame_momenta + k * 3 * N : nullptr, fr.mom, 3 * N));
+    TRY(d2h(eng, o->frame_cell ? o->frame_cell + k * 9 * B : nullptr, fr.cell, 9 * B));
+    TRY(d2h(eng, o->frame_force ? o->frame_force + k * 3 * N : nullptr, fr.force, 3 * N));
+    TRY(d2h(eng, o->frame_stress ? o->frame_stress + k * 9 * B : nullptr, fr.stress, 9 * B));
+    if (fr.cfea) TRY(d2h(eng, o->frame_crystal_fea ? o->frame_crystal_fea + k * (size_t)FEA * B : nullptr, fr.cfea, FEA * B));
   }
   HIP_TRY(eng, hipStreamSynchronize(eng->stream));
   d->ring_head = d->K > 0 ? (d->ring_head + take) % d->K : 0;
@@ -527,14 +525,13 @@ int chg_md_download(chg_engine* eng, chg_md* d, const chg_md_out_host* o) {
 
 int chg_md_download_nhc(chg_engine* eng, chg_md* d, double* nhc_state, double* frame_conserved, int32_t frame_capacity) {
   if (!eng || !d) return CHG_EINVAL;
-  if (!is_nhc(d->p.ensemble)) { eng->err = "chg_md_download_nhc: the handle was not created by chg_md_create_nhc"; return CHG_EINVAL; }
+  if (!is_nhc(d->spec.p.ensemble)) { eng->err = "chg_md_download_nhc: the handle was not created by chg_md_create_nhc"; return CHG_EINVAL; }
   HIP_TRY(eng, hipSetDevice(eng->device));
   const size_t B = d->B;
   TRY(d2h(eng, nhc_state, d->nhc, MD_NHC * B));
   const int take = std::min(d->ring_count, std::max(frame_capacity, 0));
   for (int k = 0; k < take; ++k) {   // oldest first; the ring is left as it is (chg_md_download drains it)
-    const size_t slot = (size_t)((d->ring_head + k) % std::max(d->K, 1));
-    TRY(d2h(eng, frame_conserved ? frame_conserved + k * B : nullptr, d->fr_cons + slot * B, B));
+    TRY(d2h(eng, frame_conserved ? frame_conserved + k * B : nullptr, d->ring[(d->ring_head + k) % d->K].cons, B));
   }
   HIP_TRY(eng, hipStreamSynchronize(eng->stream));
   return CHG_OK;
@@ -542,7 +539,7 @@ int chg_md_download_nhc(chg_engine* eng, chg_md* d, double* nhc_state, double* f
 
 int chg_md_download_vg(chg_engine* eng, chg_md* d, double* vg) {
   if (!eng || !d || !vg) return CHG_EINVAL;
-  if (!is_flex(d->p.ensemble)) { eng->err = "chg_md_download_vg: the handle was not created by chg_md_create_nhc_flex"; return CHG_EINVAL; }
+  if (!is_flex(d->spec.p.ensemble)) { eng->err = "chg_md_download_vg: the handle was not created by chg_md_create_nhc_flex"; return CHG_EINVAL; }
   HIP_TRY(eng, hipSetDevice(eng->device));
   TRY(d2h(eng, vg, d->vg, MD_VG * (size_t)d->B));
   HIP_TRY(eng, hipStreamSynchronize(eng->stream));
@@ -561,47 +558,67 @@ int chg_md_free(chg_engine* eng, chg_md* d) {
 
 namespace {
 
-// chg_test_md_step (seeds and nhc null), chg_test_md_step_langevin, chg_test_md_step_nhc and chg_test_md_step_nhc_flex (vg set)
-int test_step(chg_engine* eng, const char* fn, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
-              double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy, const float* force,
-              const float* stress, double* frac_next, double* lat_next, double friction, const uint64_t* seeds, int chain_length = 0,
-              double* nhc = nullptr, const uint8_t* fixed = nullptr, double* vg = nullptr) {
-  if (!eng || !params || n_struct <= 0 || !atom_off || !r || !momenta || !forces || !masses || !sd || !si || !frac_next || !lat_next)
+// what the chg_test_md_step* entry points hand over: host arrays, null where an entry point has none
+struct TestStepIo {
+  int32_t n_struct;
+  const int32_t* atom_off;
+  int32_t flags;
+  double *r, *momenta, *forces;
+  const double* masses;
+  double* sd;
+  int32_t* si;
+  const float *energy, *force, *stress;
+  double *frac_next, *lat_next, *nhc = nullptr, *vg = nullptr;
+  const uint8_t* fixed = nullptr;
+};
+
+// one step launch on uploaded copies of t's arrays; spec as for create
+int test_step(chg_engine* eng, const char* fn, const MdSpec& spec, const TestStepIo& t) {
+  if (!eng || t.n_struct <= 0 || !t.atom_off || !t.r || !t.momenta || !t.forces || !t.masses || !t.sd || !t.si || !t.frac_next || !t.lat_next)
     return CHG_EINVAL;
-  if ((flags & MD_ABSORB) && (!energy || !force)) return CHG_EINVAL;
-  if (flags & ~(MD_ABSORB | MD_KICK2 | MD_START)) return CHG_EINVAL;
-  if (const char* bad = bad_params(params, seeds != nullptr, friction, chain_length, vg != nullptr)) { eng->err = std::string(fn) + ": " + bad; return CHG_EINVAL; }
-  if (nhc_npt(params->ensemble) && (flags & MD_ABSORB) && !stress) return CHG_EINVAL;
-  const size_t B = n_struct, N = atom_off[n_struct];
-  if (atom_off[0] != 0) return CHG_EINVAL;
+  if ((t.flags & MD_ABSORB) && (!t.energy || !t.force)) return CHG_EINVAL;
+  if (t.flags & ~(MD_ABSORB | MD_KICK2 | MD_START)) return CHG_EINVAL;
+  if (const char* bad = bad_params(spec)) { eng->err = std::string(fn) + ": " + bad; return CHG_EINVAL; }
+  const int ensemble = spec.p.ensemble;
+  if (nhc_npt(ensemble) && (t.flags & MD_ABSORB) && !t.stress) return CHG_EINVAL;
+  const size_t B = t.n_struct, N = t.atom_off[t.n_struct];
+  if (t.atom_off[0] != 0) return CHG_EINVAL;
   for (size_t o = 0; o < B; ++o)
-    if (atom_off[o + 1] - atom_off[o] < (nhc ? 2 : 1)) return CHG_EINVAL;
+    if (t.atom_off[o + 1] - t.atom_off[o] < (t.nhc ? 2 : 1)) return CHG_EINVAL;
   std::vector<int> nfree(B);
-  if (fixed) TRY(check_fixed(eng, fn, (int)B, atom_off, fixed, moving_cell(params->ensemble), params->ensemble != MD_NVE, nfree.data()));
-  TestBuf bufs[] = {{r, r, sizeof(double) * 3 * N}, {momenta, momenta, sizeof(double) * 3 * N}, {forces, forces, sizeof(double) * 3 * N},
-                    {masses, nullptr, sizeof(double) * N}, {sd, sd, sizeof(double) * MD_SD * B}, {si, si, sizeof(int) * MD_SI * B},
-                    {atom_off, nullptr, sizeof(int) * (B + 1)}, {energy, nullptr, sizeof(float) * B}, {force, nullptr, sizeof(float) * 3 * N},
-                    {stress, nullptr, sizeof(float) * 9 * B}, {frac_next, frac_next, sizeof(double) * 3 * N},
-                    {lat_next, lat_next, sizeof(double) * 9 * B}, {nullptr, nullptr, sizeof(int) * B},
-                    {seeds, nullptr, sizeof(uint64_t) * B}, {nhc, nhc, sizeof(double) * MD_NHC * B}, {fixed, nullptr, 3 * N},
-                    {fixed ? nfree.data() : nullptr, nullptr, sizeof(int) * B}, {vg, vg, sizeof(double) * MD_VG * B}};
+  if (t.fixed) TRY(check_fixed(eng, fn, (int)B, t.atom_off, t.fixed, moving_cell(ensemble), ensemble != MD_NVE, nfree.data()));
+  enum { R, P, F, M, SD, SI, AOFF, ENERGY, FORCE, STRESS, FRAC_NEXT, LAT_NEXT, RETRY, SEEDS, NHC, FIXED, NFREE, VG, N_BUFS };
+  TestBuf bufs[N_BUFS];
+  bufs[R] = {t.r, t.r, sizeof(double) * 3 * N};
+  bufs[P] = {t.momenta, t.momenta, sizeof(double) * 3 * N};
+  bufs[F] = {t.forces, t.forces, sizeof(double) * 3 * N};
+  bufs[M] = {t.masses, nullptr, sizeof(double) * N};
+  bufs[SD] = {t.sd, t.sd, sizeof(double) * MD_SD * B};
+  bufs[SI] = {t.si, t.si, sizeof(int) * MD_SI * B};
+  bufs[AOFF] = {t.atom_off, nullptr, sizeof(int) * (B + 1)};
+  bufs[ENERGY] = {t.energy, nullptr, sizeof(float) * B};
+  bufs[FORCE] = {t.force, nullptr, sizeof(float) * 3 * N};
+  bufs[STRESS] = {t.stress, nullptr, sizeof(float) * 9 * B};
+  bufs[FRAC_NEXT] = {t.frac_next, t.frac_next, sizeof(double) * 3 * N};
+  bufs[LAT_NEXT] = {t.lat_next, t.lat_next, sizeof(double) * 9 * B};
+  bufs[RETRY] = {nullptr, nullptr, sizeof(int) * B};
+  bufs[SEEDS] = {spec.seeds, nullptr, sizeof(uint64_t) * B};
+  bufs[NHC] = {t.nhc, t.nhc, sizeof(double) * MD_NHC * B};
+  bufs[FIXED] = {t.fixed, nullptr, 3 * N};
+  bufs[NFREE] = {t.fixed ? nfree.data() : nullptr, nullptr, sizeof(int) * B};
+  bufs[VG] = {t.vg, t.vg, sizeof(double) * MD_VG * B};
   return run_test_step(eng, fn, bufs, [&] {
-    chg_md tmp;
-    tmp.p = *params;
-    tmp.friction = friction;
-    tmp.seeds = (unsigned long long*)bufs[13].d;
-    tmp.chain_length = chain_length;
-    tmp.nhc = (double*)bufs[14].d;
-    MdStepArgs a = base_args(&tmp);
-    a.r = (double*)bufs[0].d; a.p = (double*)bufs[1].d; a.f = (double*)bufs[2].d; a.m = (const double*)bufs[3].d;
-    a.sd = (double*)bufs[4].d; a.si = (int*)bufs[5].d; a.aoff = (const int*)bufs[6].d;
-    a.energy = energy ? (const float*)bufs[7].d : nullptr; a.force = force ? (const float*)bufs[8].d : nullptr;
-    a.stress = stress ? (const float*)bufs[9].d : nullptr;
-    a.frac_next = (double*)bufs[10].d; a.lat_next = (double*)bufs[11].d; a.retry = (int*)bufs[12].d;
-    a.flags = flags;
+    MdStepArgs a = base_args(spec);
+    a.r = (double*)bufs[R].d; a.p = (double*)bufs[P].d; a.f = (double*)bufs[F].d; a.m = (const double*)bufs[M].d;
+    a.sd = (double*)bufs[SD].d; a.si = (int*)bufs[SI].d; a.aoff = (const int*)bufs[AOFF].d;
+    a.energy = t.energy ? (const float*)bufs[ENERGY].d : nullptr; a.force = t.force ? (const float*)bufs[FORCE].d : nullptr;
+    a.stress = t.stress ? (const float*)bufs[STRESS].d : nullptr;
+    a.frac_next = (double*)bufs[FRAC_NEXT].d; a.lat_next = (double*)bufs[LAT_NEXT].d; a.retry = (int*)bufs[RETRY].d;
+    a.seeds = (const unsigned long long*)bufs[SEEDS].d; a.nhc = (double*)bufs[NHC].d; a.vg = (double*)bufs[VG].d;
+    a.flags = t.flags;
     a.final_try = 1;
-    if (fixed) { a.fixed = (const unsigned char*)bufs[15].d; a.nfree = (const int*)bufs[16].d; }
-    launch_step(eng, a, (int)B, (double*)bufs[17].d);
+    if (t.fixed) { a.fixed = (const unsigned char*)bufs[FIXED].d; a.nfree = (const int*)bufs[NFREE].d; }
+    launch_step(eng, a, (int)B);
   });
 }
 
@@ -612,54 +629,54 @@ extern "C" {
 int chg_test_md_step(chg_engine* eng, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
                      double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy, const float* force,
                      const float* stress, double* frac_next, double* lat_next) {
-  return test_step(eng, "chg_test_md_step", params, n_struct, atom_off, flags, r, momenta, forces, masses, sd, si, energy, force, stress,
-                   frac_next, lat_next, 0.0, nullptr);
+  if (!params) return CHG_EINVAL;
+  return test_step(eng, "chg_test_md_step", MdSpec{*params},
+                   {n_struct, atom_off, flags, r, momenta, forces, masses, sd, si, energy, force, stress, frac_next, lat_next});
 }
 
 int chg_test_md_step_langevin(chg_engine* eng, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
                               double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy,
                               const float* force, const float* stress, double* frac_next, double* lat_next, double friction,
                               const uint64_t* seeds) {
-  if (!seeds) return CHG_EINVAL;
-  return test_step(eng, "chg_test_md_step_langevin", params, n_struct, atom_off, flags, r, momenta, forces, masses, sd, si, energy, force,
-                   stress, frac_next, lat_next, friction, seeds);
+  if (!params || !seeds) return CHG_EINVAL;
+  return test_step(eng, "chg_test_md_step_langevin", MdSpec{*params, MdEntry::Langevin, friction, seeds},
+                   {n_struct, atom_off, flags, r, momenta, forces, masses, sd, si, energy, force, stress, frac_next, lat_next});
 }
 
 int chg_test_md_step_nhc(chg_engine* eng, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
                          double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy,
                          const float* force, const float* stress, double* frac_next, double* lat_next, int32_t chain_length, double* nhc) {
-  if (!nhc) return CHG_EINVAL;
-  return test_step(eng, "chg_test_md_step_nhc", params, n_struct, atom_off, flags, r, momenta, forces, masses, sd, si, energy, force,
-                   stress, frac_next, lat_next, 0.0, nullptr, chain_length != 0 ? chain_length : -1, nhc);
+  if (!params || !nhc) return CHG_EINVAL;
+  return test_step(eng, "chg_test_md_step_nhc", MdSpec{*params, MdEntry::Nhc, 0.0, nullptr, chain_length},
+                   {n_struct, atom_off, flags, r, momenta, forces, masses, sd, si, energy, force, stress, frac_next, lat_next, nhc});
 }
 
 int chg_test_md_step_nhc_flex(chg_engine* eng, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
                               double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy,
                               const float* force, const float* stress, double* frac_next, double* lat_next, int32_t chain_length, double* nhc,
                               double* vg, const uint8_t* fixed) {
-  if (!nhc || !vg) return CHG_EINVAL;
-  return test_step(eng, "chg_test_md_step_nhc_flex", params, n_struct, atom_off, flags, r, momenta, forces, masses, sd, si, energy, force,
-                   stress, frac_next, lat_next, 0.0, nullptr, chain_length != 0 ? chain_length : -1, nhc, fixed, vg);
+  if (!params || !nhc || !vg) return CHG_EINVAL;
+  return test_step(eng, "chg_test_md_step_nhc_flex", MdSpec{*params, MdEntry::NhcFlex, 0.0, nullptr, chain_length},
+                   {n_struct, atom_off, flags, r, momenta, forces, masses, sd, si, energy, force, stress, frac_next, lat_next, nhc, vg, fixed});
 }
 
+// the entry point follows from the ensemble: Langevin with friction and seeds, the isotropic chains with chain_length and nhc
 int chg_test_md_step_fixed(chg_engine* eng, const chg_md_params* params, int32_t n_struct, const int32_t* atom_off, int32_t flags, double* r,
                            double* momenta, double* forces, const double* masses, double* sd, int32_t* si, const float* energy,
                            const float* force, const float* stress, double* frac_next, double* lat_next, double friction,
                            const uint64_t* seeds, int32_t chain_length, double* nhc, const uint8_t* fixed) {
   if (!params) return CHG_EINVAL;
-  const char* fn = "chg_test_md_step_fixed";
+  MdSpec spec{*params};
+  TestStepIo t{n_struct, atom_off, flags, r, momenta, forces, masses, sd, si, energy, force, stress, frac_next, lat_next, nullptr, nullptr, fixed};
   if (params->ensemble == MD_NVT_LANGEVIN) {
     if (!seeds) return CHG_EINVAL;
-    return test_step(eng, fn, params, n_struct, atom_off, flags, r, momenta, forces, masses, sd, si, energy, force, stress, frac_next, lat_next,
-                     friction, seeds, 0, nullptr, fixed);
-  }
-  if (is_nhc(params->ensemble)) {
+    spec = MdSpec{*params, MdEntry::Langevin, friction, seeds};
+  } else if (is_nhc(params->ensemble)) {
     if (!nhc) return CHG_EINVAL;
-    return test_step(eng, fn, params, n_struct, atom_off, flags, r, momenta, forces, masses, sd, si, energy, force, stress, frac_next, lat_next,
-                     0.0, nullptr, chain_length != 0 ? chain_length : -1, nhc, fixed);
+    spec = MdSpec{*params, MdEntry::Nhc, 0.0, nullptr, chain_length};
+    t.nhc = nhc;
   }
-  return test_step(eng, fn, params, n_struct, atom_off, flags, r, momenta, forces, masses, sd, si, energy, force, stress, frac_next, lat_next,
-                   0.0, nullptr, 0, nullptr, fixed);
+  return test_step(eng, "chg_test_md_step_fixed", spec, t);
 }
 
 }  // extern "C"

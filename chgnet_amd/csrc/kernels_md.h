@@ -1,29 +1,33 @@
-// kernels_md.h -- one molecular-dynamics step kernel for every replica of a batched MD run (chg_md_*).
+// kernels_md.h -- the molecular-dynamics step kernels of a batched MD run (chg_md_*): one kernel per integrator family over shared helpers.
 //
 // Reference driver replaced (file:line relative to /root/reference/chgnet):
 //   MolecularDynamics: ASE VelocityVerlet / NVTBerendsen / Inhomogeneous_NPTBerendsen / NPTBerendsen   model/dynamics.py:433-780
 // tests/md_ref.py restates the semantics in float64 NumPy; DESIGN.md "Molecular dynamics" gives the state layout.
 //
-// One workgroup (4 waves) per replica.  Thread 0 does the 3x3 algebra (thermostat factor, barostat scaling, cell inverse); all 256
-// threads stream the atom rows with workgroup reductions.  All state is f64 in HBM.  No synchronisation or allocation: the launch
-// can be graph-captured.  What one launch does is chosen by `flags`:
+// One workgroup (4 waves) per replica.  Thread 0 does the 3x3 algebra (thermostat factor, chains, barostat scaling, cell inverse); all
+// 256 threads stream the atom rows with workgroup reductions.  All state is f64 in HBM.  No synchronisation or allocation: the launch
+// can be graph-captured.  What one launch does is chosen by `flags`, with the same meaning in every kernel:
 //   MD_ABSORB  take the evaluation of the configuration written last (energy, forces, stress): non-finite -> retry / NONFINITE.
-//              Phase 0 (a full step's configuration): MD_KICK2 finishes the step with the second half kick; Ekin, T and the
-//              ideal-gas tensor are formed and a frame is written when the frame pointers are set.
-//              Phase 1 (NPT: the barostat's scaled configuration, which ASE evaluates again because set_cell(scale_atoms=True) moved
-//              the atoms): first half kick with these forces, fixcm, drift.
-//   MD_START   start the next step from the cached forces: thermostat lambda, then NPT: barostat scaling, write the scaled
-//              configuration and go to phase 1; NVE / NVT: first half kick, fixcm, drift.
-//              MD_NVT_LANGEVIN (no reference counterpart; BAOAB, Leimkuhler & Matthews 2013): half kick, half drift, the
-//              Ornstein-Uhlenbeck step p <- c1 p + sqrt((1 - c1^2) m kB T) xi with counter-based noise (philox.h), mass-weighted
-//              fixcm, half drift.  tests/langevin_ref.py restates it.
-//              MD_NVT_NHC / MD_NPT_NHC (no reference counterpart; Martyna-Tobias-Klein with Nose-Hoover chains on the particles
-//              and on the isotropic barostat, Tuckerman et al., J. Phys. A 39 (2006) 5629): barostat chain, particle chain,
-//              barostat kick, half kick and drift with the strain-rate factors, cell scaled; MD_ABSORB | MD_KICK2 runs the mirror
-//              image after the kick.  One evaluation per step (phase stays 0), no fixcm.  tests/nhc_ref.py restates it.
-//              MD_NPT_NHC_FLEX / MD_NPT_NHC_AXES (k_md_step_flex, a kernel of its own so that k_md_step keeps its instruction stream):
-//              the same factorisation with a symmetric strain-rate matrix Vg in place of veps -- all six components free, or the three
-//              diagonal ones -- and 3x3 matrix exponentials in place of the scalar factors.  tests/nhc_flex_ref.py restates it.
+//              MD_KICK2 finishes the step with the second half kick; Ekin, T and the ideal-gas tensor are formed and a frame is
+//              written when a.fr is set.
+//   MD_START   start the next step from the cached forces, up to the configuration that is evaluated next.
+// The host picks the kernel from the ensemble code (engine_md.hip, launch_step); a.ensemble chooses inside a family.
+//   k_md_step       the Verlet family.  NVE, NVT Berendsen: thermostat lambda, first half kick, fixcm, drift.  The two Berendsen NPT
+//                   codes: MD_START scales cell and positions and goes to phase 1; MD_ABSORB at phase 1 takes the forces of the scaled
+//                   configuration, which ASE evaluates again because set_cell(scale_atoms=True) moved the atoms, then kicks and drifts.
+//                   MD_NVT_LANGEVIN (no reference counterpart; BAOAB, Leimkuhler & Matthews 2013): half kick, half drift, the
+//                   Ornstein-Uhlenbeck step p <- c1 p + sqrt((1 - c1^2) m kB T) xi with counter-based noise (philox.h), mass-weighted
+//                   fixcm, half drift.  tests/langevin_ref.py restates it.
+//   k_md_step_nhc   MD_NVT_NHC / MD_NPT_NHC (no reference counterpart; Martyna-Tobias-Klein with Nose-Hoover chains on the particles
+//                   and on the isotropic barostat, Tuckerman et al., J. Phys. A 39 (2006) 5629): barostat chain, particle chain,
+//                   barostat kick, half kick and drift with the scalar strain-rate factors, cell scaled; MD_ABSORB | MD_KICK2 runs the
+//                   mirror image after the kick.  One evaluation per step (phase stays 0), no fixcm.  tests/nhc_ref.py restates it.
+//   k_md_step_flex  MD_NPT_NHC_FLEX / MD_NPT_NHC_AXES: the same factorisation with a symmetric strain-rate matrix Vg in place of veps
+//                   -- all six components free, or the three diagonal ones -- and 3x3 matrix exponentials in place of the scalar
+//                   factors.  tests/nhc_flex_ref.py restates it.
+// What the families share is written once, as inlined helpers ("what every family shares" below): the replica view, the frozen and
+// finite checks with the retry protocol, the absorb row pass with the family's kick as a functor, thread 0's bookkeeping, the momentum
+// scaling pass and the next configuration; the chain families also share the chain state's way through registers and the extended energy.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -34,8 +38,9 @@
 namespace chg {
 
 enum : int { MD_RUNNING = 0, MD_NONFINITE = 1 };
-enum : int { MD_NVE = 0, MD_NVT_BERENDSEN = 1, MD_NPT_BERENDSEN_INHOMOGENEOUS = 2, MD_NPT_BERENDSEN = 3, MD_NVT_LANGEVIN = 4,
-             MD_NVT_NHC = 5, MD_NPT_NHC = 6, MD_NPT_NHC_FLEX = 7, MD_NPT_NHC_AXES = 8 };   // 7, 8: k_md_step_flex only
+enum : int { MD_NVE = 0, MD_NVT_BERENDSEN = 1, MD_NPT_BERENDSEN_INHOMOGENEOUS = 2, MD_NPT_BERENDSEN = 3, MD_NVT_LANGEVIN = 4,   // k_md_step
+             MD_NVT_NHC = 5, MD_NPT_NHC = 6,             // k_md_step_nhc
+             MD_NPT_NHC_FLEX = 7, MD_NPT_NHC_AXES = 8 };   // k_md_step_flex
 enum : int { MD_ABSORB = 1, MD_KICK2 = 2, MD_START = 4 };
 constexpr int MD_SD = 40;   // doubles per replica: L[9] L^-1[9] Epot Ekin T stress[9] (eV/A^3, no ideal gas) G[9] (sum p p / m) spare
 constexpr int MD_SI = 4;    // ints per replica: steps completed, status, phase, spare
@@ -47,6 +52,14 @@ constexpr int MD_NHC_MAX = 4;
 // flexible-cell chains (MD_NPT_NHC_FLEX / MD_NPT_NHC_AXES), doubles per replica: the symmetric strain-rate matrix Vg, row-major; it takes
 // the place of veps, which stays 0 in the chain state
 constexpr int MD_VG = 9;
+
+
+// one frame slot (null scal: no frame this launch)
+struct MdFrame {
+  double *scal, *pos, *mom, *cell;   // [B, MD_FRAME_SCAL] [N, 3] [N, 3] [B, 9]
+  double* cons;                      // [B] H - Epot (Nose-Hoover chains) or null
+  float *force, *stress, *cfea;      // [N, 3] [B, 9], [B, fea_dim] or null
+};
 
 struct MdStepArgs {
   // state, replica o owns atom rows aoff[o]..aoff[o+1] (the batch has the same numbering: every replica is evaluated every time)
@@ -63,9 +76,7 @@ struct MdStepArgs {
   const float* stress;    // [B, 9] GPa or null (task without stress)
   const float* cfea;      // [B, fea_dim] or null
   const int* sel;         // [grid] replicas this launch steps (null: all, grid = B)
-  // frame slot (null fr_scal: no frame this launch)
-  double *fr_scal, *fr_pos, *fr_mom, *fr_cell;
-  float *fr_force, *fr_stress, *fr_cfea;
+  MdFrame fr;
   // next configuration to evaluate
   double* frac_next;      // [N, 3]
   double* lat_next;       // [B, 9]
@@ -75,11 +86,12 @@ struct MdStepArgs {
   // MD_NVT_LANGEVIN: c1 = exp(-friction dt), sig = sqrt((1 - c1^2) kB T), one noise key per replica
   double lg_c1, lg_sig;
   const unsigned long long* seeds;   // [B]
-  // MD_NVT_NHC / MD_NPT_NHC (null / 0 otherwise): chain state, chain length 1..MD_NHC_MAX, frame slot of H - Epot
+  // the Nose-Hoover-chain families (null / 0 otherwise): chain state, chain length 1..MD_NHC_MAX, and the strain-rate matrices of
+  // k_md_step_flex
   double* nhc;            // [B, MD_NHC]
-  double* fr_cons;        // [B] or null
+  double* vg;             // [B, MD_VG]
   int nhc_len;
-  // constraint (DESIGN.md "Constraints"; null: none, the <false> instantiation): [N, 3] 1 = component held, and the number of free
+  // constraint (DESIGN.md "Constraints"; null: none, the <false> instantiations): [N, 3] 1 = component held, and the number of free
   // components of every replica (3 n: nothing held, the replica keeps the unconstrained degrees of freedom)
   const unsigned char* fixed;
   const int* nfree;       // [B]
@@ -95,6 +107,387 @@ __device__ __forceinline__ unsigned md_held_bits(const unsigned char* fixed, int
 // x, or 0 for a held component j
 template <bool MASK>
 __device__ __forceinline__ double md_free(unsigned held, int j, double x) { return (MASK && ((held >> j) & 1u)) ? 0.0 : x; }
+
+// ---- what every family shares --------------------------------------------------------------------------------------------------------
+// MASK: a.fixed and a.nfree are set; <false> is the unconstrained kernel.  Under MASK the absorbed forces and every write of p are
+// masked (selects, no divergent branch), so held components neither drift nor enter a sum.
+
+// the replica this workgroup steps: its rows of the state arrays, its doubles and ints
+template <bool MASK>
+struct MdReplica {
+  int o, a0, n;
+  double *r, *p, *f, *sd;
+  const double* m;
+  int* si;
+  const unsigned char* fixed;
+  const int* nfree;
+  __device__ __forceinline__ explicit MdReplica(const MdStepArgs& a) {
+    o = a.sel ? a.sel[blockIdx.x] : blockIdx.x;
+    a0 = a.aoff[o];
+    n = a.aoff[o + 1] - a0;
+    r = a.r + 3 * (size_t)a0;
+    p = a.p + 3 * (size_t)a0;
+    f = a.f + 3 * (size_t)a0;
+    m = a.m + a0;
+    sd = a.sd + (size_t)MD_SD * o;
+    si = a.si + (size_t)MD_SI * o;
+    fixed = MASK ? a.fixed + 3 * (size_t)a0 : nullptr;
+    nfree = MASK ? a.nfree + o : nullptr;
+  }
+  // degrees of freedom of the temperature and N_f of the chains (a held atom breaks momentum conservation): the free components of a
+  // replica that holds any, else 3 n and 3 (n - 1); evaluated where they are used, so <false> never reads nfree
+  __device__ __forceinline__ double dof() const { return (MASK && *nfree < 3 * n) ? (double)*nfree : 3.0 * n; }
+  __device__ __forceinline__ double nhc_nf() const { return (MASK && *nfree < 3 * n) ? (double)*nfree : 3.0 * (n - 1); }
+  __device__ __forceinline__ size_t row(int i) const { return 3 * ((size_t)a0 + i); }   // row i in the batch's numbering
+};
+
+// the LDS every kernel needs: workgroup reductions, thread 0's verdicts and factor, L^-1 of the next configuration
+struct MdShared {
+  double red[4][7], lam, Linv[9];
+  int fin[4], status, phase, go;
+};
+
+// true for a frozen replica (NONFINITE): neither moved nor logged again.  Leaves the phase in sh.phase.
+template <bool MASK>
+__device__ __forceinline__ bool md_frozen(const MdReplica<MASK>& v, MdShared& sh) {
+  if (threadIdx.x == 0) { sh.status = v.si[1]; sh.phase = v.si[2]; }
+  __syncthreads();
+  return sh.status != MD_RUNNING;
+}
+
+// MD_ABSORB: false when energy, forces or stress are non-finite; the replica then asks for the retry on the wide-range sweep, or on
+// the final try is marked NONFINITE, and the caller returns with the state untouched
+template <bool MASK>
+__device__ __forceinline__ bool md_absorb_finite(const MdStepArgs& a, const MdReplica<MASK>& v, MdShared& sh) {
+  const int tid = threadIdx.x;
+  int fin = 1;
+  for (int i = tid; i < v.n; i += 256) {
+    const float* fi = a.force + v.row(i);
+    fin &= isfinite(fi[0]) && isfinite(fi[1]) && isfinite(fi[2]);
+  }
+  fin = __all(fin);
+  if ((tid & 63) == 0) sh.fin[tid >> 6] = fin;
+  __syncthreads();
+  if (tid == 0) {
+    int ok = sh.fin[0] & sh.fin[1] & sh.fin[2] & sh.fin[3] & (int)isfinite(a.energy[v.o]);
+    if (a.stress)
+      for (int i = 0; i < 9; ++i) ok &= (int)isfinite(a.stress[9 * (size_t)v.o + i]);
+    if (!ok) {
+      if (a.final_try) v.si[1] = MD_NONFINITE;
+      else a.retry[v.o] = 1;
+    }
+    sh.go = ok;
+  }
+  __syncthreads();
+  return sh.go != 0;
+}
+
+// The row pass of MD_ABSORB: the new forces are masked and cached, p takes the family's kick -- kick(p_i[3], f_i[3]) on one row, a no-op
+// without MD_KICK2 -- and the row goes to the frame (its momenta only with FRAME_MOM: a family that scales p afterwards writes them in
+// md_scale_momenta).  G: sum p p / m as xx yy zz yz xz xy, reduced over the workgroup, on thread 0 only.
+template <bool MASK, bool FRAME_MOM, class Kick>
+__device__ __forceinline__ void md_absorb_rows(const MdStepArgs& a, const MdReplica<MASK>& v, MdShared& sh, Kick&& kick, double (&G)[6]) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const bool frame = a.fr.scal != nullptr;
+  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int i = tid; i < v.n; i += 256) {
+    const float* fi = a.force + v.row(i);
+    const unsigned held = md_held_bits<MASK>(v.fixed, i);
+    auto fm = [&](int j) -> float { return (MASK && ((held >> j) & 1u)) ? 0.0f : fi[j]; };   // cached, kicked with and reported
+    double pi[3] = {v.p[3 * i], v.p[3 * i + 1], v.p[3 * i + 2]};
+    const double fj[3] = {fm(0), fm(1), fm(2)};
+    kick(pi, fj);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      v.f[3 * i + j] = fj[j];
+      pi[j] = md_free<MASK>(held, j, pi[j]);
+      v.p[3 * i + j] = pi[j];
+    }
+    const double im = 1.0 / v.m[i];
+    acc[0] += pi[0] * pi[0] * im; acc[1] += pi[1] * pi[1] * im; acc[2] += pi[2] * pi[2] * im;
+    acc[3] += pi[1] * pi[2] * im; acc[4] += pi[0] * pi[2] * im; acc[5] += pi[0] * pi[1] * im;
+    if (frame) {
+      const size_t ro = v.row(i);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        a.fr.pos[ro + j] = v.r[3 * i + j];
+        if (FRAME_MOM) a.fr.mom[ro + j] = pi[j];
+        a.fr.force[ro + j] = fm(j);
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) acc[k] = wave_sum_f64(acc[k]);
+  if (lane == 0)
+    for (int k = 0; k < 6; ++k) sh.red[wv][k] = acc[k];
+  __syncthreads();
+  if (tid == 0)
+    for (int k = 0; k < 6; ++k) G[k] = sh.red[0][k] + sh.red[1][k] + sh.red[2][k] + sh.red[3][k];
+}
+
+// thread 0: Epot and the stress (eV/A^3) of the absorbed evaluation into sd
+template <bool MASK>
+__device__ __forceinline__ void md_store_potential(const MdStepArgs& a, const MdReplica<MASK>& v) {
+  v.sd[18] = a.energy[v.o];
+  if (a.stress)
+    for (int i = 0; i < 9; ++i) v.sd[21 + i] = (double)a.stress[9 * (size_t)v.o + i] * a.stress_weight;
+}
+
+// thread 0, after the kick: Ekin, T and sum p p / m into sd, and the frame's per-replica entries.  G is the sum before the chain's
+// factor s scaled the momenta (1: no chain), K2 = s^2 tr G; cons: H - Epot of the chain families, else null.
+template <bool MASK>
+__device__ __forceinline__ void md_store_kinetic_frame(const MdStepArgs& a, const MdReplica<MASK>& v, const double (&G)[6], double K2, double s,
+                                                       const double* cons) {
+  const size_t o = v.o;
+  const double ekin = 0.5 * K2;
+  const double T = (!MASK || v.dof() > 0.0) ? 2.0 * ekin / (v.dof() * a.kB) : 0.0;   // everything held (NVE only): T = 0
+  v.sd[19] = ekin;
+  v.sd[20] = T;
+  const double s2 = s * s;
+  const double Gm[9] = {G[0], G[5], G[4], G[5], G[1], G[3], G[4], G[3], G[2]};
+  for (int i = 0; i < 9; ++i) v.sd[30 + i] = Gm[i] * s2;
+  if (!a.fr.scal) return;
+  a.fr.scal[MD_FRAME_SCAL * o] = a.energy[o];
+  a.fr.scal[MD_FRAME_SCAL * o + 1] = ekin;
+  a.fr.scal[MD_FRAME_SCAL * o + 2] = T;
+  if (cons && a.fr.cons) a.fr.cons[o] = *cons;
+  for (int i = 0; i < 9; ++i) a.fr.cell[9 * o + i] = v.sd[i];
+  for (int i = 0; i < 9; ++i) a.fr.stress[9 * o + i] = a.stress ? a.stress[9 * o + i] : 0.0f;
+  if (a.cfea && a.fr.cfea)
+    for (int i = 0; i < a.fea_dim; ++i) a.fr.cfea[(size_t)a.fea_dim * o + i] = a.cfea[(size_t)a.fea_dim * o + i];
+}
+
+// p <- s p, and the frame's momenta when there is a frame
+template <bool MASK>
+__device__ __forceinline__ void md_scale_momenta(const MdStepArgs& a, const MdReplica<MASK>& v, double s) {
+  const bool frame = a.fr.scal != nullptr;
+  for (int i = threadIdx.x; i < v.n; i += 256) {
+    const unsigned held = md_held_bits<MASK>(v.fixed, i);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double pj = md_free<MASK>(held, j, v.p[3 * i + j] * s);
+      v.p[3 * i + j] = pj;
+      if (frame) a.fr.mom[v.row(i) + j] = pj;
+    }
+  }
+}
+
+// thread 0: the cell in sd is the one evaluated next; its inverse goes to LDS for md_write_frac
+template <bool MASK>
+__device__ __forceinline__ void md_next_cell(const MdStepArgs& a, const MdReplica<MASK>& v, MdShared& sh) {
+  for (int i = 0; i < 9; ++i) { sh.Linv[i] = v.sd[9 + i]; a.lat_next[9 * (size_t)v.o + i] = v.sd[i]; }
+}
+
+// row i of the next configuration: y L^-1 for the cartesian position y
+template <bool MASK>
+__device__ __forceinline__ void md_write_frac(const MdStepArgs& a, const MdReplica<MASK>& v, const MdShared& sh, int i, double y0, double y1,
+                                              double y2) {
+  double* fr = a.frac_next + v.row(i);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) fr[j] = y0 * sh.Linv[j] + y1 * sh.Linv[3 + j] + y2 * sh.Linv[6 + j];
+}
+
+// ---- the Verlet family: NVE, Berendsen NVT / NPT, Langevin ------------------------------------------------------------------------------
+
+// MD_START of MD_NVT_LANGEVIN, BAOAB up to the evaluation: B A O A.  The noise counter is the number of steps this replica has completed
+// (thread 0 has just counted the step that MD_KICK2 finished).
+template <bool MASK>
+__device__ __forceinline__ void md_start_langevin(const MdStepArgs& a, const MdReplica<MASK>& v, MdShared& sh) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = v.n;
+  double *r = v.r, *p = v.p;
+  const double hdt = 0.5 * a.dt;
+  __shared__ double s_mean[3];
+  __shared__ int s_steps;
+  __syncthreads();
+  if (tid == 0) {
+    s_steps = v.si[0];
+    md_next_cell(a, v, sh);
+  }
+  __syncthreads();
+  const unsigned long long seed = a.seeds[v.o];
+  const unsigned step = (unsigned)s_steps;
+  const bool noisy = a.lg_sig > 0.0;
+  double ps[4] = {0.0, 0.0, 0.0, 0.0};   // sum p, sum m
+  for (int i = tid; i < n; i += 256) {
+    const double mi = v.m[i];
+    double xi[3] = {0.0, 0.0, 0.0};
+    if (noisy) philox_normal3(seed, (unsigned)i, step, xi);
+    const double sg = a.lg_sig * sqrt(mi);
+    const unsigned held = md_held_bits<MASK>(v.fixed, i);   // the noise of a held component is drawn and dropped
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      double pj = md_free<MASK>(held, j, p[3 * i + j] + hdt * v.f[3 * i + j]);
+      r[3 * i + j] += hdt * pj / mi;
+      pj = md_free<MASK>(held, j, a.lg_c1 * pj + sg * xi[j]);
+      p[3 * i + j] = pj;
+      ps[j] += pj;
+    }
+    ps[3] += mi;
+  }
+  if (a.fixcm) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ps[j] = wave_sum_f64(ps[j]);
+    if (lane == 0)
+      for (int j = 0; j < 4; ++j) sh.red[wv][j] = ps[j];
+    __syncthreads();
+    if (tid == 0) {
+      const double im = 1.0 / (sh.red[0][3] + sh.red[1][3] + sh.red[2][3] + sh.red[3][3]);
+      for (int j = 0; j < 3; ++j) s_mean[j] = (sh.red[0][j] + sh.red[1][j] + sh.red[2][j] + sh.red[3][j]) * im;   // centre-of-mass velocity
+    }
+    __syncthreads();
+  }
+  for (int i = tid; i < n; i += 256) {
+    const double mi = v.m[i];
+    const unsigned held = md_held_bits<MASK>(v.fixed, i);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double pj = md_free<MASK>(held, j, a.fixcm ? p[3 * i + j] - mi * s_mean[j] : p[3 * i + j]);
+      p[3 * i + j] = pj;
+      r[3 * i + j] += hdt * pj / mi;
+    }
+    md_write_frac(a, v, sh, i, r[3 * i], r[3 * i + 1], r[3 * i + 2]);
+  }
+}
+
+template <bool MASK>
+static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const MdReplica<MASK> v(a);
+  const int n = v.n;
+  double *r = v.r, *p = v.p, *sd = v.sd;
+  const bool npt = a.ensemble == MD_NPT_BERENDSEN_INHOMOGENEOUS || a.ensemble == MD_NPT_BERENDSEN;
+  const double hdt = 0.5 * a.dt;
+
+  __shared__ MdShared sh;
+  __shared__ double sM[9], s_mean[3];
+
+  if (md_frozen(v, sh)) return;
+  bool advance = false;                 // first half kick, fixcm, drift follow
+
+  if (a.flags & MD_ABSORB) {
+    if (!md_absorb_finite(a, v, sh)) return;
+    if (sh.phase == 1) {                // NPT: forces of the scaled configuration
+      for (int i = tid; i < n; i += 256) {
+        const float* fi = a.force + v.row(i);
+        const unsigned held = md_held_bits<MASK>(v.fixed, i);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) v.f[3 * i + j] = md_free<MASK>(held, j, fi[j]);
+      }
+      if (tid == 0) {
+        md_store_potential(a, v);
+        v.si[2] = 0;
+        sh.lam = 1.0;
+      }
+      advance = true;
+    } else {
+      const bool kick = a.flags & MD_KICK2;
+      double G[6];
+      md_absorb_rows<MASK, true>(a, v, sh, [&](double (&pi)[3], const double (&fj)[3]) {
+        if (!kick) return;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) pi[j] = pi[j] + hdt * fj[j];
+      }, G);
+      if (tid == 0) {
+        md_store_potential(a, v);
+        md_store_kinetic_frame(a, v, G, G[0] + G[1] + G[2], 1.0, nullptr);
+        if (kick) v.si[0] += 1;
+      }
+    }
+  }
+
+  if ((a.flags & MD_START) && a.ensemble == MD_NVT_LANGEVIN) { md_start_langevin(a, v, sh); return; }
+
+  if ((a.flags & MD_START) && !advance) {
+    // thermostat (ASE NVTBerendsen.scale_velocities) and barostat (NPTBerendsen / Inhomogeneous_NPTBerendsen.scale_positions_and_cell)
+    __syncthreads();   // sd written by thread 0 above
+    if (tid == 0) {
+      double lam = 1.0;
+      if (a.ensemble != MD_NVE) {
+        const double T = sd[20];
+        const double ratio = T > 0.0 ? a.temperature / T : (a.temperature > 0.0 ? (double)INFINITY : 1.0);
+        lam = sqrt(1.0 + (ratio - 1.0) * (a.dt / a.taut));
+        if (lam > 1.1) lam = 1.1;
+        if (lam < 0.9) lam = 0.9;
+      }
+      sh.lam = lam;
+      if (npt) {
+        double L[9], Ln[9], M[9], st[9];
+        for (int i = 0; i < 9; ++i) L[i] = sd[i];
+        const double iv = 1.0 / fabs(det3(L));
+        for (int i = 0; i < 9; ++i) st[i] = sd[21 + i] - lam * lam * sd[30 + i] * iv;   // stress incl. the ideal-gas term
+        double sc[3];
+        if (a.ensemble == MD_NPT_BERENDSEN_INHOMOGENEOUS) {
+          const double taupscl = a.dt * a.compressibility / a.taup / 3.0;
+          for (int i = 0; i < 3; ++i) sc[i] = 1.0 - taupscl * (a.pressure - (-st[4 * i]));
+        } else {
+          const double taupscl = a.dt / a.taup;
+          const double old_p = -(st[0] + st[4] + st[8]) / 3.0;
+          sc[0] = sc[1] = sc[2] = 1.0 - taupscl * a.compressibility / 3.0 * (a.pressure - old_p);
+        }
+        for (int i = 0; i < 3; ++i)
+          for (int j = 0; j < 3; ++j) Ln[3 * i + j] = sc[i] * L[3 * i + j];
+        mm3(sd + 9, Ln, M);            // positions <- positions . solve(L, L')
+        for (int i = 0; i < 9; ++i) { sM[i] = M[i]; sd[i] = Ln[i]; }
+        inv3(Ln, sd + 9);
+        md_next_cell(a, v, sh);
+        v.si[2] = 1;
+      }
+    }
+    __syncthreads();
+    const double lam = sh.lam;
+    for (int i = tid; i < n; i += 256) {
+      const unsigned held = md_held_bits<MASK>(v.fixed, i);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) p[3 * i + j] = md_free<MASK>(held, j, p[3 * i + j] * lam);
+      if (npt) {
+        const double x0 = r[3 * i], x1 = r[3 * i + 1], x2 = r[3 * i + 2];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) r[3 * i + j] = x0 * sM[j] + x1 * sM[3 + j] + x2 * sM[6 + j];
+        md_write_frac(a, v, sh, i, r[3 * i], r[3 * i + 1], r[3 * i + 2]);
+      }
+    }
+    if (npt) return;                    // the scaled configuration is evaluated before the half kick
+    advance = true;
+  }
+  if (!advance) return;
+
+  // first half kick with the cached forces, fixcm (mean momentum, not mass-weighted), drift r += dt p / m
+  __syncthreads();
+  double ps[3] = {0.0, 0.0, 0.0};
+  for (int i = tid; i < n; i += 256) {
+    const unsigned held = md_held_bits<MASK>(v.fixed, i);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double pj = md_free<MASK>(held, j, p[3 * i + j] + hdt * v.f[3 * i + j]);
+      p[3 * i + j] = pj;
+      ps[j] += pj;
+    }
+  }
+  if (a.fixcm) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) ps[j] = wave_sum_f64(ps[j]);
+    if (lane == 0)
+      for (int j = 0; j < 3; ++j) sh.red[wv][j] = ps[j];
+  }
+  if (tid == 0) md_next_cell(a, v, sh);
+  __syncthreads();
+  if (tid == 0)
+    for (int j = 0; j < 3; ++j) s_mean[j] = a.fixcm ? (sh.red[0][j] + sh.red[1][j] + sh.red[2][j] + sh.red[3][j]) / (double)n : 0.0;
+  __syncthreads();
+  for (int i = tid; i < n; i += 256) {
+    const double mi = v.m[i];
+    const unsigned held = md_held_bits<MASK>(v.fixed, i);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double pj = md_free<MASK>(held, j, a.fixcm ? p[3 * i + j] - s_mean[j] : p[3 * i + j]);
+      p[3 * i + j] = pj;
+      r[3 * i + j] += a.dt * pj / mi;
+    }
+    md_write_frac(a, v, sh, i, r[3 * i], r[3 * i + 1], r[3 * i + 2]);
+  }
+}
+
+// ---- Nose-Hoover chains ----------------------------------------------------------------------------------------------------------------
 
 // masses and constants of the Nose-Hoover chains of one replica with nf_ degrees of freedom (3 (n - 1), or the free components of a
 // replica that holds some)
@@ -141,449 +534,133 @@ __device__ inline double nhc_chain(double (&v)[MD_NHC_MAX], double (&eta)[MD_NHC
   return s;
 }
 
-// H - Epot of the extended system: kinetic energy, chain energies and, for NPT, Pext V and the barostat's
-__device__ inline double nhc_extended_energy(const NhcConst& c, const double* x, int M, double K2, bool npt, double pext, double vol) {
+// half a step (tau) of the chain kept at xs[at .. at + 4) (velocities) and xs[at + 4 .. at + 8) (positions), through registers: returns s
+__device__ inline double nhc_chain_at(double* xs, int at, int M, double Q0, double Qk, double K2, double dof, double kT, double tau) {
+  double v[MD_NHC_MAX], eta[MD_NHC_MAX];
+#pragma unroll
+  for (int k = 0; k < MD_NHC_MAX; ++k) { v[k] = xs[at + k]; eta[k] = xs[at + 4 + k]; }
+  const double s = nhc_chain(v, eta, M, Q0, Qk, K2, dof, kT, tau);
+#pragma unroll
+  for (int k = 0; k < MD_NHC_MAX; ++k) { xs[at + k] = v[k]; xs[at + 4 + k] = eta[k]; }
+  return s;
+}
+
+// half a step of the particle chain: returns s, K2 *= s^2
+__device__ inline double nhc_particle_chain(const NhcConst& c, double* xs, int M, double& K2, double tau) {
+  const double s = nhc_chain_at(xs, 0, M, c.Q0, c.Qk, K2, c.nf, c.kT, tau);
+  K2 *= s * s;
+  return s;
+}
+
+// half a step of the isotropic barostat's chain: veps *= s
+__device__ inline void nhc_barostat_chain(const NhcConst& c, double* xs, int M, double& veps, double tau) {
+  veps *= nhc_chain_at(xs, 8, M, c.Qb, c.Qb, c.W * veps * veps, 1.0, c.kT, tau);
+}
+
+// H - Epot of the extended system: kinetic energy, the particle chain's energies and, for NPT, Pext V and the barostat's: Kb its
+// kinetic energy, Qb0 and db the first mass and the degrees of freedom of its chain (isotropic: Qb and 1)
+__device__ inline double nhc_extended_energy(const NhcConst& c, const double* x, int M, double K2, bool npt, double pext, double vol, double Kb,
+                                             double Qb0, double db) {
   double h = 0.5 * K2;
   for (int k = 0; k < M; ++k) h += 0.5 * (k == 0 ? c.Q0 : c.Qk) * x[k] * x[k] + (k == 0 ? c.nf : 1.0) * c.kT * x[4 + k];
   if (npt) {
-    h += pext * vol + 0.5 * c.W * x[16] * x[16];
-    for (int k = 0; k < M; ++k) h += 0.5 * c.Qb * x[8 + k] * x[8 + k] + c.kT * x[12 + k];
+    h += pext * vol + Kb;
+    for (int k = 0; k < M; ++k) h += 0.5 * (k == 0 ? Qb0 : c.Qb) * x[8 + k] * x[8 + k] + (k == 0 ? db : 1.0) * c.kT * x[12 + k];
   }
   return h;
 }
 
-// MASK: a.fixed and a.nfree are set; <false> is the unconstrained kernel, instruction for instruction.  Under MASK the absorbed forces
-// and every write of p are masked (selects, no divergent branch), so held components neither drift nor enter a sum.
+// Vt = alpha K2 - V tr sigma - 3 Pext V: the isotropic barostat's kick, veps += tau Vt / W (sd: the replica's, stress absorbed)
+__device__ __forceinline__ void nhc_barostat_kick(const NhcConst& c, double& veps, double K2, double vol, const double* sd, double pext, double tau) {
+  veps += tau * (c.alpha * K2 - vol * (sd[21] + sd[25] + sd[29]) - 3.0 * pext * vol) / c.W;
+}
+
 template <bool MASK>
-static __global__ __launch_bounds__(256) void k_md_step(MdStepArgs a) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int o = a.sel ? a.sel[blockIdx.x] : blockIdx.x;
-  const int a0 = a.aoff[o], n = a.aoff[o + 1] - a0;
-  double* r = a.r + 3 * (size_t)a0;
-  double* p = a.p + 3 * (size_t)a0;
-  double* f = a.f + 3 * (size_t)a0;
-  const double* m = a.m + a0;
-  double* sd = a.sd + (size_t)MD_SD * o;
-  int* si = a.si + (size_t)MD_SI * o;
-  const bool npt = a.ensemble == MD_NPT_BERENDSEN_INHOMOGENEOUS || a.ensemble == MD_NPT_BERENDSEN;
-  const bool nhc = a.ensemble == MD_NVT_NHC || a.ensemble == MD_NPT_NHC, nhc_npt = a.ensemble == MD_NPT_NHC;
-  double* xs = nhc ? a.nhc + (size_t)MD_NHC * o : nullptr;
+static __global__ __launch_bounds__(256) void k_md_step_nhc(MdStepArgs a) {
+  const int tid = threadIdx.x;
+  const MdReplica<MASK> v(a);
+  const int n = v.n, M = a.nhc_len;
+  double *r = v.r, *p = v.p, *sd = v.sd;
+  const bool npt = a.ensemble == MD_NPT_NHC;
+  double* xs = a.nhc + (size_t)MD_NHC * v.o;
   const double hdt = 0.5 * a.dt;
-  const unsigned char* fixed = MASK ? a.fixed + 3 * (size_t)a0 : nullptr;
-  // degrees of freedom of the temperature and N_f of the chains (a held atom breaks momentum conservation): the free components of a
-  // replica that holds any, else 3 n and 3 (n - 1); evaluated where they are used, as the unconstrained kernel always did
-  auto dof = [&]() -> double { return (MASK && a.nfree[o] < 3 * n) ? (double)a.nfree[o] : 3.0 * n; };
-  auto nhc_nf = [&]() -> double { return (MASK && a.nfree[o] < 3 * n) ? (double)a.nfree[o] : 3.0 * (n - 1); };
 
-  __shared__ double red[4][9];
-  __shared__ int rfin[4];
-  __shared__ double sLinv[9], sM[9], s_lam, s_mean[3], s_e[2];
-  __shared__ int s_status, s_phase, s_go, s_steps;
+  __shared__ MdShared sh;
+  __shared__ double s_e[2];
 
-  if (tid == 0) { s_status = si[1]; s_phase = si[2]; }
-  __syncthreads();
-  if (s_status != MD_RUNNING) return;   // frozen (NONFINITE): neither moved nor logged again
-  bool advance = false;                 // first half kick, fixcm, drift follow
+  if (md_frozen(v, sh)) return;
 
   if (a.flags & MD_ABSORB) {
-    int fin = 1;
-    for (int i = tid; i < n; i += 256) {
-      const float* fi = a.force + 3 * ((size_t)a0 + i);
-      fin &= isfinite(fi[0]) && isfinite(fi[1]) && isfinite(fi[2]);
-    }
-    fin = __all(fin);
-    if (lane == 0) rfin[wv] = fin;
-    __syncthreads();
+    if (!md_absorb_finite(a, v, sh)) return;
+    // second half of the step: kick with the strain-rate factor and sum p p / m in one pass, thread 0 runs the barostat kick and the
+    // two chains (their factor s scales p, Ekin and G without another reduction), one scaling pass writes the frame's momenta
+    const bool kick = a.flags & MD_KICK2;
+    const NhcConst c(a, v.nhc_nf());
+    const double e1 = kick ? exp(-0.5 * c.alpha * xs[16] * hdt) : 1.0;
+    double G[6];
+    md_absorb_rows<MASK, false>(a, v, sh, [&](double (&pi)[3], const double (&fj)[3]) {
+      if (!kick) return;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) pi[j] = fma(hdt, fj[j], pi[j] * e1) * e1;   // (p e1 + dt/2 f) e1, the product p e1 rounded first
+    }, G);
     if (tid == 0) {
-      int ok = rfin[0] & rfin[1] & rfin[2] & rfin[3] & (int)isfinite(a.energy[o]);
-      if (a.stress)
-        for (int i = 0; i < 9; ++i) ok &= (int)isfinite(a.stress[9 * (size_t)o + i]);
-      if (!ok) {
-        if (a.final_try) si[1] = MD_NONFINITE;
-        else a.retry[o] = 1;
+      double K2 = G[0] + G[1] + G[2], s = 1.0;
+      const double vol = fabs(det3(sd));
+      md_store_potential(a, v);
+      if (kick) {
+        double veps = xs[16];
+        if (npt) nhc_barostat_kick(c, veps, K2, vol, sd, a.pressure, hdt);
+        s = nhc_particle_chain(c, xs, M, K2, hdt);
+        if (npt) {
+          nhc_barostat_chain(c, xs, M, veps, hdt);
+          xs[16] = veps;
+        }
+        v.si[0] += 1;
       }
-      s_go = ok;
+      const double cons = nhc_extended_energy(c, xs, M, K2, npt, a.pressure, vol, 0.5 * c.W * xs[16] * xs[16], c.Qb, 1.0);
+      xs[17] = cons;
+      md_store_kinetic_frame(a, v, G, K2, s, &cons);
+      sh.lam = s;
     }
     __syncthreads();
-    if (!s_go) return;
-
-    if (s_phase == 1) {                 // NPT: forces of the scaled configuration
-      for (int i = tid; i < n; i += 256) {
-        const float* fi = a.force + 3 * ((size_t)a0 + i);
-        const unsigned held = md_held_bits<MASK>(fixed, i);
-        f[3 * i] = md_free<MASK>(held, 0, fi[0]); f[3 * i + 1] = md_free<MASK>(held, 1, fi[1]); f[3 * i + 2] = md_free<MASK>(held, 2, fi[2]);
-      }
-      if (tid == 0) {
-        sd[18] = a.energy[o];
-        if (a.stress)
-          for (int i = 0; i < 9; ++i) sd[21 + i] = (double)a.stress[9 * (size_t)o + i] * a.stress_weight;
-        si[2] = 0;
-        s_lam = 1.0;
-      }
-      advance = true;
-    } else if (nhc) {
-      // second half of the step: kick with the strain-rate factor and sum p p / m in one pass, thread 0 runs the barostat kick and the
-      // two chains (their factor s scales p, Ekin and G without another reduction), one scaling pass writes the frame's momenta
-      const bool kick = a.flags & MD_KICK2;
-      const bool frame = a.fr_scal != nullptr;
-      const NhcConst c(a, nhc_nf());
-      const double e1 = kick ? exp(-0.5 * c.alpha * xs[16] * hdt) : 1.0;
-      double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-      for (int i = tid; i < n; i += 256) {
-        const float* fi = a.force + 3 * ((size_t)a0 + i);
-        const unsigned held = md_held_bits<MASK>(fixed, i);
-        auto fm = [&](int j) -> float { return (MASK && ((held >> j) & 1u)) ? 0.0f : fi[j]; };   // cached, kicked with and reported
-        double pi[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          const double fj = fm(j);
-          f[3 * i + j] = fj;
-          pi[j] = md_free<MASK>(held, j, kick ? (p[3 * i + j] * e1 + hdt * fj) * e1 : p[3 * i + j]);
-          p[3 * i + j] = pi[j];
-        }
-        const double im = 1.0 / m[i];
-        acc[1] += pi[0] * pi[0] * im; acc[2] += pi[1] * pi[1] * im; acc[3] += pi[2] * pi[2] * im;
-        acc[4] += pi[1] * pi[2] * im; acc[5] += pi[0] * pi[2] * im; acc[6] += pi[0] * pi[1] * im;
-        if (frame) {
-          const size_t ro = 3 * ((size_t)a0 + i);
-#pragma unroll
-          for (int j = 0; j < 3; ++j) { a.fr_pos[ro + j] = r[3 * i + j]; a.fr_force[ro + j] = fm(j); }
-        }
-      }
-#pragma unroll
-      for (int k = 1; k < 7; ++k) acc[k] = wave_sum_f64(acc[k]);
-      if (lane == 0)
-        for (int k = 1; k < 7; ++k) red[wv][k] = acc[k];
-      __syncthreads();
-      if (tid == 0) {
-        double G[7];
-        for (int k = 1; k < 7; ++k) G[k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
-        double K2 = G[1] + G[2] + G[3], s = 1.0;
-        const double vol = fabs(det3(sd));
-        sd[18] = a.energy[o];
-        if (a.stress)
-          for (int i = 0; i < 9; ++i) sd[21 + i] = (double)a.stress[9 * (size_t)o + i] * a.stress_weight;
-        if (kick) {
-          const int M = a.nhc_len;
-          double v[MD_NHC_MAX], eta[MD_NHC_MAX];
-          double veps = xs[16];
-          if (nhc_npt) veps += hdt * (c.alpha * K2 - vol * (sd[21] + sd[25] + sd[29]) - 3.0 * a.pressure * vol) / c.W;
-#pragma unroll
-          for (int k = 0; k < MD_NHC_MAX; ++k) { v[k] = xs[k]; eta[k] = xs[4 + k]; }
-          s = nhc_chain(v, eta, M, c.Q0, c.Qk, K2, c.nf, c.kT, hdt);
-          K2 *= s * s;
-#pragma unroll
-          for (int k = 0; k < MD_NHC_MAX; ++k) { xs[k] = v[k]; xs[4 + k] = eta[k]; }
-          if (nhc_npt) {
-#pragma unroll
-            for (int k = 0; k < MD_NHC_MAX; ++k) { v[k] = xs[8 + k]; eta[k] = xs[12 + k]; }
-            veps *= nhc_chain(v, eta, M, c.Qb, c.Qb, c.W * veps * veps, 1.0, c.kT, hdt);
-#pragma unroll
-            for (int k = 0; k < MD_NHC_MAX; ++k) { xs[8 + k] = v[k]; xs[12 + k] = eta[k]; }
-            xs[16] = veps;
-          }
-          si[0] += 1;
-        }
-        const double ekin = 0.5 * K2;
-        const double T = (!MASK || dof() > 0.0) ? 2.0 * ekin / (dof() * a.kB) : 0.0;   // everything held (NVE only): T = 0
-        const double cons = nhc_extended_energy(c, xs, a.nhc_len, K2, nhc_npt, a.pressure, vol);
-        xs[17] = cons;
-        sd[19] = ekin;
-        sd[20] = T;
-        const double s2 = s * s;
-        const double Gm[9] = {G[1], G[6], G[5], G[6], G[2], G[4], G[5], G[4], G[3]};
-        for (int i = 0; i < 9; ++i) sd[30 + i] = Gm[i] * s2;
-        s_lam = s;
-        if (frame) {
-          a.fr_scal[MD_FRAME_SCAL * (size_t)o] = a.energy[o];
-          a.fr_scal[MD_FRAME_SCAL * (size_t)o + 1] = ekin;
-          a.fr_scal[MD_FRAME_SCAL * (size_t)o + 2] = T;
-          if (a.fr_cons) a.fr_cons[o] = cons;
-          for (int i = 0; i < 9; ++i) a.fr_cell[9 * (size_t)o + i] = sd[i];
-          for (int i = 0; i < 9; ++i) a.fr_stress[9 * (size_t)o + i] = a.stress ? a.stress[9 * (size_t)o + i] : 0.0f;
-          if (a.cfea && a.fr_cfea)
-            for (int i = 0; i < a.fea_dim; ++i) a.fr_cfea[(size_t)a.fea_dim * o + i] = a.cfea[(size_t)a.fea_dim * o + i];
-        }
-      }
-      __syncthreads();
-      if (kick || frame) {
-        const double s = s_lam;
-        for (int i = tid; i < n; i += 256) {
-          const unsigned held = md_held_bits<MASK>(fixed, i);
-#pragma unroll
-          for (int j = 0; j < 3; ++j) {
-            const double pj = md_free<MASK>(held, j, p[3 * i + j] * s);
-            p[3 * i + j] = pj;
-            if (frame) a.fr_mom[3 * ((size_t)a0 + i) + j] = pj;
-          }
-        }
-      }
-    } else {
-      const bool kick = a.flags & MD_KICK2;
-      const bool frame = a.fr_scal != nullptr;
-      double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // sum p.p / m, then G xx yy zz yz xz xy
-      for (int i = tid; i < n; i += 256) {
-        const float* fi = a.force + 3 * ((size_t)a0 + i);
-        const unsigned held = md_held_bits<MASK>(fixed, i);
-        auto fm = [&](int j) -> float { return (MASK && ((held >> j) & 1u)) ? 0.0f : fi[j]; };   // cached, kicked with and reported
-        double pi[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          const double fj = fm(j);
-          f[3 * i + j] = fj;
-          pi[j] = md_free<MASK>(held, j, kick ? p[3 * i + j] + hdt * fj : p[3 * i + j]);
-          p[3 * i + j] = pi[j];
-        }
-        const double im = 1.0 / m[i];
-        acc[1] += pi[0] * pi[0] * im; acc[2] += pi[1] * pi[1] * im; acc[3] += pi[2] * pi[2] * im;
-        acc[4] += pi[1] * pi[2] * im; acc[5] += pi[0] * pi[2] * im; acc[6] += pi[0] * pi[1] * im;
-        if (frame) {
-          const size_t ro = 3 * ((size_t)a0 + i);
-#pragma unroll
-          for (int j = 0; j < 3; ++j) { a.fr_pos[ro + j] = r[3 * i + j]; a.fr_mom[ro + j] = pi[j]; a.fr_force[ro + j] = fm(j); }
-        }
-      }
-#pragma unroll
-      for (int k = 1; k < 7; ++k) acc[k] = wave_sum_f64(acc[k]);
-      if (lane == 0)
-        for (int k = 1; k < 7; ++k) red[wv][k] = acc[k];
-      __syncthreads();
-      if (tid == 0) {
-        double G[7];
-        for (int k = 1; k < 7; ++k) G[k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
-        const double ekin = 0.5 * (G[1] + G[2] + G[3]);
-        const double T = (!MASK || dof() > 0.0) ? 2.0 * ekin / (dof() * a.kB) : 0.0;   // everything held (NVE only): T = 0
-        sd[18] = a.energy[o];
-        sd[19] = ekin;
-        sd[20] = T;
-        if (a.stress)
-          for (int i = 0; i < 9; ++i) sd[21 + i] = (double)a.stress[9 * (size_t)o + i] * a.stress_weight;
-        const double Gm[9] = {G[1], G[6], G[5], G[6], G[2], G[4], G[5], G[4], G[3]};
-        for (int i = 0; i < 9; ++i) sd[30 + i] = Gm[i];
-        if (kick) si[0] += 1;
-        if (frame) {
-          a.fr_scal[MD_FRAME_SCAL * (size_t)o] = a.energy[o];
-          a.fr_scal[MD_FRAME_SCAL * (size_t)o + 1] = ekin;
-          a.fr_scal[MD_FRAME_SCAL * (size_t)o + 2] = T;
-          for (int i = 0; i < 9; ++i) a.fr_cell[9 * (size_t)o + i] = sd[i];
-          for (int i = 0; i < 9; ++i) a.fr_stress[9 * (size_t)o + i] = a.stress ? a.stress[9 * (size_t)o + i] : 0.0f;
-          if (a.cfea && a.fr_cfea)
-            for (int i = 0; i < a.fea_dim; ++i) a.fr_cfea[(size_t)a.fea_dim * o + i] = a.cfea[(size_t)a.fea_dim * o + i];
-        }
-      }
-    }
+    if (kick || a.fr.scal) md_scale_momenta(a, v, sh.lam);
   }
 
-  if ((a.flags & MD_START) && a.ensemble == MD_NVT_LANGEVIN) {
-    // BAOAB up to the evaluation: B A O A.  The noise counter is the number of steps this replica has completed (thread 0 has
-    // just counted the step that MD_KICK2 finished)
-    __syncthreads();
-    if (tid == 0) {
-      s_steps = si[0];
-      for (int i = 0; i < 9; ++i) { sLinv[i] = sd[9 + i]; a.lat_next[9 * (size_t)o + i] = sd[i]; }
-    }
-    __syncthreads();
-    const unsigned long long seed = a.seeds[o];
-    const unsigned step = (unsigned)s_steps;
-    const bool noisy = a.lg_sig > 0.0;
-    double ps[4] = {0.0, 0.0, 0.0, 0.0};   // sum p, sum m
-    for (int i = tid; i < n; i += 256) {
-      const double mi = m[i];
-      double xi[3] = {0.0, 0.0, 0.0};
-      if (noisy) philox_normal3(seed, (unsigned)i, step, xi);
-      const double sg = a.lg_sig * sqrt(mi);
-      const unsigned held = md_held_bits<MASK>(fixed, i);   // the noise of a held component is drawn and dropped
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        double pj = md_free<MASK>(held, j, p[3 * i + j] + hdt * f[3 * i + j]);
-        r[3 * i + j] += hdt * pj / mi;
-        pj = md_free<MASK>(held, j, a.lg_c1 * pj + sg * xi[j]);
-        p[3 * i + j] = pj;
-        ps[j] += pj;
-      }
-      ps[3] += mi;
-    }
-    if (a.fixcm) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) ps[j] = wave_sum_f64(ps[j]);
-      if (lane == 0)
-        for (int j = 0; j < 4; ++j) red[wv][j] = ps[j];
-      __syncthreads();
-      if (tid == 0) {
-        const double im = 1.0 / (red[0][3] + red[1][3] + red[2][3] + red[3][3]);
-        for (int j = 0; j < 3; ++j) s_mean[j] = (red[0][j] + red[1][j] + red[2][j] + red[3][j]) * im;   // centre-of-mass velocity
-      }
-      __syncthreads();
-    }
-    for (int i = tid; i < n; i += 256) {
-      const double mi = m[i];
-      const unsigned held = md_held_bits<MASK>(fixed, i);
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const double pj = md_free<MASK>(held, j, a.fixcm ? p[3 * i + j] - mi * s_mean[j] : p[3 * i + j]);
-        p[3 * i + j] = pj;
-        r[3 * i + j] += hdt * pj / mi;
-      }
-      const double y0 = r[3 * i], y1 = r[3 * i + 1], y2 = r[3 * i + 2];
-      double* fr = a.frac_next + 3 * ((size_t)a0 + i);
-#pragma unroll
-      for (int j = 0; j < 3; ++j) fr[j] = y0 * sLinv[j] + y1 * sLinv[3 + j] + y2 * sLinv[6 + j];
-    }
-    return;
-  }
-
-  if ((a.flags & MD_START) && nhc) {
-    // up to the evaluation: barostat chain, particle chain, barostat kick (cached stress, sum p p / m scaled by s^2), then one pass
-    // p <- (p s e1 + dt/2 f) e1, r <- (r e2 + dt p / m) e2 with e1 = exp(-alpha veps dt/4), e2 = exp(veps dt/2); the cell scales by e2^2
-    __syncthreads();   // sd, the chain state and p written above
-    if (tid == 0) {
-      const NhcConst c(a, nhc_nf());
-      const int M = a.nhc_len;
-      double v[MD_NHC_MAX], eta[MD_NHC_MAX];
-      double veps = xs[16], K2 = sd[30] + sd[34] + sd[38];
-      if (nhc_npt) {
-#pragma unroll
-        for (int k = 0; k < MD_NHC_MAX; ++k) { v[k] = xs[8 + k]; eta[k] = xs[12 + k]; }
-        veps *= nhc_chain(v, eta, M, c.Qb, c.Qb, c.W * veps * veps, 1.0, c.kT, hdt);
-#pragma unroll
-        for (int k = 0; k < MD_NHC_MAX; ++k) { xs[8 + k] = v[k]; xs[12 + k] = eta[k]; }
-      }
-#pragma unroll
-      for (int k = 0; k < MD_NHC_MAX; ++k) { v[k] = xs[k]; eta[k] = xs[4 + k]; }
-      const double s = nhc_chain(v, eta, M, c.Q0, c.Qk, K2, c.nf, c.kT, hdt);
-      K2 *= s * s;
-#pragma unroll
-      for (int k = 0; k < MD_NHC_MAX; ++k) { xs[k] = v[k]; xs[4 + k] = eta[k]; }
+  if (!(a.flags & MD_START)) return;
+  // up to the evaluation: barostat chain, particle chain, barostat kick (cached stress, sum p p / m scaled by s^2), then one pass
+  // p <- (p s e1 + dt/2 f) e1, r <- (r e2 + dt p / m) e2 with e1 = exp(-alpha veps dt/4), e2 = exp(veps dt/2); the cell scales by e2^2
+  __syncthreads();   // sd, the chain state and p written above
+  if (tid == 0) {
+    const NhcConst c(a, v.nhc_nf());
+    double veps = xs[16], K2 = sd[30] + sd[34] + sd[38];
+    if (npt) nhc_barostat_chain(c, xs, M, veps, hdt);
+    const double s = nhc_particle_chain(c, xs, M, K2, hdt);
+    if (npt) {
       double L[9];
       for (int i = 0; i < 9; ++i) L[i] = sd[i];
-      if (nhc_npt) {
-        const double vol = fabs(det3(L));
-        veps += hdt * (c.alpha * K2 - vol * (sd[21] + sd[25] + sd[29]) - 3.0 * a.pressure * vol) / c.W;
-        xs[16] = veps;
-        const double eh = exp(veps * a.dt);
-        for (int i = 0; i < 9; ++i) { L[i] *= eh; sd[i] = L[i]; }
-        inv3(L, sd + 9);
-      }
-      s_lam = s;
-      s_e[0] = exp(-0.5 * c.alpha * veps * hdt);
-      s_e[1] = exp(0.5 * veps * a.dt);
-      for (int i = 0; i < 9; ++i) { sLinv[i] = sd[9 + i]; a.lat_next[9 * (size_t)o + i] = L[i]; }
+      nhc_barostat_kick(c, veps, K2, fabs(det3(L)), sd, a.pressure, hdt);
+      xs[16] = veps;
+      const double eh = exp(veps * a.dt);
+      for (int i = 0; i < 9; ++i) { L[i] *= eh; sd[i] = L[i]; }
+      inv3(L, sd + 9);
     }
-    __syncthreads();
-    const double e1 = s_e[0], e2 = s_e[1], se1 = s_lam * e1;
-    for (int i = tid; i < n; i += 256) {
-      const double idm = a.dt / m[i];
-      const unsigned held = md_held_bits<MASK>(fixed, i);
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const double pj = md_free<MASK>(held, j, (p[3 * i + j] * se1 + hdt * f[3 * i + j]) * e1);
-        p[3 * i + j] = pj;
-        r[3 * i + j] = (r[3 * i + j] * e2 + idm * pj) * e2;
-      }
-      const double y0 = r[3 * i], y1 = r[3 * i + 1], y2 = r[3 * i + 2];
-      double* fr = a.frac_next + 3 * ((size_t)a0 + i);
-#pragma unroll
-      for (int j = 0; j < 3; ++j) fr[j] = y0 * sLinv[j] + y1 * sLinv[3 + j] + y2 * sLinv[6 + j];
-    }
-    return;
+    sh.lam = s;
+    s_e[0] = exp(-0.5 * c.alpha * veps * hdt);
+    s_e[1] = exp(0.5 * veps * a.dt);
+    md_next_cell(a, v, sh);
   }
-
-  if ((a.flags & MD_START) && !advance) {
-    // thermostat (ASE NVTBerendsen.scale_velocities) and barostat (NPTBerendsen / Inhomogeneous_NPTBerendsen.scale_positions_and_cell)
-    __syncthreads();   // sd written by thread 0 above
-    if (tid == 0) {
-      double lam = 1.0;
-      if (a.ensemble != MD_NVE) {
-        const double T = sd[20];
-        const double ratio = T > 0.0 ? a.temperature / T : (a.temperature > 0.0 ? (double)INFINITY : 1.0);
-        lam = sqrt(1.0 + (ratio - 1.0) * (a.dt / a.taut));
-        if (lam > 1.1) lam = 1.1;
-        if (lam < 0.9) lam = 0.9;
-      }
-      s_lam = lam;
-      if (npt) {
-        double L[9], Ln[9], M[9], st[9];
-        for (int i = 0; i < 9; ++i) L[i] = sd[i];
-        const double iv = 1.0 / fabs(det3(L));
-        for (int i = 0; i < 9; ++i) st[i] = sd[21 + i] - lam * lam * sd[30 + i] * iv;   // stress incl. the ideal-gas term
-        double sc[3];
-        if (a.ensemble == MD_NPT_BERENDSEN_INHOMOGENEOUS) {
-          const double taupscl = a.dt * a.compressibility / a.taup / 3.0;
-          for (int i = 0; i < 3; ++i) sc[i] = 1.0 - taupscl * (a.pressure - (-st[4 * i]));
-        } else {
-          const double taupscl = a.dt / a.taup;
-          const double old_p = -(st[0] + st[4] + st[8]) / 3.0;
-          sc[0] = sc[1] = sc[2] = 1.0 - taupscl * a.compressibility / 3.0 * (a.pressure - old_p);
-        }
-        for (int i = 0; i < 3; ++i)
-          for (int j = 0; j < 3; ++j) Ln[3 * i + j] = sc[i] * L[3 * i + j];
-        mm3(sd + 9, Ln, M);            // positions <- positions . solve(L, L')
-        for (int i = 0; i < 9; ++i) { sM[i] = M[i]; sd[i] = Ln[i]; }
-        inv3(Ln, sd + 9);
-        for (int i = 0; i < 9; ++i) { sLinv[i] = sd[9 + i]; a.lat_next[9 * (size_t)o + i] = Ln[i]; }
-        si[2] = 1;
-      }
-    }
-    __syncthreads();
-    const double lam = s_lam;
-    for (int i = tid; i < n; i += 256) {
-      const unsigned held = md_held_bits<MASK>(fixed, i);
-#pragma unroll
-      for (int j = 0; j < 3; ++j) p[3 * i + j] = md_free<MASK>(held, j, p[3 * i + j] * lam);
-      if (npt) {
-        const double x0 = r[3 * i], x1 = r[3 * i + 1], x2 = r[3 * i + 2];
-        double* fr = a.frac_next + 3 * ((size_t)a0 + i);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) r[3 * i + j] = x0 * sM[j] + x1 * sM[3 + j] + x2 * sM[6 + j];
-        const double y0 = r[3 * i], y1 = r[3 * i + 1], y2 = r[3 * i + 2];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) fr[j] = y0 * sLinv[j] + y1 * sLinv[3 + j] + y2 * sLinv[6 + j];
-      }
-    }
-    if (npt) return;                    // the scaled configuration is evaluated before the half kick
-    advance = true;
-  }
-  if (!advance) return;
-
-  // first half kick with the cached forces, fixcm (mean momentum, not mass-weighted), drift r += dt p / m
   __syncthreads();
-  double ps[3] = {0.0, 0.0, 0.0};
+  const double e1 = s_e[0], e2 = s_e[1], se1 = sh.lam * e1;
   for (int i = tid; i < n; i += 256) {
-    const unsigned held = md_held_bits<MASK>(fixed, i);
+    const double idm = a.dt / v.m[i];
+    const unsigned held = md_held_bits<MASK>(v.fixed, i);
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-      const double pj = md_free<MASK>(held, j, p[3 * i + j] + hdt * f[3 * i + j]);
+      const double pj = md_free<MASK>(held, j, (p[3 * i + j] * se1 + hdt * v.f[3 * i + j]) * e1);
       p[3 * i + j] = pj;
-      ps[j] += pj;
+      r[3 * i + j] = (r[3 * i + j] * e2 + idm * pj) * e2;
     }
-  }
-  if (a.fixcm) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) ps[j] = wave_sum_f64(ps[j]);
-    if (lane == 0)
-      for (int j = 0; j < 3; ++j) red[wv][j] = ps[j];
-  }
-  if (tid == 0)
-    for (int i = 0; i < 9; ++i) sLinv[i] = sd[9 + i];
-  __syncthreads();
-  if (tid == 0) {
-    for (int j = 0; j < 3; ++j) s_mean[j] = a.fixcm ? (red[0][j] + red[1][j] + red[2][j] + red[3][j]) / (double)n : 0.0;
-    for (int i = 0; i < 9; ++i) a.lat_next[9 * (size_t)o + i] = sd[i];
-  }
-  __syncthreads();
-  for (int i = tid; i < n; i += 256) {
-    const double mi = m[i];
-    const unsigned held = md_held_bits<MASK>(fixed, i);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const double pj = md_free<MASK>(held, j, a.fixcm ? p[3 * i + j] - s_mean[j] : p[3 * i + j]);
-      p[3 * i + j] = pj;
-      r[3 * i + j] += a.dt * pj / mi;
-    }
-    const double y0 = r[3 * i], y1 = r[3 * i + 1], y2 = r[3 * i + 2];
-    double* fr = a.frac_next + 3 * ((size_t)a0 + i);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) fr[j] = y0 * sLinv[j] + y1 * sLinv[3 + j] + y2 * sLinv[6 + j];
+    md_write_frac(a, v, sh, i, r[3 * i], r[3 * i + 1], r[3 * i + 2]);
   }
 }
 
@@ -661,26 +738,9 @@ __device__ __forceinline__ void flex_barostat_kick(const NhcConst& c, const Flex
 
 // half a step of the barostat chain: Vg *= s
 __device__ inline void flex_barostat_chain(const NhcConst& c, const FlexConst& fc, double* xs, int M, double (&vg)[6], double tau) {
-  double v[MD_NHC_MAX], eta[MD_NHC_MAX];
-#pragma unroll
-  for (int k = 0; k < MD_NHC_MAX; ++k) { v[k] = xs[8 + k]; eta[k] = xs[12 + k]; }
-  const double s = nhc_chain(v, eta, M, fc.Qb0, c.Qb, flex_k2(fc, vg), fc.db, c.kT, tau);
-#pragma unroll
-  for (int k = 0; k < MD_NHC_MAX; ++k) { xs[8 + k] = v[k]; xs[12 + k] = eta[k]; }
+  const double s = nhc_chain_at(xs, 8, M, fc.Qb0, c.Qb, flex_k2(fc, vg), fc.db, c.kT, tau);
 #pragma unroll
   for (int k = 0; k < 6; ++k) vg[k] *= s;
-}
-
-// half a step of the particle chain: returns s, K2 *= s^2
-__device__ inline double flex_particle_chain(const NhcConst& c, double* xs, int M, double& K2, double tau) {
-  double v[MD_NHC_MAX], eta[MD_NHC_MAX];
-#pragma unroll
-  for (int k = 0; k < MD_NHC_MAX; ++k) { v[k] = xs[k]; eta[k] = xs[4 + k]; }
-  const double s = nhc_chain(v, eta, M, c.Q0, c.Qk, K2, c.nf, c.kT, tau);
-#pragma unroll
-  for (int k = 0; k < MD_NHC_MAX; ++k) { xs[k] = v[k]; xs[4 + k] = eta[k]; }
-  K2 *= s * s;
-  return s;
 }
 
 __device__ __forceinline__ void flex_load_vg(const double* g, double (&vg)[6]) {
@@ -706,161 +766,65 @@ __device__ __forceinline__ void row_sym(const double (&v)[3], const double* e, d
   w[2] = v[0] * e[4] + v[1] * e[3] + v[2] * e[2];
 }
 
-struct MdFlexArgs {
-  double* vg;   // [B, MD_VG]
-};
-
-// MD_NPT_NHC_FLEX / MD_NPT_NHC_AXES on the launch structure of k_md_step (one workgroup per replica, the chains and the matrix
-// exponentials in thread 0, the factors handed to the row passes through LDS); phase stays 0, no fixcm.  MASK as in k_md_step.
 template <bool MASK>
-static __global__ __launch_bounds__(256) void k_md_step_flex(MdStepArgs a, MdFlexArgs x) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int o = a.sel ? a.sel[blockIdx.x] : blockIdx.x;
-  const int a0 = a.aoff[o], n = a.aoff[o + 1] - a0;
-  double* r = a.r + 3 * (size_t)a0;
-  double* p = a.p + 3 * (size_t)a0;
-  double* f = a.f + 3 * (size_t)a0;
-  const double* m = a.m + a0;
-  double* sd = a.sd + (size_t)MD_SD * o;
-  int* si = a.si + (size_t)MD_SI * o;
-  double* xs = a.nhc + (size_t)MD_NHC * o;
-  double* gv = x.vg + (size_t)MD_VG * o;
+static __global__ __launch_bounds__(256) void k_md_step_flex(MdStepArgs a) {
+  const int tid = threadIdx.x;
+  const MdReplica<MASK> v(a);
+  const int n = v.n, M = a.nhc_len;
+  double *r = v.r, *p = v.p, *sd = v.sd;
+  double* xs = a.nhc + (size_t)MD_NHC * v.o;
+  double* gv = a.vg + (size_t)MD_VG * v.o;
   const double hdt = 0.5 * a.dt;
-  const unsigned char* fixed = MASK ? a.fixed + 3 * (size_t)a0 : nullptr;
-  auto dof = [&]() -> double { return (MASK && a.nfree[o] < 3 * n) ? (double)a.nfree[o] : 3.0 * n; };
-  auto nhc_nf = [&]() -> double { return (MASK && a.nfree[o] < 3 * n) ? (double)a.nfree[o] : 3.0 * (n - 1); };
 
-  __shared__ double red[4][7];
-  __shared__ int rfin[4];
-  __shared__ double sLinv[9], sE1[6], sE2[6], s_lam;
-  __shared__ int s_status, s_go;
+  __shared__ MdShared sh;
+  __shared__ double sE1[6], sE2[6];
 
-  if (tid == 0) s_status = si[1];
-  __syncthreads();
-  if (s_status != MD_RUNNING) return;
+  if (md_frozen(v, sh)) return;
 
   if (a.flags & MD_ABSORB) {
     const bool kick = a.flags & MD_KICK2;
-    const bool frame = a.fr_scal != nullptr;
-    int fin = 1;
-    for (int i = tid; i < n; i += 256) {
-      const float* fi = a.force + 3 * ((size_t)a0 + i);
-      fin &= isfinite(fi[0]) && isfinite(fi[1]) && isfinite(fi[2]);
+    if (tid == 0 && kick) {   // the kick's factor from the state alone: published by the barriers of the finite check
+      const NhcConst c(a, v.nhc_nf());
+      double vg[6], e[6];
+      flex_load_vg(gv, vg);
+      flex_kick_factor(c, vg, hdt, e);
+      for (int k = 0; k < 6; ++k) sE1[k] = e[k];
     }
-    fin = __all(fin);
-    if (lane == 0) rfin[wv] = fin;
-    __syncthreads();
-    if (tid == 0) {
-      int ok = rfin[0] & rfin[1] & rfin[2] & rfin[3] & (int)isfinite(a.energy[o]);
-      if (a.stress)
-        for (int i = 0; i < 9; ++i) ok &= (int)isfinite(a.stress[9 * (size_t)o + i]);
-      if (!ok) {
-        if (a.final_try) si[1] = MD_NONFINITE;
-        else a.retry[o] = 1;
-      }
-      s_go = ok;
-      if (ok && kick) {
-        const NhcConst c(a, nhc_nf());
-        double vg[6], e[6];
-        flex_load_vg(gv, vg);
-        flex_kick_factor(c, vg, hdt, e);
-        for (int k = 0; k < 6; ++k) sE1[k] = e[k];
-      }
-    }
-    __syncthreads();
-    if (!s_go) return;
+    if (!md_absorb_finite(a, v, sh)) return;
 
     // second half of the step: p <- (p E1 + dt/2 f) E1 and sum p p / m in one pass, thread 0 runs the barostat kick and the two chains,
     // one scaling pass writes the frame's momenta
-    double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int i = tid; i < n; i += 256) {
-      const float* fi = a.force + 3 * ((size_t)a0 + i);
-      const unsigned held = md_held_bits<MASK>(fixed, i);
-      auto fm = [&](int j) -> float { return (MASK && ((held >> j) & 1u)) ? 0.0f : fi[j]; };
-      double pi[3] = {p[3 * i], p[3 * i + 1], p[3 * i + 2]};
-      const double fj[3] = {fm(0), fm(1), fm(2)};
-      if (kick) {
-        double q[3];
-        row_sym(pi, sE1, q);
+    double pp[6];
+    md_absorb_rows<MASK, false>(a, v, sh, [&](double (&pi)[3], const double (&fj)[3]) {
+      if (!kick) return;
+      double q[3];
+      row_sym(pi, sE1, q);
 #pragma unroll
-        for (int j = 0; j < 3; ++j) q[j] += hdt * fj[j];
-        row_sym(q, sE1, pi);
-      }
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        f[3 * i + j] = fj[j];
-        pi[j] = md_free<MASK>(held, j, pi[j]);
-        p[3 * i + j] = pi[j];
-      }
-      const double im = 1.0 / m[i];
-      acc[1] += pi[0] * pi[0] * im; acc[2] += pi[1] * pi[1] * im; acc[3] += pi[2] * pi[2] * im;
-      acc[4] += pi[1] * pi[2] * im; acc[5] += pi[0] * pi[2] * im; acc[6] += pi[0] * pi[1] * im;
-      if (frame) {
-        const size_t ro = 3 * ((size_t)a0 + i);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) { a.fr_pos[ro + j] = r[3 * i + j]; a.fr_force[ro + j] = fm(j); }
-      }
-    }
-#pragma unroll
-    for (int k = 1; k < 7; ++k) acc[k] = wave_sum_f64(acc[k]);
-    if (lane == 0)
-      for (int k = 1; k < 7; ++k) red[wv][k] = acc[k];
-    __syncthreads();
+      for (int j = 0; j < 3; ++j) q[j] += hdt * fj[j];
+      row_sym(q, sE1, pi);
+    }, pp);
     if (tid == 0) {
-      const NhcConst c(a, nhc_nf());
+      const NhcConst c(a, v.nhc_nf());
       const FlexConst fc(c, a.ensemble);
-      double pp[6], vg[6];
-      for (int k = 0; k < 6; ++k) pp[k] = red[0][k + 1] + red[1][k + 1] + red[2][k + 1] + red[3][k + 1];
+      double vg[6];
       double K2 = pp[0] + pp[1] + pp[2], s = 1.0;
       const double vol = fabs(det3(sd));
-      sd[18] = a.energy[o];
-      if (a.stress)
-        for (int i = 0; i < 9; ++i) sd[21 + i] = (double)a.stress[9 * (size_t)o + i] * a.stress_weight;
+      md_store_potential(a, v);
       flex_load_vg(gv, vg);
       if (kick) {
         flex_barostat_kick(c, fc, vg, pp, K2, vol, sd + 21, a.pressure, hdt);
-        s = flex_particle_chain(c, xs, a.nhc_len, K2, hdt);
-        flex_barostat_chain(c, fc, xs, a.nhc_len, vg, hdt);
+        s = nhc_particle_chain(c, xs, M, K2, hdt);
+        flex_barostat_chain(c, fc, xs, M, vg, hdt);
         flex_store_vg(gv, vg);
-        si[0] += 1;
+        v.si[0] += 1;
       }
-      const double ekin = 0.5 * K2;
-      const double T = (!MASK || dof() > 0.0) ? 2.0 * ekin / (dof() * a.kB) : 0.0;
-      double cons = 0.5 * K2 + a.pressure * vol + 0.5 * flex_k2(fc, vg);
-      for (int k = 0; k < a.nhc_len; ++k)
-        cons += 0.5 * (k == 0 ? c.Q0 : c.Qk) * xs[k] * xs[k] + (k == 0 ? c.nf : 1.0) * c.kT * xs[4 + k] +
-                0.5 * (k == 0 ? fc.Qb0 : c.Qb) * xs[8 + k] * xs[8 + k] + (k == 0 ? fc.db : 1.0) * c.kT * xs[12 + k];
+      const double cons = nhc_extended_energy(c, xs, M, K2, true, a.pressure, vol, 0.5 * flex_k2(fc, vg), fc.Qb0, fc.db);
       xs[17] = cons;
-      sd[19] = ekin;
-      sd[20] = T;
-      const double s2 = s * s;
-      const double Gm[9] = {pp[0], pp[5], pp[4], pp[5], pp[1], pp[3], pp[4], pp[3], pp[2]};
-      for (int i = 0; i < 9; ++i) sd[30 + i] = Gm[i] * s2;
-      s_lam = s;
-      if (frame) {
-        a.fr_scal[MD_FRAME_SCAL * (size_t)o] = a.energy[o];
-        a.fr_scal[MD_FRAME_SCAL * (size_t)o + 1] = ekin;
-        a.fr_scal[MD_FRAME_SCAL * (size_t)o + 2] = T;
-        if (a.fr_cons) a.fr_cons[o] = cons;
-        for (int i = 0; i < 9; ++i) a.fr_cell[9 * (size_t)o + i] = sd[i];
-        for (int i = 0; i < 9; ++i) a.fr_stress[9 * (size_t)o + i] = a.stress ? a.stress[9 * (size_t)o + i] : 0.0f;
-        if (a.cfea && a.fr_cfea)
-          for (int i = 0; i < a.fea_dim; ++i) a.fr_cfea[(size_t)a.fea_dim * o + i] = a.cfea[(size_t)a.fea_dim * o + i];
-      }
+      md_store_kinetic_frame(a, v, pp, K2, s, &cons);
+      sh.lam = s;
     }
     __syncthreads();
-    if (kick || frame) {
-      const double s = s_lam;
-      for (int i = tid; i < n; i += 256) {
-        const unsigned held = md_held_bits<MASK>(fixed, i);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          const double pj = md_free<MASK>(held, j, p[3 * i + j] * s);
-          p[3 * i + j] = pj;
-          if (frame) a.fr_mom[3 * ((size_t)a0 + i) + j] = pj;
-        }
-      }
-    }
+    if (kick || a.fr.scal) md_scale_momenta(a, v, sh.lam);
   }
 
   if (!(a.flags & MD_START)) return;
@@ -868,13 +832,13 @@ static __global__ __launch_bounds__(256) void k_md_step_flex(MdStepArgs a, MdFle
   // p <- (p s E1 + dt/2 f) E1, r <- (r E2 + dt p / m) E2 with E2 = exp(Vg dt/2); the cell is multiplied by E2 E2 = exp(Vg dt)
   __syncthreads();   // sd, the chain state and p written above
   if (tid == 0) {
-    const NhcConst c(a, nhc_nf());
+    const NhcConst c(a, v.nhc_nf());
     const FlexConst fc(c, a.ensemble);
     double vg[6], e[6], e3[6], arg[6];
     flex_load_vg(gv, vg);
-    flex_barostat_chain(c, fc, xs, a.nhc_len, vg, hdt);
+    flex_barostat_chain(c, fc, xs, M, vg, hdt);
     double K2 = sd[30] + sd[34] + sd[38];
-    const double s = flex_particle_chain(c, xs, a.nhc_len, K2, hdt), s2 = s * s;
+    const double s = nhc_particle_chain(c, xs, M, K2, hdt), s2 = s * s;
     const double pp[6] = {sd[30] * s2, sd[34] * s2, sd[38] * s2, sd[35] * s2, sd[32] * s2, sd[31] * s2};
     double L[9], Ln[9];
     for (int i = 0; i < 9; ++i) L[i] = sd[i];
@@ -890,18 +854,18 @@ static __global__ __launch_bounds__(256) void k_md_step_flex(MdStepArgs a, MdFle
     mm3(L, E3, Ln);
     for (int i = 0; i < 9; ++i) sd[i] = Ln[i];
     inv3(Ln, sd + 9);
-    s_lam = s;
-    for (int i = 0; i < 9; ++i) { sLinv[i] = sd[9 + i]; a.lat_next[9 * (size_t)o + i] = Ln[i]; }
+    sh.lam = s;
+    md_next_cell(a, v, sh);
   }
   __syncthreads();
-  const double s = s_lam;
+  const double s = sh.lam;
   for (int i = tid; i < n; i += 256) {
-    const double idm = a.dt / m[i];
-    const unsigned held = md_held_bits<MASK>(fixed, i);
+    const double idm = a.dt / v.m[i];
+    const unsigned held = md_held_bits<MASK>(v.fixed, i);
     double pi[3] = {p[3 * i] * s, p[3 * i + 1] * s, p[3 * i + 2] * s}, q[3], ri[3] = {r[3 * i], r[3 * i + 1], r[3 * i + 2]}, y[3];
     row_sym(pi, sE1, q);
 #pragma unroll
-    for (int j = 0; j < 3; ++j) q[j] += hdt * f[3 * i + j];
+    for (int j = 0; j < 3; ++j) q[j] += hdt * v.f[3 * i + j];
     row_sym(q, sE1, pi);
     row_sym(ri, sE2, y);
 #pragma unroll
@@ -913,9 +877,7 @@ static __global__ __launch_bounds__(256) void k_md_step_flex(MdStepArgs a, MdFle
     row_sym(y, sE2, ri);
 #pragma unroll
     for (int j = 0; j < 3; ++j) r[3 * i + j] = ri[j];
-    double* fr = a.frac_next + 3 * ((size_t)a0 + i);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) fr[j] = ri[0] * sLinv[j] + ri[1] * sLinv[3 + j] + ri[2] * sLinv[6 + j];
+    md_write_frac(a, v, sh, i, ri[0], ri[1], ri[2]);
   }
 }
 

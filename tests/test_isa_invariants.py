@@ -151,3 +151,37 @@ def test_layernorm_affine_sums_are_not_a_read_modify_write_chain_through_scratch
                     chains += 1
                     break
         assert chains <= 4, f"{name}: {chains} store -> load round trips through the same scratch slot"
+
+
+# ---- the molecular-dynamics unit (engine_md.hip): one step kernel per integrator family ----------------------------------------------
+@pytest.fixture(scope="module")
+def md_isa(tmp_path_factory):
+    from chgnet_amd import build
+
+    try:
+        hipcc = build.hipcc_path()
+    except RuntimeError:
+        pytest.skip("hipcc not available")
+    out = tmp_path_factory.mktemp("isa_md") / "engine_md.s"
+    flags = [f for f in build.HIP_FLAGS if not f.startswith("-W")]
+    cmd = [hipcc, *flags, "-w", f"-I{build.INCLUDE}", f"-I{build.CSRC}", "--cuda-device-only", "-S",
+           os.path.join(build.CSRC, "engine_md.hip"), "-o", str(out)]
+    subprocess.run(cmd, check=True, capture_output=True, timeout=600)
+    text = out.read_text()
+    meta = {}
+    for block in re.split(r"\n  - \.agpr_count:", text)[1:]:                # one metadata entry per kernel
+        field = lambda key: re.search(rf"\.{key}:\s+(\S+)", block).group(1)  # noqa: E731
+        meta[field("name")] = {key: int(field(key)) for key in ("vgpr_count", "vgpr_spill_count", "private_segment_fixed_size")}
+    return meta
+
+
+def test_md_step_kernels_keep_their_state_in_registers(md_isa):
+    """The three step kernels (kernels_md.h) are built from inlined helpers that take the replica view, the LDS block and the family's
+    kick by reference: every instantiation must still compile without a spilled register and without scratch."""
+    for kernel in ("9k_md_step", "13k_md_step_nhc", "14k_md_step_flex"):        # mangled: length, then name
+        for mask in ("ILb0E", "ILb1E"):
+            hits = [name for name in md_isa if kernel + mask in name]
+            assert len(hits) == 1, f"{kernel}<{mask}>: found {hits} among {sorted(md_isa)}"
+            m = md_isa[hits[0]]
+            assert m["vgpr_spill_count"] == 0, f"{hits[0]}: {m}"
+            assert m["private_segment_fixed_size"] == 0, f"{hits[0]}: {m}"
