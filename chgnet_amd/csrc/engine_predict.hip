@@ -453,10 +453,9 @@ int launch_angle(chg_engine* eng, const char* label, chg_batch* b, const AngleAr
   } else if (BWD && b->win_team > 0) {
     // MD-size batch: an atom per team of waves (kernels_angle_w.h TEAM); the row-order kernel below returns at once unless the graph
     // turned out not to have the canonical angle structure
-    AngleWArgs w{};
-    w.a = a; w.w = b->win; w.n_atoms = b->N;
-    w.a.image = eng->img_angle[1][a.slot];
-    if (HIDDEN && w.a.zsave) hipLaunchKernelGGL((k_angle_bwd_w<HIDDEN, true, HIDDEN>), dim3(b->win_grid), dim3(BLOCK), angle_w_lds<HIDDEN>(), eng->stream, w);
+    AngleBwdWArgs w = angle_bwd_w_args(a, b->win, b->N);
+    w.image = eng->img_angle[1][a.slot];
+    if (HIDDEN && w.zsave) hipLaunchKernelGGL((k_angle_bwd_w<HIDDEN, true, HIDDEN>), dim3(b->win_grid), dim3(BLOCK), angle_w_lds<HIDDEN>(), eng->stream, w);
     else
     hipLaunchKernelGGL((k_angle_bwd_w<HIDDEN, true>), dim3(b->win_grid), dim3(BLOCK), angle_w_lds<HIDDEN>(), eng->stream, w);
     HIP_TRY(eng, hipGetLastError());
@@ -466,10 +465,9 @@ int launch_angle(chg_engine* eng, const char* label, chg_batch* b, const AngleAr
     // launched, the device flag picks (no host round trip, and a captured hipGraph stays valid across rebuilt graphs).  Per atom
     // against row order: AngleUpdate 2.23 -> 1.60 ms; BondConv 3.44 -> 3.03 ms once all of its contractions run in split precision
     // from row-major images.
-    AngleWArgs w{};
-    w.a = a; w.w = b->win;
-    w.a.image = eng->img_angle[1][a.slot];
-    if (HIDDEN && w.a.zsave) {
+    AngleBwdWArgs w = angle_bwd_w_args(a, b->win, b->N);
+    w.image = eng->img_angle[1][a.slot];
+    if (HIDDEN && w.zsave) {
       if (a32) hipLaunchKernelGGL((k_angle_bwd_w<HIDDEN, false, HIDDEN, true>), dim3(b->win_grid), dim3(BLOCK), angle_w_lds<HIDDEN>(), eng->stream, w);
       else hipLaunchKernelGGL((k_angle_bwd_w<HIDDEN, false, HIDDEN>), dim3(b->win_grid), dim3(BLOCK), angle_w_lds<HIDDEN>(), eng->stream, w);
     } else {
@@ -900,6 +898,7 @@ void carve(chg_batch* b, char* base, size_t& total) {
     w.head = c.take<int>(Ed); w.rank = c.take<int>(Ed); w.list = c.take<int>(A ? N * WIN_LIST : 0);
     w.q_a = c.take<int>(A); w.q_ctr = c.take<int>(A); w.q_b1c = c.take<int>(A); w.q_b2c = c.take<int>(A); w.q_ab1 = c.take<int>(A); w.q_ab2 = c.take<int>(A);
     w.abbond = c.take<int>(2 * Eb);
+    w.rows = c.take<int4>(A); w.atoms = c.take<int4>(A ? N : 0);
     w.wave_head = c.take<int>(A ? WIN_MAX_GRID * WAVES : 0); w.next_atom = c.take<int>(A ? N : 0); w.xatom = c.take<int>(WIN_MAX_GRID / 8 + 1);
     b->win_tmp = c.take<int>(N + 1);
     b->win_scan = c.take<int>(scan_scratch_ints((int)N + 1));
@@ -914,7 +913,8 @@ void carve(chg_batch* b, char* base, size_t& total) {
   {   // the largest span (bytes) a tile kernel addresses from one base pointer: decides the batch's address mode (addr32_mode)
     auto tab = [](size_t rows, size_t ld) { return rows * ld * sizeof(float); };
     size_t span = std::max({tab(N, 4 * D) /* P, GP */, tab(Eu, 2 * D) /* Q */, tab(Eb, 4 * D) /* R, GR */, tab(A, D) /* angle rows, Gang */,
-                            b->zsave_l[0] ? tab(A + TILE_ROWS, 2 * D) : 0 /* kept z rows */});   // (S, wag, agg, Gb, ...: narrower tables of the same rows)
+                            b->zsave_l[0] ? tab(A + TILE_ROWS, 2 * D) : 0 /* kept z rows */,
+                            A * sizeof(int4) /* row records of the per-atom adjoints (WinIndex::rows) */});   // (S, wag, agg, Gb, ...: narrower tables of the same rows)
     // the AtomConv forward reaches the bond rows hb0 [Eu,64] AND the bond-graph nodes' layer features hbc[l] [Eb,64] from the hb0 base
     // (bond_row_offset): the span is the distance actually covered
     for (int l = 0; l < L; ++l) {
@@ -1016,6 +1016,9 @@ int prepare_windows(chg_engine* eng, chg_batch* b) {
   }
   hipLaunchKernelGGL(k_win_groups, g1(b->win_grid / 8 + 1), dim3(256), 0, st, b->N, b->A, b->win_grid / 8, w);
   hipLaunchKernelGGL(k_win_schedule, dim3(b->win_grid / 8), dim3(64), 0, st, b->win_grid, w);
+  // the records the adjoints read: per atom of a wave's list, and per row when the graph builder wrote the order (else k_win_rows has)
+  hipLaunchKernelGGL(k_win_atoms, g1(b->N), dim3(256), 0, st, b->N, w);
+  if (ready) hipLaunchKernelGGL(k_win_pack, g1(b->A), dim3(256), 0, st, b->A, w);
   HIP_TRY(eng, hipGetLastError());
   return CHG_OK;
 }

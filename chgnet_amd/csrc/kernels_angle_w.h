@@ -13,6 +13,8 @@
 //   q_ctr, q_b1c, q_b2c its centre atom and compact bond indices
 //   q_ab1, q_ab2        the (atom, bond) pair index  boff[centre] + rank of the bond among the centre's short bonds
 //   abbond[ab]          the compact bond index behind a pair;  aoff[c] the first row of atom c
+//   rows[row]           what the adjoints' tile loop reads of a row, as ONE 16-byte record: q_a, q_b1c, q_b2c and the rank of the second
+//                       bond at the centre;  atoms[c]: what a wave reads of an atom of its list, as one record (a scalar load)
 // Inside one atom: by directed-edge index of the first bond, then the reference's order -- deterministic.
 // Graphs without this structure (hand-made bond graphs: incomplete angle sets, groups that are not contiguous) and batches too
 // small to give every wave a few atoms clear flag[0]; both adjoint kernels are always launched and the one that does not
@@ -52,6 +54,9 @@ struct WinIndex {             // built by k_win_*; all in the batch arena
   int* list;                  // [N][WIN_LIST] directed edges of the groups of an atom (unordered)
   int *q_a, *q_ctr, *q_b1c, *q_b2c, *q_ab1, *q_ab2;   // [A]
   int* abbond;                // [2 Eb]
+  int4* rows;                 // [A]  one record per row of the centre-major order for the per-atom adjoints' tile loop (ONE 16-byte load per
+                              //      row instead of four index loads): {q_a, q_b1c, q_b2c, rank of the second bond at the centre (-1: none)}
+  int4* atoms;                // [N]  one record per scheduled atom, read with ONE scalar load per atom: {na, aoff, boff, next_atom} (k_win_atoms)
 };
 
 // ---- index construction ---------------------------------------------------------------------------------
@@ -112,6 +117,16 @@ static __global__ void k_win_rows(const int* __restrict__ a_ctr, const int* __re
   w.q_a[row] = a; w.q_ctr[row] = c; w.q_b1c[row] = a_b1c[a]; w.q_b2c[row] = a_b2c[a];
   w.q_ab1[row] = w.boff[c] + r;
   w.q_ab2[row] = r2 >= 0 ? w.boff[c] + r2 : -1;
+  // the rank itself, not clamped to the private rows: the two adjoints hold 13 / 14 of them (win_ns) and compare for themselves
+  w.rows[row] = make_int4(a, a_b1c[a], a_b2c[a], r2);
+}
+
+// the same records from an index the graph builder emitted (k_angle_fill + k_multi_copy wrote the q_* arrays)
+static __global__ void k_win_pack(int A, WinIndex w) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= A) return;
+  const int ab2 = w.q_ab2[row];
+  w.rows[row] = make_int4(w.q_a[row], w.q_b1c[row], w.q_b2c[row], ab2 < 0 ? -1 : ab2 - w.boff[w.q_ctr[row]]);
 }
 
 // ---- small batches (team mode, below): the index without the schedule, in five launches -----------------------------------------
@@ -222,12 +237,66 @@ static __global__ __launch_bounds__(64) void k_win_schedule(int grid, WinIndex w
   w.wave_head[head_slot] = head;
 }
 
+// what a wave needs to know about an atom of its list, side by side (after k_win_schedule; next_atom of an atom on no list is never read)
+static __global__ void k_win_atoms(int N, WinIndex w) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < N) w.atoms[c] = make_int4(w.na[c], w.aoff[c], w.boff[c], w.next_atom[c]);
+}
+
 // ---- the adjoint kernel ---------------------------------------------------------------------------------
 struct AngleWArgs {
   AngleArgs a;                // tables, weights, gradient buffers as for k_angle
   WinIndex w;                 // incl. the per-wave atom lists (k_win_schedule); the grid is the one the schedule was built for
   int n_atoms;                // TEAM kernels: atoms of the batch
 };
+
+// The adjoint kernels' own arguments: only what they read (both kernels sat at the scalar-register ceiling, and every base pointer used in
+// the tile loop is a live scalar pair), the tables of one matrix as ONE base with a column offset, the index as records.
+struct AngleBwdWArgs {
+  const int* flag;            // WinIndex::flag
+  const float* image;         // AngleArgs::image, else the weights below
+  const float* w_ang;
+  GatedW gw;
+  const float *R, *S, *ang, *wbgc, *Gagg, *zsave;   // as in AngleArgs
+  float *Gang, *GR, *GS, *Gwbgc;
+  int first_gang;
+  const int4* rows;           // WinIndex::rows
+  const int* abbond;
+  // an atom per wave
+  const int4* atoms;          // WinIndex::atoms
+  const int* wave_head;
+  // TEAM (MD-size batches: their index may come from the graph builder, which writes the four arrays, in the same launch as the graph)
+  const int *toff, *na, *aoff, *boff, *q_a, *q_b1c, *q_b2c, *q_ab2;
+  int n_atoms;
+};
+inline AngleBwdWArgs angle_bwd_w_args(const AngleArgs& a, const WinIndex& w, int n_atoms) {
+  AngleBwdWArgs k{};
+  k.flag = w.flag; k.image = a.image; k.w_ang = a.w_ang; k.gw = a.gw;
+  k.R = a.R; k.S = a.S; k.ang = a.ang; k.wbgc = a.wbgc; k.Gagg = a.Gagg; k.zsave = a.zsave;
+  k.Gang = a.Gang; k.GR = a.GR; k.GS = a.GS; k.Gwbgc = a.Gwbgc; k.first_gang = a.first_gang;
+  k.rows = w.rows; k.abbond = w.abbond; k.atoms = w.atoms; k.wave_head = w.wave_head;
+  k.toff = w.toff; k.na = w.na; k.aoff = w.aoff; k.boff = w.boff; k.q_a = w.q_a; k.q_b1c = w.q_b1c; k.q_b2c = w.q_b2c; k.q_ab2 = w.q_ab2;
+  k.n_atoms = n_atoms;
+  return k;
+}
+
+// Element i of an index array.  A32 (the batch's address mode, mfma_tile.h grow): the byte offset in one 32-bit register against the uniform base.
+template <class T, bool A32 = false>
+__device__ __forceinline__ T index_load(const T* __restrict__ base, int i) {
+  if constexpr (A32) return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + (unsigned)i * (unsigned)sizeof(T));
+  else return base[i];
+}
+// ... at a wave-uniform index, through the scalar cache: the index is written by earlier launches only, and a scalar load does not queue
+// behind the atomics of the atom the wave has just finished (a vector load's wait does)
+__device__ __forceinline__ int4 index_load_uniform(const int4* base, int i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef const int __attribute__((address_space(4))) * ConstInt;   // the constant address space: loads at a uniform address are scalar
+  ConstInt q = (ConstInt)(unsigned long long)(base + i);
+  return make_int4(q[0], q[1], q[2], q[3]);
+#else
+  return base[i];
+#endif
+}
 
 // Private second-bond rows per wave: dE/dR_j (128 wide).  AngleUpdate: the angle block as two split images (64 KiB), 14 rows.
 // BondConv: ALL contractions in split precision from ONE row-major image per matrix (mfma_split.h: 72 KiB for the angle block and
@@ -247,7 +316,9 @@ constexpr size_t angle_w_lds() {
 struct Gather64 { f32x4 a[TILE_ROWS / 4], b[TILE_ROWS / 4], c[TILE_ROWS / 4]; };
 template <bool A32 = false>
 __device__ __forceinline__ void gather64_issue(Gather64& gr, const float* __restrict__ t0, int i0, int ld0, const float* __restrict__ t1, int i1,
-                                               int ld1, const float* __restrict__ t2, int i2, int ld2, int lane) {
+                                               int ld1, const float* __restrict__ t2, int i2, int ld2, int lane, int c0 = 0, int c1 = 0, int c2 = 0) {
+  // c0 .. c2: first column of the half inside its row (a constant: it lands in the load's immediate offset, where a second base
+  // pointer `t + c` would be one more live scalar pair)
   const int sub = lane >> 4, t = lane & 15;
   int r0[TILE_ROWS / 4], r1[TILE_ROWS / 4], r2[TILE_ROWS / 4];
 #pragma unroll
@@ -257,9 +328,9 @@ __device__ __forceinline__ void gather64_issue(Gather64& gr, const float* __rest
   }
 #pragma unroll
   for (int it = 0; it < TILE_ROWS / 4; ++it) {
-    gr.a[it] = *grow<f32x4, A32>(t0, (unsigned)r0[it], ld0, 4 * t);
-    gr.b[it] = *grow<f32x4, A32>(t1, (unsigned)r1[it], ld1, 4 * t);
-    gr.c[it] = *grow<f32x4, A32>(t2, (unsigned)r2[it], ld2, 4 * t);
+    gr.a[it] = *grow<f32x4, A32>(t0, (unsigned)r0[it], ld0, c0 + 4 * t);
+    gr.b[it] = *grow<f32x4, A32>(t1, (unsigned)r1[it], ld1, c1 + 4 * t);
+    gr.c[it] = *grow<f32x4, A32>(t2, (unsigned)r2[it], ld2, c2 + 4 * t);
   }
 }
 __device__ __forceinline__ void gather64_commit(const Gather64& gr, float* tile, int lane) {
@@ -280,31 +351,61 @@ __device__ __forceinline__ void to_columns(const V64& x, float* T, float* Trow, 
   for (int rr = 0; rr < TILE_ROWS; ++rr) c.v[rr] = T[rr * TS64 + lane];
   __builtin_amdgcn_wave_barrier();
 }
+// A wave-uniform value the compiler must take as new.  The scatter helpers below each test `rr < nvalid` for sixteen rows; left to
+// itself the compiler forms the sixteen conditions ONCE per tile as 64-bit lane masks (and a second set, inverted) and keeps them in
+// scalar registers through the whole scatter phase: 64 of the 102 there are, which is what pushed the kernels' pointers out into
+// vector lanes.  With its own copy of the count every helper compares and branches on the scalar condition code, which costs no register.
+__device__ __forceinline__ int fresh_uniform(int v) {
+  asm volatile("" : "+s"(v));
+  return v;
+}
 // Run sum for a key that is sorted along the rows, carried across tiles (`sum` / `cur` live in the caller); a finished run
 // leaves with one 256-byte atomic.
-template <bool A32 = false>
-__device__ __forceinline__ void run_sum64(const Cols64& c, int nvalid, int key, float& sum, int& cur, float* __restrict__ dst, int ld, int lane) {
+// Where the runs start is found once per tile, in the lanes that hold the keys (lane rr < 16 = row rr, every group of 16 lanes alike):
+// bit rr of the result = row rr is valid and its key differs from the row before (row 0: from the carried key `cur`).  The loop below
+// then tests a bit per row and reads a key only where a run starts -- sixteen keys read and compared per sum kept sixteen scalars
+// alive through each of them.
+__device__ __forceinline__ unsigned run_starts64(int key, int cur, int nvalid, int lane) {
+  const int prev = __builtin_amdgcn_update_dpp(cur, key, 0x111 /* row_shr:1 */, 0xF, 0xF, false);   // first lane of a row keeps `cur`
+  return (unsigned)__builtin_amdgcn_ballot_w64(key != prev && lane < nvalid);                    // (nvalid <= 16: lanes 0..15 only)
+}
+// NB column blocks of 64 that share the key: sums side by side, `col` = column of block 0 of the lane, block q at col + q D
+template <int NB, bool A32 = false>
+__device__ __forceinline__ void run_sum64(const Cols64 (&c)[NB], int nvalid, int key, unsigned starts, float (&sum)[NB], int& cur, float* __restrict__ dst,
+                                          int ld, int col) {
+  nvalid = fresh_uniform(nvalid);
 #pragma unroll
   for (int rr = 0; rr < TILE_ROWS; ++rr) {
     if (rr < nvalid) {
-      const int k = __builtin_amdgcn_readlane(key, rr);
-      if (k != cur) {
-        if (cur >= 0) atomicAdd(grow<float, A32>(dst, (unsigned)cur, ld, lane), sum);
-        sum = 0.f;
-        cur = k;
+      if (starts & (1u << rr)) {
+        if (cur >= 0) {
+          float* d = grow<float, A32>(dst, (unsigned)cur, ld, col);
+#pragma unroll
+          for (int q = 0; q < NB; ++q) atomicAdd(d + q * D, sum[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < NB; ++q) sum[q] = 0.f;
+        cur = __builtin_amdgcn_readlane(key, rr);
       }
-      sum += c.v[rr];
+#pragma unroll
+      for (int q = 0; q < NB; ++q) sum[q] += c[q].v[rr];
     }
   }
 }
-template <bool A32 = false>
-__device__ __forceinline__ void run_flush64(float& sum, int& cur, float* __restrict__ dst, int ld, int lane) {
-  if (cur >= 0) atomicAdd(grow<float, A32>(dst, (unsigned)cur, ld, lane), sum);
-  sum = 0.f;
+template <int NB, bool A32 = false>
+__device__ __forceinline__ void run_flush64(float (&sum)[NB], int& cur, float* __restrict__ dst, int ld, int col) {
+  if (cur >= 0) {
+    float* d = grow<float, A32>(dst, (unsigned)cur, ld, col);
+#pragma unroll
+    for (int q = 0; q < NB; ++q) atomicAdd(d + q * D, sum[q]);
+  }
+#pragma unroll
+  for (int q = 0; q < NB; ++q) sum[q] = 0.f;
   cur = -1;
 }
 template <bool A32 = false>
 __device__ __forceinline__ void row_add64(const Cols64& c, int nvalid, float* __restrict__ base, int row, int ld, int lane) {
+  nvalid = fresh_uniform(nvalid);
 #pragma unroll
   for (int rr = 0; rr < TILE_ROWS; ++rr)
     if (rr < nvalid) atomicAdd(grow<float, A32>(base, (unsigned)__builtin_amdgcn_readlane(row, rr), ld, lane), c.v[rr]);
@@ -315,6 +416,7 @@ __device__ __forceinline__ void row_add64(const Cols64& c, int nvalid, float* __
 // the latter are then sent as direct atomics by the caller's slow path.
 template <int NB>
 __device__ __forceinline__ void private_add(const Cols64 (&c)[NB], int nvalid, int slot, float* pacc, float* dump, int lane) {
+  nvalid = fresh_uniform(nvalid);
 #pragma unroll
   for (int rr = 0; rr < TILE_ROWS; rr += 2) {
     const int sa = __builtin_amdgcn_readlane(slot, rr), sb = __builtin_amdgcn_readlane(slot, rr + 1);
@@ -342,9 +444,9 @@ __device__ __forceinline__ void private_add(const Cols64 (&c)[NB], int nvalid, i
 // four gathered rows and the W_ang contraction.
 // A32: address mode of the table rows (mfma_tile.h grow), picked per batch by the launcher.
 template <bool HIDDEN, bool TEAM = false, bool ZS = false, bool A32 = false>
-__global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs pw) {
-  const AngleArgs& p = pw.a;
-  const WinIndex& w = pw.w;
+__global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleBwdWArgs pw) {
+  const AngleBwdWArgs& p = pw;
+  const AngleBwdWArgs& w = pw;
   if (w.flag[0] != 1) return;                   // this batch runs the plain adjoint (k_angle<.., true>)
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int NS = win_ns<HIDDEN>(), PST = win_pst<HIDDEN>();
@@ -398,7 +500,7 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
   }
   const int wt = TEAM ? wave : 0;
   constexpr int tstep = TEAM ? WAVES * TILE_ROWS : TILE_ROWS;
-  int c_next = TEAM ? 0 : w.wave_head[blockIdx.x * WAVES + wave];     // this wave's atoms (k_win_schedule): a list, one atom ahead
+  int c_next = TEAM ? 0 : w.wave_head[blockIdx.x * WAVES + wave];     // this wave's atoms (k_win_schedule): a list
   for (;;) {
     int c, n = 0, ab0 = 0, k_lo = 0, k_hi = 0x7fffffff;
     bool active = true;
@@ -413,22 +515,32 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
     } else {
       c = __builtin_amdgcn_readfirstlane(c_next);
       if (c < 0) break;
-      c_next = w.next_atom[c];
-      n = __builtin_amdgcn_readfirstlane(w.na[c]);
     }
     if (active) {
-    const int r_begin = __builtin_amdgcn_readfirstlane(w.aoff[c]), r_end = r_begin + n * (n - 1);
+    int r_begin;
+    if (TEAM) {
+      r_begin = __builtin_amdgcn_readfirstlane(w.aoff[c]);
+      ab0 = __builtin_amdgcn_readfirstlane(w.boff[c]);
+    } else {
+      const int4 atom = index_load_uniform(w.atoms, c);     // {na, aoff, boff, next_atom}
+      n = atom.x; r_begin = atom.y; ab0 = atom.z; c_next = atom.w;
+    }
+    const int r_end = r_begin + n * (n - 1);
     const int seg_end = TEAM ? min(r_end, r_begin + k_hi * TILE_ROWS) : r_end;    // (TEAM: the workgroup's part of the atom)
     const int row_first = r_begin + (TEAM ? (k_lo + wt) * TILE_ROWS : 0);
-    ab0 = __builtin_amdgcn_readfirstlane(w.boff[c]);
     // run sums carried over the tiles of this atom (lane = column): first bond (core | gate halves), centre, bond weights
-    float ri0 = 0.f, ri1 = 0.f, rs0 = 0.f, rs1 = 0.f, rg = 0.f;
-    int cur0 = -1, cur1 = -1, curg = -1;
-    int a_n, b1_n, b2_n, ab2_n;
-    {
-      const int row = min(row_first + j, r_end - 1);
-      a_n = w.q_a[row]; b1_n = w.q_b1c[row]; b2_n = w.q_b2c[row]; ab2_n = w.q_ab2[row];
-    }
+    float ri[2] = {0.f, 0.f}, rs0 = 0.f, rs1 = 0.f, rg[1] = {0.f};
+    int cur = -1, curg = -1;
+    // the rows of a tile, requested one tile ahead: {angle, first bond, second bond, rank of the second bond at this atom (-1: none)}
+    auto row_record = [&](int row) -> int4 {
+      if (!TEAM) return index_load<int4, A32>(w.rows, row);
+      const int ab2 = w.q_ab2[row];
+      return make_int4(w.q_a[row], w.q_b1c[row], w.q_b2c[row], ab2 < 0 ? -1 : ab2 - ab0);
+    };
+    // AngleUpdate, an atom per wave: the records are TAKEN (waited for) where the wait is counted -- EARLY_TAKE below
+    constexpr bool EARLY_TAKE = !HIDDEN && !TEAM;
+    int4 rec_n = row_record(min(row_first + j, r_end - 1));
+    if (EARLY_TAKE) asm volatile("" : "+v"(rec_n.x), "+v"(rec_n.y), "+v"(rec_n.z), "+v"(rec_n.w));   // the first tile's: before the loop
     for (int row0 = row_first; row0 < seg_end; row0 += tstep) {
       // lane index made opaque once per tile: everything derived from it (64-bit row pointers base + 4 lane for every buffer, row
       // constants) is recomputed where it is used instead of living -- and being spilled -- across the whole kernel; a spilled
@@ -437,13 +549,11 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
       int lane_t = lane;
       if (HIDDEN) asm volatile("" : "+v"(lane_t));
       const int nvalid = min(TILE_ROWS, r_end - row0);
-      const int a = a_n, b1 = b1_n, b2 = b2_n, ab2 = ab2_n;
-      if (row0 + tstep < seg_end) {
-        const int row = min(row0 + tstep + j, r_end - 1);
-        a_n = w.q_a[row]; b1_n = w.q_b1c[row]; b2_n = w.q_b2c[row]; ab2_n = w.q_ab2[row];
-      }
-      int s2 = ab2 - ab0;                         // rank of the second bond at this atom = private row
-      if (ab2 < 0 || s2 < 0 || s2 >= NS) s2 = -1;
+      const int a = rec_n.x, b1 = rec_n.y, b2 = rec_n.z;
+      const int s2 = (unsigned)rec_n.w < (unsigned)NS ? rec_n.w : -1;   // private row of the second bond (its rank), if the wave has one for it
+      // (EARLY_TAKE: unconditional -- the row is clamped into the atom; behind a branch the loaded registers are copied at the end of
+      // the block, with the wait right behind the request)
+      if (EARLY_TAKE || row0 + tstep < seg_end) rec_n = row_record(min(row0 + tstep + j, r_end - 1));
       // ---- gathers: angle rows, then the two halves of the table sum.  (Requesting tile t+1's rows ahead -- before tile t's scatter
       // phase -- was tried: 112 loop-carried registers for the table rows cost 225 spills (2x slower), 16 for the angle rows alone 51
       // spills (+14 %): this kernel has no registers left to pipeline with.) ----
@@ -462,8 +572,8 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
         }
       } else {
       Gather64 gc, gg;
-      gather64_issue<A32>(gc, p.R, b1, 4 * D, p.R + 2 * D, b2, 4 * D, p.S, c, 2 * D, lane_t);
-      gather64_issue<A32>(gg, p.R + D, b1, 4 * D, p.R + 3 * D, b2, 4 * D, p.S + D, c, 2 * D, lane_t);
+      gather64_issue<A32>(gc, p.R, b1, 4 * D, p.R, b2, 4 * D, p.S, c, 2 * D, lane_t, 0, 2 * D, 0);
+      gather64_issue<A32>(gg, p.R, b1, 4 * D, p.R, b2, 4 * D, p.S, c, 2 * D, lane_t, D, 3 * D, D);
       gather_rows64<A32>(T, TS64, p.ang, a, lane_t);
       __builtin_amdgcn_wave_barrier();
       V64 x;
@@ -490,6 +600,17 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
       GatedState s;
       V64 y;
       constexpr bool SLIM = HIDDEN;
+      // EARLY_TAKE: the next tile's records are taken HERE, behind the wait for this tile's rows (requested after them: the wait covers
+      // both and is counted).  Left until their first use at the top of the next tile, the wait stands behind this tile's conditional
+      // atomics, which the compiler cannot count: it waits for ALL of them before the next tile's first load is even issued.
+      // (Tied to a value of z, or the statement -- and the wait -- moves up to the request.)  Per launch on the headline batch:
+      // AngleUpdate adjoint 1.37 -> 1.30 ms.  The BondConv adjoints stay as they were: with it they need all 256 vector registers, two
+      // instantiations spill 2-3 of them, and the gain was 0.5 %.
+      if (EARLY_TAKE) {
+        float z0 = zc.t[0][0];
+        asm volatile("" : "+v"(rec_n.x), "+v"(rec_n.y), "+v"(rec_n.z), "+v"(rec_n.w), "+v"(z0));
+        zc.t[0][0] = z0;
+      }
       gated_forward<HIDDEN, SLIM, false, MODE>(zc, zg, W2c, W2g, vecs, j, g, s, y);
       V64 gy;
       if (HIDDEN) {
@@ -503,10 +624,10 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
         // the bond-weight gradients leave now (two vectors less to carry through the adjoint of the gated MLP):
         // first bond as a run sum, second bond one atomic row per angle
         {
-          Cols64 c1, c2[1];
-          to_columns(g1, T, Trow, g, lane_t, c1);
+          Cols64 c1[1], c2[1];
+          to_columns(g1, T, Trow, g, lane_t, c1[0]);
           to_columns(g2, T, Trow, g, lane_t, c2[0]);
-          run_sum64<A32>(c1, nvalid, b1, rg, curg, p.Gwbgc, D, lane_t);
+          run_sum64<1, A32>(c1, nvalid, b1, run_starts64(b1, curg, nvalid, lane_t), rg, curg, p.Gwbgc, D, lane_t);
           row_add64<A32>(c2[0], nvalid, p.Gwbgc, b2, D, lane_t);
         }
       } else {
@@ -541,16 +662,19 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
         Cols64 cc[2];
         to_columns(gzc, T, Trow, g, lane_t, cc[0]);
         to_columns(gzg, T, Trow, g, lane_t, cc[1]);
-#pragma unroll
-        for (int rr = 0; rr < TILE_ROWS; ++rr)
-          if (rr < nvalid) { rs0 += cc[0].v[rr]; rs1 += cc[1].v[rr]; }
-        run_sum64<A32>(cc[0], nvalid, b1, ri0, cur0, p.GR, 4 * D, lane_t);
-        run_sum64<A32>(cc[1], nvalid, b1, ri1, cur1, p.GR + D, 4 * D, lane_t);
-        private_add<2>(cc, nvalid, s2, pacc, T, lane_t);
-        if (__builtin_amdgcn_ballot_w64(j < nvalid && lane_t < TILE_ROWS && s2 < 0)) {   // rare: no private row for this second bond
+        {
+          const int nv = fresh_uniform(nvalid);
 #pragma unroll
           for (int rr = 0; rr < TILE_ROWS; ++rr)
-            if (rr < nvalid && __builtin_amdgcn_readlane(s2, rr) < 0) {
+            if (rr < nv) { rs0 += cc[0].v[rr]; rs1 += cc[1].v[rr]; }
+        }
+        run_sum64<2, A32>(cc, nvalid, b1, run_starts64(b1, cur, nvalid, lane_t), ri, cur, p.GR, 4 * D, lane_t);
+        private_add<2>(cc, nvalid, s2, pacc, T, lane_t);
+        if (__builtin_amdgcn_ballot_w64(j < nvalid && lane_t < TILE_ROWS && s2 < 0)) {   // rare: no private row for this second bond
+          const int nv = fresh_uniform(nvalid);
+#pragma unroll
+          for (int rr = 0; rr < TILE_ROWS; ++rr)
+            if (rr < nv && __builtin_amdgcn_readlane(s2, rr) < 0) {
               float* d = A32 ? grow<float, true>(p.GR, (unsigned)__builtin_amdgcn_readlane(b2, rr), 4 * D, 2 * D + lane_t)
                                : p.GR + (size_t)__builtin_amdgcn_readlane(b2, rr) * 4 * D + 2 * D + lane_t;
               atomicAdd(d, cc[0].v[rr]);
@@ -563,14 +687,13 @@ __global__ __launch_bounds__(BLOCK) CHG_TWO_WAVES void k_angle_bwd_w(AngleWArgs 
     // ---- the atom is done: runs, centre sum, private second-bond rows ----
     int lane_f = lane;
     if (HIDDEN) asm volatile("" : "+v"(lane_f));   // as lane_t above
-    run_flush64<A32>(ri0, cur0, p.GR, 4 * D, lane_f);
-    run_flush64<A32>(ri1, cur1, p.GR + D, 4 * D, lane_f);
-    if (HIDDEN) run_flush64<A32>(rg, curg, p.Gwbgc, D, lane_f);
+    run_flush64<2, A32>(ri, cur, p.GR, 4 * D, lane_f);
+    if (HIDDEN) run_flush64<1, A32>(rg, curg, p.Gwbgc, D, lane_f);
     atomicAdd(grow<float, A32>(p.GS, (unsigned)c, 2 * D, lane_f), rs0);
     atomicAdd(grow<float, A32>(p.GS, (unsigned)c, 2 * D, D + lane_f), rs1);
     if (!TEAM) {
       const int nrows = min(n, NS);
-      const int bond_of = w.abbond[ab0 + min(lane_f, nrows - 1)];
+      const int bond_of = index_load<int, A32>(w.abbond, ab0 + min(lane_f, nrows - 1));
       for (int sl = 0; sl < nrows; ++sl) {
         const int bond = __builtin_amdgcn_readlane(bond_of, sl);
         float* src = pacc + sl * PST;
