@@ -38,6 +38,10 @@ def __getattr__(name):  # lazy: keeps `import chgnet_amd` free of the HIP librar
         from chgnet_amd import dynamics
 
         return getattr(dynamics, name)
+    if name in ("MonteCarlo", "MCTrajectory"):
+        from chgnet_amd import montecarlo
+
+        return getattr(montecarlo, name)
     if name in ("MDObservers", "MDObservables"):
         from chgnet_amd import observables
 

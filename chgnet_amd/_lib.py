@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = (
     "chg_hessian_vector", "chg_hessian_vector_strain",
     "chg_relax_set_fixed", "chg_md_set_fixed", "chg_test_relax_step_fixed", "chg_test_lbfgs_step_fixed", "chg_test_md_step_fixed",
     "chg_md_set_observers", "chg_md_download_observables", "chg_test_md_observe",
+    "chg_mc_create", "chg_mc_set_temperatures", "chg_mc_run", "chg_mc_download", "chg_mc_free", "chg_test_mc_step",
 )
 
 
@@ -111,6 +112,22 @@ class MdObservablesHost(ctypes.Structure):
     _fields_ = [("msd", _dp), ("vacf", _dp), ("cnt", _ip), ("rdf", ctypes.POINTER(ctypes.c_uint64)), ("rdf_samples", _ip), ("vol_sum", _dp)]
 
 
+class McParams(ctypes.Structure):
+    _fields_ = [("swap_probability", ctypes.c_double), ("max_displacement", ctypes.c_double), ("kB", ctypes.c_double),
+                ("loginterval", ctypes.c_int32), ("ring_frames", ctypes.c_int32), ("r_atom", ctypes.c_double), ("r_bond", ctypes.c_double),
+                ("numerical_tol", ctypes.c_double)]
+
+
+class McOutHost(ctypes.Structure):
+    _dp, _lp = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
+    _fields_ = [("positions", _dp), ("site", c_int_p), ("energy", _dp), ("temperatures", _dp), ("status", c_int_p), ("n_trials", c_int_p),
+                ("counts", _lp), ("sums", _dp), ("best_energy", _dp), ("best_positions", _dp), ("best_site", c_int_p),
+                ("frame_capacity", ctypes.c_int32), ("n_frames", c_int_p), ("frame_trial", c_int_p), ("frame_scalars", _dp),
+                ("frame_moves", c_int_p), ("frame_positions", _dp), ("frame_site", c_int_p)]
+
+
+MC_COUNTS, MC_FRAME_SCALARS, MC_FRAME_MOVES = 8, 6, 6   # include/chgnet_hip.h CHG_MC_*
+MC_SD, MC_SI = 32, 8                                    # csrc/kernels_mc.h: state doubles and ints per replica (chg_test_mc_step)
 MD_OBS_MAX_LAGS, MD_OBS_MAX_SPECIES, MD_OBS_RDF_CELLS = 4096, 8, 16384   # csrc/kernels_md_obs.h
 MD_NHC_STATE = 20   # include/chgnet_hip.h CHG_MD_NHC_STATE
 MD_VG = 9           # include/chgnet_hip.h CHG_MD_VG
@@ -261,6 +278,16 @@ def load() -> ctypes.CDLL:
     lib.chg_md_download_observables.argtypes = [vp, vp, ctypes.POINTER(MdObservablesHost)]
     lib.chg_test_md_observe.argtypes = [vp, ctypes.POINTER(MdObserveParams), ctypes.c_int32, c_int_p, c_int_p, dp, ctypes.c_int32, dp, dp, dp,
                                         c_int_p, ctypes.POINTER(MdObservablesHost)]
+    # Monte Carlo: temperatures, seeds and the two per-atom masks travel beside the params struct
+    lp = ctypes.POINTER(ctypes.c_int64)
+    lib.chg_mc_create.argtypes = [vp, ctypes.POINTER(StructsHost), dp, u64p, u8p, u8p, ctypes.POINTER(McParams), ctypes.POINTER(vp)]
+    lib.chg_mc_set_temperatures.argtypes = [vp, vp, dp]
+    lib.chg_mc_run.argtypes = [vp, vp, ctypes.c_int32]
+    lib.chg_mc_download.argtypes = [vp, vp, ctypes.POINTER(McOutHost)]
+    lib.chg_mc_free.argtypes = [vp, vp]
+    lib.chg_test_mc_step.argtypes = [vp, ctypes.POINTER(McParams), ctypes.c_int32, c_int_p, c_int_p, u8p, u8p, dp, u64p, ctypes.c_int32,
+                                     ctypes.c_int32, ctypes.c_int32, dp, c_int_p, dp, c_int_p, lp, dp, c_int_p, c_float_p, dp, c_int_p,
+                                     dp, c_int_p, dp, c_int_p]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is ctypes.c_int and name not in ("chg_device_count", "chg_profile_count"):

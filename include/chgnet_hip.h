@@ -545,6 +545,77 @@ int chg_test_md_observe(chg_engine* eng, const chg_md_observe_params* params, in
                         const int32_t* species, const double* masses, int32_t n_samples, const double* positions, const double* momenta,
                         const double* cell, const int32_t* status, const chg_md_observables_host* out);
 
+/* ---- canonical Monte Carlo: species swaps and single-atom displacements, every structure an independent replica -----------------
+ * Not in the reference.  Every replica has a fixed cell, its own temperature (K, >= 0; 0 is greedy descent) and its own 64-bit seed; its
+ * float64 state lives in HBM.  One trial = graph built on the device from all replicas + energy-only prediction
+ * (chg_batch_build_predict, CHG_TASK_E) + one step kernel (csrc/kernels_mc.h) that decides the pending trial by the Metropolis rule and
+ * proposes the next one.  Atoms keep their species: a swap exchanges the POSITIONS of two atoms of different species, and site[a] is the
+ * input row atom a now sits on.  The random numbers of trial k are Philox4x32-10 blocks with counter (k, b, 0, 1) and the seed as key, so a
+ * replica's stream depends on (seed, k) alone: not on its slot in the batch, on retries or on how chg_mc_run calls split the trials.
+ * DESIGN.md "Monte Carlo" states the semantics exactly; tests/mc_ref.py restates them in NumPy. */
+enum { CHG_MC_RUNNING = 0, CHG_MC_NONFINITE = 1 };
+enum { CHG_MC_NONE = -1, CHG_MC_SWAP = 0, CHG_MC_DISPLACE = 1 };   /* move kinds; NONE: the frame of the configuration as given */
+typedef struct chg_mc_params {
+  double swap_probability;     /* a trial is a swap iff u_kind < swap_probability: 1 always swaps, 0 never does                */
+  double max_displacement;     /* A: a displacement is max_displacement (2 u - 1) per cartesian component                     */
+  double kB;                   /* eV/K; <= 0: 8.6173303e-5                                                                    */
+  int32_t loginterval;         /* a frame after every loginterval-th decision, the initial configuration included; 0: none    */
+  int32_t ring_frames;         /* frames the device ring holds between two chg_mc_download calls                              */
+  double r_atom, r_bond, numerical_tol;                /* graph build (6, 3, 1e-8)                                             */
+} chg_mc_params;
+typedef struct chg_mc chg_mc;
+#define CHG_MC_COUNTS 8        /* int64 per replica: swap trials, swap acceptances, displacement trials, displacement acceptances, samples, 3 spare */
+#define CHG_MC_FRAME_SCALARS 6 /* doubles per replica and frame: E_cur, E_trial (eV, total), u_acc, delta[3] (A)                 */
+#define CHG_MC_FRAME_MOVES 6   /* ints per replica and frame: trials decided, kind (CHG_MC_*), i, j, accepted, spare             */
+/* Current state, statistics and best configuration (null pointers are skipped) and up to frame_capacity of the oldest frames in the
+ * ring, which are removed from it.  Energies are totals in eV (an intensive model's eV/atom times the atom count). */
+typedef struct chg_mc_out_host {
+  double* positions;           /* [N,3]   cartesian, A: atom order kept, positions moved                                     */
+  int32_t* site;               /* [N]     input row (within the replica) atom a sits on                                      */
+  double* energy;              /* [B]     E_cur                                                                               */
+  double* temperatures;        /* [B]     K                                                                                   */
+  int32_t* status;             /* [B]     CHG_MC_*                                                                            */
+  int32_t* n_trials;           /* [B]     trials proposed                                                                     */
+  int64_t* counts;             /* [B,CHG_MC_COUNTS]                                                                           */
+  double* sums;                /* [B,2]   sum of E_cur and of E_cur^2 over the samples (one after every decision)             */
+  double* best_energy;         /* [B]     lowest energy seen ...                                                              */
+  double* best_positions;      /* [N,3]   ... with its positions ...                                                          */
+  int32_t* best_site;          /* [N]     ... and site[]                                                                      */
+  int32_t frame_capacity;      /* K: frames the arrays below hold                                                             */
+  int32_t* n_frames;           /* out: frames written                                                                         */
+  int32_t* frame_trial;        /* [K]     trials decided when the frame was written                                           */
+  double* frame_scalars;       /* [K,B,CHG_MC_FRAME_SCALARS]                                                                  */
+  int32_t* frame_moves;        /* [K,B,CHG_MC_FRAME_MOVES] the last move's record                                             */
+  double* frame_positions;     /* [K,N,3]                                                                                     */
+  int32_t* frame_site;         /* [K,N]                                                                                       */
+} chg_mc_out_host;
+/* Copies the structures, temperatures [B], seeds [B] and the two per-atom masks [N] (swap_mask: 1 = the atom's species may swap, null:
+ * all; fixed: 1 = the atom is held, null: none); no evaluation yet.  The atom lists are fixed here: movable = atoms not held, in atom
+ * order; swappable = movable atoms whose swap_mask is set, sorted by (species, atom).  CHG_EINVAL with a message naming the structure
+ * when swap_probability > 0 and its swappable list holds fewer than two species, or swap_probability < 1 and its movable list is empty. */
+int chg_mc_create(chg_engine* eng, const chg_structs_host* host, const double* temperatures, const uint64_t* seeds, const uint8_t* swap_mask,
+                  const uint8_t* fixed, const chg_mc_params* params, chg_mc** out);
+/* New temperatures [B] (K, >= 0) for the trials decided from now on: callable between runs (annealing schedules). */
+int chg_mc_set_temperatures(chg_engine* eng, chg_mc* mc, const double* temperatures);
+/* n_trials trials of every replica (the first call evaluates the configuration as given first: it sets E_cur and the best record, writes
+ * frame 0 and is neither a trial nor a sample).  A batch with a non-finite energy is evaluated again on the wide-range sweep; a replica
+ * that is non-finite even there stops as CHG_MC_NONFINITE with its configuration and statistics untouched.  CHG_EINVAL (nothing run)
+ * when the frames due do not fit the ring. */
+int chg_mc_run(chg_engine* eng, chg_mc* mc, int32_t n_trials);
+int chg_mc_download(chg_engine* eng, chg_mc* mc, const chg_mc_out_host* out);
+int chg_mc_free(chg_engine* eng, chg_mc* mc);
+/* Tests only: ONE step kernel launch on caller-given state, in place.  flags: 1 absorb the evaluation of the pending trial (energy [B]
+ * as the engine gives it: eV/atom when `intensive`), 2 propose the next trial.  z [N] are the species the lists are built from, with
+ * swap_mask and fixed as in chg_mc_create.  State: r [N,3], site [N]; sd [B,32] doubles (L[9], L^-1[9], E_cur, E_best, sumE, sumE2, E_trial
+ * of the last decision, pending u_acc, pending delta[3], spare); si [B,8] ints (trials proposed, status, first evaluation absorbed,
+ * pending kind, i, j, last decision accepted, spare); counts [B,CHG_MC_COUNTS]; best_positions, best_site.  Out: frac_next [N,3],
+ * retry [B] (1: non-finite energy with final_try == 0, state untouched), and the frame arrays of one slot (all four or none). */
+int chg_test_mc_step(chg_engine* eng, const chg_mc_params* params, int32_t n_struct, const int32_t* atom_off, const int32_t* z,
+                     const uint8_t* swap_mask, const uint8_t* fixed, const double* temperatures, const uint64_t* seeds, int32_t flags,
+                     int32_t final_try, int32_t intensive, double* r, int32_t* site, double* sd, int32_t* si, int64_t* counts,
+                     double* best_positions, int32_t* best_site, const float* energy, double* frac_next, int32_t* retry,
+                     double* frame_scalars, int32_t* frame_moves, double* frame_positions, int32_t* frame_site);
+
 /* ---- exchange steps of the multi-GPU path, straight on RCCL (one communicator per process = per GPU) ----------
  * The reference is single-device; these carry what SURVEY 8e needs and nothing else: the all-gather of per-structure
  * energies after a sweep sharded over independent structures, and the sum of the 412,525-float parameter gradient of a
