@@ -38,7 +38,7 @@ def __getattr__(name):  # lazy: keeps `import chgnet_amd` free of the HIP librar
         from chgnet_amd import dynamics
 
         return getattr(dynamics, name)
-    if name in ("MonteCarlo", "MCTrajectory"):
+    if name in ("MonteCarlo", "MCTrajectory", "ParallelTempering", "temperature_ladder"):
         from chgnet_amd import montecarlo
 
         return getattr(montecarlo, name)

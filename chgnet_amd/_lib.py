@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = (
     "chg_relax_set_fixed", "chg_md_set_fixed", "chg_test_relax_step_fixed", "chg_test_lbfgs_step_fixed", "chg_test_md_step_fixed",
     "chg_md_set_observers", "chg_md_download_observables", "chg_test_md_observe",
     "chg_mc_create", "chg_mc_set_temperatures", "chg_mc_run", "chg_mc_download", "chg_mc_free", "chg_test_mc_step",
+    "chg_mc_set_exchange", "chg_mc_download_exchange", "chg_test_mc_exchange",
 )
 
 
@@ -128,6 +129,7 @@ class McOutHost(ctypes.Structure):
 
 MC_COUNTS, MC_FRAME_SCALARS, MC_FRAME_MOVES = 8, 6, 6   # include/chgnet_hip.h CHG_MC_*
 MC_SD, MC_SI = 32, 8                                    # csrc/kernels_mc.h: state doubles and ints per replica (chg_test_mc_step)
+MC_EXCHANGE_INTS = 6                                    # include/chgnet_hip.h CHG_MC_EXCHANGE_INTS: walker, attempts, accepts, mark, trips, spare
 MD_OBS_MAX_LAGS, MD_OBS_MAX_SPECIES, MD_OBS_RDF_CELLS = 4096, 8, 16384   # csrc/kernels_md_obs.h
 MD_NHC_STATE = 20   # include/chgnet_hip.h CHG_MD_NHC_STATE
 MD_VG = 9           # include/chgnet_hip.h CHG_MD_VG
@@ -288,6 +290,11 @@ def load() -> ctypes.CDLL:
     lib.chg_test_mc_step.argtypes = [vp, ctypes.POINTER(McParams), ctypes.c_int32, c_int_p, c_int_p, u8p, u8p, dp, u64p, ctypes.c_int32,
                                      ctypes.c_int32, ctypes.c_int32, dp, c_int_p, dp, c_int_p, lp, dp, c_int_p, c_float_p, dp, c_int_p,
                                      dp, c_int_p, dp, c_int_p]
+    # replica exchange: the ladder ids in, the exchange state [B, MC_EXCHANGE_INTS] out
+    lib.chg_mc_set_exchange.argtypes = [vp, vp, c_int_p, ctypes.c_int32]
+    lib.chg_mc_download_exchange.argtypes = [vp, vp, c_int_p]
+    lib.chg_test_mc_exchange.argtypes = [vp, ctypes.c_int32, c_int_p, c_int_p, dp, u64p, ctypes.c_double, ctypes.c_int32, dp, c_int_p, dp,
+                                         c_int_p, dp, c_int_p, c_int_p]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is ctypes.c_int and name not in ("chg_device_count", "chg_profile_count"):

@@ -4,9 +4,14 @@
 // One trial of chg_mc_run is one evaluate_and_step of the shared driver (engine_stepper.h) on ALL replicas: graph build on the device,
 // energy-only prediction (CHG_TASK_E: forward sweep, no reverse sweep), then k_mc_step as the step launch (one workgroup per replica:
 // decide the pending trial, frame, propose the next one).  Every replica runs the same number of trials, so there is no compaction.
+//
+// Replica exchange (chg_mc_set_exchange, kernels_mc_exchange.h): on a trial that ends with an exchange event the step launch only
+// decides, k_mc_exchange swaps the configurations of the accepted pairs, and a propose-only launch draws the next trial from what the
+// rungs hold now.  A handle without a ladder launches exactly what it launched before.
 #include "engine_stepper.h"
 
 #include "kernels_mc.h"
+#include "kernels_mc_exchange.h"
 
 struct chg_mc : chgh::Stepper {
   chg_mc_params p{};
@@ -21,6 +26,15 @@ struct chg_mc : chgh::Stepper {
   int K = 0, ring_head = 0, ring_count = 0;
   std::vector<int> ring_trial;
   std::vector<chg::McFrame> ring;
+  // replica exchange (chg_mc_set_exchange): what a ladder's members must share, kept from creation, and an allocation of its own
+  std::vector<uint8_t> h_fixed, h_swap_mask;   // [N] as given (null: none held, all may swap)
+  std::vector<double> h_temp;                  // [B] the temperatures in force
+  std::vector<int> ladder;                     // [B] empty: no ladder set
+  int x_interval = 0;                          // an event after every x_interval-th trial; 0: none
+  char* x_mem = nullptr;                       // xi [B, MC_XI], then the pair lists of the two parities
+  int* xi = nullptr;
+  int* x_pairs[2] = {nullptr, nullptr};
+  int x_npairs[2] = {0, 0};
 };
 
 namespace {
@@ -163,6 +177,92 @@ void set_frame(chg_mc* d, McStepArgs& a, int trial) {
   d->ring_count += 1;
 }
 
+// ---- replica exchange
+// The pairs of the two parities, MC_PAIR_INTS ints each (kernels_mc_exchange.h): list[q] holds the rungs (p, p + 1) with p % 2 == q.
+struct McPairs {
+  std::vector<int> list[2];
+};
+
+// The ladders of `ladder` [B] (-1: never exchanged) against what the pair lists alone need: ids >= -1, the members of an id consecutive,
+// at least two of them, the same atom count, T > 0.  Fills the two pair lists.
+int build_pairs(chg_engine* eng, const char* fn, int B, const int* aoff, const int* ladder, const double* temperatures, McPairs& out) {
+  auto refuse = [&](int o, const std::string& what) {
+    eng->err = std::string(fn) + ": replica " + std::to_string(o) + " " + what;
+    return CHG_EINVAL;
+  };
+  out.list[0].clear(); out.list[1].clear();
+  std::vector<int> closed;   // ids whose run has ended
+  for (int first = 0; first < B;) {
+    const int id = ladder[first];
+    if (id < -1) return refuse(first, "has the ladder id " + std::to_string(id) + ", which must be -1 or >= 0");
+    if (id == -1) { first += 1; continue; }
+    if (std::find(closed.begin(), closed.end(), id) != closed.end())
+      return refuse(first, "takes up ladder " + std::to_string(id) + " again after another id: the members of a ladder must be consecutive");
+    int end = first + 1;
+    while (end < B && ladder[end] == id) ++end;
+    const int L = end - first;
+    if (L < 2) return refuse(first, "is the only member of ladder " + std::to_string(id) + ": a ladder needs at least two");
+    for (int o = first; o < end; ++o) {
+      if (aoff[o + 1] - aoff[o] != aoff[first + 1] - aoff[first])
+        return refuse(o, "has " + std::to_string(aoff[o + 1] - aoff[o]) + " atoms, the first member of ladder " + std::to_string(id) + " has " +
+                             std::to_string(aoff[first + 1] - aoff[first]));
+      if (!(temperatures[o] > 0.0) || !std::isfinite(temperatures[o]))
+        return refuse(o, "of ladder " + std::to_string(id) + " needs a temperature > 0: an exchange divides by it");
+    }
+    for (int p = 0; p + 1 < L; ++p) {
+      std::vector<int>& l = out.list[p & 1];
+      l.push_back(first + p); l.push_back(first); l.push_back(L);
+    }
+    closed.push_back(id);
+    first = end;
+  }
+  return CHG_OK;
+}
+
+// rung index as walker, walker 0 of every ladder marked as seen at the bottom
+std::vector<int> initial_xi(int B, const int* ladder) {
+  std::vector<int> xi((size_t)MC_XI * B, 0);
+  for (int o = 0, first = 0; o < B; ++o) {
+    if (ladder[o] < 0) continue;
+    if (o == 0 || ladder[o - 1] != ladder[o]) first = o;
+    xi[(size_t)MC_XI * o + MC_X_WALKER] = o - first;
+    if (o == first) xi[(size_t)MC_XI * o + MC_X_MARK] = MC_MARK_BOTTOM;
+  }
+  return xi;
+}
+
+void launch_exchange(chg_engine* eng, const McExchangeArgs& x, int grid) {
+  LaunchScope ls(eng, "mc_exchange");
+  hipLaunchKernelGGL(k_mc_exchange, dim3((unsigned)grid), dim3(256), 0, eng->stream, x);
+}
+
+void free_exchange(chg_mc* d) {
+  if (d->x_mem) hipFree(d->x_mem);
+  d->x_mem = nullptr; d->xi = nullptr; d->x_pairs[0] = d->x_pairs[1] = nullptr; d->x_npairs[0] = d->x_npairs[1] = 0;
+  d->ladder.clear();
+  d->x_interval = 0;
+}
+
+// exchange event m of the handle: the pairs of its parity, one workgroup each
+int exchange_event(chg_engine* eng, chg_mc* d, int m) {
+  const int q = (m - 1) & 1;
+  if (d->x_npairs[q] == 0) return CHG_OK;   // a batch of two-rung ladders has no pair on the odd parity
+  McExchangeArgs x{};
+  x.r = d->r; x.site = d->site; x.sd = d->sd; x.si = d->si; x.best_pos = d->best_pos; x.best_site = d->best_site;
+  x.temp = d->temp; x.seeds = d->seeds; x.aoff = d->d_aoff; x.xi = d->xi; x.pairs = d->x_pairs[q];
+  x.kB = d->p.kB > 0.0 ? d->p.kB : 8.6173303e-5; x.m = (unsigned)m;
+  launch_exchange(eng, x, d->x_npairs[q]);
+  if (hipGetLastError() != hipSuccess) { eng->err = "chg_mc_run: exchange kernel launch failed"; return CHG_EHIP; }
+  return CHG_OK;
+}
+
+// a later call's start, and what follows an exchange event: nothing is pending, propose from the current configuration
+int propose_only(chg_engine* eng, chg_mc* d) {
+  launch_step(eng, handle_args(eng, d, MC_PROPOSE), d->B);
+  if (hipGetLastError() != hipSuccess) { eng->err = "chg_mc_run: step kernel launch failed"; return CHG_EHIP; }
+  return copy_back(eng, "chg_mc_run", d, d->B, nullptr, nullptr);
+}
+
 }  // namespace
 
 extern "C" {
@@ -185,6 +285,12 @@ int chg_mc_create(chg_engine* eng, const chg_structs_host* h, const double* temp
   d->ring_trial.assign(std::max(d->K, 1), 0);
   d->task = CHG_TASK_E;
   d->r_atom = params->r_atom; d->r_bond = params->r_bond; d->numerical_tol = params->numerical_tol;
+  d->h_temp.assign(temperatures, temperatures + B);
+  d->h_fixed.assign(N, 0); d->h_swap_mask.assign(N, 1);
+  for (int i = 0; i < N; ++i) {
+    if (fixed) d->h_fixed[i] = fixed[i] ? 1 : 0;
+    if (swap_mask) d->h_swap_mask[i] = swap_mask[i] ? 1 : 0;
+  }
   int s = alloc_state(eng, fn, d, h, 0, [&](Carver& c) { carve_mc(d, c); });
   if (s != CHG_OK) { chg_mc_free(eng, d); return s; }
   // initial state on the host, one upload: cartesian positions frac . L, the cell and its inverse, site[] the identity
@@ -222,8 +328,76 @@ int chg_mc_create(chg_engine* eng, const chg_structs_host* h, const double* temp
 int chg_mc_set_temperatures(chg_engine* eng, chg_mc* d, const double* temperatures) {
   if (!eng || !d || !temperatures) return CHG_EINVAL;
   TRY(check_temperatures(eng, "chg_mc_set_temperatures", d->B, temperatures));
+  for (size_t o = 0; o < d->ladder.size(); ++o)
+    if (d->ladder[o] >= 0 && !(temperatures[o] > 0.0)) {
+      eng->err = "chg_mc_set_temperatures: replica " + std::to_string(o) + " of ladder " + std::to_string(d->ladder[o]) +
+                 " needs a temperature > 0: an exchange divides by it";
+      return CHG_EINVAL;
+    }
   HIP_TRY(eng, hipSetDevice(eng->device));
   HIP_TRY(eng, hipMemcpyAsync(d->temp, temperatures, sizeof(double) * (size_t)d->B, hipMemcpyHostToDevice, eng->stream));
+  HIP_TRY(eng, hipStreamSynchronize(eng->stream));
+  d->h_temp.assign(temperatures, temperatures + d->B);
+  return CHG_OK;
+}
+
+int chg_mc_set_exchange(chg_engine* eng, chg_mc* d, const int32_t* ladder, int32_t interval) {
+  if (!eng || !d || !ladder) return CHG_EINVAL;
+  const char* fn = "chg_mc_set_exchange";
+  const int B = d->B;
+  if (d->started) { eng->err = std::string(fn) + ": the ladders must be set before the handle's first chg_mc_run"; return CHG_EINVAL; }
+  if (interval < 0) { eng->err = std::string(fn) + ": interval must be >= 0 (0: no exchanges)"; return CHG_EINVAL; }
+  // nothing has run: the pinned staging still holds the structures as given
+  McPairs pairs;
+  TRY(build_pairs(eng, fn, B, d->h_aoff, ladder, d->h_temp.data(), pairs));
+  for (int o = 1; o < B; ++o) {
+    if (ladder[o] < 0 || ladder[o] != ladder[o - 1]) continue;
+    const int a0 = d->h_aoff[o - 1], b0 = d->h_aoff[o], n = d->h_aoff[o + 1] - b0;
+    const char* what = nullptr;
+    if (std::memcmp(d->h_z + a0, d->h_z + b0, sizeof(int) * n) != 0) what = "species in another order than";
+    else if (std::memcmp(d->h_lat + 9 * (size_t)(o - 1), d->h_lat + 9 * (size_t)o, sizeof(double) * 9) != 0) what = "another lattice than";
+    else if (std::memcmp(d->h_fixed.data() + a0, d->h_fixed.data() + b0, n) != 0) what = "other held atoms (fixed) than";
+    else if (std::memcmp(d->h_swap_mask.data() + a0, d->h_swap_mask.data() + b0, n) != 0) what = "another swap_mask than";
+    if (what) {
+      eng->err = std::string(fn) + ": replica " + std::to_string(o) + " has " + what + " replica " + std::to_string(o - 1) + " of ladder " +
+                 std::to_string(ladder[o]) + ": the rungs of a ladder exchange whole configurations";
+      return CHG_EINVAL;
+    }
+  }
+  HIP_TRY(eng, hipSetDevice(eng->device));
+  const std::vector<int> xi = initial_xi(B, ladder);
+  const size_t n0 = pairs.list[0].size(), n1 = pairs.list[1].size();
+  Carver sizer{nullptr};
+  sizer.take<int>(xi.size()); sizer.take<int>(n0); sizer.take<int>(n1);
+  char* mem = nullptr;
+  if (hipMalloc(&mem, sizer.pos) != hipSuccess) {
+    (void)hipGetLastError();
+    eng->err = std::string(fn) + ": exchange state of " + std::to_string(sizer.pos) + " bytes cannot be allocated";
+    return CHG_ENOMEM;
+  }
+  Carver c{mem};
+  int* d_xi = c.take<int>(xi.size());
+  int* d_p0 = c.take<int>(n0);
+  int* d_p1 = c.take<int>(n1);
+  StateUpload up{eng, fn};
+  up(d_xi, xi.data(), sizeof(int) * xi.size());
+  if (n0) up(d_p0, pairs.list[0].data(), sizeof(int) * n0);
+  if (n1) up(d_p1, pairs.list[1].data(), sizeof(int) * n1);
+  const int s = up.finish();
+  if (s != CHG_OK) { hipFree(mem); return s; }
+  free_exchange(d);   // a ladder set before
+  d->x_mem = mem; d->xi = d_xi; d->x_pairs[0] = d_p0; d->x_pairs[1] = d_p1;
+  d->x_npairs[0] = (int)(n0 / MC_PAIR_INTS); d->x_npairs[1] = (int)(n1 / MC_PAIR_INTS);
+  d->ladder.assign(ladder, ladder + B);
+  d->x_interval = interval;
+  return CHG_OK;
+}
+
+int chg_mc_download_exchange(chg_engine* eng, chg_mc* d, int32_t* xi) {
+  if (!eng || !d || !xi) return CHG_EINVAL;
+  if (!d->xi) { eng->err = "chg_mc_download_exchange: the handle has no ladder (chg_mc_set_exchange)"; return CHG_EINVAL; }
+  HIP_TRY(eng, hipSetDevice(eng->device));
+  TRY(d2h(eng, (int*)xi, (const int*)d->xi, (size_t)MC_XI * d->B));
   HIP_TRY(eng, hipStreamSynchronize(eng->stream));
   return CHG_OK;
 }
@@ -245,17 +419,21 @@ int chg_mc_run(chg_engine* eng, chg_mc* d, int32_t n_trials) {
     if (frame_due(d, 0)) set_frame(d, a, 0);
     TRY(evaluate_and_step(eng, d, a));
     d->started = true;
-  } else if (n_trials > 0) {   // a later call: nothing is pending, propose from the current configuration
-    launch_step(eng, handle_args(eng, d, MC_PROPOSE), d->B);
-    if (hipGetLastError() != hipSuccess) { eng->err = "chg_mc_run: step kernel launch failed"; return CHG_EHIP; }
-    TRY(copy_back(eng, "chg_mc_run", d, d->B, nullptr, nullptr));
+  } else if (n_trials > 0) {   // a later call
+    TRY(propose_only(eng, d));
   }
   for (int k = 0; k < n_trials; ++k) {
     const int next = d->trials + 1;
-    McStepArgs a = handle_args(eng, d, MC_ABSORB | (k + 1 < n_trials ? MC_PROPOSE : 0));
+    // an exchange event belongs to the trial it follows: the decision alone, the event, then the proposal from what the rungs hold now
+    const bool event = d->x_interval > 0 && next % d->x_interval == 0, more = k + 1 < n_trials;
+    McStepArgs a = handle_args(eng, d, MC_ABSORB | (more && !event ? MC_PROPOSE : 0));
     if (frame_due(d, next)) set_frame(d, a, next);
     TRY(evaluate_and_step(eng, d, a));
     d->trials = next;
+    if (event) {
+      TRY(exchange_event(eng, d, next / d->x_interval));
+      if (more) TRY(propose_only(eng, d));
+    }
   }
   if (eng->profiling) return collect_profile(eng);
   return CHG_OK;
@@ -303,6 +481,7 @@ int chg_mc_download(chg_engine* eng, chg_mc* d, const chg_mc_out_host* o) {
 int chg_mc_free(chg_engine* eng, chg_mc* d) {
   if (!d) return CHG_OK;
   release(eng, d);
+  free_exchange(d);
   delete d;
   return CHG_OK;
 }
@@ -373,6 +552,50 @@ int chg_test_mc_step(chg_engine* eng, const chg_mc_params* params, int32_t n_str
     if (frame) { a.fr.scal = (double*)bufs[FSCAL].d; a.fr.ints = (int*)bufs[FINT].d; a.fr.pos = (double*)bufs[FPOS].d; a.fr.site = (int*)bufs[FSITE].d; }
     a.final_try = final_try ? 1 : 0;
     launch_step(eng, a, (int)B);
+  });
+}
+
+int chg_test_mc_exchange(chg_engine* eng, int32_t n_struct, const int32_t* atom_off, const int32_t* ladder, const double* temperatures,
+                         const uint64_t* seeds, double kB, int32_t m, double* r, int32_t* site, double* sd, int32_t* si,
+                         double* best_positions, int32_t* best_site, int32_t* xi) {
+  if (!eng || n_struct <= 0 || !atom_off || !ladder || !temperatures || !seeds || m < 1 || !r || !site || !sd || !si || !best_positions ||
+      !best_site || !xi)
+    return CHG_EINVAL;
+  const char* fn = "chg_test_mc_exchange";
+  const size_t B = n_struct;
+  if (atom_off[0] != 0) return CHG_EINVAL;
+  for (size_t o = 0; o < B; ++o)
+    if (atom_off[o + 1] <= atom_off[o]) return CHG_EINVAL;
+  const size_t N = atom_off[n_struct];
+  McPairs pairs;
+  TRY(build_pairs(eng, fn, n_struct, atom_off, ladder, temperatures, pairs));
+  const std::vector<int>& list = pairs.list[(m - 1) & 1];
+  for (size_t k = 0; k < list.size(); k += MC_PAIR_INTS)   // the walker ids index the rows of their ladder
+    for (int o = list[k]; o <= list[k] + 1; ++o) {
+      const int w = xi[(size_t)MC_XI * o + MC_X_WALKER];
+      if (w < 0 || w >= list[k + 2]) { eng->err = std::string(fn) + ": replica " + std::to_string(o) + " holds a walker outside its ladder"; return CHG_EINVAL; }
+    }
+  if (list.empty()) return CHG_OK;   // no pair on this parity: nothing to launch
+  enum { R, SITE, SD, SI, BPOS, BSITE, TEMP, SEEDS, AOFF, XI, PAIRS, N_BUFS };
+  TestBuf bufs[N_BUFS];
+  bufs[R] = {r, r, sizeof(double) * 3 * N};
+  bufs[SITE] = {site, site, sizeof(int) * N};
+  bufs[SD] = {sd, sd, sizeof(double) * MC_SD * B};
+  bufs[SI] = {si, si, sizeof(int) * MC_SI * B};
+  bufs[BPOS] = {best_positions, best_positions, sizeof(double) * 3 * N};
+  bufs[BSITE] = {best_site, best_site, sizeof(int) * N};
+  bufs[TEMP] = {temperatures, nullptr, sizeof(double) * B};
+  bufs[SEEDS] = {seeds, nullptr, sizeof(uint64_t) * B};
+  bufs[AOFF] = {atom_off, nullptr, sizeof(int) * (B + 1)};
+  bufs[XI] = {xi, xi, sizeof(int) * MC_XI * B};
+  bufs[PAIRS] = {list.data(), nullptr, sizeof(int) * list.size()};
+  return run_test_step(eng, fn, bufs, [&] {
+    McExchangeArgs x{};
+    x.r = (double*)bufs[R].d; x.site = (int*)bufs[SITE].d; x.sd = (double*)bufs[SD].d; x.si = (const int*)bufs[SI].d;
+    x.best_pos = (double*)bufs[BPOS].d; x.best_site = (int*)bufs[BSITE].d; x.temp = (const double*)bufs[TEMP].d;
+    x.seeds = (const unsigned long long*)bufs[SEEDS].d; x.aoff = (const int*)bufs[AOFF].d; x.xi = (int*)bufs[XI].d;
+    x.pairs = (const int*)bufs[PAIRS].d; x.kB = kB > 0.0 ? kB : 8.6173303e-5; x.m = (unsigned)m;
+    launch_exchange(eng, x, (int)(list.size() / MC_PAIR_INTS));
   });
 }
 

@@ -12,6 +12,10 @@ Atoms keep their species: a swap exchanges the *positions* of two atoms of diffe
 the species permuted.  The random numbers are a pure function of (``seed``, trial number), so ``run(10); run(10)`` equals ``run(20)``.
 A replica whose trial energy is non-finite even on the engine's wide-range sweep stops with status ``NONFINITE``, its configuration
 and statistics untouched.
+
+``ParallelTempering`` (and ``run_batch(..., ladders=..., exchange_interval=...)``) adds replica exchange: the replicas of a tempering
+ladder exchange their configurations with their neighbours in temperature by a second kernel (csrc/kernels_mc_exchange.h), so the
+cold rungs leave the basin they started in.  DESIGN.md "Replica exchange" states the rule; tests/mc_exchange_ref.py restates it.
 """
 
 from __future__ import annotations
@@ -145,7 +149,8 @@ class _DeviceMC:
 
     RING = 32
 
-    def __init__(self, model, structures: list, temperatures, seeds, swap_z, fixed: list, cfg: dict) -> None:
+    def __init__(self, model, structures: list, temperatures, seeds, swap_z, fixed: list, cfg: dict, ladder=None,
+                 exchange_interval: int = 0) -> None:
         self.eng, self.model = model.engine, model
         conv = model.graph_converter
         self.prep = prep = self.eng.prepare_structures(structures)
@@ -169,6 +174,14 @@ class _DeviceMC:
             keys.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), swap_mask.ctypes.data_as(u8p), held.ctypes.data_as(u8p),
             ctypes.byref(params), ctypes.byref(self.handle)))
         self.trials = 0
+        self.ladder = None if ladder is None else np.ascontiguousarray(ladder, np.int32)
+        if self.ladder is not None:
+            try:
+                self.eng._check(self.eng.lib.chg_mc_set_exchange(self.eng.handle, self.handle, self.ladder.ctypes.data_as(_lib.c_int_p),
+                                                                 int(exchange_interval)))
+            except Exception:
+                self.free()
+                raise
 
     def free(self) -> None:
         if self.handle:
@@ -191,6 +204,9 @@ class _DeviceMC:
         o = _lib.fill_out(_lib.McOutHost(), d)
         o.frame_capacity = K
         self.eng._check(self.eng.lib.chg_mc_download(self.eng.handle, self.handle, ctypes.byref(o)))
+        d["xi"] = np.zeros((B, _lib.MC_EXCHANGE_INTS), np.int32)   # a handle without a ladder: nothing was ever exchanged
+        if self.ladder is not None:
+            self.eng._check(self.eng.lib.chg_mc_download_exchange(self.eng.handle, self.handle, d["xi"].ctypes.data_as(_lib.c_int_p)))
         return d
 
     def run(self, trials: int, sink) -> dict:
@@ -245,7 +261,11 @@ class _DeviceMC:
                 "energy": float(d["energy"][i]), "status": STATUS_NAMES[d["status"][i]], "n_trials": int(d["n_trials"][i]),
                 "counts": d["counts"][i].copy(), "sums": d["sums"][i].copy(), "temperature": float(d["temperatures"][i]),
                 "best": (float(d["best_energy"][i]), Structure(Lattice(structure.lattice.matrix.copy()), z.copy(), d["best_positions"][sl] @ inv)),
-                "best_site": d["best_site"][sl].copy()}
+                "best_site": d["best_site"][sl].copy(),
+                # replica exchange: the walker this rung holds, attempts and acceptances of the pair (this rung, the next one), and
+                # the round trips of the walker that started on this rung
+                "walker": int(d["xi"][i, 0]), "exchange_attempts": int(d["xi"][i, 1]), "exchange_accepts": int(d["xi"][i, 2]),
+                "round_trips": int(d["xi"][i, 4])}
 
 
 def _acceptance(counts) -> dict:
@@ -413,13 +433,25 @@ class MonteCarlo:
 
     # ------------------------------------------------------------------------------------------------------------------------
     @classmethod
-    def run_batch(cls, structures, trials: int, *, temperatures=300.0, seeds=None, fixed_atoms=None, model=None, **kwargs) -> list[dict]:
+    def run_batch(cls, structures, trials: int, *, temperatures=300.0, seeds=None, fixed_atoms=None, model=None, ladders=None,
+                  exchange_interval: int = 0, **kwargs) -> list[dict]:
         """Run R independent replicas (possibly of different sizes) as one device handle: each gets the chain it would get alone with
         ``MonteCarlo(structures[i], temperature=temperatures[i], seed=seeds[i], **kwargs).run(trials)``.  ``temperatures``: one number
         for all or one per replica; ``seeds=None`` numbers the replicas 0, 1, ...  Returns, per replica, ``{"trajectory",
         "final_structure", "species_on_sites", "site", "energy", "best", "acceptance", "mean_energy", "heat_capacity", "counts",
-        "status", "n_trials", "temperature"}``.  ``trajectory`` / ``logfile`` are not written here."""
+        "status", "n_trials", "temperature", "walker", "exchange_attempts", "exchange_accepts", "round_trips"}``.  ``trajectory`` /
+        ``logfile`` are not written here.
+
+        ``ladders`` (one id per replica; consecutive replicas with the same id >= 0 form a tempering ladder, -1 is never exchanged) with
+        ``exchange_interval`` K > 0 adds replica exchange: after every K-th trial neighbouring rungs of a ladder exchange their
+        configurations by the Metropolis rule on their current energies (DESIGN.md "Replica exchange").  A result is then that of a
+        *rung* -- a fixed temperature -- whatever configurations passed through it."""
         structures = list(structures)
+        exchange_interval = _number("exchange_interval", exchange_interval, low=0, integer=True)
+        if ladders is not None:
+            ladders = [_number(f"ladders[{i}]", v, low=-1, integer=True) for i, v in enumerate(ladders)]
+            if len(ladders) != len(structures):
+                raise ValueError(f"ladders needs one id per structure ({len(structures)})")
         if not structures:
             return []
         R = len(structures)
@@ -441,7 +473,7 @@ class MonteCarlo:
 
         report_isolated_atoms(first.model, [m._input for m in mc])
         run = _DeviceMC(first.model, [m._input for m in mc], [m.temperature for m in mc], [m.seed for m in mc], first.swap_z,
-                        [m._held for m in mc], first.cfg)
+                        [m._held for m in mc], first.cfg, ladder=ladders, exchange_interval=exchange_interval)
         try:
             d = run.run(trials, run.sink_into([m.traj for m in mc]))
         finally:
@@ -454,3 +486,169 @@ class MonteCarlo:
                        "heat_capacity": _heat_capacity(c, s, m.temperature) if c[4] > 0 and m.temperature > 0 else float("nan")})
             out.append(st)
         return out
+
+
+def temperature_ladder(t_min: float, t_max: float, n: int) -> np.ndarray:
+    """``n`` temperatures (K) from ``t_min`` to ``t_max`` in geometric progression: a constant ratio between neighbouring rungs gives
+    about the same exchange acceptance along the ladder where the heat capacity is flat."""
+    t_min = _number("t_min", t_min)
+    t_max = _number("t_max", t_max)
+    n = _number("n", n, low=2, integer=True)
+    if not 0.0 < t_min < t_max:
+        raise ValueError(f"a ladder needs 0 < t_min < t_max, got {t_min=} {t_max=}")
+    t = t_min * (t_max / t_min) ** (np.arange(n) / (n - 1))
+    t[0], t[-1] = t_min, t_max
+    return t
+
+
+class ParallelTempering:
+    """Replica-exchange Monte Carlo of one structure on the device: one rung per temperature of ``temperatures`` (K, all > 0), all rungs
+    one ``chg_mc`` handle that stays alive across ``run`` calls.  Every rung runs the canonical sampler of ``MonteCarlo``; after every
+    ``exchange_interval``-th trial neighbouring rungs exchange their configurations by the Metropolis rule on their current energies
+    (DESIGN.md "Replica exchange"), alternating between the pairs (0,1), (2,3), ... and (1,2), (3,4), ...  A rung keeps its temperature,
+    seed, statistics and best record; configurations (walkers) travel.  ``structure``: one structure for all rungs, or one starting
+    structure per rung with the same cell, species and atom order.  ``seeds=None`` numbers the rungs 0, 1, ...; the move parameters are
+    those of ``MonteCarlo`` and hold for every rung."""
+
+    def __init__(self, structure, temperatures, *, exchange_interval: int = 10, model=None, seeds=None, swap_species=None,
+                 swap_probability: float = 1.0, max_displacement: float = 0.1, fixed_atoms=None, loginterval: int = 1) -> None:
+        # everything is checked before a model is loaded or the device is touched
+        if isinstance(temperatures, (str, bytes)) or not hasattr(temperatures, "__iter__"):
+            raise TypeError(f"{temperatures=} must be a sequence of temperatures, one per rung")
+        temps = [_number(f"temperatures[{i}]", t) for i, t in enumerate(temperatures)]
+        if len(temps) < 2:
+            raise ValueError(f"a ladder needs at least two temperatures, got {len(temps)}")
+        for i, t in enumerate(temps):
+            if not t > 0.0:
+                raise ValueError(f"temperatures[{i}]={t!r} must be > 0: an exchange divides by it")
+        L = len(temps)
+        self.exchange_interval = _number("exchange_interval", exchange_interval, low=0, integer=True)
+        starts = [_as_structure(s) for s in structure] if isinstance(structure, (list, tuple)) else [_as_structure(structure)] * L
+        if len(starts) != L:
+            raise ValueError(f"{len(starts)} starting structures for {L} temperatures: give one structure or one per rung")
+        z0, cell0 = np.asarray(starts[0].atomic_numbers), np.asarray(starts[0].lattice.matrix)
+        for i, s in enumerate(starts[1:], 1):
+            if len(s) != len(starts[0]) or not np.array_equal(np.asarray(s.atomic_numbers), z0):
+                raise ValueError(f"the structure of rung {i} has other species, or the same in another order, than that of rung 0")
+            if not np.array_equal(np.asarray(s.lattice.matrix), cell0):
+                raise ValueError(f"the structure of rung {i} has another cell than that of rung 0")
+        seeds = list(range(L)) if seeds is None else list(seeds)
+        if len(seeds) != L:
+            raise ValueError(f"seeds needs one entry per rung ({L})")
+        self.temperatures = np.array(temps)
+        self._mc: list[MonteCarlo] = []
+        for s, t, sd in zip(starts, temps, seeds):   # MonteCarlo checks the rest; the first one loads the model when none is given
+            self._mc.append(MonteCarlo(s, model=model, temperature=t, seed=sd, swap_species=swap_species, swap_probability=swap_probability,
+                                       max_displacement=max_displacement, fixed_atoms=fixed_atoms, loginterval=loginterval))
+            model = self._mc[-1].model
+        self.model = model
+        self._run: _DeviceMC | None = None
+        self._rungs: list[dict] | None = None
+        self._base_counts = np.zeros((L, _lib.MC_COUNTS), np.int64)
+        self._base_sums = np.zeros((L, 2))
+        self._base_exchange = np.zeros((L, 3), np.int64)   # attempts, accepts, round trips
+
+    def __len__(self) -> int:
+        return len(self._mc)
+
+    def close(self) -> None:
+        if getattr(self, "_run", None) is not None:
+            self._run.free()
+            self._run = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001, S110
+            pass
+
+    def run(self, trials: int) -> list[MCTrajectory]:
+        """``trials`` more trials of every rung, exchange events included; returns one trajectory per rung (frames show a rung before the
+        event of their trial)."""
+        trials = _number("trials", trials, low=0, integer=True)
+        mc = self._mc
+        if self._run is None:
+            from chgnet_amd.calculator import report_isolated_atoms
+
+            report_isolated_atoms(self.model, [m._input for m in mc])
+            self._run = _DeviceMC(self.model, [m._input for m in mc], [m.temperature for m in mc], [m.seed for m in mc], mc[0].swap_z,
+                                  [m._held for m in mc], mc[0].cfg, ladder=[0] * len(mc), exchange_interval=self.exchange_interval)
+        d = self._run.run(trials, self._run.sink_into([m.traj for m in mc]))
+        self._rungs = [self._run.replica(d, i, m._input) for i, m in enumerate(mc)]
+        for i, st in enumerate(self._rungs):
+            st["trajectory"] = mc[i].traj
+            if st["status"] != "RUNNING":
+                print(f"ParallelTempering: rung {i} stopped at trial {st['n_trials']}: non-finite energy")
+        return [m.traj for m in mc]
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    def _need(self) -> list[dict]:
+        if self._rungs is None:
+            raise ValueError("nothing has run yet")
+        return self._rungs
+
+    @property
+    def rungs(self) -> list[dict]:
+        """Per rung, the dict ``MonteCarlo.run_batch`` returns (cumulative counts: ``reset_statistics`` does not touch them)."""
+        out = []
+        for st, m in zip(self._need(), self._mc):
+            c, s = st["counts"], st["sums"]
+            out.append({**st, "acceptance": _acceptance(c), "mean_energy": float(s[0] / c[4]) if c[4] > 0 else float("nan"),
+                        "heat_capacity": _heat_capacity(c, s, m.temperature) if c[4] > 0 else float("nan")})
+        return out
+
+    def _counts(self) -> np.ndarray:
+        return np.array([st["counts"] for st in self._need()]) - self._base_counts
+
+    def _sums(self) -> np.ndarray:
+        return np.array([st["sums"] for st in self._need()]) - self._base_sums
+
+    def _exchange(self) -> np.ndarray:
+        return np.array([[st["exchange_attempts"], st["exchange_accepts"], st["round_trips"]] for st in self._need()], np.int64) - self._base_exchange
+
+    @property
+    def exchange_acceptance(self) -> np.ndarray:
+        """Accepted fraction of the exchanges of every pair of neighbouring rungs, [L - 1]; ``nan`` where a pair was never tried."""
+        x = self._exchange()[:-1]
+        return np.array([a / n if n > 0 else np.nan for n, a in zip(x[:, 0].tolist(), x[:, 1].tolist())])
+
+    @property
+    def round_trips(self) -> np.ndarray:
+        """Completed bottom -> top -> bottom journeys per walker (the configuration lineage that started on rung w), [L]."""
+        return self._exchange()[:, 2].copy()
+
+    @property
+    def walkers(self) -> np.ndarray:
+        """The walker every rung holds now, [L]."""
+        return np.array([st["walker"] for st in self._need()])
+
+    @property
+    def mean_energies(self) -> np.ndarray:
+        """Mean of E_cur over the samples of every rung (eV), [L]."""
+        c, s = self._counts(), self._sums()
+        if (c[:, 4] <= 0).any():
+            raise ValueError("no samples yet")
+        return s[:, 0] / c[:, 4]
+
+    def heat_capacities(self) -> np.ndarray:
+        """``(<E^2> - <E>^2) / (kB T^2)`` per rung in eV/K, [L]."""
+        c, s = self._counts(), self._sums()
+        return np.array([_heat_capacity(c[i], s[i], float(t)) for i, t in enumerate(self.temperatures)])
+
+    @property
+    def acceptance(self) -> list[dict]:
+        """Accepted fraction per move kind and rung."""
+        return [_acceptance(c) for c in self._counts()]
+
+    @property
+    def best(self) -> tuple[float, Structure]:
+        """The lowest energy any rung has seen (eV) and its configuration."""
+        return min((st["best"] for st in self._need()), key=lambda b: b[0])
+
+    def reset_statistics(self) -> None:
+        """Start the counts, the sums, the exchange counts and the round trips afresh (equilibration): what has been downloaded so far
+        is remembered and subtracted; the device is not touched."""
+        if self._rungs is not None:
+            self._base_counts = np.array([st["counts"] for st in self._rungs])
+            self._base_sums = np.array([st["sums"] for st in self._rungs])
+            self._base_exchange = self._exchange() + self._base_exchange

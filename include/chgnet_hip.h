@@ -615,6 +615,28 @@ int chg_test_mc_step(chg_engine* eng, const chg_mc_params* params, int32_t n_str
                      int32_t final_try, int32_t intensive, double* r, int32_t* site, double* sd, int32_t* si, int64_t* counts,
                      double* best_positions, int32_t* best_site, const float* energy, double* frac_next, int32_t* retry,
                      double* frame_scalars, int32_t* frame_moves, double* frame_positions, int32_t* frame_site);
+/* Replica exchange (parallel tempering; DESIGN.md "Monte Carlo", part "Replica exchange"; tests/mc_exchange_ref.py restates it).
+ * ladder [B]: replicas that follow one another with the same id >= 0 form a tempering ladder, -1 is never exchanged.  A rung is a batch
+ * slot: it keeps its temperature, seed, stream, counters, sums and best record; an accepted exchange moves the configuration (positions,
+ * site[], E_cur) and its walker id between two neighbouring rungs.  With t the trials the handle has decided, exchange event m =
+ * t / interval follows the decisions of every trial with t % interval == 0, the last trial of a chg_mc_run call included, and pairs the
+ * rungs (p, p + 1) with p % 2 == (m - 1) & 1.  A pair with a member that is not CHG_MC_RUNNING is skipped.  Otherwise, a the lower
+ * and b the upper replica: accept iff D >= 0 or u < exp(D), D = (1/(kB T_a) - 1/(kB T_b)) (E_cur,a - E_cur,b), u the first uniform of
+ * Philox4x32-10(counter (m, 0, 0, 2), key seed_a).  interval 0 switches the events off.  The exchange state is an allocation of its
+ * own, freed by chg_mc_free.  CHG_EINVAL, naming the replica and changing nothing: an id that reappears after another one, a ladder of
+ * one replica, members that differ in atom count, species array, lattice (bit for bit), fixed or swap_mask, a member with T <= 0,
+ * interval < 0, a call after the handle's first chg_mc_run.  From then on chg_mc_set_temperatures refuses T <= 0 for ladder members. */
+#define CHG_MC_EXCHANGE_INTS 6 /* int32 per replica: walker held (ladder-local lineage id, the rung index at the start), exchange attempts and
+                                  acceptances of the pair (this rung, the next one) | mark (0 none, 1 bottom, 2 top) and completed
+                                  bottom -> top -> bottom round trips of walker w of the ladder at row first + w | spare                  */
+int chg_mc_set_exchange(chg_engine* eng, chg_mc* mc, const int32_t* ladder /*[B]*/, int32_t interval);
+int chg_mc_download_exchange(chg_engine* eng, chg_mc* mc, int32_t* xi /*[B,CHG_MC_EXCHANGE_INTS]*/);
+/* Tests only: exchange event m (>= 1) on caller-given state, in place, pair lists built by the host code of chg_mc_set_exchange (which
+ * here checks ids, ladder lengths, atom counts and T > 0).  r, site, sd, si, best_positions, best_site as in chg_test_mc_step; xi
+ * [B,CHG_MC_EXCHANGE_INTS]. */
+int chg_test_mc_exchange(chg_engine* eng, int32_t n_struct, const int32_t* atom_off, const int32_t* ladder, const double* temperatures,
+                         const uint64_t* seeds, double kB, int32_t m, double* r, int32_t* site, double* sd, int32_t* si,
+                         double* best_positions, int32_t* best_site, int32_t* xi);
 
 /* ---- exchange steps of the multi-GPU path, straight on RCCL (one communicator per process = per GPU) ----------
  * The reference is single-device; these carry what SURVEY 8e needs and nothing else: the all-gather of per-structure

@@ -6,6 +6,11 @@ alternate in one process, --repeats times each; one JSON line per leg, replica c
 (profiles/mc_probe.jsonl).  With --profile one more Monte Carlo run per replica count goes through the engine's profile counters
 (device time per label) to show where a trial's time outside the prediction goes.
 
+With --exchange-interval K the probe measures what replica exchange costs instead: every replica count R >= 2 runs as one tempering
+ladder (600 K to 1500 K, geometric) with an exchange event after every K-th trial (leg ``mc_exchange``), alternating in the same process
+with the same batch at the same temperatures without a ladder (leg ``mc``), --repeats times each, then one summary line per R with the
+range of both legs and of their run-by-run ratio.  Default output: profiles/mc_tempering_probe.jsonl.
+
 Weights: the trained-like golden set (tests/golden/weights_trained_like.npz).
 """
 
@@ -38,12 +43,15 @@ def main() -> None:
     ap.add_argument("--trials", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--profile", action="store_true")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "mc_probe.jsonl"))
+    ap.add_argument("--exchange-interval", type=int, default=0, help="K > 0: measure replica exchange every K trials against the same leg without")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(REPO, "profiles", "mc_tempering_probe.jsonl" if args.exchange_interval > 0 else "mc_probe.jsonl")
 
     from chgnet_amd import CHGNet, CHGNetCalculator
     from chgnet_amd.dynamics import MolecularDynamics
-    from chgnet_amd.montecarlo import MonteCarlo
+    from chgnet_amd.montecarlo import MonteCarlo, temperature_ladder
 
     W = dict(np.load(os.path.join(REPO, "tests", "golden", "weights_trained_like.npz")))
     lco = np.load(os.path.join(REPO, "tests", "golden", "case_li9co7o16.npz"))
@@ -64,12 +72,36 @@ def main() -> None:
         md_kw = dict(model=calc, ensemble="nvt", temperature=300.0, starting_temperature=300.0, timestep=2.0, loginterval=n)
         prep = eng.prepare_structures(cells)
 
-        def mc_leg():
+        def mc_leg(**extra_kw):
             t0 = time.perf_counter()
-            res = MonteCarlo.run_batch(cells, n, **mc_kw)
+            res = MonteCarlo.run_batch(cells, n, **{**mc_kw, **extra_kw})
             wall = time.perf_counter() - t0
             acc = [r["counts"][[1, 3]].sum() / n for r in res]
-            return wall, {"nonfinite": int(sum(r["status"] != "RUNNING" for r in res)), "acceptance_mean": float(np.mean(acc))}
+            out = {"nonfinite": int(sum(r["status"] != "RUNNING" for r in res)), "acceptance_mean": float(np.mean(acc))}
+            if extra_kw:
+                tried, took = sum(r["exchange_attempts"] for r in res), sum(r["exchange_accepts"] for r in res)
+                out.update(exchange_interval=args.exchange_interval, exchange_attempts=tried, exchange_accepts=took,
+                           round_trips=int(sum(r["round_trips"] for r in res)))
+            return wall, out
+
+        if args.exchange_interval > 0:   # the cost of exchanging: the same batch at the same temperatures with and without the ladder
+            if R < 2:
+                continue
+            mc_kw["temperatures"] = temperature_ladder(600.0, 1500.0, R).tolist()
+            ladder_kw = dict(ladders=[0] * R, exchange_interval=args.exchange_interval)
+            MonteCarlo.run_batch(cells, 5, **mc_kw)                               # warm-up: first builds, graph capture, both kernels
+            MonteCarlo.run_batch(cells, 5, **{**mc_kw, **ladder_kw, "exchange_interval": 1})
+            rates = {"mc": [], "mc_exchange": []}
+            for rep in range(args.repeats):
+                for name, kw in (("mc", {}), ("mc_exchange", ladder_kw)):
+                    wall, extra = mc_leg(**kw)
+                    rates[name].append(R * n / wall)
+                    emit(leg=name, replicas=R, repeat=rep, wall_s=wall, per_s=n / wall, replica_per_s=R * n / wall, **extra)
+            ratio = [x / p for x, p in zip(rates["mc_exchange"], rates["mc"])]
+            emit(leg="summary", replicas=R, exchange_interval=args.exchange_interval,
+                 mc_replica_per_s=[min(rates["mc"]), max(rates["mc"])], mc_exchange_replica_per_s=[min(rates["mc_exchange"]), max(rates["mc_exchange"])],
+                 ratio_run_by_run=[min(ratio), max(ratio)])
+            continue
 
         def ceiling_leg():
             t0 = time.perf_counter()
