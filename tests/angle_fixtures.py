@@ -27,10 +27,10 @@ def _from_cart(lattice, species, cart):
     return _structure(lattice, species, np.asarray(cart, np.float64) @ np.linalg.inv(lattice))
 
 
-def converter():
+def converter(r_atom: float = R_ATOM, r_bond: float = R_BOND):
     from chgnet_amd import CrystalGraphConverter
 
-    return CrystalGraphConverter(atom_graph_cutoff=R_ATOM, bond_graph_cutoff=R_BOND)
+    return CrystalGraphConverter(atom_graph_cutoff=r_atom, bond_graph_cutoff=r_bond)
 
 
 def shell_cluster(k: int, seed: int = 0):

@@ -27,10 +27,10 @@ def strained(g, dcart, w):
                                  lattice=lat @ (np.eye(3) + np.asarray(w, np.float64)))
 
 
-def first_derivatives(oracle, jobs, strains):
+def first_derivatives(oracle, jobs, strains, batch_size: int = 64):
     """(dE/dx [n,3], dE/deps [3,3]) of every strained graph in ``jobs`` (eps = its strain) in this parameterisation."""
     out = []
-    for p, w in zip(oracle.predict_graph(jobs, "efs", batch_size=64), strains):
+    for p, w in zip(oracle.predict_graph(jobs, "efs", batch_size=batch_size), strains):
         i_eps = np.eye(3) + np.asarray(w, np.float64)
         gx = -np.asarray(p["f"], np.float64) @ i_eps.T
         gs = np.asarray(p["s"], np.float64).reshape(3, 3) * np.linalg.det(np.asarray(jobs[len(out)].lattice)) / EV_A3_TO_GPA
@@ -38,7 +38,7 @@ def first_derivatives(oracle, jobs, strains):
     return out
 
 
-def fd_hvp_strain(oracle, graphs, directions, strains, delta: float = 1e-5):
+def fd_hvp_strain(oracle, graphs, directions, strains, delta: float = 1e-5, batch_size: int = 64):
     """[(hx [n,3], hs [3,3])] per graph: central differences along (u, W), scaled so that the largest of |u| and |W| is 1."""
     jobs, ws, scale = [], [], []
     for g, u, w in zip(graphs, directions, strains):
@@ -48,7 +48,7 @@ def fd_hvp_strain(oracle, graphs, directions, strains, delta: float = 1e-5):
         for h in (delta / s, -delta / s):
             jobs.append(strained(g, h * u, h * w))
             ws.append(h * w)
-    d = first_derivatives(oracle, jobs, ws)
+    d = first_derivatives(oracle, jobs, ws, batch_size)
     return [((d[2 * i][0] - d[2 * i + 1][0]) / (2 * delta) * scale[i], (d[2 * i][1] - d[2 * i + 1][1]) / (2 * delta) * scale[i])
             for i in range(len(graphs))]
 

@@ -23,6 +23,11 @@ Writes
                            make_grad_golden.py on the five cases in one batch (train mode, create_graph=True: the
                            reference's own double backward, trainer.py:399-411) -- pins the oracle's autograd for this
                            architecture, ``mlp_out`` biases included
+  batch_v020_low.npz       the batch-level switch of the BondConv biases (model.py:459 tests the BATCH's angle count): the pair,
+                           the trimer and the zigzag chain of tests/v020_fixtures.py predicted in ONE ``predict_graph`` call
+                           (``trio_*``: the zero-angle pair receives the biases) and the pair predicted alone (``alone_*``: it does
+                           not), e / f / s / m for both weight sets (``tl_`` prefix: trained-like).  ``--low-only`` writes this
+                           file alone, with the committed weight files.
 """
 
 from __future__ import annotations
@@ -74,11 +79,50 @@ def make_v020_model() -> RefCHGNet:
     return model
 
 
+def record_low_batch(model: RefCHGNet, model_tl: RefCHGNet) -> None:
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import v020_fixtures as vf
+
+    conv = RefConverter(atom_graph_cutoff=5, bond_graph_cutoff=3, algorithm="fast", on_isolated_atoms="ignore")
+    assert conv.algorithm == "fast"
+    ours = vf.converter()
+    trio = []
+    for s in vf.structure_groups()["low"]:
+        nl, arrays = neighbour_list(s, vf.R_ATOM, vf.R_BOND)
+        rg = conv(DuckStructure(s, nl))
+        g = ours(s)                                 # what the tests feed the oracle and the engine: the same graph
+        assert np.array_equal(rg.atom_graph.numpy(), g.atom_graph) and np.array_equal(rg.bond_graph.numpy().reshape(-1, 5), np.asarray(g.bond_graph).reshape(-1, 5))
+        assert np.array_equal(rg.atom_frac_coord.detach().numpy(), g.atom_frac_coord) and np.array_equal(rg.neighbor_image.numpy(), g.neighbor_image)
+        trio.append(rg)
+    assert len(trio[0].bond_graph) == 0 and sum(len(g.bond_graph) for g in trio) > 0
+    save = {"n_atoms": np.array([len(g.atomic_number) for g in trio]), "n_angles": np.array([len(g.bond_graph) for g in trio])}
+    for prefix, m in (("", model), ("tl_", model_tl)):
+        outs = m.predict_graph(trio, task="efsm", batch_size=len(trio))
+        alone = m.predict_graph(trio[0], task="efsm")
+        for k in ("e", "f", "s", "m"):
+            for i, o in enumerate(outs):
+                save[f"{prefix}trio_{i}_{k}"] = np.asarray(o[k], np.float32)
+            save[f"{prefix}alone_{k}"] = np.asarray(alone[k], np.float32)
+        print("low batch", prefix or "seed", "pair e in the trio", float(outs[0]["e"]), "alone", float(alone["e"]))
+    np.savez_compressed(os.path.join(HERE, "batch_v020_low.npz"), **save)
+
+
+def load_committed(fname: str) -> RefCHGNet:
+    model = RefCHGNet(**V020_ARGS)
+    model.load_state_dict({k: torch.tensor(v) for k, v in np.load(os.path.join(HERE, fname)).items()})
+    model.eval()
+    return model
+
+
 def main() -> None:
     torch.set_num_threads(1)
+    if "--low-only" in sys.argv[1:]:
+        record_low_batch(load_committed("weights_v020.npz"), load_committed("weights_v020_trained_like.npz"))
+        return
     model = make_v020_model()
     assert model.n_params == 403126, model.n_params
     model_tl = make_trained_like(make_v020_model())
+    record_low_batch(model, model_tl)
     for fname, m in (("weights_v020.npz", model), ("weights_v020_trained_like.npz", model_tl)):
         np.savez_compressed(os.path.join(HERE, fname), **{k: v.detach().numpy().copy() for k, v in m.state_dict().items()})
     conv = RefConverter(atom_graph_cutoff=5, bond_graph_cutoff=3, algorithm="fast", on_isolated_atoms="ignore")

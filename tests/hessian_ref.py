@@ -39,15 +39,16 @@ def displaced(g, dcart):
     return types.SimpleNamespace(**{k: getattr(g, k) for k in GRAPH_KEYS}, atom_frac_coord=frac, lattice=lat)
 
 
-def fd_hvp(oracle, graphs, directions, delta: float = 1e-5) -> list[np.ndarray]:
-    """H u ~ -(F(x + d u) - F(x - d u)) / (2 d) per graph, u scaled to a largest atom displacement of 1 (d in A)."""
+def fd_hvp(oracle, graphs, directions, delta: float = 1e-5, batch_size: int = 64) -> list[np.ndarray]:
+    """H u ~ -(F(x + d u) - F(x - d u)) / (2 d) per graph, u scaled to a largest atom displacement of 1 (d in A).  ``batch_size``: the
+    oracle's chunk (an architecture with ``mlp_out`` biases switches them per chunk: model.py:459)."""
     jobs, scale = [], []
     for g, u in zip(graphs, directions):
         u = np.asarray(u, np.float64)
         s = float(np.abs(u).max()) or 1.0
         scale.append(s)
         jobs += [displaced(g, delta * u / s), displaced(g, -delta * u / s)]
-    f = [np.asarray(p["f"], np.float64) for p in oracle.predict_graph(jobs, "ef", batch_size=64)]
+    f = [np.asarray(p["f"], np.float64) for p in oracle.predict_graph(jobs, "ef", batch_size=batch_size)]
     return [-(f[2 * i] - f[2 * i + 1]) / (2 * delta) * scale[i] for i in range(len(graphs))]
 
 
