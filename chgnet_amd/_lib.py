@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = (
     "chg_hessian_vector", "chg_hessian_vector_strain",
     "chg_relax_set_fixed", "chg_md_set_fixed", "chg_test_relax_step_fixed", "chg_test_lbfgs_step_fixed", "chg_test_md_step_fixed",
     "chg_md_set_observers", "chg_md_download_observables", "chg_test_md_observe",
+    "chg_md_set_transport", "chg_md_download_transport", "chg_test_md_transport",
     "chg_mc_create", "chg_mc_set_temperatures", "chg_mc_run", "chg_mc_download", "chg_mc_free", "chg_test_mc_step",
     "chg_mc_set_exchange", "chg_mc_download_exchange", "chg_test_mc_exchange",
 )
@@ -113,6 +114,16 @@ class MdObservablesHost(ctypes.Structure):
     _fields_ = [("msd", _dp), ("vacf", _dp), ("cnt", _ip), ("rdf", ctypes.POINTER(ctypes.c_uint64)), ("rdf_samples", _ip), ("vol_sum", _dp)]
 
 
+class MdTransportParams(ctypes.Structure):
+    _fields_ = [("collective", ctypes.c_int32), ("non_gaussian", ctypes.c_int32), ("vh_bins", ctypes.c_int32), ("vh_lags", ctypes.c_int32),
+                ("vh_stride", ctypes.c_int32), ("reserved", ctypes.c_int32), ("vh_rmax", ctypes.c_double)]
+
+
+class MdTransportHost(ctypes.Structure):
+    _dp, _ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
+    _fields_ = [("msd4", _dp), ("cmsd", _dp), ("jacf", _dp), ("vh", ctypes.POINTER(ctypes.c_uint64)), ("samples", _ip), ("vol_sum", _dp)]
+
+
 class McParams(ctypes.Structure):
     _fields_ = [("swap_probability", ctypes.c_double), ("max_displacement", ctypes.c_double), ("kB", ctypes.c_double),
                 ("loginterval", ctypes.c_int32), ("ring_frames", ctypes.c_int32), ("r_atom", ctypes.c_double), ("r_bond", ctypes.c_double),
@@ -131,6 +142,7 @@ MC_COUNTS, MC_FRAME_SCALARS, MC_FRAME_MOVES = 8, 6, 6   # include/chgnet_hip.h C
 MC_SD, MC_SI = 32, 8                                    # csrc/kernels_mc.h: state doubles and ints per replica (chg_test_mc_step)
 MC_EXCHANGE_INTS = 6                                    # include/chgnet_hip.h CHG_MC_EXCHANGE_INTS: walker, attempts, accepts, mark, trips, spare
 MD_OBS_MAX_LAGS, MD_OBS_MAX_SPECIES, MD_OBS_RDF_CELLS = 4096, 8, 16384   # csrc/kernels_md_obs.h
+MD_OBS_VH_CELLS = 4096                                                   # csrc/kernels_md_transport.h
 MD_NHC_STATE = 20   # include/chgnet_hip.h CHG_MD_NHC_STATE
 MD_VG = 9           # include/chgnet_hip.h CHG_MD_VG
 MD_CELL_MODES = {"flexible": 1, "axes": 2}   # CHG_MD_CELL_*
@@ -280,6 +292,11 @@ def load() -> ctypes.CDLL:
     lib.chg_md_download_observables.argtypes = [vp, vp, ctypes.POINTER(MdObservablesHost)]
     lib.chg_test_md_observe.argtypes = [vp, ctypes.POINTER(MdObserveParams), ctypes.c_int32, c_int_p, c_int_p, dp, ctypes.c_int32, dp, dp, dp,
                                         c_int_p, ctypes.POINTER(MdObservablesHost)]
+    lib.chg_md_set_transport.argtypes = [vp, vp, ctypes.POINTER(MdTransportParams)]
+    lib.chg_md_download_transport.argtypes = [vp, vp, ctypes.POINTER(MdTransportHost)]
+    lib.chg_test_md_transport.argtypes = [vp, ctypes.POINTER(MdObserveParams), ctypes.POINTER(MdTransportParams), ctypes.c_int32, c_int_p,
+                                          c_int_p, dp, ctypes.c_int32, dp, dp, dp, c_int_p, ctypes.POINTER(MdObservablesHost),
+                                          ctypes.POINTER(MdTransportHost)]
     # Monte Carlo: temperatures, seeds and the two per-atom masks travel beside the params struct
     lp = ctypes.POINTER(ctypes.c_int64)
     lib.chg_mc_create.argtypes = [vp, ctypes.POINTER(StructsHost), dp, u64p, u8p, u8p, ctypes.POINTER(McParams), ctypes.POINTER(vp)]

@@ -14,6 +14,16 @@
 
 #include "kernels_md.h"
 #include "kernels_md_obs.h"
+#include "kernels_md_transport.h"
+
+// chg_md_set_transport / chg_test_md_transport: parameters and one device allocation of its own (current ring and accumulators)
+struct MdTransport {
+  chg_md_transport_params p{};
+  char* mem = nullptr;
+  double *ring_j = nullptr, *msd4 = nullptr, *cmsd = nullptr, *jacf = nullptr, *vol_sum = nullptr;
+  unsigned long long* vh = nullptr;
+  long long* samples = nullptr;
+};
 
 // chg_md_set_observers / chg_test_md_observe: parameters, one device allocation of its own (ring, accumulators, and for a run the
 // private frame slot), and the number of samples taken
@@ -27,6 +37,7 @@ struct MdObservers {
   long long *cnt = nullptr, *rdf_samples = nullptr;
   unsigned long long* hist = nullptr;
   chg::MdFrame fr{};             // private frame slot: what the step kernels write of a completed step that is sampled but not logged
+  MdTransport* tr = nullptr;     // chg_md_set_transport: reads the ring above
 };
 
 // the chg_md_create* / chg_test_md_step* entry point that was called: it decides which ensembles may run (bad_params)
@@ -283,8 +294,15 @@ void carve_obs(MdObservers* x, Carver& c, bool frame_slot) {
   if (frame_slot) x->fr = carve_frame(c, B, N, false, false);
 }
 
+void free_transport(MdTransport* t) {
+  if (!t) return;
+  if (t->mem) hipFree(t->mem);
+  delete t;
+}
+
 void free_observers(MdObservers* x) {
   if (!x) return;
+  free_transport(x->tr);
   if (x->mem) hipFree(x->mem);
   delete x;
 }
@@ -331,6 +349,86 @@ int create_observers(chg_engine* eng, const char* fn, const chg_md_observe_param
   return CHG_OK;
 }
 
+// ---- transport accumulators on the observers' ring (kernels_md_transport.h)
+
+const char* bad_transport(const MdObservers* x, const chg_md_transport_params* t) {
+  if (!x || x->p.n_lags == 0) return "transport needs observers with n_lags > 0 (chg_md_set_observers)";
+  if (t->vh_bins < 0) return "vh_bins must be >= 0";
+  if (!t->collective && !t->non_gaussian && t->vh_bins == 0) return "nothing requested: collective, non_gaussian and vh_bins are all 0";
+  if (t->vh_bins > 0) {
+    if (!(t->vh_rmax > 0.0) || !std::isfinite(t->vh_rmax)) return "vh_rmax must be > 0 and finite";
+    if (t->vh_stride < 1) return "vh_stride must be >= 1";
+    if (t->vh_lags < 1) return "vh_lags must be >= 1";
+    if (((int64_t)t->vh_lags - 1) * t->vh_stride >= x->p.n_lags) return "(vh_lags - 1) * vh_stride must be < n_lags";
+    if ((int64_t)x->p.n_species * t->vh_bins > MD_OBS_VH_CELLS) return "n_species * vh_bins must be <= 4096 (the histogram lives in 16 KB of LDS)";
+  }
+  return nullptr;
+}
+
+void carve_transport(const MdObservers* x, MdTransport* t, Carver& c) {
+  const size_t B = x->B, L = x->p.n_lags, S = x->p.n_species;
+  const size_t cells = t->p.vh_bins > 0 ? B * t->p.vh_lags * S * t->p.vh_bins : 0;
+  t->ring_j = c.take<double>(t->p.collective ? L * B * S * 3 : 0);
+  t->msd4 = c.take<double>(t->p.non_gaussian ? B * L * S : 0);
+  t->cmsd = c.take<double>(t->p.collective ? B * L * S * S : 0);
+  t->jacf = c.take<double>(t->p.collective ? B * L * S * S : 0);
+  t->vh = c.take<unsigned long long>(cells);
+  t->samples = c.take<long long>(B);
+  t->vol_sum = c.take<double>(B);
+}
+
+// parameters checked against the observers they hang on, buffers allocated and zeroed (synchronised)
+int create_transport(chg_engine* eng, const char* fn, const MdObservers* x, const chg_md_transport_params* p, MdTransport** out) {
+  if (const char* bad = bad_transport(x, p)) { eng->err = std::string(fn) + ": " + bad; return CHG_EINVAL; }
+  MdTransport* t = new MdTransport();
+  t->p = *p;
+  if (t->p.vh_bins == 0) { t->p.vh_lags = 0; t->p.vh_stride = 1; t->p.vh_rmax = 0.0; }
+  Carver sizer{nullptr};
+  carve_transport(x, t, sizer);
+  if (hipMalloc(&t->mem, sizer.pos) != hipSuccess) {
+    (void)hipGetLastError();
+    t->mem = nullptr;
+    free_transport(t);
+    eng->err = std::string(fn) + ": transport accumulators of " + std::to_string(sizer.pos) + " bytes cannot be allocated";
+    return CHG_ENOMEM;
+  }
+  Carver carver{t->mem};
+  carve_transport(x, t, carver);
+  StateUpload up{eng, fn};
+  up.zero(t->mem, carver.pos);
+  const int s = up.finish();
+  if (s != CHG_OK) { free_transport(t); return s; }
+  *out = t;
+  return CHG_OK;
+}
+
+// the transport kernels of the sample k_md_obs_push has just put into the ring (a: the arguments of that launch)
+void observe_transport(chg_engine* eng, const MdObservers* x, const MdObsArgs& a, unsigned lags) {
+  const MdTransport* t = x->tr;
+  MdTransportArgs b{};
+  b.cell = a.cell; b.species = a.species; b.status = a.status; b.status_stride = a.status_stride; b.aoff = a.aoff;
+  b.N = a.N; b.B = a.B; b.S = a.S;
+  b.ring_pos = a.ring_pos; b.ring_vel = a.ring_vel; b.ring_com = a.ring_com; b.ring_j = t->ring_j; b.L = a.L; b.slot = a.slot; b.k = a.k;
+  b.subtract_com = a.subtract_com; b.collective = t->p.collective != 0; b.non_gaussian = t->p.non_gaussian != 0;
+  b.msd4 = t->msd4; b.cmsd = t->cmsd; b.jacf = t->jacf; b.vh = t->vh; b.samples = t->samples; b.vol_sum = t->vol_sum;
+  b.vh_bins = t->p.vh_bins; b.vh_lags = t->p.vh_lags; b.vh_stride = t->p.vh_stride; b.vh_rmax = t->p.vh_rmax;
+  hipLaunchKernelGGL(k_md_obs_current, dim3((unsigned)x->B), dim3(256), 0, eng->stream, b);
+  hipLaunchKernelGGL(k_md_obs_transport, dim3(lags, (unsigned)x->B), dim3(256), 0, eng->stream, b);
+}
+
+int download_transport(chg_engine* eng, const MdObservers* x, const chg_md_transport_host* o) {
+  const MdTransport* t = x->tr;
+  const size_t B = x->B, L = x->p.n_lags, S = x->p.n_species;
+  TRY(d2h(eng, o->msd4, t->msd4, t->p.non_gaussian ? B * L * S : 0));
+  TRY(d2h(eng, o->cmsd, t->cmsd, t->p.collective ? B * L * S * S : 0));
+  TRY(d2h(eng, o->jacf, t->jacf, t->p.collective ? B * L * S * S : 0));
+  TRY(d2h(eng, (unsigned long long*)o->vh, t->vh, t->p.vh_bins > 0 ? B * t->p.vh_lags * S * t->p.vh_bins : 0));
+  TRY(d2h(eng, (long long*)o->samples, t->samples, B));
+  TRY(d2h(eng, o->vol_sum, t->vol_sum, B));
+  HIP_TRY(eng, hipStreamSynchronize(eng->stream));
+  return CHG_OK;
+}
+
 // one sample: the snapshot of a completed step through the ring and the accumulators (enqueued on the engine's stream)
 int observe(chg_engine* eng, const char* fn, MdObservers* x, const double* pos, const double* mom, const double* cell, const double* mass,
             const int* status, int status_stride, const int* d_aoff) {
@@ -347,6 +445,7 @@ int observe(chg_engine* eng, const char* fn, MdObservers* x, const double* pos, 
     const unsigned lags = (unsigned)std::min<long long>(x->k, p.n_lags - 1) + 1;
     hipLaunchKernelGGL(k_md_obs_push, dim3((unsigned)x->B), dim3(256), 0, eng->stream, a);
     hipLaunchKernelGGL(k_md_obs_corr, dim3(lags, (unsigned)x->B), dim3(256), 0, eng->stream, a);
+    if (x->tr) observe_transport(eng, x, a, lags);
   }
   if (p.rdf_bins > 0) {
     const unsigned chunks = (unsigned)((x->n_max + MD_OBS_RDF_ROWS - 1) / MD_OBS_RDF_ROWS);
@@ -443,6 +542,25 @@ int chg_md_set_observers(chg_engine* eng, chg_md* d, const chg_md_observe_params
   free_observers(d->obs);
   d->obs = x;
   return CHG_OK;
+}
+
+int chg_md_set_transport(chg_engine* eng, chg_md* d, const chg_md_transport_params* params) {
+  if (!eng || !d || !params) return CHG_EINVAL;
+  const char* fn = "chg_md_set_transport";
+  if (d->started) { eng->err = std::string(fn) + ": the run has already started"; return CHG_EINVAL; }
+  HIP_TRY(eng, hipSetDevice(eng->device));
+  MdTransport* t = nullptr;
+  TRY(create_transport(eng, fn, d->obs, params, &t));
+  free_transport(d->obs->tr);
+  d->obs->tr = t;
+  return CHG_OK;
+}
+
+int chg_md_download_transport(chg_engine* eng, chg_md* d, const chg_md_transport_host* o) {
+  if (!eng || !d || !o) return CHG_EINVAL;
+  if (!d->obs || !d->obs->tr) { eng->err = "chg_md_download_transport: the handle has no transport accumulators (chg_md_set_transport)"; return CHG_EINVAL; }
+  HIP_TRY(eng, hipSetDevice(eng->device));
+  return download_transport(eng, d->obs, o);
 }
 
 int chg_md_download_observables(chg_engine* eng, chg_md* d, const chg_md_observables_host* o) {
@@ -681,14 +799,16 @@ int chg_test_md_step_fixed(chg_engine* eng, const chg_md_params* params, int32_t
 
 }  // extern "C"
 
-extern "C" int chg_test_md_observe(chg_engine* eng, const chg_md_observe_params* params, int32_t n_struct, const int32_t* atom_off,
-                                   const int32_t* species, const double* masses, int32_t n_samples, const double* positions,
-                                   const double* momenta, const double* cell, const int32_t* status,
-                                   const chg_md_observables_host* out) {
+namespace {
+
+// chg_test_md_observe / chg_test_md_transport: caller-given snapshots through observe(), then the downloads that were asked for
+int test_observe(chg_engine* eng, const char* fn, const chg_md_observe_params* params, const chg_md_transport_params* transport,
+                 int32_t n_struct, const int32_t* atom_off, const int32_t* species, const double* masses, int32_t n_samples,
+                 const double* positions, const double* momenta, const double* cell, const int32_t* status,
+                 const chg_md_observables_host* out, const chg_md_transport_host* tout) {
   using namespace chgh;
-  if (!eng || !params || n_struct <= 0 || !atom_off || !species || !masses || n_samples < 1 || !positions || !momenta || !cell || !status || !out)
+  if (!eng || !params || n_struct <= 0 || !atom_off || !species || !masses || n_samples < 1 || !positions || !momenta || !cell || !status)
     return CHG_EINVAL;
-  const char* fn = "chg_test_md_observe";
   const size_t B = n_struct, T = n_samples;
   if (atom_off[0] != 0) return CHG_EINVAL;
   for (size_t o = 0; o < B; ++o)
@@ -697,6 +817,10 @@ extern "C" int chg_test_md_observe(chg_engine* eng, const chg_md_observe_params*
   HIP_TRY(eng, hipSetDevice(eng->device));
   MdObservers* x = nullptr;
   TRY(create_observers(eng, fn, params, n_struct, atom_off, species, false, &x));
+  if (transport) {
+    const int s = create_transport(eng, fn, x, transport, &x->tr);
+    if (s != CHG_OK) { free_observers(x); return s; }
+  }
   TestBuf bufs[] = {{positions, nullptr, sizeof(double) * T * 3 * N}, {momenta, nullptr, sizeof(double) * T * 3 * N},
                     {cell, nullptr, sizeof(double) * T * 9 * B}, {status, nullptr, sizeof(int) * T * B}, {masses, nullptr, sizeof(double) * N},
                     {atom_off, nullptr, sizeof(int) * (B + 1)}};
@@ -707,7 +831,28 @@ extern "C" int chg_test_md_observe(chg_engine* eng, const chg_md_observe_params*
                    (const double*)bufs[4].d, (const int*)bufs[3].d + t * B, 1, (const int*)bufs[5].d);
   });
   if (s == CHG_OK) s = rc;
-  if (s == CHG_OK) s = download_observables(eng, x, out);
+  if (s == CHG_OK && out) s = download_observables(eng, x, out);
+  if (s == CHG_OK && tout) s = download_transport(eng, x, tout);
   free_observers(x);
   return s;
+}
+
+}  // namespace
+
+extern "C" int chg_test_md_observe(chg_engine* eng, const chg_md_observe_params* params, int32_t n_struct, const int32_t* atom_off,
+                                   const int32_t* species, const double* masses, int32_t n_samples, const double* positions,
+                                   const double* momenta, const double* cell, const int32_t* status,
+                                   const chg_md_observables_host* out) {
+  if (!out) return CHG_EINVAL;
+  return test_observe(eng, "chg_test_md_observe", params, nullptr, n_struct, atom_off, species, masses, n_samples, positions, momenta, cell,
+                      status, out, nullptr);
+}
+
+extern "C" int chg_test_md_transport(chg_engine* eng, const chg_md_observe_params* params, const chg_md_transport_params* transport,
+                                     int32_t n_struct, const int32_t* atom_off, const int32_t* species, const double* masses,
+                                     int32_t n_samples, const double* positions, const double* momenta, const double* cell,
+                                     const int32_t* status, const chg_md_observables_host* plain, const chg_md_transport_host* out) {
+  if (!transport || !out) return CHG_EINVAL;
+  return test_observe(eng, "chg_test_md_transport", params, transport, n_struct, atom_off, species, masses, n_samples, positions, momenta,
+                      cell, status, plain, out);
 }

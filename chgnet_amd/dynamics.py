@@ -53,7 +53,9 @@ except in NVE.
 Observables (DESIGN.md "MD observables"): ``observers=MDObservers(...)`` (chgnet_amd/observables.py) accumulates the mean-squared
 displacement and velocity autocorrelation per species and the pair histogram of the radial distribution function on the device
 while the run goes on, whatever ``loginterval`` is; ``md.observables`` (``"observables"`` in the results of ``run_batch``) downloads
-the sums as an ``MDObservables``.  ``set_atoms`` opens a new handle and so starts them from zero.  Without observers nothing changes.
+the sums as an ``MDObservables``.  ``set_atoms`` opens a new handle and so starts them from zero.  Without observers nothing changes.  The transport options of
+``MDObservers`` (``collective``, ``non_gaussian``, ``vanhove_bins``) travel with the same object: ionic conductivity, Haven ratio,
+non-Gaussian parameter and the self part of the van Hove function come out of the same ``MDObservables``.
 
 Out of scope, refused with ``ValueError``: ``thermostat="Nose-Hoover"`` (ASE ``NPT``; use ``"Nose-Hoover-Chain"``), and NPT with a
 Berendsen barostat without ``bulk_modulus`` (the reference then fits an equation of state).  Deviations from the reference:
@@ -79,6 +81,7 @@ from chgnet_amd.calculator import (CHGNetCalculator, atoms_to_structure, check_f
 from chgnet_amd.graph.structure import Lattice, Structure
 from chgnet_amd.observables import MDObservables, MDObservers
 from chgnet_amd.observables import download as download_observables
+from chgnet_amd.observables import download_transport
 
 # ase.units (CODATA 2014)
 _E, _AMU, _KB_J = 1.6021766208e-19, 1.660539040e-27, 1.38064852e-23
@@ -263,15 +266,19 @@ class _DeviceRun:
         if observers is not None:        # species: the sorted unique atomic numbers of the batch
             try:
                 self.species, self.species_index = observers.species_map(prep.z)
+                tp = observers.transport_params(len(self.species))
             except ValueError:
                 self.free()
                 raise
             op = observers.params(len(self.species))
             rc = self.eng.lib.chg_md_set_observers(self.eng.handle, self.handle, ctypes.byref(op),
                                                    self.species_index.ctypes.data_as(_lib.c_int_p))
+            if rc == 0 and tp is not None:   # transport accumulators on the observers' ring; without them the call is never made
+                rc = self.eng.lib.chg_md_set_transport(self.eng.handle, self.handle, ctypes.byref(tp))
             if rc != 0:
                 self.free()
                 self.eng._check(rc)
+            self.transport = tp is not None
             self.sample_dt_fs = observers.sample_interval * cfg["dt"] / FS
         self.chain_length = int(cfg["chain_length"]) if self.nhc else 0
         self.started = False
@@ -308,8 +315,11 @@ class _DeviceRun:
         """The observers' sums as they stand, one ``MDObservables`` per replica (nothing is reset on the device)."""
         ob = self.observers
         d = download_observables(self.eng, self.handle, self.B, ob.msd_lags, len(self.species), ob.rdf_bins)
+        t = (download_transport(self.eng, self.handle, self.B, ob.msd_lags, len(self.species), ob.vanhove_lags, ob.vanhove_bins)
+             if self.transport else None)
         off = self.prep.atom_off
-        return [MDObservables.from_download(d, i, self.species, self.species_index[off[i]:off[i + 1]], self.sample_dt_fs, ob.rdf_rmax)
+        return [MDObservables.from_download(d, i, self.species, self.species_index[off[i]:off[i + 1]], self.sample_dt_fs, ob.rdf_rmax,
+                                            transport=t, observers=ob)
                 for i in range(self.B)]
 
     def thermostat_state(self, d: dict, i: int) -> dict | None:

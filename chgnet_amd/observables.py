@@ -11,6 +11,12 @@ its species: every sample is a time origin.  Positions are the unwrapped ones of
 keeps its displacement; with ``subtract_com`` they are taken relative to the replica's mass-weighted centre of mass.  With
 ``rdf_bins`` every sample adds all ordered pairs and lattice images closer than ``rdf_rmax`` to a histogram per species pair.
 
+Transport (``collective``, ``non_gaussian``, ``vanhove_bins``; csrc/kernels_md_transport.h) rides on the same ring and needs
+``msd_lags > 0``: for every lag the fourth moment of the displacement per species (the non-Gaussian parameter), the collective
+displacement ``U_a = sum_{i in a} u_i`` and current ``J_a = sum_{i in a} v_i`` of every species correlated with every other (ionic
+conductivity in its Einstein form with the Onsager cross terms, against the Nernst-Einstein estimate from the tracer MSD: the Haven
+ratio), and the histogram of ``|u_i|`` per species at every ``vanhove_stride``-th lag (the self part of the van Hove function).
+
 ``MDObservables`` is plain NumPy on the raw sums (which stay available as attributes), so its arithmetic runs without a device.
 """
 
@@ -23,19 +29,29 @@ import numpy as np
 from chgnet_amd import _lib
 
 # ase.units (CODATA 2014), as chgnet_amd.dynamics: one ASE time unit in fs
-_E, _AMU = 1.6021766208e-19, 1.660539040e-27
+_E, _AMU, _KB_J = 1.6021766208e-19, 1.660539040e-27, 1.38064852e-23
 _FS = 1e-15 * (1e10 * np.sqrt(_E / _AMU))
+_KB = _KB_J / _E                       # eV/K, the value of chgnet_amd.dynamics
+# 1 e^2 / (A fs eV) in S/cm: e / V is e coulomb per volt, an angstrom-femtosecond is 1e-25 m s, and 1 S/m is 0.01 S/cm
+_E2_PER_A_FS_EV_IN_S_PER_CM = _E / (1e-10 * 1e-15) * 1e-2
 
 
 class MDObservers:
     """What a run accumulates.  ``msd_lags``: lags of the MSD / VACF (0: none, at most 4096), in units of ``sample_interval`` steps;
     ``rdf_rmax`` (A) and ``rdf_bins``: the pair histogram (``rdf_bins=0``: none); ``subtract_com``: displacements relative to the
     centre of mass.  ``n_species**2 * rdf_bins`` may not exceed 16384 and a batch may not hold more than 8 species: both are checked
-    when the species are known (``species_map``)."""
+    when the species are known (``species_map``).
+
+    Transport, all off by default and each needing ``msd_lags > 0``: ``collective``: the species-by-species correlations of the summed
+    displacements and currents (ionic conductivity); ``non_gaussian``: the fourth moment of the displacement; ``vanhove_bins`` bins
+    up to ``vanhove_rmax`` (A) of ``|u_i|`` per species at lags 0, ``vanhove_stride``, ..., ``(vanhove_lags - 1) * vanhove_stride``
+    (``vanhove_lags=None``: as many as fit ``msd_lags``).  ``n_species * vanhove_bins`` may not exceed 4096 (``transport_params``)."""
 
     def __init__(self, sample_interval: int = 1, msd_lags: int = 0, rdf_rmax: float | None = None, rdf_bins: int = 0,
-                 subtract_com: bool = True) -> None:
-        for name, v in (("sample_interval", sample_interval), ("msd_lags", msd_lags), ("rdf_bins", rdf_bins)):
+                 subtract_com: bool = True, collective: bool = False, non_gaussian: bool = False, vanhove_bins: int = 0,
+                 vanhove_rmax: float | None = None, vanhove_lags: int | None = None, vanhove_stride: int = 1) -> None:
+        for name, v in (("sample_interval", sample_interval), ("msd_lags", msd_lags), ("rdf_bins", rdf_bins), ("vanhove_bins", vanhove_bins),
+                        ("vanhove_stride", vanhove_stride), *((("vanhove_lags", vanhove_lags),) if vanhove_lags is not None else ())):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
                 raise ValueError(f"{name}={v!r} must be an integer")
         if sample_interval < 1:
@@ -55,6 +71,32 @@ class MDObservers:
         self.sample_interval, self.msd_lags, self.rdf_bins = int(sample_interval), int(msd_lags), int(rdf_bins)
         self.rdf_rmax = float(rdf_rmax) if rdf_bins > 0 else 0.0
         self.subtract_com = bool(subtract_com)
+        # transport
+        if vanhove_bins < 0:
+            raise ValueError(f"{vanhove_bins=} must be >= 0")
+        for name, on in (("collective", collective), ("non_gaussian", non_gaussian), ("vanhove_bins", vanhove_bins)):
+            if on and msd_lags == 0:
+                raise ValueError(f"{name} needs msd_lags > 0: it is a correlation over the ring of samples")
+        if vanhove_bins > _lib.MD_OBS_VH_CELLS:
+            raise ValueError(f"{vanhove_bins=} exceeds the {_lib.MD_OBS_VH_CELLS} van Hove cells of the device")
+        if vanhove_bins > 0 and (vanhove_rmax is None or not np.isfinite(vanhove_rmax) or not vanhove_rmax > 0):
+            raise ValueError(f"{vanhove_rmax=} must be > 0 and finite when vanhove_bins > 0")
+        if vanhove_bins == 0 and (vanhove_rmax is not None or vanhove_lags is not None or vanhove_stride != 1):
+            raise ValueError("vanhove_rmax, vanhove_lags and vanhove_stride need vanhove_bins > 0")
+        if vanhove_stride < 1:
+            raise ValueError(f"{vanhove_stride=} must be >= 1")
+        if vanhove_lags is not None and vanhove_lags < 1:
+            raise ValueError(f"{vanhove_lags=} must be >= 1")
+        if vanhove_bins > 0:
+            if vanhove_lags is None:
+                vanhove_lags = (msd_lags - 1) // vanhove_stride + 1
+            if (vanhove_lags - 1) * vanhove_stride >= msd_lags:
+                raise ValueError(f"lag (vanhove_lags - 1) * vanhove_stride = {(vanhove_lags - 1) * vanhove_stride} is not among the "
+                                 f"{msd_lags=} lags of the ring")
+        self.collective, self.non_gaussian, self.vanhove_bins = bool(collective), bool(non_gaussian), int(vanhove_bins)
+        self.vanhove_rmax = float(vanhove_rmax) if vanhove_bins > 0 else 0.0
+        self.vanhove_lags = int(vanhove_lags) if vanhove_bins > 0 else 0
+        self.vanhove_stride = int(vanhove_stride)
 
     def species_map(self, atomic_numbers) -> tuple[np.ndarray, np.ndarray]:
         """(species, index): the sorted unique atomic numbers of the batch and every atom's index into them."""
@@ -69,6 +111,16 @@ class MDObservers:
     def params(self, n_species: int) -> _lib.MdObserveParams:
         return _lib.MdObserveParams(sample_interval=self.sample_interval, n_lags=self.msd_lags, subtract_com=int(self.subtract_com),
                                     n_species=int(n_species), rdf_bins=self.rdf_bins, reserved=0, rdf_rmax=self.rdf_rmax)
+
+    def transport_params(self, n_species: int) -> _lib.MdTransportParams | None:
+        """What ``chg_md_set_transport`` is given; ``None`` when no transport was asked for (and then it is never called)."""
+        if not (self.collective or self.non_gaussian or self.vanhove_bins):
+            return None
+        if n_species * self.vanhove_bins > _lib.MD_OBS_VH_CELLS:
+            raise ValueError(f"{n_species} species x vanhove_bins={self.vanhove_bins} exceeds the {_lib.MD_OBS_VH_CELLS} van Hove cells "
+                             "of the device: use fewer bins")
+        return _lib.MdTransportParams(collective=int(self.collective), non_gaussian=int(self.non_gaussian), vh_bins=self.vanhove_bins,
+                                      vh_lags=self.vanhove_lags, vh_stride=self.vanhove_stride, reserved=0, vh_rmax=self.vanhove_rmax)
 
 
 def empty_arrays(B: int, L: int, S: int, bins: int) -> dict:
@@ -85,15 +137,35 @@ def download(eng, handle, B: int, L: int, S: int, bins: int) -> dict:
     return d
 
 
+def empty_transport_arrays(B: int, L: int, S: int, vh_lags: int, vh_bins: int) -> dict:
+    """Host arrays named like the fields of ``chg_md_transport_host``."""
+    return {"msd4": np.zeros((B, L, S)), "cmsd": np.zeros((B, L, S, S)), "jacf": np.zeros((B, L, S, S)),
+            "vh": np.zeros((B, vh_lags, S, vh_bins), np.uint64), "samples": np.zeros(B, np.int64), "vol_sum": np.zeros(B)}
+
+
+def download_transport(eng, handle, B: int, L: int, S: int, vh_lags: int, vh_bins: int) -> dict:
+    """``chg_md_download_transport`` of a device handle: the raw transport sums of all B replicas (zeros where none were requested)."""
+    d = empty_transport_arrays(B, L, S, vh_lags, vh_bins)
+    out = _lib.fill_out(_lib.MdTransportHost(), d)
+    eng._check(eng.lib.chg_md_download_transport(eng.handle, handle, ctypes.byref(out)))
+    return d
+
+
 class MDObservables:
     """The observables of ONE replica from its raw sums.
 
     ``species``: atomic numbers [S]; ``n_per_species`` [S]: atoms of each in the replica; ``sample_dt_fs``: time between two samples;
     ``msd_sum`` / ``vacf_sum`` [L, S] and ``cnt`` [L]; ``rdf_hist`` [S, S, bins], ``rdf_samples``, ``vol_sum`` and ``rdf_rmax``.
-    Species are addressed by atomic number."""
+    Species are addressed by atomic number.
+
+    Transport (optional keywords): ``msd4_sum`` [L, S]; ``cmsd_sum`` / ``jacf_sum`` [L, S, S]; ``vanhove_hist`` [vanhove_lags, S, bins]
+    with ``vanhove_rmax`` and ``vanhove_stride``; ``transport_samples`` and ``transport_vol_sum`` (the mean volume is their quotient).
+    ``cnt`` normalises them as it does the MSD."""
 
     def __init__(self, species, n_per_species, sample_dt_fs: float, msd_sum=None, vacf_sum=None, cnt=None, rdf_hist=None,
-                 rdf_samples: int = 0, vol_sum: float = 0.0, rdf_rmax: float = 0.0) -> None:
+                 rdf_samples: int = 0, vol_sum: float = 0.0, rdf_rmax: float = 0.0, msd4_sum=None, cmsd_sum=None, jacf_sum=None,
+                 vanhove_hist=None, vanhove_rmax: float = 0.0, vanhove_stride: int = 1, transport_samples: int = 0,
+                 transport_vol_sum: float = 0.0) -> None:
         self.species = np.asarray(species, np.int64)
         self.n_per_species = np.asarray(n_per_species, np.int64)
         S = len(self.species)
@@ -107,13 +179,40 @@ class MDObservables:
         if self.msd_sum.shape != self.vacf_sum.shape or self.msd_sum.shape != (len(self.cnt), S) or self.rdf_hist.shape[:2] != (S, S):
             raise ValueError("the raw arrays do not have the shapes [L, S], [L, S], [L] and [S, S, bins]")
         self.rdf_samples, self.vol_sum, self.rdf_rmax = int(rdf_samples), float(vol_sum), float(rdf_rmax)
+        L = len(self.cnt)
+        self.msd4_sum = None if msd4_sum is None else np.asarray(msd4_sum, np.float64)
+        self.cmsd_sum = None if cmsd_sum is None else np.asarray(cmsd_sum, np.float64)
+        self.jacf_sum = None if jacf_sum is None else np.asarray(jacf_sum, np.float64)
+        self.vanhove_hist = None if vanhove_hist is None else np.asarray(vanhove_hist, np.uint64)
+        if self.msd4_sum is not None and self.msd4_sum.shape != (L, S):
+            raise ValueError("msd4_sum does not have the shape [L, S]")
+        for name, x in (("cmsd_sum", self.cmsd_sum), ("jacf_sum", self.jacf_sum)):
+            if x is not None and x.shape != (L, S, S):
+                raise ValueError(f"{name} does not have the shape [L, S, S]")
+        self.vanhove_rmax, self.vanhove_stride = float(vanhove_rmax), int(vanhove_stride)
+        if self.vanhove_hist is not None:
+            if self.vanhove_hist.ndim != 3 or self.vanhove_hist.shape[1] != S:
+                raise ValueError("vanhove_hist does not have the shape [vanhove_lags, S, bins]")
+            if self.vanhove_stride < 1 or (len(self.vanhove_hist) - 1) * self.vanhove_stride >= max(L, 1) or not self.vanhove_rmax > 0:
+                raise ValueError("vanhove_hist needs vanhove_rmax > 0 and lags (vanhove_lags - 1) * vanhove_stride among those of cnt")
+        self.transport_samples, self.transport_vol_sum = int(transport_samples), float(transport_vol_sum)
 
     @classmethod
-    def from_download(cls, d: dict, i: int, species, index_i, sample_dt_fs: float, rdf_rmax: float) -> "MDObservables":
-        """Replica ``i`` of a ``download``; ``index_i``: the species index of each of its atoms."""
+    def from_download(cls, d: dict, i: int, species, index_i, sample_dt_fs: float, rdf_rmax: float, transport: dict | None = None,
+                      observers: "MDObservers | None" = None) -> "MDObservables":
+        """Replica ``i`` of a ``download`` (and of a ``download_transport`` made for ``observers``); ``index_i``: the species index of
+        each of its atoms."""
         n_per = np.bincount(np.asarray(index_i), minlength=len(species))
+        kw = {}
+        if transport is not None:
+            ob, t = observers, transport
+            kw = {"msd4_sum": t["msd4"][i].copy() if ob.non_gaussian else None,
+                  "cmsd_sum": t["cmsd"][i].copy() if ob.collective else None, "jacf_sum": t["jacf"][i].copy() if ob.collective else None,
+                  "vanhove_hist": t["vh"][i].copy() if ob.vanhove_bins else None, "vanhove_rmax": ob.vanhove_rmax,
+                  "vanhove_stride": ob.vanhove_stride, "transport_samples": int(t["samples"][i]),
+                  "transport_vol_sum": float(t["vol_sum"][i])}
         return cls(species, n_per, sample_dt_fs, d["msd"][i].copy(), d["vacf"][i].copy(), d["cnt"][i].copy(), d["rdf"][i].copy(),
-                   int(d["rdf_samples"][i]), float(d["vol_sum"][i]), rdf_rmax)
+                   int(d["rdf_samples"][i]), float(d["vol_sum"][i]), rdf_rmax, **kw)
 
     def _s(self, z) -> int:
         hit = np.flatnonzero(self.species == int(z))
@@ -141,15 +240,99 @@ class MDObservables:
         c = self._per_atom_and_origin(self.vacf_sum, species) * _FS ** 2   # ASE velocity units -> A/fs
         return c / c[0] if normalized else c
 
-    def diffusion_coefficient(self, species, fit: tuple[float, float]) -> float:
-        """The least-squares slope of the MSD over the lags with ``fit[0] <= t <= fit[1]`` (fs), divided by 6, in cm^2/s."""
+    def _slope(self, y: np.ndarray, fit: tuple[float, float]) -> float:
+        """The least-squares slope of ``y`` over the lags with ``fit[0] <= t <= fit[1]`` (fs), per fs."""
         t = self.lag_times_fs
-        y = self.msd(species)
         pick = (t >= fit[0]) & (t <= fit[1]) & np.isfinite(y)
         if pick.sum() < 2:
             raise ValueError(f"fewer than two lags fall into the window {fit} fs")
-        slope = np.polyfit(t[pick], y[pick], 1)[0]      # A^2/fs
-        return float(slope / 6.0 * 0.1)                 # 1 A^2/fs = 1e-16 cm^2 / 1e-15 s = 0.1 cm^2/s
+        return float(np.polyfit(t[pick], y[pick], 1)[0])
+
+    def diffusion_coefficient(self, species, fit: tuple[float, float]) -> float:
+        """The least-squares slope of the MSD over the lags with ``fit[0] <= t <= fit[1]`` (fs), divided by 6, in cm^2/s."""
+        return self._slope(self.msd(species), fit) / 6.0 * 0.1   # 1 A^2/fs = 1e-16 cm^2 / 1e-15 s = 0.1 cm^2/s
+
+    # ---- transport -------------------------------------------------------------------------------------------------------------
+    def _need(self, name: str, what: str) -> np.ndarray:
+        x = getattr(self, name)
+        if x is None:
+            raise ValueError(f"no {name} was accumulated: pass {what} to MDObservers")
+        return x
+
+    def _per_origin(self, sums: np.ndarray) -> np.ndarray:
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(self.cnt > 0, sums / self.cnt, np.nan)   # a lag no sample pair has reached yet: nan
+
+    def non_gaussian_parameter(self, species) -> np.ndarray:
+        """[L] alpha_2 = 3 <r^4> / (5 <r^2>^2) - 1 of the displacements of the species: 0 for a Gaussian (diffusive) distribution,
+        positive when a few atoms hop far while most rattle in place; nan where the MSD is 0 (lag 0) or the lag was not reached."""
+        r4 = self._per_atom_and_origin(self._need("msd4_sum", "non_gaussian=True"), species)
+        r2 = self.msd(species)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(r2 > 0, 3.0 * r4 / (5.0 * r2 * r2) - 1.0, np.nan)
+
+    def collective_msd(self, a, b) -> np.ndarray:
+        """[L] A^2: <U_a(t) . U_b(t)> per time origin, U_a the summed displacement of the atoms of species ``a``."""
+        return self._per_origin(self._need("cmsd_sum", "collective=True")[:, self._s(a), self._s(b)])
+
+    def current_correlation(self, a, b) -> np.ndarray:
+        """[L] A^2/fs^2: <J_a(t) . J_b(0)> per time origin, J_a the summed velocity of the atoms of species ``a`` (not symmetric in a, b)."""
+        return self._per_origin(self._need("jacf_sum", "collective=True")[:, self._s(a), self._s(b)]) * _FS ** 2
+
+    @property
+    def mean_volume(self) -> float:
+        """A^3: the mean cell volume over the samples of the transport accumulators."""
+        if self.transport_samples == 0:
+            raise ValueError("no transport sample was accumulated")
+        return self.transport_vol_sum / self.transport_samples
+
+    def _charges(self, charges: dict) -> np.ndarray:
+        for z in charges:
+            self._s(z)
+        return np.array([float(charges.get(int(z), 0.0)) for z in self.species])   # species without a charge count as 0
+
+    def ionic_conductivity(self, charges: dict, temperature: float, fit: tuple[float, float]) -> float:
+        """S/cm, Einstein form: the least-squares slope of ``sum_ab q_a q_b <U_a . U_b>`` over the lags with ``fit[0] <= t <= fit[1]``
+        (fs), divided by ``6 <V> k_B T``.  ``charges``: ``{atomic number: charge in e}``; the cross terms between species and between
+        atoms of one species are all in, so this is the real conductivity and not the Nernst-Einstein estimate."""
+        q = self._charges(charges)
+        y = self._per_origin(np.einsum("a,lab,b->l", q, self._need("cmsd_sum", "collective=True"), q))
+        return self._slope(y, fit) / (6.0 * self.mean_volume * _KB * float(temperature)) * _E2_PER_A_FS_EV_IN_S_PER_CM
+
+    def nernst_einstein_conductivity(self, charges: dict, temperature: float, fit: tuple[float, float]) -> float:
+        """S/cm: ``sum_a q_a^2 n_a`` times the slope of the tracer MSD of ``a``, over ``6 <V> k_B T``: what the conductivity would be
+        if no two atoms moved in a correlated way."""
+        q = self._charges(charges)
+        total = sum(q[s] ** 2 * self.n_per_species[s] * self._slope(self.msd(self.species[s]), fit)
+                    for s in range(len(self.species)) if q[s] != 0.0 and self.n_per_species[s] > 0)
+        return float(total) / (6.0 * self.mean_volume * _KB * float(temperature)) * _E2_PER_A_FS_EV_IN_S_PER_CM
+
+    def haven_ratio(self, charges: dict, temperature: float, fit: tuple[float, float]) -> float:
+        """``nernst_einstein_conductivity / ionic_conductivity``: 1 for independent carriers, below 1 for concerted motion."""
+        return self.nernst_einstein_conductivity(charges, temperature, fit) / self.ionic_conductivity(charges, temperature, fit)
+
+    @property
+    def vanhove_r(self) -> np.ndarray:
+        """The bin centres of the van Hove histogram (A)."""
+        bins = self._need("vanhove_hist", "vanhove_bins").shape[2]
+        return (np.arange(bins) + 0.5) * (self.vanhove_rmax / bins)
+
+    @property
+    def vanhove_lag_times_fs(self) -> np.ndarray:
+        return np.arange(len(self._need("vanhove_hist", "vanhove_bins"))) * self.vanhove_stride * self.sample_dt_fs
+
+    def van_hove_self(self, species) -> np.ndarray:
+        """[vanhove_lags, bins] G_s(r, t) per A^3: the probability density of finding an atom of the species displaced by r after
+        t, counts / (time origins x atoms x shell volume); lags not reached are nan.  Displacements at or beyond ``vanhove_rmax`` are
+        not counted, so ``sum(G_s 4 pi r^2 dr)`` over the bins is the fraction that stayed inside, not 1."""
+        hist = self._need("vanhove_hist", "vanhove_bins")
+        s = self._s(species)
+        lags, _, bins = hist.shape
+        edges = np.arange(bins + 1) * (self.vanhove_rmax / bins)
+        shell = 4.0 / 3.0 * np.pi * (edges[1:] ** 3 - edges[:-1] ** 3)
+        norm = (self.cnt[np.arange(lags) * self.vanhove_stride] * self.n_per_species[s]).astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(norm[:, None] > 0, hist[:, s].astype(np.float64) / (norm[:, None] * shell[None, :]), np.nan)
 
     # ---- RDF -----------------------------------------------------------------------------------------------------------------
     @property

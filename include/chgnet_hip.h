@@ -116,7 +116,9 @@ typedef struct chg_out_host {
  * mask travels as an argument to entry points of its own; so were chg_md_create_nhc_flex, chg_md_download_vg and
  * chg_test_md_step_nhc_flex: the cell mode travels as an argument, the strain-rate matrix in an array of its own;
  * so were chg_md_set_observers, chg_md_download_observables and chg_test_md_observe: their parameters and results travel in two structs
- * of their own, chg_md_observe_params and chg_md_observables_host, and no older struct or signature changed).  A binding compiled against another value must refuse the
+ * of their own, chg_md_observe_params and chg_md_observables_host, and no older struct or signature changed;
+ * so were chg_md_set_transport, chg_md_download_transport and chg_test_md_transport, with chg_md_transport_params and
+ * chg_md_transport_host).  A binding compiled against another value must refuse the
  * library: chg_engine_create COPIES *desc, so an older, shorter chg_model_desc would be read past its end. */
 #define CHG_ABI_VERSION 5
 int chg_abi_version(void);
@@ -544,6 +546,53 @@ int chg_md_download_observables(chg_engine* eng, chg_md* md, const chg_md_observ
 int chg_test_md_observe(chg_engine* eng, const chg_md_observe_params* params, int32_t n_struct, const int32_t* atom_off,
                         const int32_t* species, const double* masses, int32_t n_samples, const double* positions, const double* momenta,
                         const double* cell, const int32_t* status, const chg_md_observables_host* out);
+
+/* Transport accumulators (csrc/kernels_md_transport.h; tests/md_transport_ref.py restates them in NumPy) hang on observers with
+ * n_lags = L > 0 and use their sample_interval, ring, subtract_com, species map and status rule: a replica that is not
+ * CHG_MD_RUNNING is skipped for good.  For sample number k, replica o and every lag l in 0 .. min(k, L - 1), with
+ *   u_i  = (r_i(k) - R_o(k)) - (r_i(k-l) - R_o(k-l))      the displacement the MSD is made of (R_o = 0 without subtract_com)
+ *   U_a  = sum_{i in o, species a} u_i                     summed over the atoms in a fixed order, never as a difference of position sums
+ *   J_a(k) = sum_{i in o, species a} p_i / m_i             raw velocities, as the VACF uses them; kept per sample in a ring [L,B,S,3]
+ * the sums are
+ *   msd4[o,l,s_i] += (|u_i|^2)^2                           (non_gaussian)
+ *   cmsd[o,l,a,b] += U_a . U_b                             (collective; the full S x S block, symmetric bit for bit)
+ *   jacf[o,l,a,b] += J_a(k) . J_b(k-l)                     (collective; not symmetric in a, b)
+ *   vh[o, l / vh_stride, s_i, floor(|u_i| / vh_rmax * vh_bins)] += 1   if l % vh_stride == 0, l / vh_stride < vh_lags and
+ *                                                          |u_i| < vh_rmax: integer counts, a displacement at or beyond vh_rmax is not counted
+ * and per sample samples[o] += 1, vol_sum[o] += |det L| (the vol_sum of chg_md_observables_host exists only with an RDF and is left
+ * alone).  cnt[o,l] of chg_md_observables_host normalises these sums too.  Float64, no floating-point atomics: every cell has one
+ * owning workgroup, the histogram is counted in LDS (n_species * vh_bins <= 4096) and flushed once, so two runs of the same input
+ * give the same bits.  chg_md_set_transport is valid after chg_md_set_observers and before the first run (a second call replaces the
+ * first; a later chg_md_set_observers drops it); CHG_EINVAL with a message for: no observers or n_lags == 0; nothing requested;
+ * vh_bins < 0; with vh_bins > 0 a vh_rmax that is not finite and positive, vh_stride < 1, vh_lags < 1, (vh_lags - 1) * vh_stride >= L
+ * or n_species * vh_bins > 4096; a call after the first run.  CHG_ENOMEM when the accumulators (24 L B S bytes of ring,
+ * 8 B L S (1 + 2 S) + 8 B vh_lags S vh_bins of sums) do not fit.  chg_md_free releases them.  A run without transport launches
+ * exactly what it launched before it existed. */
+typedef struct chg_md_transport_params {
+  int32_t collective;       /* cmsd and jacf */
+  int32_t non_gaussian;     /* msd4 */
+  int32_t vh_bins;          /* 0: no van Hove histogram */
+  int32_t vh_lags;          /* histograms kept: lags 0, vh_stride, .., (vh_lags - 1) vh_stride */
+  int32_t vh_stride;
+  int32_t reserved;
+  double vh_rmax;           /* A, > 0 when vh_bins > 0 */
+} chg_md_transport_params;
+int chg_md_set_transport(chg_engine* eng, chg_md* md, const chg_md_transport_params* params);
+typedef struct chg_md_transport_host {
+  double* msd4;             /* [B,L,S]   */
+  double* cmsd;             /* [B,L,S,S] */
+  double* jacf;             /* [B,L,S,S] ASE velocity units squared */
+  uint64_t* vh;             /* [B,vh_lags,S,vh_bins] */
+  int64_t* samples;         /* [B] */
+  double* vol_sum;          /* [B] A^3 */
+} chg_md_transport_host;
+/* The accumulators as they stand; null pointers and sums that were not requested are skipped.  CHG_EINVAL for a handle without transport. */
+int chg_md_download_transport(chg_engine* eng, chg_md* md, const chg_md_transport_host* out);
+/* Tests only: as chg_test_md_observe with the transport accumulators on top; plain (the sums of the observers) may be null. */
+int chg_test_md_transport(chg_engine* eng, const chg_md_observe_params* params, const chg_md_transport_params* transport, int32_t n_struct,
+                          const int32_t* atom_off, const int32_t* species, const double* masses, int32_t n_samples,
+                          const double* positions, const double* momenta, const double* cell, const int32_t* status,
+                          const chg_md_observables_host* plain, const chg_md_transport_host* out);
 
 /* ---- canonical Monte Carlo: species swaps and single-atom displacements, every structure an independent replica -----------------
  * Not in the reference.  Every replica has a fixed cell, its own temperature (K, >= 0; 0 is greedy descent) and its own 64-bit seed; its

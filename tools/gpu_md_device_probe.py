@@ -13,6 +13,9 @@ of R = 1, 8, 64 replicas of the 256-atom 2x2x2 Li9Co7O16 cell, NVT Berendsen at 
       --observe               accumulate observables on the device while the run goes on (MDObservers: every step, 256 MSD / VACF
                               lags, RDF with 200 bins up to 6 A); lines go to profiles/md_observe_probe.jsonl unless --out is given.
                               Compare it with the same leg without the flag: their ratio is the cost of observing
+      --observe --transport   the same leg with the transport accumulators on top (collective displacements and currents, the
+                              non-Gaussian parameter, van Hove histograms of 64 bins up to 4 A at every 16th lag); lines go to
+                              profiles/md_transport_probe.jsonl unless --out is given.  Compare it with --observe alone
   --leg host                  one replica, BerendsenNVT + CHGNetCalculator.calculate per step
 
 Weights: the trained-like golden set (tests/golden/weights_trained_like.npz).  Run every leg under its own time limit.
@@ -52,10 +55,14 @@ def main() -> None:
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--fixed-fraction", type=float, default=0.0)
     ap.add_argument("--observe", action="store_true")
+    ap.add_argument("--transport", action="store_true", help="with --observe")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.transport and not args.observe:
+        ap.error("--transport belongs to --observe")
     if args.out is None:
-        args.out = os.path.join(REPO, "profiles", "md_observe_probe.jsonl" if args.observe else "md_device_probe.jsonl")
+        name = "md_transport_probe.jsonl" if args.transport else "md_observe_probe.jsonl" if args.observe else "md_device_probe.jsonl"
+        args.out = os.path.join(REPO, "profiles", name)
     if args.observe and args.leg != "device":
         ap.error("--observe belongs to --leg device")
     if args.ensemble == "npt" and args.thermostat != "nhc":
@@ -89,8 +96,11 @@ def main() -> None:
         if args.observe:
             from chgnet_amd.observables import MDObservers
 
-            kw.update(observers=MDObservers(sample_interval=1, msd_lags=256, rdf_rmax=6.0, rdf_bins=200))
-            out.update(observe={"sample_interval": 1, "msd_lags": 256, "rdf_bins": 200, "rdf_rmax": 6.0})
+            observe = {"sample_interval": 1, "msd_lags": 256, "rdf_bins": 200, "rdf_rmax": 6.0}
+            if args.transport:
+                observe.update(collective=True, non_gaussian=True, vanhove_bins=64, vanhove_rmax=4.0, vanhove_stride=16)
+            kw.update(observers=MDObservers(**observe))
+            out.update(observe=observe)
         MolecularDynamics.run_batch(cells, 5, seeds=list(range(R)), **kw)          # warm-up: engine creation, first builds
         for rep in range(args.repeats):
             t0 = time.perf_counter()
@@ -104,6 +114,10 @@ def main() -> None:
                 reached = int(np.flatnonzero(ob.cnt > 0)[-1])
                 out.update(li_msd_A2=float(ob.msd(3)[reached]), li_msd_lag_fs=float(ob.lag_times_fs[reached]),
                            rdf_samples=int(ob.rdf_samples), o_around_co=ob.coordination_number(27, 8, 2.4))
+            if args.transport:                   # the Li-Li collective displacement and alpha_2 at that lag, and the van Hove mass inside 4 A
+                out.update(li_collective_msd_A2=float(ob.collective_msd(3, 3)[reached]), li_alpha2=float(ob.non_gaussian_parameter(3)[reached]),
+                           transport_samples=int(ob.transport_samples),
+                           li_vanhove_inside=float(ob.vanhove_hist[0, ob._s(3)].sum() / (ob.cnt[0] * ob.n_per_species[ob._s(3)])))
             lines.append(json.dumps(out))
     else:
         from chgnet_amd.md import BerendsenNVT
