@@ -35,6 +35,8 @@ EXPORTED_SYMBOLS = (
     "chg_relax_set_fixed", "chg_md_set_fixed", "chg_test_relax_step_fixed", "chg_test_lbfgs_step_fixed", "chg_test_md_step_fixed",
     "chg_md_set_observers", "chg_md_download_observables", "chg_test_md_observe",
     "chg_md_set_transport", "chg_md_download_transport", "chg_test_md_transport",
+    "chg_md_set_magmoms", "chg_md_download_magmoms",
+    "chg_md_set_charge_states", "chg_md_download_charge_states", "chg_test_md_charge_states",
     "chg_mc_create", "chg_mc_set_temperatures", "chg_mc_run", "chg_mc_download", "chg_mc_free", "chg_test_mc_step",
     "chg_mc_set_exchange", "chg_mc_download_exchange", "chg_test_mc_exchange",
 )
@@ -124,6 +126,17 @@ class MdTransportHost(ctypes.Structure):
     _fields_ = [("msd4", _dp), ("cmsd", _dp), ("jacf", _dp), ("vh", ctypes.POINTER(ctypes.c_uint64)), ("samples", _ip), ("vol_sum", _dp)]
 
 
+class MdChargeParams(ctypes.Structure):
+    _fields_ = [("n_bounds", ctypes.c_int32 * 8), ("mag_bins", ctypes.c_int32), ("center_species", ctypes.c_int32),
+                ("srdf_bins", ctypes.c_int32), ("reserved", ctypes.c_int32), ("mag_max", ctypes.c_double), ("srdf_rmax", ctypes.c_double)]
+
+
+class MdChargeHost(ctypes.Structure):
+    _dp, _ip, _up = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_uint64)
+    _fields_ = [("mhist", _up), ("msum", _dp), ("msq", _dp), ("pop", _ip), ("trans", _ip), ("occ", _ip), ("mcorr", _dp), ("same", _ip),
+                ("shist", _up), ("samples", _ip), ("skipped", _ip), ("vol_sum", _dp)]
+
+
 class McParams(ctypes.Structure):
     _fields_ = [("swap_probability", ctypes.c_double), ("max_displacement", ctypes.c_double), ("kB", ctypes.c_double),
                 ("loginterval", ctypes.c_int32), ("ring_frames", ctypes.c_int32), ("r_atom", ctypes.c_double), ("r_bond", ctypes.c_double),
@@ -143,6 +156,7 @@ MC_SD, MC_SI = 32, 8                                    # csrc/kernels_mc.h: sta
 MC_EXCHANGE_INTS = 6                                    # include/chgnet_hip.h CHG_MC_EXCHANGE_INTS: walker, attempts, accepts, mark, trips, spare
 MD_OBS_MAX_LAGS, MD_OBS_MAX_SPECIES, MD_OBS_RDF_CELLS = 4096, 8, 16384   # csrc/kernels_md_obs.h
 MD_OBS_VH_CELLS = 4096                                                   # csrc/kernels_md_transport.h
+MD_CHG_STATES, MD_CHG_BOUNDS, MD_CHG_HIST_CELLS, MD_CHG_SRDF_CELLS = 4, 3, 4096, 16384   # csrc/kernels_md_magmom.h
 MD_NHC_STATE = 20   # include/chgnet_hip.h CHG_MD_NHC_STATE
 MD_VG = 9           # include/chgnet_hip.h CHG_MD_VG
 MD_CELL_MODES = {"flexible": 1, "axes": 2}   # CHG_MD_CELL_*
@@ -297,6 +311,14 @@ def load() -> ctypes.CDLL:
     lib.chg_test_md_transport.argtypes = [vp, ctypes.POINTER(MdObserveParams), ctypes.POINTER(MdTransportParams), ctypes.c_int32, c_int_p,
                                           c_int_p, dp, ctypes.c_int32, dp, dp, dp, c_int_p, ctypes.POINTER(MdObservablesHost),
                                           ctypes.POINTER(MdTransportHost)]
+    # moments per frame and charge-state observers: boundaries [S, 3] and the moments of the test snapshots travel beside the params struct
+    lib.chg_md_set_magmoms.argtypes = [vp, vp, ctypes.c_int32]
+    lib.chg_md_download_magmoms.argtypes = [vp, vp, c_float_p, c_float_p, ctypes.c_int32]
+    lib.chg_md_set_charge_states.argtypes = [vp, vp, ctypes.POINTER(MdChargeParams), dp]
+    lib.chg_md_download_charge_states.argtypes = [vp, vp, ctypes.POINTER(MdChargeHost)]
+    lib.chg_test_md_charge_states.argtypes = [vp, ctypes.POINTER(MdObserveParams), ctypes.POINTER(MdChargeParams), dp, ctypes.c_int32, c_int_p,
+                                              c_int_p, dp, ctypes.c_int32, dp, dp, dp, c_int_p, c_float_p, ctypes.POINTER(MdObservablesHost),
+                                              ctypes.POINTER(MdChargeHost)]
     # Monte Carlo: temperatures, seeds and the two per-atom masks travel beside the params struct
     lp = ctypes.POINTER(ctypes.c_int64)
     lib.chg_mc_create.argtypes = [vp, ctypes.POINTER(StructsHost), dp, u64p, u8p, u8p, ctypes.POINTER(McParams), ctypes.POINTER(vp)]

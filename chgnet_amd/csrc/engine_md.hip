@@ -9,12 +9,26 @@
 // step, frame, start the next one).  Every replica runs the same number of
 // steps, so there is no compaction.  NPT takes two evaluations per step, as ASE does: the barostat's set_cell(scale_atoms=True)
 // moves the atoms and the forces are evaluated again before the first half kick.  The Nose-Hoover-chain NPT scales the cell inside
-// the step and takes one evaluation (task efs) like every other ensemble.
+// the step and takes one evaluation (task efs) like every other ensemble.  chg_md_set_magmoms / chg_md_set_charge_states add the site
+// moments to the task and one gather launch (kernels_md_magmom.h) after the step launch of every evaluation that completes a step.
 #include "engine_stepper.h"
 
 #include "kernels_md.h"
 #include "kernels_md_obs.h"
 #include "kernels_md_transport.h"
+#include "kernels_md_magmom.h"
+
+// chg_md_set_charge_states / chg_test_md_charge_states: parameters and one device allocation of its own (boundaries, moment and state
+// ring, accumulators, and for a run the moment slot of the observers' private frame)
+struct MdCharge {
+  chg_md_charge_params p{};
+  char* mem = nullptr;
+  double *bounds = nullptr, *ring_m = nullptr, *msum = nullptr, *msq = nullptr, *mcorr = nullptr, *vol_sum = nullptr;
+  int *n_bounds = nullptr, *ring_q = nullptr, *prev_q = nullptr;
+  unsigned long long *mhist = nullptr, *shist = nullptr;
+  long long *pop = nullptr, *trans = nullptr, *occ = nullptr, *same = nullptr, *samples = nullptr, *skipped = nullptr;
+  float* fr_mag = nullptr;
+};
 
 // chg_md_set_transport / chg_test_md_transport: parameters and one device allocation of its own (current ring and accumulators)
 struct MdTransport {
@@ -38,6 +52,7 @@ struct MdObservers {
   unsigned long long* hist = nullptr;
   chg::MdFrame fr{};             // private frame slot: what the step kernels write of a completed step that is sampled but not logged
   MdTransport* tr = nullptr;     // chg_md_set_transport: reads the ring above
+  MdCharge* cs = nullptr;        // chg_md_set_charge_states: its own ring, the same sample number and slot
 };
 
 // the chg_md_create* / chg_test_md_step* entry point that was called: it decides which ensembles may run (bad_params)
@@ -68,6 +83,9 @@ struct chg_md : chgh::Stepper {
   std::vector<int> ring_step;
   std::vector<chg::MdFrame> ring;        // cfea only when logged, cons only for Nose-Hoover chains
   MdObservers* obs = nullptr;            // chg_md_set_observers
+  // chg_md_set_magmoms (or implied by chg_md_set_charge_states): task M, k_md_mag_gather after every evaluation that completes a step
+  bool mag = false, mag_frames = false;
+  float *mag_mem = nullptr, *mag_last = nullptr;   // [N] moments of the last completed step, then the ring frames' slots
 };
 
 namespace {
@@ -193,14 +211,20 @@ void launch_step(chg_engine* eng, const MdStepArgs& a, int grid) {
   hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), 0, eng->stream, a);
 }
 
-// evaluate all replicas, then one step launch with `a` (flags and frame slot set by the caller)
-int evaluate_and_step(chg_engine* eng, chg_md* d, MdStepArgs a) {
+// evaluate all replicas, then one step launch with `a` (flags and frame slot set by the caller); completes: the evaluation finishes a
+// step, so with chg_md_set_magmoms its moments are gathered under the rule the step kernel wrote the frame by
+int evaluate_and_step(chg_engine* eng, chg_md* d, MdStepArgs a, bool completes) {
   return chgh::evaluate_and_step(eng, "chg_md_run", d, d->B, nullptr, nullptr, [&](const chg_batch* b, const int* sel, int final_try, int grid) {
     a.energy = b->energy; a.force = b->force; a.stress = (d->task & CHG_TASK_S) ? b->virial : nullptr;
     a.cfea = a.fr.cfea ? b->crystal_fea : nullptr;
     a.sel = sel;
     a.final_try = final_try;
     launch_step(eng, a, grid);
+    if (d->mag && completes) {
+      LaunchScope ls(eng, "md_mag_gather");
+      const MdMagArgs g{b->magmom, a.fr.mag, d->mag_last, d->si, d->retry, sel, d->d_aoff, final_try};
+      hipLaunchKernelGGL(k_md_mag_gather, dim3((unsigned)grid), dim3(256), 0, eng->stream, g);
+    }
   });
 }
 
@@ -300,9 +324,16 @@ void free_transport(MdTransport* t) {
   delete t;
 }
 
+void free_charge(MdCharge* c) {
+  if (!c) return;
+  if (c->mem) hipFree(c->mem);
+  delete c;
+}
+
 void free_observers(MdObservers* x) {
   if (!x) return;
   free_transport(x->tr);
+  free_charge(x->cs);
   if (x->mem) hipFree(x->mem);
   delete x;
 }
@@ -429,9 +460,140 @@ int download_transport(chg_engine* eng, const MdObservers* x, const chg_md_trans
   return CHG_OK;
 }
 
+// ---- charge-state observers on the observers' sample counter (kernels_md_magmom.h)
+
+const char* bad_charge(const MdObservers* x, const chg_md_charge_params* p, const double* bounds) {
+  if (!x) return "charge states need observers (chg_md_set_observers)";
+  const int S = x->p.n_species;
+  int total = 0;
+  for (int s = 0; s < S; ++s) {
+    if (p->n_bounds[s] < 0 || p->n_bounds[s] > MD_CHG_BOUNDS) return "n_bounds must be 0..3";
+    for (int j = 0; j < p->n_bounds[s]; ++j) {
+      const double v = bounds[MD_CHG_BOUNDS * s + j];
+      if (!std::isfinite(v) || v < 0.0 || (j > 0 && !(v > bounds[MD_CHG_BOUNDS * s + j - 1]))) return "boundaries must be finite, >= 0 and ascending";
+    }
+    total += p->n_bounds[s];
+  }
+  if (p->mag_bins < 0) return "mag_bins must be >= 0";
+  if (p->srdf_bins < 0) return "srdf_bins must be >= 0";
+  if (total == 0 && p->mag_bins == 0 && p->srdf_bins == 0) return "nothing requested: no boundary, mag_bins and srdf_bins are 0";
+  if ((int64_t)S * p->mag_bins > MD_CHG_HIST_CELLS) return "n_species * mag_bins must be <= 4096 (the histogram lives in 16 KB of LDS)";
+  if (p->mag_bins > 0 && (!(p->mag_max > 0.0) || !std::isfinite(p->mag_max))) return "mag_max must be > 0 and finite";
+  if ((int64_t)MD_CHG_STATES * S * p->srdf_bins > MD_CHG_SRDF_CELLS)
+    return "4 * n_species * srdf_bins must be <= 16384 (the histogram lives in 64 KB of LDS)";
+  if (p->srdf_bins > 0) {
+    if (p->center_species < 0 || p->center_species >= S) return "center_species must be 0 .. n_species - 1 when srdf_bins > 0";
+    if (!(p->srdf_rmax > 0.0) || !std::isfinite(p->srdf_rmax)) return "srdf_rmax must be > 0 and finite";
+  }
+  return nullptr;
+}
+
+void carve_charge(const MdObservers* x, MdCharge* c, Carver& k, bool frame_slot) {
+  const size_t B = x->B, N = x->N, L = x->p.n_lags, S = x->p.n_species, Q = MD_CHG_STATES;
+  c->bounds = k.take<double>(S * MD_CHG_BOUNDS);
+  c->n_bounds = k.take<int>(S);
+  c->ring_m = k.take<double>(L * N);
+  c->ring_q = k.take<int>(L * N);
+  c->prev_q = k.take<int>(N);
+  c->mhist = k.take<unsigned long long>(B * S * c->p.mag_bins);
+  c->msum = k.take<double>(B * S);
+  c->msq = k.take<double>(B * S);
+  c->pop = k.take<long long>(B * S * Q);
+  c->trans = k.take<long long>(B * S * Q * Q);
+  c->occ = k.take<long long>(N * Q);
+  c->mcorr = k.take<double>(B * L * S);
+  c->same = k.take<long long>(B * L * S * Q);
+  c->shist = k.take<unsigned long long>(B * Q * S * c->p.srdf_bins);
+  c->samples = k.take<long long>(B);
+  c->skipped = k.take<long long>(B);
+  c->vol_sum = k.take<double>(B);
+  if (frame_slot) c->fr_mag = k.take<float>(N);
+}
+
+// parameters checked against the observers they hang on, buffers allocated and zeroed, boundaries uploaded (synchronised)
+int create_charge(chg_engine* eng, const char* fn, const MdObservers* x, const chg_md_charge_params* p, const double* bounds, bool frame_slot,
+                  MdCharge** out) {
+  if (const char* bad = bad_charge(x, p, bounds)) { eng->err = std::string(fn) + ": " + bad; return CHG_EINVAL; }
+  MdCharge* c = new MdCharge();
+  c->p = *p;
+  const int S = x->p.n_species;
+  if (c->p.mag_bins == 0) c->p.mag_max = 0.0;
+  if (c->p.srdf_bins == 0) { c->p.center_species = -1; c->p.srdf_rmax = 0.0; }
+  Carver sizer{nullptr};
+  carve_charge(x, c, sizer, frame_slot);
+  if (hipMalloc(&c->mem, sizer.pos) != hipSuccess) {
+    (void)hipGetLastError();
+    c->mem = nullptr;
+    free_charge(c);
+    eng->err = std::string(fn) + ": charge-state ring and accumulators of " + std::to_string(sizer.pos) + " bytes cannot be allocated";
+    return CHG_ENOMEM;
+  }
+  Carver carver{c->mem};
+  carve_charge(x, c, carver, frame_slot);
+  std::vector<double> hb((size_t)S * MD_CHG_BOUNDS, 0.0);
+  for (int s = 0; s < S; ++s)
+    for (int j = 0; j < p->n_bounds[s]; ++j) hb[MD_CHG_BOUNDS * s + j] = bounds[MD_CHG_BOUNDS * s + j];
+  StateUpload up{eng, fn};
+  up.zero(c->mem, carver.pos);
+  if (up.s == CHG_OK && hipMemsetAsync(c->prev_q, 0xFF, sizeof(int) * (size_t)x->N, eng->stream) != hipSuccess) up.fail("state initialisation failed");
+  up(c->bounds, hb.data(), sizeof(double) * hb.size());
+  up(c->n_bounds, p->n_bounds, sizeof(int) * S);
+  int s = up.finish();
+  if (s == CHG_OK && p->srdf_bins > 0 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(k_md_chg_srdf), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)(sizeof(unsigned) * MD_CHG_STATES * S * p->srdf_bins)) != hipSuccess) {
+    eng->err = std::string(fn) + ": the histogram does not fit the LDS";
+    s = CHG_EHIP;
+  }
+  if (s != CHG_OK) { free_charge(c); return s; }
+  *out = c;
+  return CHG_OK;
+}
+
+// the charge-state kernels of sample x->k (a: the arguments of the plain observers' launches of the same sample; mag: its moments)
+void observe_charge(chg_engine* eng, const MdObservers* x, const MdObsArgs& a, const float* mag) {
+  const MdCharge* c = x->cs;
+  MdChgArgs b{};
+  b.mag = mag; b.pos = a.pos; b.cell = a.cell; b.species = a.species; b.status = a.status; b.status_stride = a.status_stride; b.aoff = a.aoff;
+  b.N = a.N; b.B = a.B; b.S = a.S; b.bounds = c->bounds; b.n_bounds = c->n_bounds;
+  b.ring_m = c->ring_m; b.ring_q = c->ring_q; b.L = a.L; b.slot = a.L > 0 ? (int)(x->k % a.L) : 0; b.k = x->k; b.prev_q = c->prev_q;
+  b.mhist = c->mhist; b.msum = c->msum; b.msq = c->msq; b.pop = c->pop; b.trans = c->trans; b.occ = c->occ; b.mcorr = c->mcorr;
+  b.same = c->same; b.shist = c->shist; b.samples = c->samples; b.skipped = c->skipped; b.vol_sum = c->vol_sum;
+  b.mag_bins = c->p.mag_bins; b.center = c->p.center_species; b.srdf_bins = c->p.srdf_bins; b.mag_max = c->p.mag_max; b.srdf_rmax = c->p.srdf_rmax;
+  hipLaunchKernelGGL(k_md_chg_sample, dim3((unsigned)x->B), dim3(256), 0, eng->stream, b);
+  if (a.L > 0) {
+    const unsigned lags = (unsigned)std::min<long long>(x->k, a.L - 1) + 1;
+    hipLaunchKernelGGL(k_md_chg_corr, dim3(lags, (unsigned)x->B), dim3(256), 0, eng->stream, b);
+  }
+  if (c->p.srdf_bins > 0) {
+    const unsigned chunks = (unsigned)((x->n_max + MD_OBS_RDF_ROWS - 1) / MD_OBS_RDF_ROWS);
+    const size_t lds = sizeof(unsigned) * MD_CHG_STATES * a.S * c->p.srdf_bins;
+    hipLaunchKernelGGL(k_md_chg_srdf, dim3(chunks, (unsigned)x->B), dim3(256), lds, eng->stream, b);
+  }
+}
+
+int download_charge(chg_engine* eng, const MdObservers* x, const chg_md_charge_host* o) {
+  const MdCharge* c = x->cs;
+  const size_t B = x->B, N = x->N, L = x->p.n_lags, S = x->p.n_species, Q = MD_CHG_STATES;
+  TRY(d2h(eng, (unsigned long long*)o->mhist, c->mhist, B * S * c->p.mag_bins));
+  TRY(d2h(eng, o->msum, c->msum, B * S));
+  TRY(d2h(eng, o->msq, c->msq, B * S));
+  TRY(d2h(eng, (long long*)o->pop, c->pop, B * S * Q));
+  TRY(d2h(eng, (long long*)o->trans, c->trans, B * S * Q * Q));
+  TRY(d2h(eng, (long long*)o->occ, c->occ, N * Q));
+  TRY(d2h(eng, o->mcorr, c->mcorr, B * L * S));
+  TRY(d2h(eng, (long long*)o->same, c->same, B * L * S * Q));
+  TRY(d2h(eng, (unsigned long long*)o->shist, c->shist, B * Q * S * c->p.srdf_bins));
+  TRY(d2h(eng, (long long*)o->samples, c->samples, B));
+  TRY(d2h(eng, (long long*)o->skipped, c->skipped, B));
+  TRY(d2h(eng, o->vol_sum, c->vol_sum, B));
+  HIP_TRY(eng, hipStreamSynchronize(eng->stream));
+  return CHG_OK;
+}
+
 // one sample: the snapshot of a completed step through the ring and the accumulators (enqueued on the engine's stream)
 int observe(chg_engine* eng, const char* fn, MdObservers* x, const double* pos, const double* mom, const double* cell, const double* mass,
-            const int* status, int status_stride, const int* d_aoff) {
+            const int* status, int status_stride, const int* d_aoff, const float* mag = nullptr) {
   LaunchScope ls(eng, "md_observe");
   const chg_md_observe_params& p = x->p;
   MdObsArgs a{};
@@ -452,6 +614,7 @@ int observe(chg_engine* eng, const char* fn, MdObservers* x, const double* pos, 
     const size_t lds = sizeof(unsigned) * p.n_species * p.n_species * p.rdf_bins;
     hipLaunchKernelGGL(k_md_obs_rdf, dim3(chunks, (unsigned)x->B), dim3(256), lds, eng->stream, a);
   }
+  if (x->cs) observe_charge(eng, x, a, mag);
   x->k += 1;
   if (hipGetLastError() != hipSuccess) { eng->err = std::string(fn) + ": observer kernel launch failed"; return CHG_EHIP; }
   return CHG_OK;
@@ -477,8 +640,31 @@ int evaluate_step_observe(chg_engine* eng, chg_md* d, MdStepArgs& a, int step) {
   const bool sample = sample_due(d, step);
   if (frame_due(d, step)) set_frame(d, a, step);
   else if (sample) a.fr = d->obs->fr;
-  TRY(evaluate_and_step(eng, d, a));
-  if (sample) TRY(observe(eng, "chg_md_run", d->obs, a.fr.pos, a.fr.mom, a.fr.cell, d->m, d->si + 1, MD_SI, d->d_aoff));
+  if (sample && d->obs->cs && !a.fr.mag) a.fr.mag = d->obs->cs->fr_mag;   // a ring frame without moment slots: the observers' own
+  TRY(evaluate_and_step(eng, d, a, true));
+  if (sample) TRY(observe(eng, "chg_md_run", d->obs, a.fr.pos, a.fr.mom, a.fr.cell, d->m, d->si + 1, MD_SI, d->d_aoff, a.fr.mag));
+  return CHG_OK;
+}
+
+// task M and the moment slots: [N] of the last completed step, then [N] per ring frame with log_frames
+int enable_magmoms(chg_engine* eng, const char* fn, chg_md* d, bool log_frames) {
+  const size_t N = d->N, slots = 1 + (log_frames ? (size_t)d->K : 0);
+  float* mem = nullptr;
+  if (hipMalloc(&mem, sizeof(float) * N * slots) != hipSuccess) {
+    (void)hipGetLastError();
+    eng->err = std::string(fn) + ": moment slots of " + std::to_string(sizeof(float) * N * slots) + " bytes cannot be allocated";
+    return CHG_ENOMEM;
+  }
+  StateUpload up{eng, fn};
+  up.zero(mem, sizeof(float) * N * slots);
+  const int s = up.finish();
+  if (s != CHG_OK) { hipFree(mem); return s; }
+  if (d->mag_mem) hipFree(d->mag_mem);
+  d->mag_mem = d->mag_last = mem;
+  for (int k = 0; k < d->K; ++k) d->ring[k].mag = log_frames ? mem + N * (size_t)(k + 1) : nullptr;
+  d->mag = true;
+  d->mag_frames = log_frames;
+  d->task |= CHG_TASK_M;
   return CHG_OK;
 }
 }  // namespace
@@ -563,6 +749,54 @@ int chg_md_download_transport(chg_engine* eng, chg_md* d, const chg_md_transport
   return download_transport(eng, d->obs, o);
 }
 
+int chg_md_set_magmoms(chg_engine* eng, chg_md* d, int32_t log_frames) {
+  if (!eng || !d) return CHG_EINVAL;
+  const char* fn = "chg_md_set_magmoms";
+  if (d->started) { eng->err = std::string(fn) + ": the run has already started"; return CHG_EINVAL; }
+  HIP_TRY(eng, hipSetDevice(eng->device));
+  return enable_magmoms(eng, fn, d, log_frames != 0);
+}
+
+int chg_md_download_magmoms(chg_engine* eng, chg_md* d, float* magmom, float* frame_magmom, int32_t frame_capacity) {
+  if (!eng || !d) return CHG_EINVAL;
+  if (!d->mag) { eng->err = "chg_md_download_magmoms: the handle does not evaluate moments (chg_md_set_magmoms)"; return CHG_EINVAL; }
+  HIP_TRY(eng, hipSetDevice(eng->device));
+  const size_t N = d->N;
+  TRY(d2h(eng, magmom, d->mag_last, N));
+  const int take = d->mag_frames ? std::min(d->ring_count, std::max(frame_capacity, 0)) : 0;
+  for (int k = 0; k < take; ++k) {   // oldest first; the ring is left as it is (chg_md_download drains it)
+    TRY(d2h(eng, frame_magmom ? frame_magmom + k * N : nullptr, d->ring[(d->ring_head + k) % d->K].mag, N));
+  }
+  HIP_TRY(eng, hipStreamSynchronize(eng->stream));
+  return CHG_OK;
+}
+
+int chg_md_set_charge_states(chg_engine* eng, chg_md* d, const chg_md_charge_params* params, const double* bounds) {
+  if (!eng || !d || !params || !bounds) return CHG_EINVAL;
+  const char* fn = "chg_md_set_charge_states";
+  if (d->started) { eng->err = std::string(fn) + ": the run has already started"; return CHG_EINVAL; }
+  HIP_TRY(eng, hipSetDevice(eng->device));
+  MdCharge* c = nullptr;
+  TRY(create_charge(eng, fn, d->obs, params, bounds, true, &c));
+  if (!d->mag) {   // the observers read moments: task M and the gather, no frame slots
+    const int s = enable_magmoms(eng, fn, d, false);
+    if (s != CHG_OK) { free_charge(c); return s; }
+  }
+  free_charge(d->obs->cs);
+  d->obs->cs = c;
+  return CHG_OK;
+}
+
+int chg_md_download_charge_states(chg_engine* eng, chg_md* d, const chg_md_charge_host* o) {
+  if (!eng || !d || !o) return CHG_EINVAL;
+  if (!d->obs || !d->obs->cs) {
+    eng->err = "chg_md_download_charge_states: the handle has no charge-state observers (chg_md_set_charge_states)";
+    return CHG_EINVAL;
+  }
+  HIP_TRY(eng, hipSetDevice(eng->device));
+  return download_charge(eng, d->obs, o);
+}
+
 int chg_md_download_observables(chg_engine* eng, chg_md* d, const chg_md_observables_host* o) {
   if (!eng || !d || !o) return CHG_EINVAL;
   if (!d->obs) { eng->err = "chg_md_download_observables: the handle has no observers (chg_md_set_observers)"; return CHG_EINVAL; }
@@ -594,7 +828,7 @@ int chg_md_run(chg_engine* eng, chg_md* d, int32_t n_steps) {
   }
   for (int k = 0; k < n_steps; ++k) {
     if (npt) {   // the barostat's scaled configuration: forces, first half kick, fixcm, drift
-      TRY(evaluate_and_step(eng, d, handle_args(d, MD_ABSORB)));
+      TRY(evaluate_and_step(eng, d, handle_args(d, MD_ABSORB), false));
     }
     const int next = d->step + 1;
     MdStepArgs a = handle_args(d, MD_ABSORB | MD_KICK2 | (k + 1 < n_steps ? MD_START : 0));
@@ -668,6 +902,7 @@ int chg_md_free(chg_engine* eng, chg_md* d) {
   if (!d) return CHG_OK;
   release(eng, d);
   free_observers(d->obs);
+  if (d->mag_mem) hipFree(d->mag_mem);
   delete d;
   return CHG_OK;
 }
@@ -801,11 +1036,20 @@ int chg_test_md_step_fixed(chg_engine* eng, const chg_md_params* params, int32_t
 
 namespace {
 
-// chg_test_md_observe / chg_test_md_transport: caller-given snapshots through observe(), then the downloads that were asked for
+// what chg_test_md_charge_states adds to the snapshots
+struct TestCharge {
+  const chg_md_charge_params* params;
+  const double* bounds;
+  const float* magmoms;   // [T, N]
+  const chg_md_charge_host* out;
+};
+
+// chg_test_md_observe / chg_test_md_transport / chg_test_md_charge_states: caller-given snapshots through observe(), then the
+// downloads that were asked for
 int test_observe(chg_engine* eng, const char* fn, const chg_md_observe_params* params, const chg_md_transport_params* transport,
                  int32_t n_struct, const int32_t* atom_off, const int32_t* species, const double* masses, int32_t n_samples,
                  const double* positions, const double* momenta, const double* cell, const int32_t* status,
-                 const chg_md_observables_host* out, const chg_md_transport_host* tout) {
+                 const chg_md_observables_host* out, const chg_md_transport_host* tout, const TestCharge* charge = nullptr) {
   using namespace chgh;
   if (!eng || !params || n_struct <= 0 || !atom_off || !species || !masses || n_samples < 1 || !positions || !momenta || !cell || !status)
     return CHG_EINVAL;
@@ -821,18 +1065,25 @@ int test_observe(chg_engine* eng, const char* fn, const chg_md_observe_params* p
     const int s = create_transport(eng, fn, x, transport, &x->tr);
     if (s != CHG_OK) { free_observers(x); return s; }
   }
+  if (charge) {
+    const int s = create_charge(eng, fn, x, charge->params, charge->bounds, false, &x->cs);
+    if (s != CHG_OK) { free_observers(x); return s; }
+  }
   TestBuf bufs[] = {{positions, nullptr, sizeof(double) * T * 3 * N}, {momenta, nullptr, sizeof(double) * T * 3 * N},
                     {cell, nullptr, sizeof(double) * T * 9 * B}, {status, nullptr, sizeof(int) * T * B}, {masses, nullptr, sizeof(double) * N},
-                    {atom_off, nullptr, sizeof(int) * (B + 1)}};
+                    {atom_off, nullptr, sizeof(int) * (B + 1)},
+                    {charge ? charge->magmoms : nullptr, nullptr, sizeof(float) * (charge ? T * N : 1)}};
   int rc = CHG_OK;
   int s = run_test_step(eng, fn, bufs, [&] {
     for (size_t t = 0; t < T && rc == CHG_OK; ++t)
       rc = observe(eng, fn, x, (const double*)bufs[0].d + t * 3 * N, (const double*)bufs[1].d + t * 3 * N, (const double*)bufs[2].d + t * 9 * B,
-                   (const double*)bufs[4].d, (const int*)bufs[3].d + t * B, 1, (const int*)bufs[5].d);
+                   (const double*)bufs[4].d, (const int*)bufs[3].d + t * B, 1, (const int*)bufs[5].d,
+                   charge ? (const float*)bufs[6].d + t * N : nullptr);
   });
   if (s == CHG_OK) s = rc;
   if (s == CHG_OK && out) s = download_observables(eng, x, out);
   if (s == CHG_OK && tout) s = download_transport(eng, x, tout);
+  if (s == CHG_OK && charge) s = download_charge(eng, x, charge->out);
   free_observers(x);
   return s;
 }
@@ -855,4 +1106,15 @@ extern "C" int chg_test_md_transport(chg_engine* eng, const chg_md_observe_param
   if (!transport || !out) return CHG_EINVAL;
   return test_observe(eng, "chg_test_md_transport", params, transport, n_struct, atom_off, species, masses, n_samples, positions, momenta,
                       cell, status, plain, out);
+}
+
+extern "C" int chg_test_md_charge_states(chg_engine* eng, const chg_md_observe_params* params, const chg_md_charge_params* charge,
+                                         const double* bounds, int32_t n_struct, const int32_t* atom_off, const int32_t* species,
+                                         const double* masses, int32_t n_samples, const double* positions, const double* momenta,
+                                         const double* cell, const int32_t* status, const float* magmoms,
+                                         const chg_md_observables_host* plain, const chg_md_charge_host* out) {
+  if (!charge || !bounds || !magmoms || !out) return CHG_EINVAL;
+  const TestCharge tc{charge, bounds, magmoms, out};
+  return test_observe(eng, "chg_test_md_charge_states", params, nullptr, n_struct, atom_off, species, masses, n_samples, positions, momenta,
+                      cell, status, plain, nullptr, &tc);
 }

@@ -59,6 +59,7 @@ struct MdFrame {
   double *scal, *pos, *mom, *cell;   // [B, MD_FRAME_SCAL] [N, 3] [N, 3] [B, 9]
   double* cons;                      // [B] H - Epot (Nose-Hoover chains) or null
   float *force, *stress, *cfea;      // [N, 3] [B, 9], [B, fea_dim] or null
+  float* mag;                        // [N] site moments or null: written by k_md_mag_gather (kernels_md_magmom.h), not by the step kernels
 };
 
 struct MdStepArgs {

@@ -64,7 +64,14 @@ Berendsen barostat without ``bulk_modulus`` (the reference then fits an equation
   - a replica whose energy or forces are non-finite even on the engine's wide-range sweep stops with status ``NONFINITE`` and
     its state untouched (ASE carries the NaN on);
   - there is no ASE ``.traj`` writer: ``trajectory`` names a pickle with ``TrajectoryObserver``'s keys plus ``momenta`` and
-    ``temperature``; ``magmoms`` stay empty (the step evaluates energy and forces, plus stress for NPT).
+    ``temperature``; ``magmoms`` stay empty unless ``log_magmoms=True`` (the step evaluates energy and forces, plus stress for
+    NPT; with ``log_magmoms`` or charge-state observers also the site moments).
+
+Charge-informed MD (DESIGN.md "MD observables -> Charge states"): ``log_magmoms=True`` evaluates the site magnetic moments with every
+step (``chg_md_set_magmoms``), puts one float32 ``[n]`` array per frame into ``MDTrajectory.magmoms`` (the reference's ``"magmoms"`` key
+of the pickled trajectory) and keeps ``md.magmoms``, the moments of the last completed step.  The charge-state keywords of
+``MDObservers`` (``magmom_states``, ``magmom_bins``, ``state_rdf_bins``) classify and accumulate them on the device at every sample,
+with or without ``log_magmoms``.
 """
 
 from __future__ import annotations
@@ -81,7 +88,7 @@ from chgnet_amd.calculator import (CHGNetCalculator, atoms_to_structure, check_f
 from chgnet_amd.graph.structure import Lattice, Structure
 from chgnet_amd.observables import MDObservables, MDObservers
 from chgnet_amd.observables import download as download_observables
-from chgnet_amd.observables import download_transport
+from chgnet_amd.observables import ChargeStateSums, download_charge, download_transport
 
 # ase.units (CODATA 2014)
 _E, _AMU, _KB_J = 1.6021766208e-19, 1.660539040e-27, 1.38064852e-23
@@ -216,7 +223,7 @@ class _DeviceRun:
     RING = 32
 
     def __init__(self, calc: CHGNetCalculator, structures: list, masses: np.ndarray, momenta: np.ndarray, kind: str, cfg: dict,
-                 seeds=None, fixed: list | None = None, observers: MDObservers | None = None) -> None:
+                 seeds=None, fixed: list | None = None, observers: MDObservers | None = None, log_magmoms: bool = False) -> None:
         model = calc.model
         self.eng, self.model, self.calc = model.engine, model, calc
         conv = model.graph_converter
@@ -262,11 +269,18 @@ class _DeviceRun:
             if rc != 0:
                 self.free()
                 self.eng._check(rc)
+        self.log_magmoms = bool(log_magmoms)
+        if self.log_magmoms:             # task M and a moment slot in every ring frame; without the keyword the call is never made
+            rc = self.eng.lib.chg_md_set_magmoms(self.eng.handle, self.handle, 1)
+            if rc != 0:
+                self.free()
+                self.eng._check(rc)
         self.observers = observers
         if observers is not None:        # species: the sorted unique atomic numbers of the batch
             try:
                 self.species, self.species_index = observers.species_map(prep.z)
                 tp = observers.transport_params(len(self.species))
+                self.charge = observers.charge_params(self.species)
             except ValueError:
                 self.free()
                 raise
@@ -275,6 +289,9 @@ class _DeviceRun:
                                                    self.species_index.ctypes.data_as(_lib.c_int_p))
             if rc == 0 and tp is not None:   # transport accumulators on the observers' ring; without them the call is never made
                 rc = self.eng.lib.chg_md_set_transport(self.eng.handle, self.handle, ctypes.byref(tp))
+            if rc == 0 and self.charge is not None:   # charge-state observers (they imply the moments); likewise never called without
+                rc = self.eng.lib.chg_md_set_charge_states(self.eng.handle, self.handle, ctypes.byref(self.charge[0]),
+                                                           self.charge[1].ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
             if rc != 0:
                 self.free()
                 self.eng._check(rc)
@@ -307,6 +324,10 @@ class _DeviceRun:
             if self.cell_dof != "isotropic":
                 extra["vg"] = np.empty((B, 3, 3))
                 self.eng._check(self.eng.lib.chg_md_download_vg(self.eng.handle, self.handle, extra["vg"].ctypes.data_as(dp)))
+        if self.log_magmoms:             # likewise before the ring is drained
+            extra["magmom"], extra["frame_magmom"] = np.empty(N, np.float32), np.empty((K, N), np.float32)
+            self.eng._check(self.eng.lib.chg_md_download_magmoms(self.eng.handle, self.handle, extra["magmom"].ctypes.data_as(_lib.c_float_p),
+                                                                 extra["frame_magmom"].ctypes.data_as(_lib.c_float_p), K))
         self.eng._check(self.eng.lib.chg_md_download(self.eng.handle, self.handle, ctypes.byref(o)))
         d.update(extra)
         return d
@@ -318,8 +339,14 @@ class _DeviceRun:
         t = (download_transport(self.eng, self.handle, self.B, ob.msd_lags, len(self.species), ob.vanhove_lags, ob.vanhove_bins)
              if self.transport else None)
         off = self.prep.atom_off
+        charge = [None] * self.B
+        if self.charge is not None:
+            p, bounds = self.charge
+            c = download_charge(self.eng, self.handle, self.B, self.N, ob.msd_lags, len(self.species), ob.magmom_bins, ob.state_rdf_bins)
+            charge = [ChargeStateSums(c, i, slice(off[i], off[i + 1]), list(p.n_bounds)[:len(self.species)], bounds, ob.magmom_max,
+                                      p.center_species, ob.state_rdf_rmax) for i in range(self.B)]
         return [MDObservables.from_download(d, i, self.species, self.species_index[off[i]:off[i + 1]], self.sample_dt_fs, ob.rdf_rmax,
-                                            transport=t, observers=ob)
+                                            transport=t, observers=ob, charge=charge[i])
                 for i in range(self.B)]
 
     def thermostat_state(self, d: dict, i: int) -> dict | None:
@@ -352,7 +379,8 @@ class _DeviceRun:
 class MolecularDynamics:
     """Molecular dynamics on the device (reference MolecularDynamics: same arguments and defaults, plus ``seed``, and
     ``thermostat="Langevin"`` with ``friction`` in 1/fs for NVT and ``thermostat="Nose-Hoover-Chain"`` with ``chain_length`` for NVT and
-    NPT and ``cell_dof`` ("isotropic", "flexible", "axes") for NPT, see the module docstring)."""
+    NPT and ``cell_dof`` ("isotropic", "flexible", "axes") for NPT, and ``log_magmoms`` for the site moments of every frame, see the
+    module docstring)."""
 
     def __init__(self, atoms, *, model=None, ensemble: str = "nvt", thermostat: str = "Berendsen_inhomogeneous", temperature: float = 300,
                  starting_temperature: float | None = None, timestep: float = 2.0, pressure: float = 1.01325e-4, taut: float | None = None,
@@ -360,8 +388,10 @@ class MolecularDynamics:
                  loginterval: int = 1, crystal_feas_logfile: str | None = None, append_trajectory: bool = False,  # noqa: ARG002
                  on_isolated_atoms: str = "warn", return_site_energies: bool = False, use_device: str | None = None,
                  seed: int | None = None, friction: float | None = None, chain_length: int | None = None, fixed_atoms=None,
-                 cell_dof: str = "isotropic", observers: MDObservers | None = None) -> None:
+                 cell_dof: str = "isotropic", observers: MDObservers | None = None, log_magmoms: bool = False) -> None:
         self.ensemble, self.thermostat = ensemble, thermostat
+        self.log_magmoms = bool(log_magmoms)
+        self.magmoms: np.ndarray | None = None    # log_magmoms: float32 [n] of the last completed step
         if observers is not None and not isinstance(observers, MDObservers):
             raise ValueError(f"{observers=} must be an MDObservers")
         self.observers = observers
@@ -457,6 +487,7 @@ class MolecularDynamics:
             if not constrained:
                 self._momenta = self._momenta - self._masses[:, None] * (self._momenta.sum(axis=0) / self._masses.sum())
             self.thermostat_state = None
+        self.magmoms = None              # a new handle: nothing has been evaluated yet
         self._step_offset = getattr(self, "nsteps", 0)
         self.nsteps = self._step_offset
         self.traj = MDTrajectory(self._structure.atomic_numbers)
@@ -483,7 +514,10 @@ class MolecularDynamics:
         return self._momenta
 
     def _observer_kw(self) -> dict:
-        return {} if self.observers is None else {"observers": self.observers}   # without observers the handle is made as it always was
+        kw = {} if self.observers is None else {"observers": self.observers}   # without observers the handle is made as it always was
+        if self.log_magmoms:
+            kw["log_magmoms"] = True
+        return kw
 
     @property
     def observables(self) -> MDObservables:
@@ -531,6 +565,8 @@ class MolecularDynamics:
                 tr.cells.append(d["frame_cell"][k, i].copy())
                 if run.nhc:
                     tr.conserved.append(float(d["frame_conserved"][k, i]) + e)
+                if run.log_magmoms:
+                    tr.magmoms.append(d["frame_magmom"][k, sl].copy())
                 if run.cfea:
                     cfeas[i].append(d["frame_crystal_fea"][k, i].copy())
                 if i == 0:
@@ -573,6 +609,8 @@ class MolecularDynamics:
         self._structure = self._with_fixed(Structure(Lattice(lat), self._structure.atomic_numbers, d["positions"] @ np.linalg.inv(lat)))
         self._momenta = d["momenta"].copy()
         self.thermostat_state = self._run.thermostat_state(d, 0)
+        if self._run.log_magmoms:
+            self.magmoms = d["magmom"].copy()
 
     # ------------------------------------------------------------------------------------------------------------------------
     @classmethod
@@ -581,7 +619,8 @@ class MolecularDynamics:
         alone with ``MolecularDynamics(structures[i], seed=seeds[i], **kwargs).run(steps)`` (with the Langevin thermostat ``seeds[i]`` is
         also replica i's noise key; ``seeds=None`` draws one per replica).  Returns, per replica, ``{"trajectory",
         "final_structure", "momenta", "status", "n_steps", "thermostat_state"}`` (the last one ``None`` unless the thermostat is
-        "Nose-Hoover-Chain"), plus ``"observables"`` when ``observers`` are given (one species map for the whole batch).  ``trajectory`` / ``logfile`` / ``crystal_feas_logfile`` are not
+        "Nose-Hoover-Chain"), plus ``"observables"`` when ``observers`` are given (one species map for the whole batch) and ``"magmoms"``
+        (the last completed step's) with ``log_magmoms=True``.  ``trajectory`` / ``logfile`` / ``crystal_feas_logfile`` are not
         written here.  ``fixed_atoms``: one entry per structure (``None``: that structure's own ``selective_dynamics``, or nothing
         held)."""
         structures = list(structures)
@@ -620,6 +659,8 @@ class MolecularDynamics:
             out.append({"trajectory": tr, "final_structure": fin, "momenta": d["momenta"][sl].copy(),
                         "status": STATUS_NAMES[d["status"][i]], "n_steps": int(d["n_steps"][i]),
                         "thermostat_state": run.thermostat_state(d, i)})
+            if run.log_magmoms:
+                out[-1]["magmoms"] = d["magmom"][sl].copy()
             if observed is not None:
                 out[-1]["observables"] = observed[i]
         return out

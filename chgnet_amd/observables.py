@@ -17,6 +17,12 @@ displacement ``U_a = sum_{i in a} u_i`` and current ``J_a = sum_{i in a} v_i`` o
 conductivity in its Einstein form with the Onsager cross terms, against the Nernst-Einstein estimate from the tracer MSD: the Haven
 ratio), and the histogram of ``|u_i|`` per species at every ``vanhove_stride``-th lag (the self part of the van Hove function).
 
+Charge states (``magmom_states``, ``magmom_bins``, ``state_rdf_bins``; csrc/kernels_md_magmom.h) follow the reference's
+charge-informed MD on the device: every sample classifies each atom's site moment against the boundaries of its element and
+accumulates the moment histogram, mean and spread per species, the populations of the states, the transitions between consecutive
+samples, each site's occupancy of each state, the moment autocorrelation and state persistence over the lags of the ring, and the
+radial distribution around one element resolved by the state of the centre atom.
+
 ``MDObservables`` is plain NumPy on the raw sums (which stay available as attributes), so its arithmetic runs without a device.
 """
 
@@ -36,6 +42,19 @@ _KB = _KB_J / _E                       # eV/K, the value of chgnet_amd.dynamics
 _E2_PER_A_FS_EV_IN_S_PER_CM = _E / (1e-10 * 1e-15) * 1e-2
 
 
+def _atomic_number(key) -> int:
+    """An element given as a symbol or as an atomic number."""
+    from chgnet_amd.graph.structure import SYMBOL_TO_Z, Z_TO_SYMBOL
+
+    if isinstance(key, str):
+        if key not in SYMBOL_TO_Z:
+            raise ValueError(f"unknown element symbol {key!r}")
+        return SYMBOL_TO_Z[key]
+    if isinstance(key, bool) or not isinstance(key, (int, np.integer)) or int(key) not in Z_TO_SYMBOL:
+        raise ValueError(f"{key!r} is neither an element symbol nor an atomic number")
+    return int(key)
+
+
 class MDObservers:
     """What a run accumulates.  ``msd_lags``: lags of the MSD / VACF (0: none, at most 4096), in units of ``sample_interval`` steps;
     ``rdf_rmax`` (A) and ``rdf_bins``: the pair histogram (``rdf_bins=0``: none); ``subtract_com``: displacements relative to the
@@ -45,13 +64,23 @@ class MDObservers:
     Transport, all off by default and each needing ``msd_lags > 0``: ``collective``: the species-by-species correlations of the summed
     displacements and currents (ionic conductivity); ``non_gaussian``: the fourth moment of the displacement; ``vanhove_bins`` bins
     up to ``vanhove_rmax`` (A) of ``|u_i|`` per species at lags 0, ``vanhove_stride``, ..., ``(vanhove_lags - 1) * vanhove_stride``
-    (``vanhove_lags=None``: as many as fit ``msd_lags``).  ``n_species * vanhove_bins`` may not exceed 4096 (``transport_params``)."""
+    (``vanhove_lags=None``: as many as fit ``msd_lags``).  ``n_species * vanhove_bins`` may not exceed 4096 (``transport_params``).
+
+    Charge states, all off by default (csrc/kernels_md_magmom.h; the run then evaluates the site moments every step):
+    ``magmom_states={"Mn": [3.4, 4.2]}``: up to 3 ascending boundaries (mu_B) per element, given by symbol or atomic number; an atom's
+    state is the number of boundaries at or below its moment.  ``magmom_bins`` bins up to ``magmom_max`` of the moments per species;
+    ``state_rdf_bins`` bins up to ``state_rdf_rmax`` (A) of the distances from atoms of ``state_rdf_center`` to every species,
+    resolved by the state of the centre.  ``n_species * magmom_bins`` may not exceed 4096 and ``4 * n_species * state_rdf_bins``
+    16384 (``charge_params``)."""
 
     def __init__(self, sample_interval: int = 1, msd_lags: int = 0, rdf_rmax: float | None = None, rdf_bins: int = 0,
                  subtract_com: bool = True, collective: bool = False, non_gaussian: bool = False, vanhove_bins: int = 0,
-                 vanhove_rmax: float | None = None, vanhove_lags: int | None = None, vanhove_stride: int = 1) -> None:
+                 vanhove_rmax: float | None = None, vanhove_lags: int | None = None, vanhove_stride: int = 1,
+                 magmom_states: dict | None = None, magmom_bins: int = 0, magmom_max: float | None = None, state_rdf_center=None,
+                 state_rdf_bins: int = 0, state_rdf_rmax: float | None = None) -> None:
         for name, v in (("sample_interval", sample_interval), ("msd_lags", msd_lags), ("rdf_bins", rdf_bins), ("vanhove_bins", vanhove_bins),
-                        ("vanhove_stride", vanhove_stride), *((("vanhove_lags", vanhove_lags),) if vanhove_lags is not None else ())):
+                        ("vanhove_stride", vanhove_stride), ("magmom_bins", magmom_bins), ("state_rdf_bins", state_rdf_bins),
+                        *((("vanhove_lags", vanhove_lags),) if vanhove_lags is not None else ())):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
                 raise ValueError(f"{name}={v!r} must be an integer")
         if sample_interval < 1:
@@ -97,6 +126,74 @@ class MDObservers:
         self.vanhove_rmax = float(vanhove_rmax) if vanhove_bins > 0 else 0.0
         self.vanhove_lags = int(vanhove_lags) if vanhove_bins > 0 else 0
         self.vanhove_stride = int(vanhove_stride)
+        # charge states
+        self.magmom_states = {}
+        for key, bounds in (magmom_states or {}).items():
+            z = _atomic_number(key)
+            b = [float(v) for v in np.atleast_1d(np.asarray(bounds, np.float64))]
+            if len(b) > _lib.MD_CHG_BOUNDS:
+                raise ValueError(f"magmom_states[{key!r}] has {len(b)} boundaries: at most {_lib.MD_CHG_BOUNDS} ({_lib.MD_CHG_STATES} states)")
+            if not all(np.isfinite(v) and v >= 0 for v in b):
+                raise ValueError(f"magmom_states[{key!r}]={b} must be finite and >= 0 (the model's moments are magnitudes)")
+            if any(hi <= lo for lo, hi in zip(b, b[1:])):
+                raise ValueError(f"magmom_states[{key!r}]={b} must be ascending")
+            if z in self.magmom_states:
+                raise ValueError(f"magmom_states names element {z} twice")
+            self.magmom_states[z] = b
+        if magmom_bins < 0 or state_rdf_bins < 0:
+            raise ValueError(f"{magmom_bins=} and {state_rdf_bins=} must be >= 0")
+        if magmom_bins > _lib.MD_CHG_HIST_CELLS:
+            raise ValueError(f"{magmom_bins=} exceeds the {_lib.MD_CHG_HIST_CELLS} moment-histogram cells of the device")
+        if magmom_bins > 0 and (magmom_max is None or not np.isfinite(magmom_max) or not magmom_max > 0):
+            raise ValueError(f"{magmom_max=} must be > 0 and finite when magmom_bins > 0")
+        if magmom_bins == 0 and magmom_max is not None:
+            raise ValueError(f"{magmom_max=} needs magmom_bins > 0")
+        if state_rdf_bins > 0:
+            if state_rdf_center is None:
+                raise ValueError("state_rdf_bins > 0 needs state_rdf_center, the element whose states the distribution is resolved by")
+            if state_rdf_rmax is None or not np.isfinite(state_rdf_rmax) or not state_rdf_rmax > 0:
+                raise ValueError(f"{state_rdf_rmax=} must be > 0 and finite when state_rdf_bins > 0")
+            if _lib.MD_CHG_STATES * state_rdf_bins > _lib.MD_CHG_SRDF_CELLS:
+                raise ValueError(f"{state_rdf_bins=} exceeds the {_lib.MD_CHG_SRDF_CELLS} histogram cells of the device")
+        elif state_rdf_center is not None or state_rdf_rmax is not None:
+            raise ValueError("state_rdf_center and state_rdf_rmax need state_rdf_bins > 0")
+        self.magmom_bins, self.state_rdf_bins = int(magmom_bins), int(state_rdf_bins)
+        self.magmom_max = float(magmom_max) if magmom_bins > 0 else 0.0
+        self.state_rdf_center = _atomic_number(state_rdf_center) if state_rdf_bins > 0 else None
+        self.state_rdf_rmax = float(state_rdf_rmax) if state_rdf_bins > 0 else 0.0
+
+    @property
+    def charge_states(self) -> bool:
+        """Whether any of the charge-state keywords was given (``chg_md_set_charge_states`` is called only then)."""
+        return bool(self.magmom_states or self.magmom_bins or self.state_rdf_bins)
+
+    def charge_params(self, species) -> "tuple[_lib.MdChargeParams, np.ndarray] | None":
+        """What ``chg_md_set_charge_states`` is given for the batch's ``species`` (sorted atomic numbers): the params struct and the
+        boundaries [S, 3]; ``None`` without charge-state keywords.  An element named in ``magmom_states`` or as ``state_rdf_center``
+        that the batch does not hold is refused."""
+        if not self.charge_states:
+            return None
+        species = [int(z) for z in species]
+        S = len(species)
+        for z in self.magmom_states:
+            if z not in species:
+                raise ValueError(f"magmom_states names element {z}, which is not among the species {species} of the run")
+        if self.state_rdf_bins and self.state_rdf_center not in species:
+            raise ValueError(f"state_rdf_center={self.state_rdf_center} is not among the species {species} of the run")
+        if S * self.magmom_bins > _lib.MD_CHG_HIST_CELLS:
+            raise ValueError(f"{S} species x magmom_bins={self.magmom_bins} exceeds the {_lib.MD_CHG_HIST_CELLS} moment-histogram cells "
+                             "of the device: use fewer bins")
+        if _lib.MD_CHG_STATES * S * self.state_rdf_bins > _lib.MD_CHG_SRDF_CELLS:
+            raise ValueError(f"{_lib.MD_CHG_STATES} states x {S} species x state_rdf_bins={self.state_rdf_bins} exceeds the "
+                             f"{_lib.MD_CHG_SRDF_CELLS} histogram cells of the device: use fewer bins")
+        bounds = np.zeros((S, _lib.MD_CHG_BOUNDS))
+        p = _lib.MdChargeParams(mag_bins=self.magmom_bins, center_species=species.index(self.state_rdf_center) if self.state_rdf_bins else -1,
+                                srdf_bins=self.state_rdf_bins, reserved=0, mag_max=self.magmom_max, srdf_rmax=self.state_rdf_rmax)
+        for s, z in enumerate(species):
+            b = self.magmom_states.get(z, [])
+            p.n_bounds[s] = len(b)
+            bounds[s, :len(b)] = b
+        return p, bounds
 
     def species_map(self, atomic_numbers) -> tuple[np.ndarray, np.ndarray]:
         """(species, index): the sorted unique atomic numbers of the batch and every atom's index into them."""
@@ -151,6 +248,38 @@ def download_transport(eng, handle, B: int, L: int, S: int, vh_lags: int, vh_bin
     return d
 
 
+def empty_charge_arrays(B: int, N: int, L: int, S: int, mag_bins: int, srdf_bins: int) -> dict:
+    """Host arrays named like the fields of ``chg_md_charge_host``."""
+    Q = _lib.MD_CHG_STATES
+    return {"mhist": np.zeros((B, S, mag_bins), np.uint64), "msum": np.zeros((B, S)), "msq": np.zeros((B, S)),
+            "pop": np.zeros((B, S, Q), np.int64), "trans": np.zeros((B, S, Q, Q), np.int64), "occ": np.zeros((N, Q), np.int64),
+            "mcorr": np.zeros((B, L, S)), "same": np.zeros((B, L, S, Q), np.int64), "shist": np.zeros((B, Q, S, srdf_bins), np.uint64),
+            "samples": np.zeros(B, np.int64), "skipped": np.zeros(B, np.int64), "vol_sum": np.zeros(B)}
+
+
+def download_charge(eng, handle, B: int, N: int, L: int, S: int, mag_bins: int, srdf_bins: int) -> dict:
+    """``chg_md_download_charge_states`` of a device handle: the raw charge-state sums of all B replicas."""
+    d = empty_charge_arrays(B, N, L, S, mag_bins, srdf_bins)
+    out = _lib.fill_out(_lib.MdChargeHost(), d)
+    eng._check(eng.lib.chg_md_download_charge_states(eng.handle, handle, ctypes.byref(out)))
+    return d
+
+
+class ChargeStateSums:
+    """The raw charge-state sums of ONE replica (include/chgnet_hip.h "Charge-informed MD"): ``mhist`` [S, bins], ``msum`` / ``msq``
+    [S], ``pop`` [S, Q], ``trans`` [S, Q, Q] (from, to), ``occ`` [n, Q], ``mcorr`` [L, S], ``same`` [L, S, Q], ``shist`` [Q, S, bins],
+    ``samples``, ``skipped``, ``vol_sum``, with ``n_bounds`` [S], ``bounds`` [S, 3], ``mag_max``, ``center`` (species index or -1)
+    and ``srdf_rmax``."""
+
+    def __init__(self, d: dict, i: int, atoms: slice, n_bounds, bounds, mag_max: float, center: int, srdf_rmax: float) -> None:
+        for name in ("mhist", "msum", "msq", "pop", "trans", "mcorr", "same", "shist"):
+            setattr(self, name, d[name][i].copy())
+        self.occ = d["occ"][atoms].copy()
+        self.samples, self.skipped, self.vol_sum = int(d["samples"][i]), int(d["skipped"][i]), float(d["vol_sum"][i])
+        self.n_bounds, self.bounds = np.asarray(n_bounds, np.int64).copy(), np.asarray(bounds, np.float64).copy()
+        self.mag_max, self.center, self.srdf_rmax = float(mag_max), int(center), float(srdf_rmax)
+
+
 class MDObservables:
     """The observables of ONE replica from its raw sums.
 
@@ -165,7 +294,8 @@ class MDObservables:
     def __init__(self, species, n_per_species, sample_dt_fs: float, msd_sum=None, vacf_sum=None, cnt=None, rdf_hist=None,
                  rdf_samples: int = 0, vol_sum: float = 0.0, rdf_rmax: float = 0.0, msd4_sum=None, cmsd_sum=None, jacf_sum=None,
                  vanhove_hist=None, vanhove_rmax: float = 0.0, vanhove_stride: int = 1, transport_samples: int = 0,
-                 transport_vol_sum: float = 0.0) -> None:
+                 transport_vol_sum: float = 0.0, charge: "ChargeStateSums | None" = None) -> None:
+        self.charge = charge               # the raw charge-state sums, or None
         self.species = np.asarray(species, np.int64)
         self.n_per_species = np.asarray(n_per_species, np.int64)
         S = len(self.species)
@@ -199,7 +329,7 @@ class MDObservables:
 
     @classmethod
     def from_download(cls, d: dict, i: int, species, index_i, sample_dt_fs: float, rdf_rmax: float, transport: dict | None = None,
-                      observers: "MDObservers | None" = None) -> "MDObservables":
+                      observers: "MDObservers | None" = None, charge: "ChargeStateSums | None" = None) -> "MDObservables":
         """Replica ``i`` of a ``download`` (and of a ``download_transport`` made for ``observers``); ``index_i``: the species index of
         each of its atoms."""
         n_per = np.bincount(np.asarray(index_i), minlength=len(species))
@@ -212,7 +342,7 @@ class MDObservables:
                   "vanhove_stride": ob.vanhove_stride, "transport_samples": int(t["samples"][i]),
                   "transport_vol_sum": float(t["vol_sum"][i])}
         return cls(species, n_per, sample_dt_fs, d["msd"][i].copy(), d["vacf"][i].copy(), d["cnt"][i].copy(), d["rdf"][i].copy(),
-                   int(d["rdf_samples"][i]), float(d["vol_sum"][i]), rdf_rmax, **kw)
+                   int(d["rdf_samples"][i]), float(d["vol_sum"][i]), rdf_rmax, charge=charge, **kw)
 
     def _s(self, z) -> int:
         hit = np.flatnonzero(self.species == int(z))
@@ -369,3 +499,111 @@ class MDObservables:
         upper = np.arange(1, bins + 1) * (self.rdf_rmax / bins)
         inside = upper <= r_cut * (1 + 1e-12)
         return float(self.rdf_hist[sa, sb][inside].sum() / (self.rdf_samples * self.n_per_species[sa]))
+
+    # ---- charge states --------------------------------------------------------------------------------------------------------
+    def _charge(self) -> ChargeStateSums:
+        if self.charge is None:
+            raise ValueError("no charge states were accumulated: pass magmom_states, magmom_bins or state_rdf_bins to MDObservers")
+        return self.charge
+
+    def n_states(self, species) -> int:
+        """The number of states of the species: its boundaries plus one."""
+        return int(self._charge().n_bounds[self._s(species)]) + 1
+
+    def _counted(self, s: int) -> int:
+        return int(self._charge().pop[s].sum())          # atom-samples of the species with a finite moment
+
+    @property
+    def magmom_bin_centres(self) -> np.ndarray:
+        c = self._charge()
+        bins = c.mhist.shape[1]
+        return (np.arange(bins) + 0.5) * (c.mag_max / bins) if bins else np.zeros(0)
+
+    def magmom_histogram(self, species) -> np.ndarray:
+        """[magmom_bins] per mu_B: the probability density of the moments of the species over atoms and samples; moments at or beyond
+        ``magmom_max`` are not counted, so it integrates to the fraction below."""
+        c, s = self._charge(), self._s(species)
+        bins = c.mhist.shape[1]
+        if bins == 0:
+            raise ValueError("no moment histogram was accumulated: pass magmom_bins to MDObservers")
+        n = self._counted(s)
+        return c.mhist[s].astype(np.float64) / (n * c.mag_max / bins) if n else np.full(bins, np.nan)
+
+    def mean_magmom(self, species) -> float:
+        """mu_B: the mean moment of the species over atoms and samples."""
+        s = self._s(species)
+        n = self._counted(s)
+        return float(self._charge().msum[s] / n) if n else float("nan")
+
+    def magmom_std(self, species) -> float:
+        """mu_B: the standard deviation of the moments of the species over atoms and samples."""
+        s = self._s(species)
+        n = self._counted(s)
+        if not n:
+            return float("nan")
+        c = self._charge()
+        return float(np.sqrt(max(c.msq[s] / n - (c.msum[s] / n) ** 2, 0.0)))
+
+    def state_populations(self, species) -> np.ndarray:
+        """[states] the fraction of atom-samples of the species in each state."""
+        s = self._s(species)
+        n = self._counted(s)
+        pop = self._charge().pop[s, :self.n_states(species)].astype(np.float64)
+        return pop / n if n else np.full(len(pop), np.nan)
+
+    def transition_counts(self, species) -> np.ndarray:
+        """[states, states] (from, to): atoms of the species seen in ``from`` at one sample and in ``to`` at the next; the diagonal
+        counts those that stayed."""
+        q = self.n_states(species)
+        return self._charge().trans[self._s(species), :q, :q].copy()
+
+    def transition_rate(self, species, q_from: int, q_to: int) -> float:
+        """Per ps: transitions ``q_from -> q_to`` per atom-sample spent in ``q_from`` (with a following sample) and per sample spacing."""
+        t = self.transition_counts(species)
+        if not (0 <= q_from < len(t) and 0 <= q_to < len(t)):
+            raise ValueError(f"states {q_from}, {q_to} are not among the {len(t)} states of species {species}")
+        base = t[q_from].sum()
+        return float(t[q_from, q_to] / base / (self.sample_dt_fs * 1e-3)) if base else float("nan")
+
+    def state_persistence(self, species, q: int) -> np.ndarray:
+        """[L] same[l] / same[0] per time origin: the fraction of atoms found in state ``q`` at both ends of lag l (not necessarily
+        in between), relative to lag 0; nan where the lag was not reached."""
+        if not 0 <= q < self.n_states(species):
+            raise ValueError(f"state {q} is not among the {self.n_states(species)} states of species {species}")
+        per = self._per_origin(self._charge().same[:, self._s(species), q].astype(np.float64))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(per[:1] > 0, per / per[:1], np.nan) if len(per) else per
+
+    def magmom_correlation(self, species) -> np.ndarray:
+        """[L] mu_B^2: <m_i(t) m_i(0)> per atom of the species and time origin."""
+        return self._per_atom_and_origin(self._charge().mcorr, species)
+
+    def site_occupancy(self) -> np.ndarray:
+        """[n, Q] the fraction of its counted samples every atom spent in each state (nan for an atom never counted)."""
+        occ = self._charge().occ.astype(np.float64)
+        tot = occ.sum(axis=1, keepdims=True)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(tot > 0, occ / tot, np.nan)
+
+    @property
+    def state_rdf_r(self) -> np.ndarray:
+        c = self._charge()
+        bins = c.shist.shape[2]
+        return (np.arange(bins) + 0.5) * (c.srdf_rmax / bins) if bins else np.zeros(0)
+
+    def state_rdf(self, q: int, species_b) -> np.ndarray:
+        """g(r) [state_rdf_bins] of ``species_b`` around the centre atoms that are in state ``q``: the histogram over what an ideal gas
+        of the mean density of ``species_b`` puts into each shell around the ``pop[centre, q]`` centre atom-samples."""
+        c, sb = self._charge(), self._s(species_b)
+        bins = c.shist.shape[2]
+        if bins == 0 or c.center < 0 or c.samples == 0:
+            raise ValueError("no state-resolved radial distribution was accumulated: pass state_rdf_bins to MDObservers")
+        if not 0 <= q < int(c.n_bounds[c.center]) + 1:
+            raise ValueError(f"state {q} is not among the states of the centre species")
+        centres = int(c.pop[c.center, q])
+        if centres == 0 or self.n_per_species[sb] == 0:
+            raise ValueError(f"no centre atom was ever in state {q}, or the replica has no atom of species {species_b}")
+        edges = np.arange(bins + 1) * (c.srdf_rmax / bins)
+        shell = 4.0 / 3.0 * np.pi * (edges[1:] ** 3 - edges[:-1] ** 3)
+        density = self.n_per_species[sb] / (c.vol_sum / c.samples)
+        return c.shist[q, sb].astype(np.float64) / (centres * density * shell)

@@ -118,7 +118,8 @@ typedef struct chg_out_host {
  * so were chg_md_set_observers, chg_md_download_observables and chg_test_md_observe: their parameters and results travel in two structs
  * of their own, chg_md_observe_params and chg_md_observables_host, and no older struct or signature changed;
  * so were chg_md_set_transport, chg_md_download_transport and chg_test_md_transport, with chg_md_transport_params and
- * chg_md_transport_host).  A binding compiled against another value must refuse the
+ * chg_md_transport_host; so were chg_md_set_magmoms, chg_md_download_magmoms, chg_md_set_charge_states, chg_md_download_charge_states
+ * and chg_test_md_charge_states, with chg_md_charge_params and chg_md_charge_host).  A binding compiled against another value must refuse the
  * library: chg_engine_create COPIES *desc, so an older, shorter chg_model_desc would be read past its end. */
 #define CHG_ABI_VERSION 5
 int chg_abi_version(void);
@@ -593,6 +594,84 @@ int chg_test_md_transport(chg_engine* eng, const chg_md_observe_params* params, 
                           const int32_t* atom_off, const int32_t* species, const double* masses, int32_t n_samples,
                           const double* positions, const double* momenta, const double* cell, const int32_t* status,
                           const chg_md_observables_host* plain, const chg_md_transport_host* out);
+
+/* ---- Charge-informed MD: site magnetic moments per frame and charge-state observers (csrc/kernels_md_magmom.h; DESIGN.md "MD
+ * observables -> Charge states"; tests/md_charge_ref.py restates the sums in NumPy) ------------------------------------------------
+ * Both are opt-in; a handle that uses neither evaluates the task it always did and launches what it always launched.
+ *
+ * chg_md_set_magmoms adds CHG_TASK_M to what every evaluation of the handle predicts.  After every evaluation that COMPLETES a step
+ * (step 0 included; not NPT Berendsen's first evaluation) one more launch copies the moments of every replica that wrote its frame --
+ * CHG_MD_RUNNING and not held back for the wide-range retry, whose launch then writes them -- into an array of the last completed
+ * step and, with log_frames, into a float [N] slot of the ring frame of that step.  A non-finite moment is stored as it is.  Valid
+ * between create and the first run (a second call replaces the first); CHG_EINVAL with a message afterwards; CHG_ENOMEM when the
+ * slots (4 N (ring_frames + 1) bytes) do not fit.  chg_md_params and chg_md_out_host keep their layout: the moments are read with
+ * chg_md_download_magmoms -- magmom [N] of the last completed step (zeros before the first run), frame_magmom [K,N] of the oldest
+ * min(frames in the ring, frame_capacity) frames in the order chg_md_download returns them (only with log_frames).  The ring is NOT
+ * drained: call it before chg_md_download.  Null pointers are skipped.  CHG_EINVAL on a handle without chg_md_set_magmoms (the
+ * charge-state observers below imply it without frame slots). */
+int chg_md_set_magmoms(chg_engine* eng, chg_md* md, int32_t log_frames);
+int chg_md_download_magmoms(chg_engine* eng, chg_md* md, float* magmom /* [N], may be null */, float* frame_magmom /* [K,N] */,
+                            int32_t frame_capacity);
+
+/* Charge-state observers hang on the observers (chg_md_set_observers; n_lags = L may be 0) and use their sample_interval, sample
+ * number k, species map, ring index k % L and status rule; they imply CHG_TASK_M and the gather above.  Species s has n_bounds[s] in
+ * 0..3 ascending boundaries bounds[s][0..n_bounds[s]) (mu_B, >= 0) and so 1..4 states; every array has Q = CHG_MD_CHARGE_STATES slots.
+ * For sample k, a running replica o and atom i of species s, with m = (double)mag_i(k):
+ *   q_i(k) = the number of boundaries of s that are <= m      (a moment exactly on a boundary belongs to the upper state)
+ * An atom whose m is not finite has state -1: it is left out of every sum of that sample and of every lag pair it is part of, and
+ * counted in skipped[o].  Otherwise
+ *   mhist[o,s,floor(m / mag_max * mag_bins)] += 1   if 0 <= m < mag_max            (mag_bins > 0)
+ *   msum[o,s] += m,  msq[o,s] += m^2                                               (summed over the atoms in a fixed order)
+ *   pop[o,s,q_i(k)] += 1,  occ[i,q_i(k)] += 1
+ *   trans[o,s,q_i(k-1),q_i(k)] += 1                 for k >= 1 and q_i(k-1) >= 0   (diagonal included)
+ * and for every lag l in 0 .. min(k, L - 1), over the atoms with q_i(k) >= 0 and q_i(k-l) >= 0
+ *   mcorr[o,l,s] += sum_i m_i(k) m_i(k-l)
+ *   same[o,l,s,q] += the number of i with q_i(k-l) = q_i(k) = q
+ * and, with srdf_bins > 0, for every atom i of species center_species with q_i(k) >= 0, every atom j of the replica (whatever its
+ * moment) and every lattice shift n (i == j with n == 0 excluded) with d = |r_j - r_i + n L| < srdf_rmax
+ *   shist[o,q_i(k),s_j,floor(d / srdf_rmax * srdf_bins)] += 1
+ * with positions and cell of the snapshot the plain observers read; per sample samples[o] += 1 and vol_sum[o] += |det L|.  cnt[o,l]
+ * of chg_md_observables_host normalises the lag sums.  Float64 and integers, no floating-point atomics, every float cell has one
+ * owning workgroup: two runs of the same input give the same bits.  chg_md_set_charge_states is valid after chg_md_set_observers and
+ * before the first run (a second call replaces the first; a later chg_md_set_observers drops it); CHG_EINVAL with a message for: no
+ * observers; n_bounds outside 0..3; boundaries that are not finite, not ascending or negative; nothing requested (no boundary,
+ * mag_bins == 0 and srdf_bins == 0); mag_bins < 0 or n_species * mag_bins > 4096; with mag_bins > 0 a mag_max that is not finite and
+ * positive; srdf_bins < 0 or Q * n_species * srdf_bins > 16384; srdf_bins > 0 without a center_species in 0 .. n_species - 1 or a
+ * finite positive srdf_rmax; a call after the first run.  CHG_ENOMEM when the ring (12 L N bytes) and the sums do not fit. */
+#define CHG_MD_CHARGE_STATES 4
+#define CHG_MD_CHARGE_BOUNDS 3
+typedef struct chg_md_charge_params {
+  int32_t n_bounds[8];      /* per species, 0..3; entries from n_species on are ignored */
+  int32_t mag_bins;         /* 0: no moment histogram */
+  int32_t center_species;   /* -1: none */
+  int32_t srdf_bins;        /* 0: no state-resolved RDF */
+  int32_t reserved;
+  double mag_max;           /* mu_B, > 0 when mag_bins > 0 */
+  double srdf_rmax;         /* A, > 0 when srdf_bins > 0 */
+} chg_md_charge_params;
+int chg_md_set_charge_states(chg_engine* eng, chg_md* md, const chg_md_charge_params* params, const double* bounds /* [S,3] */);
+typedef struct chg_md_charge_host {
+  uint64_t* mhist;          /* [B,S,mag_bins] */
+  double* msum;             /* [B,S] */
+  double* msq;              /* [B,S] */
+  int64_t* pop;             /* [B,S,Q] */
+  int64_t* trans;           /* [B,S,Q,Q] from, to */
+  int64_t* occ;             /* [N,Q] */
+  double* mcorr;            /* [B,L,S] */
+  int64_t* same;            /* [B,L,S,Q] */
+  uint64_t* shist;          /* [B,Q,S,srdf_bins] */
+  int64_t* samples;         /* [B] */
+  int64_t* skipped;         /* [B] */
+  double* vol_sum;          /* [B] A^3 */
+} chg_md_charge_host;
+/* The accumulators as they stand; null pointers are skipped.  CHG_EINVAL for a handle without charge-state observers. */
+int chg_md_download_charge_states(chg_engine* eng, chg_md* md, const chg_md_charge_host* out);
+/* Tests only: chg_test_md_observe plus the moments magmoms [T,N] of every snapshot, through exactly the ring logic and kernels of a
+ * run; plain (the sums of the observers) may be null. */
+int chg_test_md_charge_states(chg_engine* eng, const chg_md_observe_params* params, const chg_md_charge_params* charge, const double* bounds,
+                              int32_t n_struct, const int32_t* atom_off, const int32_t* species, const double* masses, int32_t n_samples,
+                              const double* positions, const double* momenta, const double* cell, const int32_t* status,
+                              const float* magmoms, const chg_md_observables_host* plain, const chg_md_charge_host* out);
 
 /* ---- canonical Monte Carlo: species swaps and single-atom displacements, every structure an independent replica -----------------
  * Not in the reference.  Every replica has a fixed cell, its own temperature (K, >= 0; 0 is greedy descent) and its own 64-bit seed; its

@@ -16,6 +16,12 @@ of R = 1, 8, 64 replicas of the 256-atom 2x2x2 Li9Co7O16 cell, NVT Berendsen at 
       --observe --transport   the same leg with the transport accumulators on top (collective displacements and currents, the
                               non-Gaussian parameter, van Hove histograms of 64 bins up to 4 A at every 16th lag); lines go to
                               profiles/md_transport_probe.jsonl unless --out is given.  Compare it with --observe alone
+      --magmoms               evaluate the site moments every step and keep those of the logged frames (log_magmoms=True: task M plus
+                              one gather launch per step); lines go to profiles/md_magmom_probe.jsonl unless --out is given.  Compare
+                              it with the plain leg of the same session
+      --observe --charge-states  the --observe leg with the charge-state observers on top (Co states split at 0.5 and 1.0 mu_B, O at
+                              0.1, a moment histogram of 64 bins up to 2 mu_B, the Co-centred state-resolved RDF with 100 bins up to
+                              6 A); same file.  Compare it with --observe alone
   --leg host                  one replica, BerendsenNVT + CHGNetCalculator.calculate per step
 
 Weights: the trained-like golden set (tests/golden/weights_trained_like.npz).  Run every leg under its own time limit.
@@ -56,12 +62,19 @@ def main() -> None:
     ap.add_argument("--fixed-fraction", type=float, default=0.0)
     ap.add_argument("--observe", action="store_true")
     ap.add_argument("--transport", action="store_true", help="with --observe")
+    ap.add_argument("--magmoms", action="store_true")
+    ap.add_argument("--charge-states", action="store_true", help="with --observe")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.transport and not args.observe:
         ap.error("--transport belongs to --observe")
+    if args.charge_states and not args.observe:
+        ap.error("--charge-states belongs to --observe")
+    if args.magmoms and args.leg != "device":
+        ap.error("--magmoms belongs to --leg device")
     if args.out is None:
-        name = "md_transport_probe.jsonl" if args.transport else "md_observe_probe.jsonl" if args.observe else "md_device_probe.jsonl"
+        name = ("md_magmom_probe.jsonl" if args.magmoms or args.charge_states else "md_transport_probe.jsonl" if args.transport
+                else "md_observe_probe.jsonl" if args.observe else "md_device_probe.jsonl")
         args.out = os.path.join(REPO, "profiles", name)
     if args.observe and args.leg != "device":
         ap.error("--observe belongs to --leg device")
@@ -99,8 +112,14 @@ def main() -> None:
             observe = {"sample_interval": 1, "msd_lags": 256, "rdf_bins": 200, "rdf_rmax": 6.0}
             if args.transport:
                 observe.update(collective=True, non_gaussian=True, vanhove_bins=64, vanhove_rmax=4.0, vanhove_stride=16)
+            if args.charge_states:
+                observe.update(magmom_states={27: [0.5, 1.0], 8: [0.1]}, magmom_bins=64, magmom_max=2.0, state_rdf_center=27, state_rdf_bins=100,
+                               state_rdf_rmax=6.0)
             kw.update(observers=MDObservers(**observe))
-            out.update(observe=observe)
+            out.update(observe={k: ({str(z): b for z, b in v.items()} if isinstance(v, dict) else v) for k, v in observe.items()})
+        if args.magmoms:
+            kw.update(log_magmoms=True)
+            out.update(magmoms=True)
         MolecularDynamics.run_batch(cells, 5, seeds=list(range(R)), **kw)          # warm-up: engine creation, first builds
         for rep in range(args.repeats):
             t0 = time.perf_counter()
@@ -118,6 +137,13 @@ def main() -> None:
                 out.update(li_collective_msd_A2=float(ob.collective_msd(3, 3)[reached]), li_alpha2=float(ob.non_gaussian_parameter(3)[reached]),
                            transport_samples=int(ob.transport_samples),
                            li_vanhove_inside=float(ob.vanhove_hist[0, ob._s(3)].sum() / (ob.cnt[0] * ob.n_per_species[ob._s(3)])))
+            if args.charge_states:               # what a user reads off: the Co moments and how the Co atoms spread over their states
+                out.update(co_mean_magmom=ob.mean_magmom(27), co_magmom_std=ob.magmom_std(27), co_state_populations=ob.state_populations(27).tolist(),
+                           co_transitions=int(ob.transition_counts(27).sum() - np.trace(ob.transition_counts(27))),
+                           charge_samples=int(ob.charge.samples))
+            if args.magmoms:
+                out.update(co_last_magmom_mean=float(np.mean(res[0]["magmoms"][np.asarray(cells[0].atomic_numbers) == 27])),
+                           frames_with_magmoms=len(res[0]["trajectory"].magmoms))
             lines.append(json.dumps(out))
     else:
         from chgnet_amd.md import BerendsenNVT
