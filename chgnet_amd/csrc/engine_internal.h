@@ -262,6 +262,33 @@ struct Carver {
   }
 };
 
+// One device block for the arrays carve(Carver&) takes: called once to size the block and once, after the allocation, to place them.
+// Gives the base and the byte count; on failure *mem is null and the error reads "<fn>: <what> of <n> bytes<detail> cannot be allocated".
+template <class Carve>
+int alloc_block(chg_engine* eng, const char* fn, const char* what, Carve&& carve, char** mem, size_t* bytes = nullptr, const std::string& detail = "") {
+  Carver sizer{nullptr};
+  carve(sizer);
+  if (bytes) *bytes = sizer.pos;
+  if (hipMalloc(mem, sizer.pos) != hipSuccess) {
+    (void)hipGetLastError();
+    *mem = nullptr;
+    eng->err = std::string(fn) + ": " + what + " of " + std::to_string(sizer.pos) + " bytes" + detail + " cannot be allocated";
+    return CHG_ENOMEM;
+  }
+  Carver placer{*mem};
+  carve(placer);
+  return CHG_OK;
+}
+
+// a device allocation that is freed with its owner
+struct DeviceBlock {
+  char* p = nullptr;
+  DeviceBlock() = default;
+  DeviceBlock(const DeviceBlock&) = delete;
+  DeviceBlock& operator=(const DeviceBlock&) = delete;
+  ~DeviceBlock() { if (p) hipFree(p); }
+};
+
 inline dim3 g1(int64_t n, int b = 256) { return dim3((unsigned)std::max<int64_t>(1, (n + b - 1) / b)); }
 inline int wave_grid(chg_engine* eng, int64_t items) {   // one wave per item, 4 waves per block, grid-stride
   return (int)std::max<int64_t>(1, std::min<int64_t>((items + 3) / 4, 16 * (int64_t)eng->num_cus));

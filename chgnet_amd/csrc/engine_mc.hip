@@ -367,18 +367,9 @@ int chg_mc_set_exchange(chg_engine* eng, chg_mc* d, const int32_t* ladder, int32
   HIP_TRY(eng, hipSetDevice(eng->device));
   const std::vector<int> xi = initial_xi(B, ladder);
   const size_t n0 = pairs.list[0].size(), n1 = pairs.list[1].size();
-  Carver sizer{nullptr};
-  sizer.take<int>(xi.size()); sizer.take<int>(n0); sizer.take<int>(n1);
   char* mem = nullptr;
-  if (hipMalloc(&mem, sizer.pos) != hipSuccess) {
-    (void)hipGetLastError();
-    eng->err = std::string(fn) + ": exchange state of " + std::to_string(sizer.pos) + " bytes cannot be allocated";
-    return CHG_ENOMEM;
-  }
-  Carver c{mem};
-  int* d_xi = c.take<int>(xi.size());
-  int* d_p0 = c.take<int>(n0);
-  int* d_p1 = c.take<int>(n1);
+  int *d_xi = nullptr, *d_p0 = nullptr, *d_p1 = nullptr;
+  TRY(alloc_block(eng, fn, "exchange state", [&](Carver& c) { d_xi = c.take<int>(xi.size()); d_p0 = c.take<int>(n0); d_p1 = c.take<int>(n1); }, &mem));
   StateUpload up{eng, fn};
   up(d_xi, xi.data(), sizeof(int) * xi.size());
   if (n0) up(d_p0, pairs.list[0].data(), sizeof(int) * n0);

@@ -11,49 +11,11 @@
 // moves the atoms and the forces are evaluated again before the first half kick.  The Nose-Hoover-chain NPT scales the cell inside
 // the step and takes one evaluation (task efs) like every other ensemble.  chg_md_set_magmoms / chg_md_set_charge_states add the site
 // moments to the task and one gather launch (kernels_md_magmom.h) after the step launch of every evaluation that completes a step.
+// The observers' host side is engine_md_observe.h; this unit creates them, asks sample_due and hands observe() the frame of a sample.
 #include "engine_stepper.h"
 
 #include "kernels_md.h"
-#include "kernels_md_obs.h"
-#include "kernels_md_transport.h"
-#include "kernels_md_magmom.h"
-
-// chg_md_set_charge_states / chg_test_md_charge_states: parameters and one device allocation of its own (boundaries, moment and state
-// ring, accumulators, and for a run the moment slot of the observers' private frame)
-struct MdCharge {
-  chg_md_charge_params p{};
-  char* mem = nullptr;
-  double *bounds = nullptr, *ring_m = nullptr, *msum = nullptr, *msq = nullptr, *mcorr = nullptr, *vol_sum = nullptr;
-  int *n_bounds = nullptr, *ring_q = nullptr, *prev_q = nullptr;
-  unsigned long long *mhist = nullptr, *shist = nullptr;
-  long long *pop = nullptr, *trans = nullptr, *occ = nullptr, *same = nullptr, *samples = nullptr, *skipped = nullptr;
-  float* fr_mag = nullptr;
-};
-
-// chg_md_set_transport / chg_test_md_transport: parameters and one device allocation of its own (current ring and accumulators)
-struct MdTransport {
-  chg_md_transport_params p{};
-  char* mem = nullptr;
-  double *ring_j = nullptr, *msd4 = nullptr, *cmsd = nullptr, *jacf = nullptr, *vol_sum = nullptr;
-  unsigned long long* vh = nullptr;
-  long long* samples = nullptr;
-};
-
-// chg_md_set_observers / chg_test_md_observe: parameters, one device allocation of its own (ring, accumulators, and for a run the
-// private frame slot), and the number of samples taken
-struct MdObservers {
-  chg_md_observe_params p{};
-  int B = 0, N = 0, n_max = 0;   // n_max: atoms of the largest replica (grid of k_md_obs_rdf)
-  long long k = 0;               // samples taken
-  char* mem = nullptr;
-  int* species = nullptr;
-  double *ring_pos = nullptr, *ring_vel = nullptr, *ring_com = nullptr, *msd = nullptr, *vacf = nullptr, *vol_sum = nullptr;
-  long long *cnt = nullptr, *rdf_samples = nullptr;
-  unsigned long long* hist = nullptr;
-  chg::MdFrame fr{};             // private frame slot: what the step kernels write of a completed step that is sampled but not logged
-  MdTransport* tr = nullptr;     // chg_md_set_transport: reads the ring above
-  MdCharge* cs = nullptr;        // chg_md_set_charge_states: its own ring, the same sample number and slot
-};
+#include "engine_md_observe.h"
 
 // the chg_md_create* / chg_test_md_step* entry point that was called: it decides which ensembles may run (bad_params)
 enum class MdEntry { Plain, Langevin, Nhc, NhcFlex };
@@ -82,10 +44,11 @@ struct chg_md : chgh::Stepper {
   int K = 0, ring_head = 0, ring_count = 0;
   std::vector<int> ring_step;
   std::vector<chg::MdFrame> ring;        // cfea only when logged, cons only for Nose-Hoover chains
-  MdObservers* obs = nullptr;            // chg_md_set_observers
+  std::unique_ptr<MdObservers> obs;      // chg_md_set_observers
   // chg_md_set_magmoms (or implied by chg_md_set_charge_states): task M, k_md_mag_gather after every evaluation that completes a step
   bool mag = false, mag_frames = false;
-  float *mag_mem = nullptr, *mag_last = nullptr;   // [N] moments of the last completed step, then the ring frames' slots
+  DeviceBlock mag_mem;
+  float* mag_last = nullptr;   // [N] moments of the last completed step, then the ring frames' slots
 };
 
 namespace {
@@ -95,20 +58,6 @@ constexpr int FEA = chg::D;
 bool is_npt(int e) { return e == MD_NPT_BERENDSEN_INHOMOGENEOUS || e == MD_NPT_BERENDSEN; }   // the two-evaluation Berendsen loop
 bool is_flex(int e) { return e == MD_NPT_NHC_FLEX || e == MD_NPT_NHC_AXES; }   // chg_md_create_nhc_flex only
 bool is_nhc(int e) { return e == MD_NVT_NHC || e == MD_NPT_NHC || is_flex(e); }
-
-// one frame slot
-MdFrame carve_frame(Carver& c, size_t B, size_t N, bool cfea, bool cons) {
-  MdFrame f{};
-  f.scal = c.take<double>(MD_FRAME_SCAL * B);
-  f.pos = c.take<double>(3 * N);
-  f.mom = c.take<double>(3 * N);
-  f.cell = c.take<double>(9 * B);
-  f.force = c.take<float>(3 * N);
-  f.stress = c.take<float>(9 * B);
-  if (cfea) f.cfea = c.take<float>(FEA * B);
-  if (cons) f.cons = c.take<double>(B);
-  return f;
-}
 
 void carve_md(chg_md* d, Carver& c) {
   const size_t B = d->B, N = d->N;
@@ -289,382 +238,40 @@ int create(chg_engine* eng, const char* fn, const chg_structs_host* h, const dou
   return CHG_OK;
 }
 
-// ---- observers (kernels_md_obs.h)
-
-const char* bad_observe(const chg_md_observe_params* p) {
-  if (p->sample_interval < 1) return "sample_interval must be >= 1";
-  if (p->n_lags < 0 || p->n_lags > MD_OBS_MAX_LAGS) return "n_lags must be 0..4096";
-  if (p->n_species < 1 || p->n_species > MD_OBS_SPECIES) return "n_species must be 1..8";
-  if (p->rdf_bins < 0) return "rdf_bins must be >= 0";
-  if (p->rdf_bins > 0 && (!(p->rdf_rmax > 0.0) || !std::isfinite(p->rdf_rmax))) return "rdf_rmax must be > 0 and finite";
-  if ((int64_t)p->n_species * p->n_species * p->rdf_bins > MD_OBS_RDF_CELLS)
-    return "n_species * n_species * rdf_bins must be <= 16384 (the histogram lives in 64 KB of LDS)";
-  if (p->n_lags == 0 && p->rdf_bins == 0) return "nothing to observe: n_lags and rdf_bins are both 0";
-  return nullptr;
-}
-
-void carve_obs(MdObservers* x, Carver& c, bool frame_slot) {
-  const size_t B = x->B, N = x->N, L = x->p.n_lags, S = x->p.n_species, bins = x->p.rdf_bins;
-  x->species = c.take<int>(N);
-  x->ring_pos = c.take<double>(L * 3 * N);
-  x->ring_vel = c.take<double>(L * 3 * N);
-  x->ring_com = c.take<double>(L * 3 * B);
-  x->msd = c.take<double>(B * L * S);
-  x->vacf = c.take<double>(B * L * S);
-  x->cnt = c.take<long long>(B * L);
-  x->hist = c.take<unsigned long long>(B * S * S * bins);
-  x->rdf_samples = c.take<long long>(B);
-  x->vol_sum = c.take<double>(B);
-  if (frame_slot) x->fr = carve_frame(c, B, N, false, false);
-}
-
-void free_transport(MdTransport* t) {
-  if (!t) return;
-  if (t->mem) hipFree(t->mem);
-  delete t;
-}
-
-void free_charge(MdCharge* c) {
-  if (!c) return;
-  if (c->mem) hipFree(c->mem);
-  delete c;
-}
-
-void free_observers(MdObservers* x) {
-  if (!x) return;
-  free_transport(x->tr);
-  free_charge(x->cs);
-  if (x->mem) hipFree(x->mem);
-  delete x;
-}
-
-// parameters and species checked, buffers allocated, accumulators zeroed, species uploaded (synchronised)
-int create_observers(chg_engine* eng, const char* fn, const chg_md_observe_params* p, int B, const int* aoff, const int32_t* species,
-                     bool frame_slot, MdObservers** out) {
-  if (const char* bad = bad_observe(p)) { eng->err = std::string(fn) + ": " + bad; return CHG_EINVAL; }
-  const int N = aoff[B];
-  for (int i = 0; i < N; ++i)
-    if (species[i] < 0 || species[i] >= p->n_species) {
-      eng->err = std::string(fn) + ": species index " + std::to_string(species[i]) + " of atom " + std::to_string(i) + " is outside 0.." +
-                 std::to_string(p->n_species - 1);
-      return CHG_EINVAL;
-    }
-  MdObservers* x = new MdObservers();
-  x->p = *p;
-  x->B = B; x->N = N;
-  for (int o = 0; o < B; ++o) x->n_max = std::max(x->n_max, aoff[o + 1] - aoff[o]);
-  Carver sizer{nullptr};
-  carve_obs(x, sizer, frame_slot);
-  if (hipMalloc(&x->mem, sizer.pos) != hipSuccess) {
-    (void)hipGetLastError();
-    x->mem = nullptr;
-    free_observers(x);
-    eng->err = std::string(fn) + ": observer state of " + std::to_string(sizer.pos) + " bytes (ring of " + std::to_string(p->n_lags) +
-               " snapshots) cannot be allocated";
-    return CHG_ENOMEM;
-  }
-  Carver carver{x->mem};
-  carve_obs(x, carver, frame_slot);
-  StateUpload up{eng, fn};
-  up(x->species, species, sizeof(int) * (size_t)N);
-  up.zero(x->msd, (size_t)((char*)(x->vol_sum + B) - (char*)x->msd));   // every accumulator: msd .. vol_sum are carved in a row
-  int s = up.finish();
-  if (s == CHG_OK && p->rdf_bins > 0 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(k_md_obs_rdf), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)(sizeof(unsigned) * p->n_species * p->n_species * p->rdf_bins)) != hipSuccess) {
-    eng->err = std::string(fn) + ": the histogram does not fit the LDS";
-    s = CHG_EHIP;
-  }
-  if (s != CHG_OK) { free_observers(x); return s; }
-  *out = x;
-  return CHG_OK;
-}
-
-// ---- transport accumulators on the observers' ring (kernels_md_transport.h)
-
-const char* bad_transport(const MdObservers* x, const chg_md_transport_params* t) {
-  if (!x || x->p.n_lags == 0) return "transport needs observers with n_lags > 0 (chg_md_set_observers)";
-  if (t->vh_bins < 0) return "vh_bins must be >= 0";
-  if (!t->collective && !t->non_gaussian && t->vh_bins == 0) return "nothing requested: collective, non_gaussian and vh_bins are all 0";
-  if (t->vh_bins > 0) {
-    if (!(t->vh_rmax > 0.0) || !std::isfinite(t->vh_rmax)) return "vh_rmax must be > 0 and finite";
-    if (t->vh_stride < 1) return "vh_stride must be >= 1";
-    if (t->vh_lags < 1) return "vh_lags must be >= 1";
-    if (((int64_t)t->vh_lags - 1) * t->vh_stride >= x->p.n_lags) return "(vh_lags - 1) * vh_stride must be < n_lags";
-    if ((int64_t)x->p.n_species * t->vh_bins > MD_OBS_VH_CELLS) return "n_species * vh_bins must be <= 4096 (the histogram lives in 16 KB of LDS)";
-  }
-  return nullptr;
-}
-
-void carve_transport(const MdObservers* x, MdTransport* t, Carver& c) {
-  const size_t B = x->B, L = x->p.n_lags, S = x->p.n_species;
-  const size_t cells = t->p.vh_bins > 0 ? B * t->p.vh_lags * S * t->p.vh_bins : 0;
-  t->ring_j = c.take<double>(t->p.collective ? L * B * S * 3 : 0);
-  t->msd4 = c.take<double>(t->p.non_gaussian ? B * L * S : 0);
-  t->cmsd = c.take<double>(t->p.collective ? B * L * S * S : 0);
-  t->jacf = c.take<double>(t->p.collective ? B * L * S * S : 0);
-  t->vh = c.take<unsigned long long>(cells);
-  t->samples = c.take<long long>(B);
-  t->vol_sum = c.take<double>(B);
-}
-
-// parameters checked against the observers they hang on, buffers allocated and zeroed (synchronised)
-int create_transport(chg_engine* eng, const char* fn, const MdObservers* x, const chg_md_transport_params* p, MdTransport** out) {
-  if (const char* bad = bad_transport(x, p)) { eng->err = std::string(fn) + ": " + bad; return CHG_EINVAL; }
-  MdTransport* t = new MdTransport();
-  t->p = *p;
-  if (t->p.vh_bins == 0) { t->p.vh_lags = 0; t->p.vh_stride = 1; t->p.vh_rmax = 0.0; }
-  Carver sizer{nullptr};
-  carve_transport(x, t, sizer);
-  if (hipMalloc(&t->mem, sizer.pos) != hipSuccess) {
-    (void)hipGetLastError();
-    t->mem = nullptr;
-    free_transport(t);
-    eng->err = std::string(fn) + ": transport accumulators of " + std::to_string(sizer.pos) + " bytes cannot be allocated";
-    return CHG_ENOMEM;
-  }
-  Carver carver{t->mem};
-  carve_transport(x, t, carver);
-  StateUpload up{eng, fn};
-  up.zero(t->mem, carver.pos);
-  const int s = up.finish();
-  if (s != CHG_OK) { free_transport(t); return s; }
-  *out = t;
-  return CHG_OK;
-}
-
-// the transport kernels of the sample k_md_obs_push has just put into the ring (a: the arguments of that launch)
-void observe_transport(chg_engine* eng, const MdObservers* x, const MdObsArgs& a, unsigned lags) {
-  const MdTransport* t = x->tr;
-  MdTransportArgs b{};
-  b.cell = a.cell; b.species = a.species; b.status = a.status; b.status_stride = a.status_stride; b.aoff = a.aoff;
-  b.N = a.N; b.B = a.B; b.S = a.S;
-  b.ring_pos = a.ring_pos; b.ring_vel = a.ring_vel; b.ring_com = a.ring_com; b.ring_j = t->ring_j; b.L = a.L; b.slot = a.slot; b.k = a.k;
-  b.subtract_com = a.subtract_com; b.collective = t->p.collective != 0; b.non_gaussian = t->p.non_gaussian != 0;
-  b.msd4 = t->msd4; b.cmsd = t->cmsd; b.jacf = t->jacf; b.vh = t->vh; b.samples = t->samples; b.vol_sum = t->vol_sum;
-  b.vh_bins = t->p.vh_bins; b.vh_lags = t->p.vh_lags; b.vh_stride = t->p.vh_stride; b.vh_rmax = t->p.vh_rmax;
-  hipLaunchKernelGGL(k_md_obs_current, dim3((unsigned)x->B), dim3(256), 0, eng->stream, b);
-  hipLaunchKernelGGL(k_md_obs_transport, dim3(lags, (unsigned)x->B), dim3(256), 0, eng->stream, b);
-}
-
-int download_transport(chg_engine* eng, const MdObservers* x, const chg_md_transport_host* o) {
-  const MdTransport* t = x->tr;
-  const size_t B = x->B, L = x->p.n_lags, S = x->p.n_species;
-  TRY(d2h(eng, o->msd4, t->msd4, t->p.non_gaussian ? B * L * S : 0));
-  TRY(d2h(eng, o->cmsd, t->cmsd, t->p.collective ? B * L * S * S : 0));
-  TRY(d2h(eng, o->jacf, t->jacf, t->p.collective ? B * L * S * S : 0));
-  TRY(d2h(eng, (unsigned long long*)o->vh, t->vh, t->p.vh_bins > 0 ? B * t->p.vh_lags * S * t->p.vh_bins : 0));
-  TRY(d2h(eng, (long long*)o->samples, t->samples, B));
-  TRY(d2h(eng, o->vol_sum, t->vol_sum, B));
-  HIP_TRY(eng, hipStreamSynchronize(eng->stream));
-  return CHG_OK;
-}
-
-// ---- charge-state observers on the observers' sample counter (kernels_md_magmom.h)
-
-const char* bad_charge(const MdObservers* x, const chg_md_charge_params* p, const double* bounds) {
-  if (!x) return "charge states need observers (chg_md_set_observers)";
-  const int S = x->p.n_species;
-  int total = 0;
-  for (int s = 0; s < S; ++s) {
-    if (p->n_bounds[s] < 0 || p->n_bounds[s] > MD_CHG_BOUNDS) return "n_bounds must be 0..3";
-    for (int j = 0; j < p->n_bounds[s]; ++j) {
-      const double v = bounds[MD_CHG_BOUNDS * s + j];
-      if (!std::isfinite(v) || v < 0.0 || (j > 0 && !(v > bounds[MD_CHG_BOUNDS * s + j - 1]))) return "boundaries must be finite, >= 0 and ascending";
-    }
-    total += p->n_bounds[s];
-  }
-  if (p->mag_bins < 0) return "mag_bins must be >= 0";
-  if (p->srdf_bins < 0) return "srdf_bins must be >= 0";
-  if (total == 0 && p->mag_bins == 0 && p->srdf_bins == 0) return "nothing requested: no boundary, mag_bins and srdf_bins are 0";
-  if ((int64_t)S * p->mag_bins > MD_CHG_HIST_CELLS) return "n_species * mag_bins must be <= 4096 (the histogram lives in 16 KB of LDS)";
-  if (p->mag_bins > 0 && (!(p->mag_max > 0.0) || !std::isfinite(p->mag_max))) return "mag_max must be > 0 and finite";
-  if ((int64_t)MD_CHG_STATES * S * p->srdf_bins > MD_CHG_SRDF_CELLS)
-    return "4 * n_species * srdf_bins must be <= 16384 (the histogram lives in 64 KB of LDS)";
-  if (p->srdf_bins > 0) {
-    if (p->center_species < 0 || p->center_species >= S) return "center_species must be 0 .. n_species - 1 when srdf_bins > 0";
-    if (!(p->srdf_rmax > 0.0) || !std::isfinite(p->srdf_rmax)) return "srdf_rmax must be > 0 and finite";
-  }
-  return nullptr;
-}
-
-void carve_charge(const MdObservers* x, MdCharge* c, Carver& k, bool frame_slot) {
-  const size_t B = x->B, N = x->N, L = x->p.n_lags, S = x->p.n_species, Q = MD_CHG_STATES;
-  c->bounds = k.take<double>(S * MD_CHG_BOUNDS);
-  c->n_bounds = k.take<int>(S);
-  c->ring_m = k.take<double>(L * N);
-  c->ring_q = k.take<int>(L * N);
-  c->prev_q = k.take<int>(N);
-  c->mhist = k.take<unsigned long long>(B * S * c->p.mag_bins);
-  c->msum = k.take<double>(B * S);
-  c->msq = k.take<double>(B * S);
-  c->pop = k.take<long long>(B * S * Q);
-  c->trans = k.take<long long>(B * S * Q * Q);
-  c->occ = k.take<long long>(N * Q);
-  c->mcorr = k.take<double>(B * L * S);
-  c->same = k.take<long long>(B * L * S * Q);
-  c->shist = k.take<unsigned long long>(B * Q * S * c->p.srdf_bins);
-  c->samples = k.take<long long>(B);
-  c->skipped = k.take<long long>(B);
-  c->vol_sum = k.take<double>(B);
-  if (frame_slot) c->fr_mag = k.take<float>(N);
-}
-
-// parameters checked against the observers they hang on, buffers allocated and zeroed, boundaries uploaded (synchronised)
-int create_charge(chg_engine* eng, const char* fn, const MdObservers* x, const chg_md_charge_params* p, const double* bounds, bool frame_slot,
-                  MdCharge** out) {
-  if (const char* bad = bad_charge(x, p, bounds)) { eng->err = std::string(fn) + ": " + bad; return CHG_EINVAL; }
-  MdCharge* c = new MdCharge();
-  c->p = *p;
-  const int S = x->p.n_species;
-  if (c->p.mag_bins == 0) c->p.mag_max = 0.0;
-  if (c->p.srdf_bins == 0) { c->p.center_species = -1; c->p.srdf_rmax = 0.0; }
-  Carver sizer{nullptr};
-  carve_charge(x, c, sizer, frame_slot);
-  if (hipMalloc(&c->mem, sizer.pos) != hipSuccess) {
-    (void)hipGetLastError();
-    c->mem = nullptr;
-    free_charge(c);
-    eng->err = std::string(fn) + ": charge-state ring and accumulators of " + std::to_string(sizer.pos) + " bytes cannot be allocated";
-    return CHG_ENOMEM;
-  }
-  Carver carver{c->mem};
-  carve_charge(x, c, carver, frame_slot);
-  std::vector<double> hb((size_t)S * MD_CHG_BOUNDS, 0.0);
-  for (int s = 0; s < S; ++s)
-    for (int j = 0; j < p->n_bounds[s]; ++j) hb[MD_CHG_BOUNDS * s + j] = bounds[MD_CHG_BOUNDS * s + j];
-  StateUpload up{eng, fn};
-  up.zero(c->mem, carver.pos);
-  if (up.s == CHG_OK && hipMemsetAsync(c->prev_q, 0xFF, sizeof(int) * (size_t)x->N, eng->stream) != hipSuccess) up.fail("state initialisation failed");
-  up(c->bounds, hb.data(), sizeof(double) * hb.size());
-  up(c->n_bounds, p->n_bounds, sizeof(int) * S);
-  int s = up.finish();
-  if (s == CHG_OK && p->srdf_bins > 0 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(k_md_chg_srdf), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)(sizeof(unsigned) * MD_CHG_STATES * S * p->srdf_bins)) != hipSuccess) {
-    eng->err = std::string(fn) + ": the histogram does not fit the LDS";
-    s = CHG_EHIP;
-  }
-  if (s != CHG_OK) { free_charge(c); return s; }
-  *out = c;
-  return CHG_OK;
-}
-
-// the charge-state kernels of sample x->k (a: the arguments of the plain observers' launches of the same sample; mag: its moments)
-void observe_charge(chg_engine* eng, const MdObservers* x, const MdObsArgs& a, const float* mag) {
-  const MdCharge* c = x->cs;
-  MdChgArgs b{};
-  b.mag = mag; b.pos = a.pos; b.cell = a.cell; b.species = a.species; b.status = a.status; b.status_stride = a.status_stride; b.aoff = a.aoff;
-  b.N = a.N; b.B = a.B; b.S = a.S; b.bounds = c->bounds; b.n_bounds = c->n_bounds;
-  b.ring_m = c->ring_m; b.ring_q = c->ring_q; b.L = a.L; b.slot = a.L > 0 ? (int)(x->k % a.L) : 0; b.k = x->k; b.prev_q = c->prev_q;
-  b.mhist = c->mhist; b.msum = c->msum; b.msq = c->msq; b.pop = c->pop; b.trans = c->trans; b.occ = c->occ; b.mcorr = c->mcorr;
-  b.same = c->same; b.shist = c->shist; b.samples = c->samples; b.skipped = c->skipped; b.vol_sum = c->vol_sum;
-  b.mag_bins = c->p.mag_bins; b.center = c->p.center_species; b.srdf_bins = c->p.srdf_bins; b.mag_max = c->p.mag_max; b.srdf_rmax = c->p.srdf_rmax;
-  hipLaunchKernelGGL(k_md_chg_sample, dim3((unsigned)x->B), dim3(256), 0, eng->stream, b);
-  if (a.L > 0) {
-    const unsigned lags = (unsigned)std::min<long long>(x->k, a.L - 1) + 1;
-    hipLaunchKernelGGL(k_md_chg_corr, dim3(lags, (unsigned)x->B), dim3(256), 0, eng->stream, b);
-  }
-  if (c->p.srdf_bins > 0) {
-    const unsigned chunks = (unsigned)((x->n_max + MD_OBS_RDF_ROWS - 1) / MD_OBS_RDF_ROWS);
-    const size_t lds = sizeof(unsigned) * MD_CHG_STATES * a.S * c->p.srdf_bins;
-    hipLaunchKernelGGL(k_md_chg_srdf, dim3(chunks, (unsigned)x->B), dim3(256), lds, eng->stream, b);
-  }
-}
-
-int download_charge(chg_engine* eng, const MdObservers* x, const chg_md_charge_host* o) {
-  const MdCharge* c = x->cs;
-  const size_t B = x->B, N = x->N, L = x->p.n_lags, S = x->p.n_species, Q = MD_CHG_STATES;
-  TRY(d2h(eng, (unsigned long long*)o->mhist, c->mhist, B * S * c->p.mag_bins));
-  TRY(d2h(eng, o->msum, c->msum, B * S));
-  TRY(d2h(eng, o->msq, c->msq, B * S));
-  TRY(d2h(eng, (long long*)o->pop, c->pop, B * S * Q));
-  TRY(d2h(eng, (long long*)o->trans, c->trans, B * S * Q * Q));
-  TRY(d2h(eng, (long long*)o->occ, c->occ, N * Q));
-  TRY(d2h(eng, o->mcorr, c->mcorr, B * L * S));
-  TRY(d2h(eng, (long long*)o->same, c->same, B * L * S * Q));
-  TRY(d2h(eng, (unsigned long long*)o->shist, c->shist, B * Q * S * c->p.srdf_bins));
-  TRY(d2h(eng, (long long*)o->samples, c->samples, B));
-  TRY(d2h(eng, (long long*)o->skipped, c->skipped, B));
-  TRY(d2h(eng, o->vol_sum, c->vol_sum, B));
-  HIP_TRY(eng, hipStreamSynchronize(eng->stream));
-  return CHG_OK;
-}
-
-// one sample: the snapshot of a completed step through the ring and the accumulators (enqueued on the engine's stream)
-int observe(chg_engine* eng, const char* fn, MdObservers* x, const double* pos, const double* mom, const double* cell, const double* mass,
-            const int* status, int status_stride, const int* d_aoff, const float* mag = nullptr) {
-  LaunchScope ls(eng, "md_observe");
-  const chg_md_observe_params& p = x->p;
-  MdObsArgs a{};
-  a.pos = pos; a.mom = mom; a.cell = cell; a.mass = mass; a.species = x->species; a.status = status; a.status_stride = status_stride;
-  a.aoff = d_aoff; a.N = x->N; a.B = x->B; a.S = p.n_species;
-  a.ring_pos = x->ring_pos; a.ring_vel = x->ring_vel; a.ring_com = x->ring_com; a.L = p.n_lags; a.k = x->k;
-  a.subtract_com = p.subtract_com; a.msd = x->msd; a.vacf = x->vacf; a.cnt = x->cnt;
-  a.hist = x->hist; a.rdf_samples = x->rdf_samples; a.vol_sum = x->vol_sum; a.bins = p.rdf_bins; a.rmax = p.rdf_rmax;
-  if (p.n_lags > 0) {
-    a.slot = (int)(x->k % p.n_lags);
-    const unsigned lags = (unsigned)std::min<long long>(x->k, p.n_lags - 1) + 1;
-    hipLaunchKernelGGL(k_md_obs_push, dim3((unsigned)x->B), dim3(256), 0, eng->stream, a);
-    hipLaunchKernelGGL(k_md_obs_corr, dim3(lags, (unsigned)x->B), dim3(256), 0, eng->stream, a);
-    if (x->tr) observe_transport(eng, x, a, lags);
-  }
-  if (p.rdf_bins > 0) {
-    const unsigned chunks = (unsigned)((x->n_max + MD_OBS_RDF_ROWS - 1) / MD_OBS_RDF_ROWS);
-    const size_t lds = sizeof(unsigned) * p.n_species * p.n_species * p.rdf_bins;
-    hipLaunchKernelGGL(k_md_obs_rdf, dim3(chunks, (unsigned)x->B), dim3(256), lds, eng->stream, a);
-  }
-  if (x->cs) observe_charge(eng, x, a, mag);
-  x->k += 1;
-  if (hipGetLastError() != hipSuccess) { eng->err = std::string(fn) + ": observer kernel launch failed"; return CHG_EHIP; }
-  return CHG_OK;
-}
-
-int download_observables(chg_engine* eng, MdObservers* x, const chg_md_observables_host* o) {
-  const size_t B = x->B, L = x->p.n_lags, S = x->p.n_species, bins = x->p.rdf_bins;
-  TRY(d2h(eng, o->msd, x->msd, B * L * S));
-  TRY(d2h(eng, o->vacf, x->vacf, B * L * S));
-  TRY(d2h(eng, (long long*)o->cnt, x->cnt, B * L));
-  TRY(d2h(eng, (unsigned long long*)o->rdf, x->hist, B * S * S * bins));
-  TRY(d2h(eng, (long long*)o->rdf_samples, x->rdf_samples, B));
-  TRY(d2h(eng, o->vol_sum, x->vol_sum, B));
-  HIP_TRY(eng, hipStreamSynchronize(eng->stream));
-  return CHG_OK;
-}
-
-bool sample_due(const chg_md* d, int step) { return d->obs && step % d->obs->p.sample_interval == 0; }
-
 // one evaluation that completes step `step`: its frame goes to the ring when one is due, to the observers' private slot (not part
 // of the ring, not counted in ring_count) when only a sample is, and the observers read it once the step launch -- a wide-range retry included -- has returned
 int evaluate_step_observe(chg_engine* eng, chg_md* d, MdStepArgs& a, int step) {
-  const bool sample = sample_due(d, step);
+  const bool sample = sample_due(d->obs.get(), step);
   if (frame_due(d, step)) set_frame(d, a, step);
   else if (sample) a.fr = d->obs->fr;
   if (sample && d->obs->cs && !a.fr.mag) a.fr.mag = d->obs->cs->fr_mag;   // a ring frame without moment slots: the observers' own
   TRY(evaluate_and_step(eng, d, a, true));
-  if (sample) TRY(observe(eng, "chg_md_run", d->obs, a.fr.pos, a.fr.mom, a.fr.cell, d->m, d->si + 1, MD_SI, d->d_aoff, a.fr.mag));
+  if (sample) TRY(observe(eng, "chg_md_run", d->obs.get(), a.fr.pos, a.fr.mom, a.fr.cell, d->m, d->si + 1, MD_SI, d->d_aoff, a.fr.mag));
   return CHG_OK;
 }
 
 // task M and the moment slots: [N] of the last completed step, then [N] per ring frame with log_frames
 int enable_magmoms(chg_engine* eng, const char* fn, chg_md* d, bool log_frames) {
   const size_t N = d->N, slots = 1 + (log_frames ? (size_t)d->K : 0);
+  DeviceBlock block;
   float* mem = nullptr;
-  if (hipMalloc(&mem, sizeof(float) * N * slots) != hipSuccess) {
-    (void)hipGetLastError();
-    eng->err = std::string(fn) + ": moment slots of " + std::to_string(sizeof(float) * N * slots) + " bytes cannot be allocated";
-    return CHG_ENOMEM;
-  }
+  TRY(alloc_block(eng, fn, "moment slots", [&](Carver& c) { mem = c.take<float>(N * slots); }, &block.p));
   StateUpload up{eng, fn};
   up.zero(mem, sizeof(float) * N * slots);
-  const int s = up.finish();
-  if (s != CHG_OK) { hipFree(mem); return s; }
-  if (d->mag_mem) hipFree(d->mag_mem);
-  d->mag_mem = d->mag_last = mem;
+  TRY(up.finish());
+  std::swap(d->mag_mem.p, block.p);   // slots of an earlier call go with the block
+  d->mag_last = mem;
   for (int k = 0; k < d->K; ++k) d->ring[k].mag = log_frames ? mem + N * (size_t)(k + 1) : nullptr;
   d->mag = true;
   d->mag_frames = log_frames;
   d->task |= CHG_TASK_M;
+  return CHG_OK;
+}
+
+// the observer and moment setters: before the first chg_md_run only, on the engine's device (chg_md_set_fixed checks its mask in between)
+int before_run(chg_engine* eng, const char* fn, const chg_md* d) {
+  if (d->started) { eng->err = std::string(fn) + ": the run has already started"; return CHG_EINVAL; }
+  HIP_TRY(eng, hipSetDevice(eng->device));
   return CHG_OK;
 }
 }  // namespace
@@ -721,24 +328,17 @@ int chg_md_set_fixed(chg_engine* eng, chg_md* d, const uint8_t* fixed) {
 int chg_md_set_observers(chg_engine* eng, chg_md* d, const chg_md_observe_params* params, const int32_t* species) {
   if (!eng || !d || !params || !species) return CHG_EINVAL;
   const char* fn = "chg_md_set_observers";
-  if (d->started) { eng->err = std::string(fn) + ": the run has already started"; return CHG_EINVAL; }
-  HIP_TRY(eng, hipSetDevice(eng->device));
-  MdObservers* x = nullptr;
-  TRY(create_observers(eng, fn, params, d->B, d->h_aoff, species, true, &x));
-  free_observers(d->obs);
-  d->obs = x;
-  return CHG_OK;
+  TRY(before_run(eng, fn, d));
+  return create_observers(eng, fn, params, d->B, d->h_aoff, species, true, d->obs);   // replaces earlier ones only on success
 }
 
 int chg_md_set_transport(chg_engine* eng, chg_md* d, const chg_md_transport_params* params) {
   if (!eng || !d || !params) return CHG_EINVAL;
   const char* fn = "chg_md_set_transport";
-  if (d->started) { eng->err = std::string(fn) + ": the run has already started"; return CHG_EINVAL; }
-  HIP_TRY(eng, hipSetDevice(eng->device));
-  MdTransport* t = nullptr;
-  TRY(create_transport(eng, fn, d->obs, params, &t));
-  free_transport(d->obs->tr);
-  d->obs->tr = t;
+  TRY(before_run(eng, fn, d));
+  std::unique_ptr<MdTransport> t;
+  TRY(create_transport(eng, fn, d->obs.get(), params, t));   // refuses a handle without observers
+  d->obs->tr = std::move(t);
   return CHG_OK;
 }
 
@@ -746,14 +346,13 @@ int chg_md_download_transport(chg_engine* eng, chg_md* d, const chg_md_transport
   if (!eng || !d || !o) return CHG_EINVAL;
   if (!d->obs || !d->obs->tr) { eng->err = "chg_md_download_transport: the handle has no transport accumulators (chg_md_set_transport)"; return CHG_EINVAL; }
   HIP_TRY(eng, hipSetDevice(eng->device));
-  return download_transport(eng, d->obs, o);
+  return download_transport(eng, d->obs.get(), o);
 }
 
 int chg_md_set_magmoms(chg_engine* eng, chg_md* d, int32_t log_frames) {
   if (!eng || !d) return CHG_EINVAL;
   const char* fn = "chg_md_set_magmoms";
-  if (d->started) { eng->err = std::string(fn) + ": the run has already started"; return CHG_EINVAL; }
-  HIP_TRY(eng, hipSetDevice(eng->device));
+  TRY(before_run(eng, fn, d));
   return enable_magmoms(eng, fn, d, log_frames != 0);
 }
 
@@ -774,16 +373,11 @@ int chg_md_download_magmoms(chg_engine* eng, chg_md* d, float* magmom, float* fr
 int chg_md_set_charge_states(chg_engine* eng, chg_md* d, const chg_md_charge_params* params, const double* bounds) {
   if (!eng || !d || !params || !bounds) return CHG_EINVAL;
   const char* fn = "chg_md_set_charge_states";
-  if (d->started) { eng->err = std::string(fn) + ": the run has already started"; return CHG_EINVAL; }
-  HIP_TRY(eng, hipSetDevice(eng->device));
-  MdCharge* c = nullptr;
-  TRY(create_charge(eng, fn, d->obs, params, bounds, true, &c));
-  if (!d->mag) {   // the observers read moments: task M and the gather, no frame slots
-    const int s = enable_magmoms(eng, fn, d, false);
-    if (s != CHG_OK) { free_charge(c); return s; }
-  }
-  free_charge(d->obs->cs);
-  d->obs->cs = c;
+  TRY(before_run(eng, fn, d));
+  std::unique_ptr<MdCharge> c;
+  TRY(create_charge(eng, fn, d->obs.get(), params, bounds, true, c));   // refuses a handle without observers
+  if (!d->mag) TRY(enable_magmoms(eng, fn, d, false));   // the observers read moments: task M and the gather, no frame slots
+  d->obs->cs = std::move(c);
   return CHG_OK;
 }
 
@@ -794,14 +388,14 @@ int chg_md_download_charge_states(chg_engine* eng, chg_md* d, const chg_md_charg
     return CHG_EINVAL;
   }
   HIP_TRY(eng, hipSetDevice(eng->device));
-  return download_charge(eng, d->obs, o);
+  return download_charge(eng, d->obs.get(), o);
 }
 
 int chg_md_download_observables(chg_engine* eng, chg_md* d, const chg_md_observables_host* o) {
   if (!eng || !d || !o) return CHG_EINVAL;
   if (!d->obs) { eng->err = "chg_md_download_observables: the handle has no observers (chg_md_set_observers)"; return CHG_EINVAL; }
   HIP_TRY(eng, hipSetDevice(eng->device));
-  return download_observables(eng, d->obs, o);
+  return download_observables(eng, d->obs.get(), o);
 }
 
 int chg_md_run(chg_engine* eng, chg_md* d, int32_t n_steps) {
@@ -901,9 +495,7 @@ int chg_md_download_vg(chg_engine* eng, chg_md* d, double* vg) {
 int chg_md_free(chg_engine* eng, chg_md* d) {
   if (!d) return CHG_OK;
   release(eng, d);
-  free_observers(d->obs);
-  if (d->mag_mem) hipFree(d->mag_mem);
-  delete d;
+  delete d;   // the observers and the moment slots go with it
   return CHG_OK;
 }
 
@@ -1033,88 +625,3 @@ int chg_test_md_step_fixed(chg_engine* eng, const chg_md_params* params, int32_t
 }
 
 }  // extern "C"
-
-namespace {
-
-// what chg_test_md_charge_states adds to the snapshots
-struct TestCharge {
-  const chg_md_charge_params* params;
-  const double* bounds;
-  const float* magmoms;   // [T, N]
-  const chg_md_charge_host* out;
-};
-
-// chg_test_md_observe / chg_test_md_transport / chg_test_md_charge_states: caller-given snapshots through observe(), then the
-// downloads that were asked for
-int test_observe(chg_engine* eng, const char* fn, const chg_md_observe_params* params, const chg_md_transport_params* transport,
-                 int32_t n_struct, const int32_t* atom_off, const int32_t* species, const double* masses, int32_t n_samples,
-                 const double* positions, const double* momenta, const double* cell, const int32_t* status,
-                 const chg_md_observables_host* out, const chg_md_transport_host* tout, const TestCharge* charge = nullptr) {
-  using namespace chgh;
-  if (!eng || !params || n_struct <= 0 || !atom_off || !species || !masses || n_samples < 1 || !positions || !momenta || !cell || !status)
-    return CHG_EINVAL;
-  const size_t B = n_struct, T = n_samples;
-  if (atom_off[0] != 0) return CHG_EINVAL;
-  for (size_t o = 0; o < B; ++o)
-    if (atom_off[o + 1] <= atom_off[o]) return CHG_EINVAL;
-  const size_t N = atom_off[n_struct];
-  HIP_TRY(eng, hipSetDevice(eng->device));
-  MdObservers* x = nullptr;
-  TRY(create_observers(eng, fn, params, n_struct, atom_off, species, false, &x));
-  if (transport) {
-    const int s = create_transport(eng, fn, x, transport, &x->tr);
-    if (s != CHG_OK) { free_observers(x); return s; }
-  }
-  if (charge) {
-    const int s = create_charge(eng, fn, x, charge->params, charge->bounds, false, &x->cs);
-    if (s != CHG_OK) { free_observers(x); return s; }
-  }
-  TestBuf bufs[] = {{positions, nullptr, sizeof(double) * T * 3 * N}, {momenta, nullptr, sizeof(double) * T * 3 * N},
-                    {cell, nullptr, sizeof(double) * T * 9 * B}, {status, nullptr, sizeof(int) * T * B}, {masses, nullptr, sizeof(double) * N},
-                    {atom_off, nullptr, sizeof(int) * (B + 1)},
-                    {charge ? charge->magmoms : nullptr, nullptr, sizeof(float) * (charge ? T * N : 1)}};
-  int rc = CHG_OK;
-  int s = run_test_step(eng, fn, bufs, [&] {
-    for (size_t t = 0; t < T && rc == CHG_OK; ++t)
-      rc = observe(eng, fn, x, (const double*)bufs[0].d + t * 3 * N, (const double*)bufs[1].d + t * 3 * N, (const double*)bufs[2].d + t * 9 * B,
-                   (const double*)bufs[4].d, (const int*)bufs[3].d + t * B, 1, (const int*)bufs[5].d,
-                   charge ? (const float*)bufs[6].d + t * N : nullptr);
-  });
-  if (s == CHG_OK) s = rc;
-  if (s == CHG_OK && out) s = download_observables(eng, x, out);
-  if (s == CHG_OK && tout) s = download_transport(eng, x, tout);
-  if (s == CHG_OK && charge) s = download_charge(eng, x, charge->out);
-  free_observers(x);
-  return s;
-}
-
-}  // namespace
-
-extern "C" int chg_test_md_observe(chg_engine* eng, const chg_md_observe_params* params, int32_t n_struct, const int32_t* atom_off,
-                                   const int32_t* species, const double* masses, int32_t n_samples, const double* positions,
-                                   const double* momenta, const double* cell, const int32_t* status,
-                                   const chg_md_observables_host* out) {
-  if (!out) return CHG_EINVAL;
-  return test_observe(eng, "chg_test_md_observe", params, nullptr, n_struct, atom_off, species, masses, n_samples, positions, momenta, cell,
-                      status, out, nullptr);
-}
-
-extern "C" int chg_test_md_transport(chg_engine* eng, const chg_md_observe_params* params, const chg_md_transport_params* transport,
-                                     int32_t n_struct, const int32_t* atom_off, const int32_t* species, const double* masses,
-                                     int32_t n_samples, const double* positions, const double* momenta, const double* cell,
-                                     const int32_t* status, const chg_md_observables_host* plain, const chg_md_transport_host* out) {
-  if (!transport || !out) return CHG_EINVAL;
-  return test_observe(eng, "chg_test_md_transport", params, transport, n_struct, atom_off, species, masses, n_samples, positions, momenta,
-                      cell, status, plain, out);
-}
-
-extern "C" int chg_test_md_charge_states(chg_engine* eng, const chg_md_observe_params* params, const chg_md_charge_params* charge,
-                                         const double* bounds, int32_t n_struct, const int32_t* atom_off, const int32_t* species,
-                                         const double* masses, int32_t n_samples, const double* positions, const double* momenta,
-                                         const double* cell, const int32_t* status, const float* magmoms,
-                                         const chg_md_observables_host* plain, const chg_md_charge_host* out) {
-  if (!charge || !bounds || !magmoms || !out) return CHG_EINVAL;
-  const TestCharge tc{charge, bounds, magmoms, out};
-  return test_observe(eng, "chg_test_md_charge_states", params, nullptr, n_struct, atom_off, species, masses, n_samples, positions, momenta,
-                      cell, status, plain, nullptr, &tc);
-}

@@ -95,16 +95,7 @@ template <class Carve>
 int alloc_state(chg_engine* eng, const char* fn, Stepper* s, const chg_structs_host* h, int extra, Carve&& carve) {
   const size_t B = h->n_struct, N = h->n_atoms;
   s->B = (int)B; s->N = (int)N;
-  Carver sizer{nullptr};
-  carve(sizer);
-  if (hipMalloc(&s->d_mem, sizer.pos) != hipSuccess) {
-    (void)hipGetLastError();
-    s->d_mem = nullptr;
-    eng->err = std::string(fn) + ": device state of " + std::to_string(sizer.pos) + " bytes cannot be allocated";
-    return CHG_ENOMEM;
-  }
-  Carver carver{s->d_mem};
-  carve(carver);
+  TRY(alloc_block(eng, fn, "device state", carve, &s->d_mem));
   const size_t hbytes = sizeof(double) * (3 * N + 9 * B) + sizeof(int) * (N + (3 + extra) * B + 1) + 1024;
   if (hipHostMalloc(&s->h_mem, hbytes, hipHostMallocDefault) != hipSuccess) {
     (void)hipGetLastError();

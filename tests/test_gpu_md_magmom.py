@@ -22,6 +22,7 @@ import pytest
 
 import md_charge_ref as ref
 from conftest import GOLDEN, load_case
+from md_hard_cells import BINS, HARD, RMAX, hard_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -167,6 +168,40 @@ def test_charge_state_kernels_match_the_restatement(hip_engine):
         else:
             assert np.array_equal(got[name][STOPPED], early[name][STOPPED]), name
     assert got["samples"][STOPPED] == STOP_AT
+
+
+# ---- 1b. the state-resolved pair histogram on the hard cells: the plain one, split by the state of the centre ---------------------------
+HARD_CENTER = 1                        # the species present in eight of the nine hard cells
+HARD_BOUNDS = [1.0, 2.0]               # case (b): three states
+
+
+@pytest.mark.parametrize("n_bounds", [pytest.param(0, id="one_state"), pytest.param(2, id="three_states")])
+def test_state_resolved_pair_histogram_is_the_plain_one_on_hard_cells(hip_engine, n_bounds):
+    """k_md_chg_srdf and k_md_obs_rdf run the same image pass (kernels_md_sample.h) and differ only in the histogram row of a pair, so on
+    the nine hard cells -- two snapshots each, the one-atom cell and the replica stopped before the second snapshot included -- the
+    state-resolved counts of a centre species, summed over its states, are the plain counts of that species to the last integer.  The
+    plain counts themselves are held to the float64 restatement, as in tests/test_gpu_md_observe.py."""
+    aoff, species, S, pos, cells, status, want = hard_batch()
+    assert sum(np.any(species[aoff[o]:aoff[o + 1]] == HARD_CENTER) for o in range(len(HARD))) >= 2
+    mag = np.random.default_rng(5).uniform(0.0, 3.0, (2, int(aoff[-1]))).astype(np.float32)   # all finite, spread over the three states
+    bounds = np.zeros((S, 3))
+    bounds[HARD_CENTER, :2] = HARD_BOUNDS
+    nb = [n_bounds if s == HARD_CENTER else 0 for s in range(S)]
+    rc, plain, got = _charge(hip_engine, {"n_species": S, "rdf_bins": BINS, "rdf_rmax": RMAX},
+                             {"n_bounds": nb, "center_species": HARD_CENTER, "srdf_bins": BINS, "srdf_rmax": RMAX}, bounds, aoff, species,
+                             np.ones(aoff[-1]), pos, np.zeros_like(pos), cells, status, mag)
+    assert rc == 0, hip_engine.lib.chg_last_error(hip_engine.handle)
+    for o, name in enumerate(HARD):
+        assert np.array_equal(plain["rdf"][o], want["rdf"][o]), name                                  # the reference: the restatement
+    assert np.array_equal(plain["rdf_samples"], want["rdf_samples"]) and got["samples"].tolist() == want["rdf_samples"].tolist()
+    shist, rdf = got["shist"], plain["rdf"]
+    assert shist.shape == (len(HARD), Q, S, BINS) and rdf[:, HARD_CENTER].sum() > 1000
+    if n_bounds == 0:
+        assert np.array_equal(shist[:, 0], rdf[:, HARD_CENTER]) and np.all(shist[:, 1:] == 0)
+    else:
+        assert np.array_equal(shist.sum(axis=1), rdf[:, HARD_CENTER])
+        assert np.all(got["pop"][:, HARD_CENTER, :3].sum(axis=0) > 0) and np.all(shist[:, :3].sum(axis=(0, 2, 3)) > 0) and np.all(shist[:, 3] == 0)
+    assert shist[HARD.index("thin_cube16")].sum() == 0                                                # one atom of another species: no centre
 
 
 # ---- 2. determinism -----------------------------------------------------------------------------------------------------------------

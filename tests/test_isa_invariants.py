@@ -171,7 +171,8 @@ def md_isa(tmp_path_factory):
     meta = {}
     for block in re.split(r"\n  - \.agpr_count:", text)[1:]:                # one metadata entry per kernel
         field = lambda key: re.search(rf"\.{key}:\s+(\S+)", block).group(1)  # noqa: E731
-        meta[field("name")] = {key: int(field(key)) for key in ("vgpr_count", "vgpr_spill_count", "private_segment_fixed_size")}
+        meta[field("name")] = {key: int(field(key)) for key in ("vgpr_count", "vgpr_spill_count", "private_segment_fixed_size",
+                                                                "group_segment_fixed_size")}
     return meta
 
 
@@ -185,3 +186,23 @@ def test_md_step_kernels_keep_their_state_in_registers(md_isa):
             m = md_isa[hits[0]]
             assert m["vgpr_spill_count"] == 0, f"{hits[0]}: {m}"
             assert m["private_segment_fixed_size"] == 0, f"{hits[0]}: {m}"
+
+
+# static LDS bytes of the observer kernels (kernels_md_obs.h, kernels_md_transport.h, kernels_md_magmom.h) as they were before they were
+# rebuilt over the helpers of kernels_md_sample.h: a helper that quietly adds an LDS array, or a pair-image kernel that stops sharing
+# its cell block, shows here
+MD_OBSERVER_LDS = {"k_md_obs_push": 128, "k_md_obs_corr": 512, "k_md_obs_rdf": 184, "k_md_obs_current": 768, "k_md_obs_transport": 17600,
+                   "k_md_mag_gather": 0, "k_md_chg_sample": 17768, "k_md_chg_corr": 384, "k_md_chg_srdf": 248}
+
+
+def test_md_observer_kernels_keep_nothing_in_scratch_and_their_lds(md_isa):
+    """The observer kernels promise "the per-species accumulators are selected, never indexed, so nothing lives in scratch"; they are
+    built from inlined helpers that take accumulator arrays by reference.  Every one must compile without a spilled register and
+    without scratch, and with the static LDS it had before the helpers."""
+    for kernel, lds in MD_OBSERVER_LDS.items():
+        hits = [name for name in md_isa if f"{len(kernel)}{kernel}E" in name]     # mangled: length, then name
+        assert len(hits) == 1, f"{kernel}: found {hits} among {sorted(md_isa)}"
+        m = md_isa[hits[0]]
+        assert m["vgpr_spill_count"] == 0, f"{kernel}: {m}"
+        assert m["private_segment_fixed_size"] == 0, f"{kernel}: {m}"
+        assert m["group_segment_fixed_size"] == lds, f"{kernel}: {m}"
