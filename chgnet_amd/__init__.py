@@ -42,6 +42,10 @@ def __getattr__(name):  # lazy: keeps `import chgnet_amd` free of the HIP librar
         from chgnet_amd import montecarlo
 
         return getattr(montecarlo, name)
+    if name == "NudgedElasticBand":
+        from chgnet_amd.neb import NudgedElasticBand
+
+        return NudgedElasticBand
     if name in ("MDObservers", "MDObservables"):
         from chgnet_amd import observables
 

@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = (
     "chg_md_set_charge_states", "chg_md_download_charge_states", "chg_test_md_charge_states",
     "chg_mc_create", "chg_mc_set_temperatures", "chg_mc_run", "chg_mc_download", "chg_mc_free", "chg_test_mc_step",
     "chg_mc_set_exchange", "chg_mc_download_exchange", "chg_test_mc_exchange",
+    "chg_neb_create", "chg_neb_set_fixed", "chg_neb_run", "chg_neb_download", "chg_neb_free", "chg_test_neb_step",
 )
 
 
@@ -151,6 +152,21 @@ class McOutHost(ctypes.Structure):
                 ("frame_moves", c_int_p), ("frame_positions", _dp), ("frame_site", c_int_p)]
 
 
+class NebParams(ctypes.Structure):
+    _fields_ = [("fmax", ctypes.c_double), ("max_steps", ctypes.c_int32), ("climb", ctypes.c_int32),
+                ("dt", ctypes.c_double), ("maxstep", ctypes.c_double), ("dtmax", ctypes.c_double), ("finc", ctypes.c_double),
+                ("fdec", ctypes.c_double), ("astart", ctypes.c_double), ("fa", ctypes.c_double), ("nmin", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("spring", ctypes.c_double), ("r_atom", ctypes.c_double), ("r_bond", ctypes.c_double),
+                ("numerical_tol", ctypes.c_double)]
+
+
+class NebOutHost(ctypes.Structure):
+    _fields_ = [("frac", ctypes.POINTER(ctypes.c_double)), ("energy", c_float_p), ("force", c_float_p),
+                ("neb_fmax", ctypes.POINTER(ctypes.c_double)), ("climbing_image", c_int_p), ("n_steps", c_int_p), ("status", c_int_p),
+                ("n_evaluated", c_int_p)]
+
+
+NEB_SD, NEB_SI, NEB_MAX_IMAGES = 24, 4, 66              # csrc/kernels_neb.h: state doubles and ints per band (chg_test_neb_step)
 MC_COUNTS, MC_FRAME_SCALARS, MC_FRAME_MOVES = 8, 6, 6   # include/chgnet_hip.h CHG_MC_*
 MC_SD, MC_SI = 32, 8                                    # csrc/kernels_mc.h: state doubles and ints per replica (chg_test_mc_step)
 MC_EXCHANGE_INTS = 6                                    # include/chgnet_hip.h CHG_MC_EXCHANGE_INTS: walker, attempts, accepts, mark, trips, spare
@@ -334,6 +350,14 @@ def load() -> ctypes.CDLL:
     lib.chg_mc_download_exchange.argtypes = [vp, vp, c_int_p]
     lib.chg_test_mc_exchange.argtypes = [vp, ctypes.c_int32, c_int_p, c_int_p, dp, u64p, ctypes.c_double, ctypes.c_int32, dp, c_int_p, dp,
                                          c_int_p, dp, c_int_p, c_int_p]
+    # nudged elastic band: the band offsets travel beside the structures, the mask [N,3] over all images as an argument of its own
+    lib.chg_neb_create.argtypes = [vp, ctypes.POINTER(StructsHost), c_int_p, ctypes.c_int32, ctypes.POINTER(NebParams), ctypes.POINTER(vp)]
+    lib.chg_neb_set_fixed.argtypes = [vp, vp, u8p]
+    lib.chg_neb_run.argtypes = [vp, vp, ctypes.c_int32, c_int_p]
+    lib.chg_neb_download.argtypes = [vp, vp, ctypes.POINTER(NebOutHost)]
+    lib.chg_neb_free.argtypes = [vp, vp]
+    lib.chg_test_neb_step.argtypes = [vp, ctypes.POINTER(NebParams), ctypes.c_int32, c_int_p, c_int_p, dp, dp, dp, dp, c_int_p, c_float_p,
+                                      c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32, u8p, dp, c_int_p]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is ctypes.c_int and name not in ("chg_device_count", "chg_profile_count"):

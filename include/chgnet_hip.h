@@ -119,7 +119,8 @@ typedef struct chg_out_host {
  * of their own, chg_md_observe_params and chg_md_observables_host, and no older struct or signature changed;
  * so were chg_md_set_transport, chg_md_download_transport and chg_test_md_transport, with chg_md_transport_params and
  * chg_md_transport_host; so were chg_md_set_magmoms, chg_md_download_magmoms, chg_md_set_charge_states, chg_md_download_charge_states
- * and chg_test_md_charge_states, with chg_md_charge_params and chg_md_charge_host).  A binding compiled against another value must refuse the
+ * and chg_test_md_charge_states, with chg_md_charge_params and chg_md_charge_host; so were the chg_neb_* entry points and
+ * chg_test_neb_step, with chg_neb_params and chg_neb_out_host).  A binding compiled against another value must refuse the
  * library: chg_engine_create COPIES *desc, so an older, shorter chg_model_desc would be read past its end. */
 #define CHG_ABI_VERSION 5
 int chg_abi_version(void);
@@ -765,6 +766,65 @@ int chg_mc_download_exchange(chg_engine* eng, chg_mc* mc, int32_t* xi /*[B,CHG_M
 int chg_test_mc_exchange(chg_engine* eng, int32_t n_struct, const int32_t* atom_off, const int32_t* ladder, const double* temperatures,
                          const uint64_t* seeds, double kB, int32_t m, double* r, int32_t* site, double* sd, int32_t* si,
                          double* best_positions, int32_t* best_site, int32_t* xi);
+
+/* ---- nudged elastic band: batched bands, improved tangents, climbing image, one FIRE optimizer per band ------------------------
+ * A band is M images (3 <= M <= 66) that share one fixed cell and one species order; images 0 and M-1 never move.  The state holds the
+ * UNWRAPPED cartesian positions frac . L of every image in float64: the caller applies the minimum image when it interpolates, the step
+ * takes plain differences between neighbouring images.  Every image of every band is an independent structure for the graph build and
+ * the force sweep (chg_batch_build_predict, task ef); the first evaluation predicts all images, every later one the interior images of
+ * the bands still running, and one step kernel (csrc/kernels_neb.h, one workgroup per band) follows it.  For interior image i with
+ * t+ = R[i+1] - R[i], t- = R[i] - R[i-1] and the engine's f32 energies E compared as they are:
+ *   tau = t+ when E[i+1] > E[i] > E[i-1], t- when E[i+1] < E[i] < E[i-1]; otherwise, dmax / dmin the larger / smaller of |E[i+1] - E[i]|
+ *   and |E[i-1] - E[i]|: t+ dmax + t- dmin when E[i+1] > E[i-1], else t+ dmin + t- dmax (ties take these branches); tau is normalised
+ *   (a tangent of length 0 stays 0);  G[i] = F[i] - (F[i] . tau) tau + spring (|t+| - |t-|) tau;  with `climb` the interior image of
+ *   highest energy (first index on ties, chosen anew at every evaluation) takes G = F - 2 (F . tau) tau instead.
+ * Held components (chg_neb_set_fixed) of F count as 0 before the projection, those of G are zeroed after it.  FIRE as in
+ * chg_relax_params runs over the concatenated interior rows of a band (maxstep clamps the norm of the whole band's step); the band is
+ * converged when the largest row norm of G at the evaluated configuration is below fmax.  Statuses are CHG_RELAX_*.  A band with a
+ * non-finite energy or force in any evaluated image is held back as a whole; the batch is evaluated again on the wide-range sweep and
+ * a band that is non-finite even there stops as CHG_RELAX_NONFINITE, untouched.  DESIGN.md "Nudged elastic band"; tests/neb_ref.py
+ * restates the step in float64 NumPy. */
+typedef struct chg_neb_params {
+  double fmax;
+  int32_t max_steps, climb;
+  double dt, maxstep, dtmax, finc, fdec, astart, fa;   /* ASE FIRE: 0.1, 0.2, 1.0, 1.1, 0.5, 0.1, 0.99                          */
+  int32_t nmin, reserved;                              /* 5, 0                                                                  */
+  double spring;                                       /* eV/A^2 (0.1)                                                          */
+  double r_atom, r_bond, numerical_tol;                /* graph build (6, 3, 1e-8)                                              */
+} chg_neb_params;
+typedef struct chg_neb chg_neb;
+/* Null pointers are skipped.  B images, N atoms, n_bands bands, all in the order they were given. */
+typedef struct chg_neb_out_host {
+  double* frac;             /* [N,3] fractional coordinates of the last evaluated configuration (end points: as given, bit for bit) */
+  float* energy;            /* [B]   as last evaluated, eV/atom if is_intensive else eV                                               */
+  float* force;             /* [N,3] the engine's force of the last evaluated configuration, eV/A (not projected, not masked)          */
+  double* neb_fmax;         /* [n_bands] largest row norm of G at the last evaluated configuration                                   */
+  int32_t* climbing_image;  /* [n_bands] index within the band, -1: none                                                             */
+  int32_t* n_steps;         /* [n_bands] optimizer steps taken                                                                       */
+  int32_t* status;          /* [n_bands] CHG_RELAX_*                                                                                 */
+  int32_t* n_evaluated;     /* [n_bands] structures of the band predicted so far                                                     */
+} chg_neb_out_host;
+/* host: the images band after band; band_off [n_bands + 1]: image offsets, from 0 to host->n_struct.  Copies everything; no evaluation
+ * yet.  CHG_EINVAL with a message: a band with fewer than 3 or more than 66 images; images of a band that differ in atom count,
+ * species or cell (bit for bit).  CHG_ENOMEM when the state cannot be allocated. */
+int chg_neb_create(chg_engine* eng, const chg_structs_host* host, const int32_t* band_off, int32_t n_bands, const chg_neb_params* params,
+                   chg_neb** out);
+/* The mask [N,3] over all images (1 = component held; null: none), valid until the first chg_neb_run. */
+int chg_neb_set_fixed(chg_engine* eng, chg_neb* neb, const uint8_t* fixed);
+/* Up to n_steps evaluations, each followed by a step of every band still running; *n_active = bands still running (0: done). */
+int chg_neb_run(chg_engine* eng, chg_neb* neb, int32_t n_steps, int32_t* n_active);
+int chg_neb_download(chg_engine* eng, chg_neb* neb, const chg_neb_out_host* out);
+int chg_neb_free(chg_engine* eng, chg_neb* neb);
+/* Tests only: ONE launch of the step kernel on caller-given state and results, in place.  atom_off [B + 1] over the images, band_off as
+ * above.  State: r, v, g [N,3]; sd [n_bands,24] doubles (L[9], L^-1[9], dt, a, neb_fmax, 3 spare); si [n_bands,4] ints (FIRE Nsteps,
+ * steps taken, status, climbing image); e_img [B] the energies the state holds (the end points' are read when all_images == 0).
+ * Results: all_images 1: energy [B] and force [N,3] of every image; 0: of the interior images only, band after band.  final_try 0: a
+ * band with non-finite results is left untouched and retry[band] is set to 1 (retry [n_bands] is in / out, the caller zeroes it);
+ * 1: it stops as CHG_RELAX_NONFINITE.  fixed [N,3] or null.  out: frac_next [N,3], of which the first sum (M - 2) n rows are
+ * written: the interior images of the bands that moved, band after band. */
+int chg_test_neb_step(chg_engine* eng, const chg_neb_params* params, int32_t n_bands, const int32_t* band_off, const int32_t* atom_off,
+                      double* r, double* v, double* g, double* sd, int32_t* si, float* e_img, const float* energy, const float* force,
+                      int32_t all_images, int32_t final_try, const uint8_t* fixed, double* frac_next, int32_t* retry);
 
 /* ---- exchange steps of the multi-GPU path, straight on RCCL (one communicator per process = per GPU) ----------
  * The reference is single-device; these carry what SURVEY 8e needs and nothing else: the all-gather of per-structure
