@@ -46,6 +46,14 @@ def __getattr__(name):  # lazy: keeps `import chgnet_amd` free of the HIP librar
         from chgnet_amd.neb import NudgedElasticBand
 
         return NudgedElasticBand
+    if name == "DimerSearch":
+        from chgnet_amd.dimer import DimerSearch
+
+        return DimerSearch
+    if name == "vineyard_prefactor":
+        from chgnet_amd.phonons import vineyard_prefactor
+
+        return vineyard_prefactor
     if name in ("MDObservers", "MDObservables"):
         from chgnet_amd import observables
 

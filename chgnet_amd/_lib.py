@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "chg_mc_create", "chg_mc_set_temperatures", "chg_mc_run", "chg_mc_download", "chg_mc_free", "chg_test_mc_step",
     "chg_mc_set_exchange", "chg_mc_download_exchange", "chg_test_mc_exchange",
     "chg_neb_create", "chg_neb_set_fixed", "chg_neb_run", "chg_neb_download", "chg_neb_free", "chg_test_neb_step",
+    "chg_dimer_create", "chg_dimer_set_fixed", "chg_dimer_run", "chg_dimer_download", "chg_dimer_free", "chg_test_dimer_step",
 )
 
 
@@ -166,7 +167,22 @@ class NebOutHost(ctypes.Structure):
                 ("n_evaluated", c_int_p)]
 
 
+class DimerParams(ctypes.Structure):
+    _fields_ = [("fmax", ctypes.c_double), ("max_steps", ctypes.c_int32), ("max_rotations", ctypes.c_int32),
+                ("dt", ctypes.c_double), ("maxstep", ctypes.c_double), ("dtmax", ctypes.c_double), ("finc", ctypes.c_double),
+                ("fdec", ctypes.c_double), ("astart", ctypes.c_double), ("fa", ctypes.c_double), ("nmin", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("delta", ctypes.c_double), ("angle_tol", ctypes.c_double), ("r_atom", ctypes.c_double),
+                ("r_bond", ctypes.c_double), ("numerical_tol", ctypes.c_double)]
+
+
+class DimerOutHost(ctypes.Structure):
+    _dp = ctypes.POINTER(ctypes.c_double)
+    _fields_ = [("frac", _dp), ("mode", _dp), ("force", _dp), ("image_energy", c_float_p), ("image_force", c_float_p), ("curvature", _dp), ("fmax", _dp), ("n_steps", c_int_p),
+                ("n_rotations", c_int_p), ("n_evaluated", c_int_p), ("status", c_int_p), ("phase", c_int_p)]
+
+
 NEB_SD, NEB_SI, NEB_MAX_IMAGES = 24, 4, 66              # csrc/kernels_neb.h: state doubles and ints per band (chg_test_neb_step)
+DIMER_SD, DIMER_SI, DIMER_MAX_ROTATIONS = 24, 8, 32     # csrc/kernels_dimer.h: state doubles and ints per search (chg_test_dimer_step)
 MC_COUNTS, MC_FRAME_SCALARS, MC_FRAME_MOVES = 8, 6, 6   # include/chgnet_hip.h CHG_MC_*
 MC_SD, MC_SI = 32, 8                                    # csrc/kernels_mc.h: state doubles and ints per replica (chg_test_mc_step)
 MC_EXCHANGE_INTS = 6                                    # include/chgnet_hip.h CHG_MC_EXCHANGE_INTS: walker, attempts, accepts, mark, trips, spare
@@ -358,6 +374,14 @@ def load() -> ctypes.CDLL:
     lib.chg_neb_free.argtypes = [vp, vp]
     lib.chg_test_neb_step.argtypes = [vp, ctypes.POINTER(NebParams), ctypes.c_int32, c_int_p, c_int_p, dp, dp, dp, dp, c_int_p, c_float_p,
                                       c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32, u8p, dp, c_int_p]
+    # dimer saddle search: the modes [N,3] travel beside the structures, the mask [N,3] as an argument of its own
+    lib.chg_dimer_create.argtypes = [vp, ctypes.POINTER(StructsHost), dp, ctypes.POINTER(DimerParams), ctypes.POINTER(vp)]
+    lib.chg_dimer_set_fixed.argtypes = [vp, vp, u8p]
+    lib.chg_dimer_run.argtypes = [vp, vp, ctypes.c_int32, c_int_p]
+    lib.chg_dimer_download.argtypes = [vp, vp, ctypes.POINTER(DimerOutHost)]
+    lib.chg_dimer_free.argtypes = [vp, vp]
+    lib.chg_test_dimer_step.argtypes = [vp, ctypes.POINTER(DimerParams), ctypes.c_int32, c_int_p, dp, dp, dp, dp, dp, dp, dp, c_int_p, c_float_p,
+                                        c_float_p, c_float_p, c_float_p, ctypes.c_int32, u8p, dp, c_int_p, c_int_p, c_int_p]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is ctypes.c_int and name not in ("chg_device_count", "chg_profile_count"):

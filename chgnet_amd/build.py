@@ -24,7 +24,7 @@ GRAPH_LIB = os.path.join(LIB_DIR, "libchgnet_graph.so")
 HIP_LIB = os.path.join(LIB_DIR, "libchgnet_hip.so")
 
 # one translation unit per subsystem (csrc/engine_internal.h): a kernel edit recompiles the unit that launches it
-HIP_SOURCES = ["engine.hip", "engine_predict.hip", "engine_predict_wide.hip", "engine_train.hip", "engine_train_wide.hip", "engine_graph.hip", "engine_relax.hip", "engine_md.hip", "engine_mc.hip", "engine_neb.hip", "comm.hip"]
+HIP_SOURCES = ["engine.hip", "engine_predict.hip", "engine_predict_wide.hip", "engine_train.hip", "engine_train_wide.hip", "engine_graph.hip", "engine_relax.hip", "engine_md.hip", "engine_mc.hip", "engine_neb.hip", "engine_dimer.hip", "comm.hip"]
 HIP_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
     "-munsafe-fp-atomics",      # native global_atomic_add_f32, no CAS loops

@@ -120,7 +120,8 @@ typedef struct chg_out_host {
  * so were chg_md_set_transport, chg_md_download_transport and chg_test_md_transport, with chg_md_transport_params and
  * chg_md_transport_host; so were chg_md_set_magmoms, chg_md_download_magmoms, chg_md_set_charge_states, chg_md_download_charge_states
  * and chg_test_md_charge_states, with chg_md_charge_params and chg_md_charge_host; so were the chg_neb_* entry points and
- * chg_test_neb_step, with chg_neb_params and chg_neb_out_host).  A binding compiled against another value must refuse the
+ * chg_test_neb_step, with chg_neb_params and chg_neb_out_host; so were the chg_dimer_* entry points and chg_test_dimer_step, with
+ * chg_dimer_params and chg_dimer_out_host).  A binding compiled against another value must refuse the
  * library: chg_engine_create COPIES *desc, so an older, shorter chg_model_desc would be read past its end. */
 #define CHG_ABI_VERSION 5
 int chg_abi_version(void);
@@ -825,6 +826,76 @@ int chg_neb_free(chg_engine* eng, chg_neb* neb);
 int chg_test_neb_step(chg_engine* eng, const chg_neb_params* params, int32_t n_bands, const int32_t* band_off, const int32_t* atom_off,
                       double* r, double* v, double* g, double* sd, int32_t* si, float* e_img, const float* energy, const float* force,
                       int32_t all_images, int32_t final_try, const uint8_t* fixed, double* frac_next, int32_t* retry);
+
+/* ---- dimer saddle search: batched searches from one basin, rotation by a trial angle, one FIRE optimizer per search --------------
+ * A search is a centre R (n atoms, one fixed cell, UNWRAPPED cartesian positions frac . L in float64) and a unit axis N over all 3 n
+ * components.  Every image of every search is an independent structure for the graph build and the force sweep
+ * (chg_batch_build_predict, task ef).  An evaluation in phase PROBE (0) predicts R and R + delta N of a search, one in phase TRIAL (1)
+ * predicts R + delta N* alone, N* = N cos phi1 + Theta sin phi1: the centre stands still during rotations and its force F0 is kept.
+ * One step kernel (csrc/kernels_dimer.h, one workgroup per search) follows every evaluation, on float64 copies of the engine's f32
+ * forces:
+ *   TRIAL: Ct = (F0 - F1t).N* / delta, b1 = -gn, a1 = (C0 - Ct + b1 sin 2 phi1) / (1 - cos 2 phi1), phim = atan2(b1, a1) / 2, moved by
+ *   pi/2 (towards 0) when it is a maximum of the fit C0 - a1 + a1 cos 2 phi + b1 sin 2 phi;  F1 <- sin(phi1 - phim) / sin(phi1) F1 +
+ *   sin(phim) / sin(phi1) F1t + (1 - cos phim - sin phim tan(phi1 / 2)) F0;  N <- normalise(N cos phim + Theta sin phim)
+ *   then, in both phases: d = F1 - F0, C0 = -(d.N) / delta (curvature along N, eV/A^2), g = (d - (d.N) N) / delta, gn = |g|,
+ *   phi1 = atan2(gn, |C0|) / 2;  while fewer than max_rotations rotations were made since the last translation and phi1 >= angle_tol:
+ *   Theta = g / gn and the next evaluation is a TRIAL
+ *   otherwise the translation: CHG_RELAX_CONVERGED when C0 < 0 and the largest row norm of F0 is below fmax, CHG_RELAX_MAX_STEPS after
+ *   max_steps translations, else one FIRE step (as in chg_relax_params, over all 3 n components, maxstep clamps the whole step) on
+ *   G = F0 - 2 (F0.N) N when C0 < 0, G = -(F0.N) N otherwise; the next evaluation is a PROBE.
+ * Held components (chg_dimer_set_fixed) of N are zeroed before N is normalised, those of every evaluated force count as 0.  A search
+ * with a non-finite energy or force in an evaluated image is held back as a whole; the batch is evaluated again on the wide-range
+ * sweep and a search that is non-finite even there stops as CHG_RELAX_NONFINITE, untouched.  Statuses are CHG_RELAX_*.  DESIGN.md
+ * "Dimer saddle search"; tests/dimer_ref.py restates the step in float64 NumPy. */
+typedef struct chg_dimer_params {
+  double fmax;
+  int32_t max_steps, max_rotations;                    /* translations; rotations per translation, 0..32 (4)                    */
+  double dt, maxstep, dtmax, finc, fdec, astart, fa;   /* ASE FIRE: 0.1, 0.2, 1.0, 1.1, 0.5, 0.1, 0.99                          */
+  int32_t nmin, reserved;                              /* 5, 0                                                                  */
+  double delta, angle_tol;                             /* A in (0, 0.5] (0.01); rad in [1e-4, pi/4) (0.05)                      */
+  double r_atom, r_bond, numerical_tol;                /* graph build (6, 3, 1e-8)                                              */
+} chg_dimer_params;
+typedef struct chg_dimer chg_dimer;
+/* Null pointers are skipped.  S searches, N atoms, in the order they were given. */
+typedef struct chg_dimer_out_host {
+  double* frac;           /* [N,3] fractional coordinates R L^-1 of the centre (unwrapped)                                        */
+  double* mode;           /* [N,3] the axis N                                                                                     */
+  double* force;          /* [N,3] F0: the engine's force at the last evaluated centre, eV/A, held components 0                   */
+  float* image_energy;    /* [S,2] as last evaluated, eV/atom if is_intensive else eV: the centre (at the last PROBE), then the    */
+                          /*       displaced image (PROBE) or the trial image (TRIAL)                                             */
+  float* image_force;     /* [2N,3] the engine's forces of the same two images, eV/A, not masked: search k owns rows               */
+                          /*       2 atom_off[k] .. 2 atom_off[k+1], the centre first                                             */
+  double* curvature;      /* [S]   C0, eV/A^2                                                                                     */
+  double* fmax;           /* [S]   largest row norm of F0                                                                         */
+  int32_t* n_steps;       /* [S]   translations taken                                                                             */
+  int32_t* n_rotations;   /* [S]   rotations made in all                                                                          */
+  int32_t* n_evaluated;   /* [S]   structures of the search predicted so far                                                      */
+  int32_t* status;        /* [S]   CHG_RELAX_*                                                                                    */
+  int32_t* phase;         /* [S]   what the next evaluation of the search predicts: 0 PROBE, 1 TRIAL                              */
+} chg_dimer_out_host;
+/* host: the centres; mode [N,3]: one direction per search, normalised here.  Copies everything; no evaluation yet.  CHG_EINVAL with a
+ * message: delta, max_rotations or angle_tol outside their ranges; a mode that is zero or not finite.  CHG_ENOMEM when the state
+ * cannot be allocated. */
+int chg_dimer_create(chg_engine* eng, const chg_structs_host* host, const double* mode, const chg_dimer_params* params, chg_dimer** out);
+/* The mask [N,3] (1 = component held; null: none), valid until the first chg_dimer_run.  CHG_EINVAL with a message, the handle
+ * unchanged, when a mode has no free component. */
+int chg_dimer_set_fixed(chg_engine* eng, chg_dimer* dimer, const uint8_t* fixed);
+/* Up to n_evaluations evaluations, each followed by a step of every search still running; *n_active = searches still running. */
+int chg_dimer_run(chg_engine* eng, chg_dimer* dimer, int32_t n_evaluations, int32_t* n_active);
+int chg_dimer_download(chg_engine* eng, chg_dimer* dimer, const chg_dimer_out_host* out);
+int chg_dimer_free(chg_engine* eng, chg_dimer* dimer);
+/* Tests only: ONE launch of the step kernel on caller-given state and results, in place.  atom_off [S + 1].  State: r, nvec, theta, v,
+ * f0, f1 [N,3]; sd [S,24] doubles (L[9], L^-1[9], dt, a, C0, gn, phi1, fmax); si [S,8] ints (FIRE Nsteps, translations, status, phase,
+ * rotations since the last translation, rotations in all, 2 spare); e_img [S,2] and f_img [2N,3] as image_energy and image_force of
+ * chg_dimer_out_host.  Results, search after search: energy and force of two
+ * structures (R, R + delta N) where si says PROBE, of one where it says TRIAL (stopped searches included).  final_try 0: a search with
+ * non-finite results is left untouched and retry[search] is set to 1 (retry [S] is in / out, the caller zeroes it); 1: it stops as
+ * CHG_RELAX_NONFINITE.  fixed [N,3] or null.  out: frac_next [2 N,3], search k owns rows 2 atom_off[k] .. 2 atom_off[k + 1] and
+ * writes the first 2 n of them (next phase PROBE), the first n (TRIAL) or none (stopped, held back); phase_next, status_next [S]. */
+int chg_test_dimer_step(chg_engine* eng, const chg_dimer_params* params, int32_t n_searches, const int32_t* atom_off, double* r, double* nvec,
+                        double* theta, double* v, double* f0, double* f1, double* sd, int32_t* si, float* e_img, float* f_img,
+                        const float* energy, const float* force, int32_t final_try, const uint8_t* fixed, double* frac_next,
+                        int32_t* phase_next, int32_t* status_next, int32_t* retry);
 
 /* ---- exchange steps of the multi-GPU path, straight on RCCL (one communicator per process = per GPU) ----------
  * The reference is single-device; these carry what SURVEY 8e needs and nothing else: the all-gather of per-structure
